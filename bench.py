@@ -3,11 +3,18 @@
 src/main.cpp:146-185: GBuffer::render -> ReSTIRDirect -> [LeveledEAWFilter] -> copyImageToPBO -> GBuffer::update), 32 candidates,
 spatiotemporal reuse, on the procedural scenes of BASELINE.json's configs.
 
-    python bench.py --gpus N --steps K --warmup W [--config 3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 3|4|5] [--full] [--dump-outputs DIR]
 
   --config 3 (default, the headline)  Sponza-class scene (262 144 triangles, 1 024 emissive), 1920x1080
   --config 4                          the same scene at 3840x2160 (the config BASELINE defines on 8 GPUs)
   --config 5                          Bistro-class scene (2.83 M triangles, 10 240 emissive), 1920x1080, + the 5-level EAW filter
+  --full                              everything besides the headline figure as well (the fields listed below); a plain run sets up,
+                                      warms up, times the K steps and prints the contract's fields (metric, value, unit,
+                                      higher_is_better, dtype, ms_per_step) with the workload's description and, N > 1, per_rank
+  --dump-outputs DIR                  after the timed steps: what the last timed step computed, as DIR/<name>.npy in float32, one row
+                                      per pixel (row y * width + x) -- radiance (ReSTIRDirect's image), filtered (config 5: the EAW
+                                      result), display (copyImageToPBO's RGBA8 values); N > 1: display only, gathered on rank 0.  More
+                                      than 64 MB in all: the same seeded sample of pixels from every array, their indices in pixel_index
 
 A step = one frame.  A ray = one BVH walk (intersect or testOcclusion call): 1 G-buffer ray + 1 shading ray per pixel + 1 shadow ray
 per shaded pixel; counted by the kernels.
@@ -33,7 +40,7 @@ restir_amd/rccl.py); torch.distributed (gloo) is the control plane only: the id 
                              automatic; 1 with the denoiser of config 5).  The streams themselves are chosen by measurement
                              (`config.internal_streams`, per rank in `per_rank`), again after ncclCommInitRank
 
-One JSON line is printed by rank 0; besides the contract's fields it carries
+One JSON line is printed by rank 0; with --full, besides the contract's fields it carries
   roofline      the spatial-reuse pass (k_spatial_shade): algorithmic 92 B/px over its average launch duration by HIP
                 events (20 back-to-back launches on the stream the kernel is launched on), against the 8 TB/s HBM3E peak; `traffic` is
                 filled from profiles/ PMC runs when known
@@ -72,6 +79,7 @@ TONEMAP = 2                    # ToneMapping::ACES (Settings default, src/common
 ALGO_BYTES_PER_PIXEL = 92      # spatial-reuse pass
 EAW_BYTES_PER_PIXEL_LEVEL = 44 # (12 colour + 20 id/normal/depth) read + 12 written per pixel and level
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_BUDGET_BYTES = 64_000_000 # --dump-outputs: at most 64 MB in all
 
 CONFIGS = {
     3: dict(width=1920, height=1080, scene="sponza", denoise=False, cpu_frames=3,
@@ -159,6 +167,22 @@ def host_threads():
     except Exception:
         pass
     return max(1, min(n, 64))
+
+
+def write_outputs(d, arrays, pixels):
+    """--dump-outputs: {name: host array with one row per pixel} as d/<name>.npy in float32.  Beyond DUMP_BUDGET_BYTES in all, every
+    array keeps the same seeded sample of pixels (in pixel order), and their indices go to d/pixel_index.npy (float64, exact)."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32).reshape(pixels, -1) for k, a in arrays.items()}
+    per_pixel = sum(a.shape[1] * 4 for a in arrays.values())
+    if per_pixel * pixels > DUMP_BUDGET_BYTES:
+        keep = (DUMP_BUDGET_BYTES - 4096) // (per_pixel + 8)          # (8: the index itself; 4096: the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(pixels, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 # ---- what a rank is doing, for the launcher's diagnosis of a failed run --------------------------------------------------------------------
@@ -459,8 +483,11 @@ def main():
     ap.add_argument("--config", type=int, default=3, choices=sorted(CONFIGS), help="BASELINE.json config (3 = the headline)")
     ap.add_argument("--cpu-frames", type=int, default=None, help="frames timed for cpu_baseline (0 = skip; default depends on the config)")
     ap.add_argument("--orbit", action="store_true", help="orbit the camera (runCuda animateCamera) instead of the static default")
-    ap.add_argument("--sustained-frames", type=int, default=2000, help="overlapped frames run AFTER the timed region for ms_per_step_sustained (10 windows; 0 = skip)")
-    ap.add_argument("--only-timed", action="store_true", help="stop after the timed region and the sustained frames (profiling: every frame of the process is then an overlapped one)")
+    ap.add_argument("--full", action="store_true", help="measure and check everything besides the headline figure as well (sustained and latency figures, "
+                                                         "per-pass times, rooflines, parity, CPU baselines); off: set up, warm up, time --steps, print")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--sustained-frames", type=int, default=2000, help="with --full: overlapped frames run AFTER the timed region for ms_per_step_sustained (10 windows; 0 = skip)")
+    ap.add_argument("--only-timed", action="store_true", help="with --full: stop after the timed region and the sustained frames (profiling: every frame of the process is then an overlapped one)")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     WIDTH, HEIGHT, DENOISE = cfg["width"], cfg["height"], cfg["denoise"]
@@ -633,6 +660,15 @@ def main():
 
         def pbo_ptr():
             return pbos[0].data_ptr() + y0 * WIDTH * 4
+
+        def last_outputs():
+            # rank 0, after barrier(): the last frame's display image, gathered from every strip; one rank holds the whole frame's images
+            outs = {"display": pbos[(state["frame_no"] - 1) % 2]}
+            if world == 1:
+                outs["radiance"] = backend.image
+                if DENOISE:
+                    outs["filtered"] = device_copy(state["shown"])
+            return outs
     else:
         # ---- restir_amd/tiling.py over torch.distributed (N = 1: the plain calls) -----------------------------------------------
         # (init_process_group / ncclCommInitRank made streams after the library had chosen its own during the calibration of the strip
@@ -680,6 +716,23 @@ def main():
 
         def pbo_ptr():
             return pbos[0].data_ptr()
+
+        def last_outputs():
+            # rank 0, after barrier(): the last frame's display image (N > 1: the strips gathered from every rank) [, radiance, filtered image]
+            k = (state["frame_no"] - 1) % len(pbos)
+            if world > 1:
+                return {"display": torch.cat([gather_outs[k][r][:(b - a) * WIDTH] for r, (a, b) in enumerate(strips.bounds)])}
+            outs = {"radiance": backend.image, "display": pbos[k][:HEIGHT * WIDTH]}
+            if DENOISE:
+                outs["filtered"] = device_copy(state["shown"])
+            return outs
+
+    def device_copy(ptr):
+        """A copy of the full-frame float3 image at `ptr` (a buffer the library owns, e.g. the filter's result)."""
+        capi.join_denoise_stream(); capi.synchronize()          # (BENCH_DENOISE_STREAM=1: the filter ran on the denoise stream)
+        t = torch.empty_like(backend.image)
+        capi.hip_memcpy_d2d(t.data_ptr(), ptr, t.numel() * 4)
+        return t
 
     def barrier():
         finish_gathers()                   # every frame's image has reached rank 0 before the clock stops
@@ -753,6 +806,98 @@ def main():
     counted = min(args.steps, 1024)
     # G-buffer rays: only the strip's own rows count (the +-5 halo rows a strip re-renders are overhead, not throughput)
     local_rays = backend.restir.ray_total(counted) / counted * args.steps + rows * WIDTH * args.steps
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in last_outputs().items()}, WIDTH * HEIGHT)
+
+    t = torch.tensor([elapsed, float(local_rays)], dtype=torch.float64, device=ctl_device)
+    if world > 1:
+        tmax = t.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        tsum = t.clone(); dist.all_reduce(tsum, op=dist.ReduceOp.SUM)
+        elapsed, total_rays = float(tmax[0]), float(tsum[1])
+    else:
+        total_rays = float(local_rays)
+    # what every rank saw, for the reader of a multi-GPU line: the slowest rank decides the frame time (--full adds its other figures)
+    mine = {"rank": rank, "device": device, "rows": rows, "ms_per_step": own_elapsed / args.steps * 1e3, "rays_per_frame": local_rays / args.steps,
+            "internal_streams": list(capi.internal_streams_info())}      # (priority level, calibration us of the chosen three, fastest candidate us) on this rank
+
+    def per_rank():
+        if world == 1:
+            return [mine]
+        everyone = [None] * world
+        dist.all_gather_object(everyone, mine)
+        return everyone
+
+    out = None
+    if rank == 0:
+        fused, chains = timed_form                            # what the timed frames launched, as the library reported it then
+        how = {-2: "not measured: a launch below three rounds of wave slots, or a form that is forced", -1: "measurement not finished within this run", 0: "measured", 1: "measured"}[backend.restir.launch_choice()]
+        lvl, chosen_us, fastest_us = capi.internal_streams_info()
+        out = {
+            "metric": "Mrays/s (%dx%d ReSTIR-DI, 32 candidates, spatiotemporal reuse%s)" % (WIDTH, HEIGHT, " + 5-level EAW filter" if DENOISE else ""),
+            "value": total_rays / elapsed / 1e6,
+            "unit": "Mrays/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": cfg["workload"],
+                       "baseline_config": args.config,
+                       "camera": "orbit" if args.orbit else "static",
+                       "sampler": "default engine (thrust minstd_rand, SAMPLER_USE_SOBOL false: the reference's default)" if sobol_num is None else
+                                  "Sobol (src/sampler.h:9-36) over the build's own %d x 200 table" % sobol_num,
+                       "launches": "asynchronous (rs_set_sync(0)): consecutive frames overlap on the library's auxiliary streams; GBuffer::render is walked "
+                                   "together with the primary rays when the library measures that to be faster (it measures in untimed frames before the warm-up); "
+                                   "ms_per_frame_synchronous (--full) is one frame alone with a synchronisation after every call, the reference's mode",
+                       "tiling": (f"{world} row strips of " + "/".join(str(b - a) for a, b in bounds) + " rows (" +
+                                  ("equal heights" if os.environ.get("BENCH_EVEN_STRIPS", "0") == "1" else "cost-balanced by measurement") + "), "
+                                  "5 border rows of reservoirs + G-buffer id / normal / depth point-to-point (68 B/px)" +
+                                  (", 32 G-buffer rows + 2 << level colour rows per EAW level" if DENOISE else "") + ", RGBA8 gather to rank 0") if world > 1 else "none",
+                       "strip_driver": {"c": "librestir_hip rs_strips_frame / " + ("rs_strips_eaw_filter / " if DENOISE else "") + "rs_strips_gather_begin,_end (restir_amd/csrc/strips.hip)",
+                                        "py": "restir_amd/tiling.py over torch.distributed (%s)" % backend_name,
+                                        "none": "none (single GPU: rs_gbuffer_render + rs_restir_direct" + (" + rs_eaw_filter)" if DENOISE else ")")}[driver],
+                       "transport": ("none" if driver == "none" else "torch.distributed " + backend_name if driver == "py" else
+                                     "RCCL ncclSend / ncclRecv groups on the library stream, one group per frame (rs_comm_create_rccl_lib), ncclComm_t made by ncclCommInitRank from " + str(rccl.path)
+                                     if transport == "rccl" else "host callbacks over torch.distributed gloo (rehearsal, not RCCL)"),
+                       "rccl_ranks": (world if (driver == "c" and transport == "rccl") else (world if (driver == "py" and backend_name == "nccl" and world > 1) else 0)),
+                       "strip_rows_per_rank": [b - a for a, b in bounds],
+                       "strip_transfers_on": comm_choice,
+                       "strip_transfers_trial_ms": comm_trial,
+                       "strip_driver_fallback": fallback,
+                       "rays_per_frame": total_rays / args.steps,
+                       "launch_choice": "%s (%s), chains on %d streams in turn" % ("one fused launch" if fused == 1 else "two launches", how, chains),
+                       "calibration_frames_before_warmup": calibration_frames,
+                       "internal_streams": {"priority_level": lvl, "calibration_us": chosen_us, "fastest_candidate_us": fastest_us,
+                                            "note": "the library's three own streams, chosen by measurement next to the caller's stream (rs_internal_streams_info)"}},
+        }
+
+    def teardown():
+        # orderly teardown: the strip driver (waits for its streams), then the communicator, then the control plane
+        finish_gathers()
+        capi.synchronize(); torch.cuda.synchronize()
+        if driver == "c":
+            drv.destroy(); comm.destroy()
+            if rccl is not None:
+                if world > 1:
+                    dist.barrier()                 # every rank has left its last transfer before any rank destroys the communicator
+                rccl.destroy()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        set_phase("done", mine=mine)
+
+    if not args.full:
+        everyone = per_rank()
+        if rank == 0:
+            if world > 1:
+                out["per_rank"] = everyone
+            print(json.dumps(out), flush=True)
+        teardown()
+        return
 
     # A sustained figure next to the timed region's (the driver's --steps 20 is a burst of ~20 ms): --sustained-frames more overlapped
     # frames in ten windows, each bracketed like the timed region (the windows' ends drain the pipeline: ten drains in all).
@@ -780,20 +925,9 @@ def main():
     backend.restir.enable_timing(False)
     if args.only_timed:
         if rank == 0:
-            print(json.dumps({"metric": "Mrays/s", "only_timed": True, "n_gpus": world, "steps": args.steps, "ms_per_step": elapsed / args.steps * 1e3,
+            print(json.dumps({"metric": "Mrays/s", "only_timed": True, "n_gpus": world, "steps": args.steps, "ms_per_step": own_elapsed / args.steps * 1e3,
                               "sustained": sustained, "spatial_in_frame_us": float(np.mean(spatial_in_frame_ms)) * 1e3 if spatial_in_frame_ms else None}), flush=True)
-        finish_gathers()
-        capi.synchronize(); torch.cuda.synchronize()
-        if driver == "c":
-            drv.destroy(); comm.destroy()
-            if rccl is not None:
-                if world > 1:
-                    dist.barrier()
-                rccl.destroy()
-        if world > 1:
-            dist.barrier()
-            dist.destroy_process_group()
-        set_phase("done")
+        teardown()
         return
 
     # latency of one frame when nothing overlaps: the reference's own mode (every call synchronises, cudaUtil.h:15)
@@ -948,29 +1082,14 @@ def main():
                                     "oracle): " + ("filtered image" if DENOISE else "radiance") + " of the gathered strips bit for bit after every frame, the last two "
                                     "asynchronously gathered RGBA8 display images byte for byte; launches overlapped as in the timed region"}
 
-    # what every rank saw, for the reader of a multi-GPU line: the slowest rank decides the frame time
-    mine = {"rank": rank, "device": device, "rows": rows, "ms_per_step": own_elapsed / args.steps * 1e3,
-            "ms_per_frame_synchronous": float(np.median(sync_ms[2:])),
-            "ms_per_frame_single_in_flight": float(np.median(single_ms[2:])),
-            "halo_wait_ms": (float(np.median(halo_wait)) if halo_wait else None),
-            "pass_ms": {"gbuffer": float(np.median(gb_ms)), "to_rgba8": float(np.median(pbo_ms)), "primary": float(pass_ms[0]), "ris": float(pass_ms[1]),
-                        "shadow_temporal": float(pass_ms[2]), "spatial_shade": float(pass_ms[3]),
-                        **({"eaw_positions": eaw_level_ms[0], "eaw_levels": eaw_level_ms[1:]} if eaw_level_ms else {})},
-            "rays_per_frame": local_rays / args.steps,
-            "internal_streams": list(capi.internal_streams_info())}      # (priority level, calibration us of the chosen three, fastest candidate us) on this rank
-    per_rank = [mine]
+    mine.update({"ms_per_frame_synchronous": float(np.median(sync_ms[2:])),
+                 "ms_per_frame_single_in_flight": float(np.median(single_ms[2:])),
+                 "halo_wait_ms": (float(np.median(halo_wait)) if halo_wait else None),
+                 "pass_ms": {"gbuffer": float(np.median(gb_ms)), "to_rgba8": float(np.median(pbo_ms)), "primary": float(pass_ms[0]), "ris": float(pass_ms[1]),
+                             "shadow_temporal": float(pass_ms[2]), "spatial_shade": float(pass_ms[3]),
+                             **({"eaw_positions": eaw_level_ms[0], "eaw_levels": eaw_level_ms[1:]} if eaw_level_ms else {})}})
     set_phase("parity", mine=mine)                          # (the launcher quotes it if a later step fails)
-    if world > 1:
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, mine)
-
-    t = torch.tensor([elapsed, float(local_rays)], dtype=torch.float64, device=ctl_device)
-    if world > 1:
-        tmax = t.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        tsum = t.clone(); dist.all_reduce(tsum, op=dist.ReduceOp.SUM)
-        elapsed, total_rays = float(tmax[0]), float(tsum[1])
-    else:
-        total_rays = float(local_rays)
+    everyone = per_rank()
 
     # HBM bandwidth as this box delivers it to a plain device-to-device copy (report the roofline fraction "of spec"
     # and "of measured copy"): 1 GiB read + 1 GiB written per copy, best of 10
@@ -995,48 +1114,11 @@ def main():
         traffic, traffic_us, traffic_src = pmc_traffic(args.config, "k_spatial_shade")
         algo_bytes = ALGO_BYTES_PER_PIXEL * WIDTH * rows
         achieved = algo_bytes / (spatial_us * 1e-6) / 1e9
-        out = {
-            "metric": "Mrays/s (%dx%d ReSTIR-DI, 32 candidates, spatiotemporal reuse%s)" % (WIDTH, HEIGHT, " + 5-level EAW filter" if DENOISE else ""),
-            "value": total_rays / elapsed / 1e6,
-            "unit": "Mrays/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
+        out.update({
             "ms_per_step_sustained": sustained["ms_per_step"] if sustained else None,
             "sustained": sustained,
-            "ms_per_frame_synchronous": float(np.median(sync_ms[2:])),
-            "ms_per_frame_single_in_flight": float(np.median(single_ms[2:])),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": cfg["workload"],
-                       "baseline_config": args.config,
-                       "camera": "orbit" if args.orbit else "static",
-                       "sampler": "default engine (thrust minstd_rand, SAMPLER_USE_SOBOL false: the reference's default)" if sobol_num is None else
-                                  "Sobol (src/sampler.h:9-36) over the build's own %d x 200 table" % sobol_num,
-                       "launches": "asynchronous (rs_set_sync(0)): consecutive frames overlap on the library's auxiliary streams; GBuffer::render is walked "
-                                   "together with the primary rays when the library measures that to be faster (it measures in untimed frames before the warm-up); "
-                                   "ms_per_frame_synchronous is one frame alone with a synchronisation after every call, the reference's mode",
-                       "tiling": (f"{world} row strips of " + "/".join(str(b - a) for a, b in bounds) + " rows (" +
-                                  ("equal heights" if os.environ.get("BENCH_EVEN_STRIPS", "0") == "1" else "cost-balanced by measurement") + "), "
-                                  "5 border rows of reservoirs + G-buffer id / normal / depth point-to-point (68 B/px)" +
-                                  (", 32 G-buffer rows + 2 << level colour rows per EAW level" if DENOISE else "") + ", RGBA8 gather to rank 0") if world > 1 else "none",
-                       "strip_driver": {"c": "librestir_hip rs_strips_frame / " + ("rs_strips_eaw_filter / " if DENOISE else "") + "rs_strips_gather_begin,_end (restir_amd/csrc/strips.hip)",
-                                        "py": "restir_amd/tiling.py over torch.distributed (%s)" % backend_name,
-                                        "none": "none (single GPU: rs_gbuffer_render + rs_restir_direct" + (" + rs_eaw_filter)" if DENOISE else ")")}[driver],
-                       "transport": ("none" if driver == "none" else "torch.distributed " + backend_name if driver == "py" else
-                                     "RCCL ncclSend / ncclRecv groups on the library stream, one group per frame (rs_comm_create_rccl_lib), ncclComm_t made by ncclCommInitRank from " + str(rccl.path)
-                                     if transport == "rccl" else "host callbacks over torch.distributed gloo (rehearsal, not RCCL)"),
-                       "rccl_ranks": (world if (driver == "c" and transport == "rccl") else (world if (driver == "py" and backend_name == "nccl" and world > 1) else 0)),
-                       "strip_rows_per_rank": [b - a for a, b in bounds],
-                       "strip_transfers_on": comm_choice,
-                       "strip_transfers_trial_ms": comm_trial,
-                       "strip_driver_fallback": fallback,
-                       "halo_wait_ms_rank0": (float(np.median(halo_wait)) if halo_wait else None),
-                       "rays_per_frame": total_rays / args.steps},
+            "ms_per_frame_synchronous": mine["ms_per_frame_synchronous"],
+            "ms_per_frame_single_in_flight": mine["ms_per_frame_single_in_flight"],
             "roofline": {"bound": "hbm", "kernel": "k_spatial_shade", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic if world == 1 else None,
                          "traffic_source": (("profiles/" + os.path.basename(traffic_src) + " (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command; "
@@ -1065,7 +1147,8 @@ def main():
                          "measured_copy_GBps": copy_gbs, "frac_of_measured_copy": achieved / copy_gbs if copy_gbs else None,
                          "note": "rank 0's strip; the timed span includes the wait for the halo rows" if world > 1 else "full frame"},
             "pass_ms": mine["pass_ms"],
-        }
+        })
+        out["config"]["halo_wait_ms_rank0"] = mine["halo_wait_ms"]
         if eaw_level_ms:
             eaw_us = sum(eaw_level_ms[1:]) * 1e3
             eaw_bytes = EAW_BYTES_PER_PIXEL_LEVEL * WIDTH * rows * 5
@@ -1076,18 +1159,10 @@ def main():
                                    "positions_us": eaw_level_ms[0] * 1e3,
                                    "note": "44 B per pixel and level (SURVEY.md 8d); `traffic` = mean HBM bytes of ONE level launch from the committed counters"}
         if world > 1:
-            out["per_rank"] = per_rank
+            out["per_rank"] = everyone
             exp = expected_compute_only(args.config, world)
             out["expected_compute_only_ms"] = exp["ms"] if exp else None
             out["expected_compute_only"] = exp
-        fused, chains = timed_form                            # what the timed frames launched, as the library reported it then
-        form = "one fused launch" if fused == 1 else "two launches"
-        how = {-2: "not measured: a launch below three rounds of wave slots, or a form that is forced", -1: "measurement not finished within this run", 0: "measured", 1: "measured"}[backend.restir.launch_choice()]
-        out["config"]["launch_choice"] = "%s (%s), chains on %d streams in turn" % (form, how, chains)
-        out["config"]["calibration_frames_before_warmup"] = calibration_frames
-        lvl, chosen_us, fastest_us = capi.internal_streams_info()
-        out["config"]["internal_streams"] = {"priority_level": lvl, "calibration_us": chosen_us, "fastest_candidate_us": fastest_us,
-                                             "note": "the library's three own streams, chosen by measurement next to the caller's stream (rs_internal_streams_info)"}
         if strips_parity is not None:
             out["parity" if world > 1 else "strips_parity"] = strips_parity       # N = 1 through the strip driver keeps the oracle's `parity` below
         if world == 1 and args.cpu_frames > 0 and sobol_num is None:
@@ -1110,18 +1185,7 @@ def main():
             if ref_loop is not None:
                 out["cpu_reference_loop"] = ref_loop
         print(json.dumps(out), flush=True)
-    # orderly teardown: the strip driver (waits for its streams), then the communicator, then the control plane
-    if driver == "c":
-        capi.synchronize(); torch.cuda.synchronize()
-        drv.destroy(); comm.destroy()
-        if rccl is not None:
-            if world > 1:
-                dist.barrier()                 # every rank has left its last transfer before any rank destroys the communicator
-            rccl.destroy()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    set_phase("done", mine=mine)
+    teardown()
 
 
 if __name__ == "__main__":

@@ -2,6 +2,9 @@
 library, drive both through the reference's per-frame call sequence (runCuda, src/main.cpp:146-185)
 and compare."""
 import ctypes as C
+import hashlib
+import json
+import os
 
 import numpy as np
 
@@ -15,6 +18,62 @@ def bits_equal(a, b):
     if a.dtype == np.float32:
         return np.array_equal(a.view(np.uint32), b.view(np.uint32))
     return np.array_equal(a, b)
+
+
+REF_DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_digests.json")
+
+
+def _digest(arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(("%s%s" % (a.dtype.str, a.shape)).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+class RefOutputs:
+    """The reference's outputs in one test, in the order the test compares them.  Where oracle/_ref is built (it needs the reference's
+    sources), each is computed live and compared with ours as before, and its SHA-256 digest (dtype, shape, bytes) must equal the one
+    stored in tests/golden/ref_digests.json (made by RESTIR_RECORD_REF_DIGESTS=1 python -m pytest <the tests>).  Elsewhere the digest
+    of OUR output must equal the stored one: the same bit-for-bit assertion against the same reference bits."""
+
+    def __init__(self, test_id, live):
+        self.id, self.live, self.n = test_id, live, 0
+        self.record = live and os.environ.get("RESTIR_RECORD_REF_DIGESTS") == "1"
+        with open(REF_DIGESTS) as fh:
+            self.table = json.load(fh)
+        self.got = [] if self.record else None
+        self.want = self.table.get(test_id)
+        assert self.record or self.want is not None, "no stored reference digests for " + test_id
+
+    def same(self, ours, ref):
+        """ours: a tuple of arrays; ref: a callable that returns the reference's tuple (called only where oracle/_ref is built)."""
+        ours = tuple(ours)
+        if self.live:
+            theirs = tuple(ref())
+            assert len(theirs) == len(ours)
+            for i, (a, b) in enumerate(zip(ours, theirs)):
+                assert bits_equal(a, b), (self.id, self.n, i)
+            d = _digest(theirs)
+        else:
+            d = _digest(ours)
+        if self.record:
+            self.got.append(d)
+        else:
+            assert self.n < len(self.want) and d == self.want[self.n], (self.id, self.n, "differs from the reference's stored output")
+        self.n += 1
+
+    def finish(self):
+        if self.record:
+            with open(REF_DIGESTS) as fh:
+                table = json.load(fh)
+            table[self.id] = self.got
+            with open(REF_DIGESTS, "w") as fh:
+                json.dump(table, fh, indent=0, sort_keys=True)
+                fh.write("\n")
+        else:
+            assert self.n == len(self.want), (self.id, self.n, len(self.want))
 
 
 def mismatch_fraction(a, b):

@@ -4,7 +4,8 @@ and the instance baking of buildDevData (/root/reference/src/scene.cpp:27-61,96-
 Three layers, each bit-exact:
   * the oracle restatement (oracle/scene_format.py + orc_bake_instance) against the reference's own loaders -- tinyobj::LoadObj,
     stbi_loadf, safeGetline / tokenizeString, Math::buildTransformationMatrix + GLM -- through the committed fixture
-    tests/golden/scene_files.npz (made by tests/golden/make_scene_golden.py) and, in the build container, live on fuzzed inputs;
+    tests/golden/scene_files.npz (made by tests/golden/make_scene_golden.py) and on seeded fuzzed inputs -- live where oracle/_ref is
+    built, elsewhere against the digests of the reference's outputs (tests/golden/ref_digests.json, tests.common.RefOutputs);
   * the product (rs_scene_file_load & co. of librestir_hip.so, host code) against the oracle and the same fixture;
   * on the GPU: a scene loaded from disk by the product renders the same frames as the oracle rendering the oracle-parsed scene.
 """
@@ -18,12 +19,18 @@ from oracle import binding as ob
 from oracle import scene_format as sf
 from restir_amd import capi
 from tests import scene_file_cases as cases
-from tests.common import bits_equal
+from tests.common import RefOutputs, bits_equal
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "scene_files.npz")
 RL = ob.ref_loaders()
 RS = ob.ref_subset()
-needs_ref = pytest.mark.skipif(RL is None or RS is None, reason="oracle/_ref not built (no /root/reference here)")
+
+
+@pytest.fixture
+def ref(request):
+    r = RefOutputs(request.node.nodeid, RL is not None and RS is not None)
+    yield r
+    r.finish()
 
 
 @pytest.fixture(scope="module")
@@ -42,6 +49,20 @@ def case_dir(g, tmp_path_factory):
 
 def _joined(lines):
     return "".join("\t".join(sf.tokenize(l)) + "\n" for l in lines).encode("latin-1")
+
+def _ref_image(p, flip, h, w):
+    """stbi_loadf through the reference's Image: (height, width, floats)."""
+    ww, hh = C.c_int(), C.c_int()
+    buf = np.zeros(h * w * 3, np.float32)
+    assert RL.ref_image_load(p.encode(), flip, C.byref(ww), C.byref(hh), buf.ctypes.data, buf.size) == 0
+    return np.int64(hh.value), np.int64(ww.value), buf.reshape(h, w, 3)
+
+
+def _ref_obj(p, cap):
+    """tinyobj::LoadObj through the reference's loader: (count, positions, normals, texcoords)."""
+    v = np.zeros((cap, 3), np.float32); nn = np.zeros((cap, 3), np.float32); t = np.zeros((cap, 2), np.float32)
+    cnt = RL.ref_obj_load(str(p).encode(), cap, v.ctypes.data, nn.ctypes.data, t.ctypes.data)
+    return np.int64(cnt), v[:cnt], nn[:cnt], t[:cnt]
 
 
 # ---- oracle vs the reference's loaders (fixture) ----------------------------------------------------------------------
@@ -89,9 +110,8 @@ def test_oracle_baking_matches_glm(g):
         assert bits_equal(v, g["bake_verts_out"][i]) and bits_equal(n, g["bake_normals_out"][i]), i
 
 
-# ---- oracle vs the reference's loaders, live (build container) --------------------------------------------------------
-@needs_ref
-def test_obj_number_syntax_fuzz_against_tinyobj(tmp_path):
+# ---- oracle vs the reference's loaders on fuzzed inputs (live where oracle/_ref is built, else its stored digests) ---------
+def test_obj_number_syntax_fuzz_against_tinyobj(tmp_path, ref):
     rng = np.random.default_rng(21)
     toks = []
     for _ in range(6000):
@@ -120,24 +140,20 @@ def test_obj_number_syntax_fuzz_against_tinyobj(tmp_path):
         f.write("vn 0 1 0\n")
         for i in range(n // 3):
             f.write(f"f {3 * i + 1}//1 {3 * i + 2}//1 {3 * i + 3}//1\n")
-    cap = n + 8
-    v = np.zeros((cap, 3), np.float32); nn = np.zeros((cap, 3), np.float32); t = np.zeros((cap, 2), np.float32)
-    cnt = RL.ref_obj_load(str(p).encode(), cap, v.ctypes.data, nn.ctypes.data, t.ctypes.data)
     mv, mn, mt = sf.load_obj(str(p))
-    assert cnt == len(mv) == (n // 3) * 3
-    assert bits_equal(v[:cnt], mv) and bits_equal(nn[:cnt], mn) and bits_equal(t[:cnt], mt)
+    assert len(mv) == (n // 3) * 3
+    ref.same((np.int64(len(mv)), mv, mn, mt), lambda: _ref_obj(p, n + 8))
     # the product reads the same numbers: a one-object scene with the identity instance, against the oracle's baking of the
-    # reference's numbers (vertices pass through the baking arithmetic unchanged unless they are not finite)
+    # reference's numbers, bit-equal to the oracle's (vertices pass through the baking arithmetic unchanged unless they are not finite)
     scene = tmp_path / "fuzz.txt"
     scene.write_text("Object o\n" + str(p) + "\nMaterial Null\nScale 1 1 1\n\nCamera\nResolution 8 8\nFovY 20\nLensRadius 0\nFocalDist 1\n"
                      "ApertureMask Null\nSample 1\nDepth 1\nFile x\nEye 0 0 3\nRotation -90 0 0\nUp 0 1 0\n\n")
     a = capi.SceneFile(str(scene))
-    bv, bn = ob.bake_instance((0, 0, 0), (0, 0, 0), (1, 1, 1), v[:cnt], nn[:cnt])
+    bv, bn = ob.bake_instance((0, 0, 0), (0, 0, 0), (1, 1, 1), mv, mn)
     assert bits_equal(a.vertices.reshape(-1, 3), bv) and bits_equal(a.normals.reshape(-1, 3), bn)
 
 
-@needs_ref
-def test_hdr_decoder_fuzz_against_stb_image(tmp_path):
+def test_hdr_decoder_fuzz_against_stb_image(tmp_path, ref):
     """Random Radiance pictures -- widths on both sides of the run-length limits, long runs, zero exponents, flat and coded --
     decoded by the oracle restatement and by the product equal stbi_loadf's floats under both flip settings."""
     from restir_amd import scene_io
@@ -152,12 +168,8 @@ def test_hdr_decoder_fuzz_against_stb_image(tmp_path):
         p = str(tmp_path / f"r{i}.hdr")
         scene_io.write_hdr(p, img, rle=rle)
         for flip in (0, 1):
-            ww, hh = C.c_int(), C.c_int()
-            buf = np.zeros(h * w * 3, np.float32)
-            assert RL.ref_image_load(p.encode(), flip, C.byref(ww), C.byref(hh), buf.ctypes.data, buf.size) == 0
-            assert (hh.value, ww.value) == (h, w)
-            ref = buf.reshape(h, w, 3)
-            assert bits_equal(sf.load_hdr(p, bool(flip)), ref), (i, flip)
+            dec = sf.load_hdr(p, bool(flip))
+            ref.same((np.int64(h), np.int64(w), dec), lambda: _ref_image(p, flip, h, w))
             # the product: as a texture (flipped) or as the environment map (not flipped) of a one-triangle scene
             scene = tmp_path / "s.txt"
             if flip:
@@ -166,13 +178,12 @@ def test_hdr_decoder_fuzz_against_stb_image(tmp_path):
             else:
                 scene.write_text(f"Object o\n{obj}\nMaterial Null\nScale 1 1 1\n\n" + cam + f"EnvMap {p}\n")
             a = capi.SceneFile(str(scene))
-            assert len(a.textures) == 1 and bits_equal(a.textures[0], ref), (i, flip)
+            assert len(a.textures) == 1 and bits_equal(a.textures[0], dec), (i, flip)
         dec = sf.load_hdr(p, False)                                            # RGBE keeps 8 bits of a pixel's largest component
         assert (np.abs(dec - img).max(axis=2) <= img.max(axis=2) / 128 + 1e-30).all()
 
 
-@needs_ref
-def test_png_decoder_against_stb_image(tmp_path):
+def test_png_decoder_against_stb_image(tmp_path, ref):
     """Every legal PNG colour type / bit depth, plain and Adam7-interlaced, all five scan-line filters, stored / fixed / dynamic
     deflate blocks and split IDAT chunks: the oracle restatement and the product's own inflate + unfilter equal stbi_loadf's
     floats under both flip settings."""
@@ -198,11 +209,8 @@ def test_png_decoder_against_stb_image(tmp_path):
         scene_io.write_png(p, smp, ct, dp, palette=pal, interlace=il, level=(0, 1, 9)[i % 3] if not big else 9,
                            idat_split=37 if i % 2 else 0, filters=None if i % 4 else int(rng.integers(0, 5)))
         for flip in (0, 1):
-            ww, hh = C.c_int(), C.c_int()
-            buf = np.zeros(h * w * 3, np.float32)
-            assert RL.ref_image_load(p.encode(), flip, C.byref(ww), C.byref(hh), buf.ctypes.data, buf.size) == 0
-            ref = buf.reshape(h, w, 3)
-            assert bits_equal(sf.load_png(p, bool(flip)), ref), (ct, dp, il, flip)
+            dec = sf.load_png(p, bool(flip))
+            ref.same((dec,), lambda: _ref_image(p, flip, h, w)[2:])
             scene = tmp_path / "s.txt"
             if flip:
                 scene.write_text(f"Material m\nType Lambertian\nBaseColor {p}\nMetallic 0\nRoughness 1\nIor 1.5\nNormalMap Null\n\n"
@@ -210,11 +218,10 @@ def test_png_decoder_against_stb_image(tmp_path):
             else:
                 scene.write_text(f"Object o\n{obj}\nMaterial Null\nScale 1 1 1\n\n" + cam + f"EnvMap {p}\n")
             a = capi.SceneFile(str(scene))
-            assert len(a.textures) == 1 and bits_equal(a.textures[0], ref), (ct, dp, il, flip)
+            assert len(a.textures) == 1 and bits_equal(a.textures[0], dec), (ct, dp, il, flip)
 
 
-@needs_ref
-def test_polygon_triangulation_fuzz_against_tinyobj(tmp_path):
+def test_polygon_triangulation_fuzz_against_tinyobj(tmp_path, ref):
     """Polygons with 5..11 corners -- convex, star-shaped, self-intersecting, tilted out of every coordinate plane, with repeated
     corners -- are ear-clipped into the triangles tinyobjloader makes of them, by the oracle restatement and by the product."""
     rng = np.random.default_rng(3)
@@ -239,33 +246,31 @@ def test_polygon_triangulation_fuzz_against_tinyobj(tmp_path):
             nv += n
         p = tmp_path / "poly.obj"
         p.write_text("\n".join(lines + faces) + "\n")
-        cap = 4096
-        v = np.zeros((cap, 3), np.float32); nn = np.zeros((cap, 3), np.float32); t = np.zeros((cap, 2), np.float32)
-        cnt = RL.ref_obj_load(str(p).encode(), cap, v.ctypes.data, nn.ctypes.data, t.ctypes.data)
         mv, mn, mt = sf.load_obj(str(p))
-        assert cnt == len(mv) and bits_equal(v[:cnt], mv), it
-        if cnt:
+        ref.same((np.int64(len(mv)), mv), lambda: _ref_obj(p, 4096)[:2])
+        if len(mv):
             scene = tmp_path / "poly.txt"
             scene.write_text(f"Object o\n{p}\nMaterial Null\nScale 1 1 1\n\n" + _CAMERA)
             a = capi.SceneFile(str(scene))
-            bv, _ = ob.bake_instance((0, 0, 0), (0, 0, 0), (1, 1, 1), v[:cnt], nn[:cnt])
+            bv, _ = ob.bake_instance((0, 0, 0), (0, 0, 0), (1, 1, 1), mv, mn)
             assert bits_equal(a.vertices.reshape(-1, 3), bv), it
 
 
-@needs_ref
-def test_baking_fuzz_against_glm():
+def test_baking_fuzz_against_glm(ref):
     rng = np.random.default_rng(8)
     for i in range(400):
         t = rng.uniform(-50, 50, 3).astype(np.float32)
         r = rng.uniform(-720, 720, 3).astype(np.float32)
         s = (np.exp(rng.uniform(-4, 4, 3)) * rng.choice([-1.0, 1.0], 3)).astype(np.float32)
         verts = rng.uniform(-10, 10, (16, 3)).astype(np.float32); nrm = rng.normal(size=(16, 3)).astype(np.float32)
-        m = np.zeros(16, np.float32); vo = np.zeros(48, np.float32); no = np.zeros(48, np.float32)
-        RS.ref_build_transformation_matrix(t, r, s, m)
-        RS.ref_bake_instance(t, r, s, 16, verts.reshape(-1), nrm.reshape(-1), vo, no)
-        assert bits_equal(ob.build_transformation_matrix(t, r, s).reshape(-1), m)
+
+        def ref_bake():
+            m = np.zeros(16, np.float32); vo = np.zeros(48, np.float32); no = np.zeros(48, np.float32)
+            RS.ref_build_transformation_matrix(t, r, s, m)
+            RS.ref_bake_instance(t, r, s, 16, verts.reshape(-1), nrm.reshape(-1), vo, no)
+            return m, vo, no
         v, n = ob.bake_instance(t, r, s, verts, nrm)
-        assert bits_equal(v.reshape(-1), vo) and bits_equal(n.reshape(-1), no)
+        ref.same((ob.build_transformation_matrix(t, r, s).reshape(-1), v.reshape(-1), n.reshape(-1)), ref_bake)
 
 
 # ---- product (host code of librestir_hip.so) vs oracle and fixture ----------------------------------------------------
@@ -375,8 +380,7 @@ def test_product_bmp_decoder_matches_stb_image_fixture(g, tmp_path):
         assert bits_equal(_decode_through_scene(tmp_path, p, False), g["pnm_noflip_" + key]), key
 
 
-@needs_ref
-def test_jpeg_decoder_fuzz_against_stb_image(tmp_path):
+def test_jpeg_decoder_fuzz_against_stb_image(tmp_path, ref):
     Image = pytest.importorskip("PIL.Image")
     rng = np.random.default_rng(9)
     n = 0
@@ -402,10 +406,7 @@ def test_jpeg_decoder_fuzz_against_stb_image(tmp_path):
         p = str(tmp_path / f"f{i}.jpg")
         (Image.fromarray(pic[..., 0]) if grey else Image.fromarray(pic)).save(p, "JPEG", **opt)
         for flip in (0, 1):
-            ww, hh = C.c_int(), C.c_int()
-            buf = np.zeros(h * w * 3, np.float32)
-            assert RL.ref_image_load(p.encode(), flip, C.byref(ww), C.byref(hh), buf.ctypes.data, buf.size) == 0
-            assert bits_equal(_decode_through_scene(tmp_path, p, bool(flip)), buf.reshape(h, w, 3)), (i, opt, flip)
+            ref.same((_decode_through_scene(tmp_path, p, bool(flip)),), lambda: _ref_image(p, flip, h, w)[2:])
             n += 1
     assert n == 180
 

@@ -7,7 +7,7 @@ mkdir -p $OUT
 for kv in "$@"; do export "$kv"; done
 cd /tmp && export TMPDIR=/tmp
 export RS_SIDE_STREAM=0
-CMD=${PMC_CMD:-"python $R/bench.py --steps 6 --warmup 2 --cpu-frames 0"}      # PMC_CMD="python $R/tools/bench_denoisers.py eaw": another workload
+CMD=${PMC_CMD:-"python $R/bench.py --full --steps 6 --warmup 2 --cpu-frames 0"}      # PMC_CMD="python $R/tools/bench_denoisers.py eaw": another workload
 i=0
 for set in "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum TCP_PENDING_STALL_CYCLES_sum" \
            "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_READ_sum" \

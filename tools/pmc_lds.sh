@@ -6,7 +6,7 @@ OUT=$R/gpurun_out/pmclds_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export RS_SIDE_STREAM=0
-CMD="python $R/bench.py --steps 6 --warmup 2 --cpu-frames 0"
+CMD="python $R/bench.py --full --steps 6 --warmup 2 --cpu-frames 0"
 i=0
 for set in "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS" "SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM"; do
   i=$((i+1))

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $R/bench.py --config $CONFIG --steps 20 --warmup 3 --cpu-frames 0 --sustained-frames 200"
+CMD="python $R/bench.py --full --config $CONFIG --steps 20 --warmup 3 --cpu-frames 0 --sustained-frames 200"
 # per-kernel durations with every kernel on one stream (what bench.py's roofline / pass_ms section measures: kernels that
 # share the CUs with another frame's kernels last longer without doing more work) ...
 RS_SIDE_STREAM=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $CMD > $OUT/trace.log 2>&1
