@@ -255,6 +255,19 @@ int  rs_scene_host_desc(const rs_scene* scene, rs_scene_desc* desc);
  * (src/sampler.h:38-49) again.  In Sobol mode `looper` must stay in [0, numSamples): the caller wraps it as the reference does,
  * State::looper = (State::looper + 1) % SobolSampleNum (src/restir.cu:441-445; restir_compat.h does).  The table is copied. */
 int  rs_scene_set_sample_sequence(rs_scene* scene, const uint32_t* data, int numSamples, int numDims);
+/* Emission (baseColor) of Light-type materials.  Host arrays: count material ids, 3 floats each.  Enqueued on the
+ * library stream; does not synchronize the device.  The light table and alias table are rebuilt as rs_scene_build does
+ * (the environment map's entry keeps its power), so that the scene equals one built afresh from the edited materials:
+ * rs_scene_host_desc returns the new materials, lightUnitRadiance, lightProb, lightFailId and sumLightPower.  On the
+ * device the tables go to the next of a small ring of versions: launches enqueued before the call (frames in flight,
+ * a G-buffer render recorded but not launched yet) read the old emission, launches after it the new one -- G-buffer
+ * albedo, RIS, pathTraceDirect, pathTrace*, ReSTIRIndirect.  The host waits only when the ring runs out, i.e. when a
+ * launch that read the version eight edits back has not finished.  Refused with RS_ERR_INVALID_ARGUMENT, the scene
+ * unchanged: count < 0, an id out of range or of a material that is not a Light, a negative, NaN or infinite
+ * radiance, an edit that leaves the light sampler without a positive total power; with RS_ERR_UNSUPPORTED while the
+ * library stream is being captured into a graph (captured frames keep the emission they were captured with).
+ * Textured emission, the environment map and the emitters' geometry are not edited. */
+int  rs_scene_set_emission(rs_scene* scene, int count, const int* materialIds, const float* radiance);
 /* Scene::clear / DevScene::destroy (src/scene.cpp:217-220,511-532). */
 int  rs_scene_destroy(rs_scene* scene);
 
@@ -379,6 +392,20 @@ int  rs_restir_rows_unpack(rs_restir* r, int which, int y0, int rows, const void
  * written), 2 = devDirectTemp. */
 int  rs_restir_download(const rs_restir* r, int which, rs_reservoir* host);
 int  rs_restir_upload(rs_restir* r, int which, const rs_reservoir* host);
+/* Temporal re-evaluation under changed emission (rs_scene_set_emission).  Default 0: the reference's merge, which reuses
+ * last frame's sample with the Li and weight it was drawn with (src/restir.cu:180-185) -- a light just switched off can
+ * keep winning the merge for many frames.  1: the RIS passes record the light-sampler index of their winner, the
+ * reservoirs carry it, and the temporal merge rescales the reused sample to the current emission first,
+ * W *= luminance(Le_now) / luminance(Li) and Li = Le_now (not for the environment map's entry, an unknown light or
+ * W = 0); so is the published copy the spatial pass gathers from where a pixel shaded nothing this frame and keeps an
+ * older reservoir.  With no edit the results are bit-identical to 0.  Switching on starts every reservoir's light as
+ * unknown.
+ * Costs 16 B/px of memory traffic per frame (RIS writes 4, the temporal merge reads 8 and writes 4).  A tracked rs_restir is refused by
+ * rs_strips_frame / rs_strips_exchange_history with RS_ERR_UNSUPPORTED. */
+int  rs_restir_set_light_tracking(rs_restir* r, int enable);
+/* The light-sampler index of every reservoir's sample, width x height ints; which as rs_restir_download.  -1 = none
+ * or unknown (all -1 while tracking is off).  Waits for the library stream. */
+int  rs_restir_download_light_ids(const rs_restir* r, int which, int* host);
 /* BVH walks (intersect + testOcclusion calls) performed by the last rs_restir_direct / phase_a,
  * for the Mrays/s metric. Synchronises. */
 int  rs_restir_ray_count(rs_restir* r, unsigned long long* rays);

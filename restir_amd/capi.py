@@ -110,11 +110,11 @@ class GBufferView(C.Structure):
 EXPORTS = [
     "rs_last_error", "rs_context_create", "rs_context_destroy", "rs_context_set_current", "rs_init", "rs_set_stream", "rs_set_sync", "rs_set_side_stream", "rs_set_ris_table_pixels", "rs_set_internal_stream_priority", "rs_internal_streams_info", "rs_choose_internal_streams_again", "rs_prepare_streams", "rs_set_stream_plan", "rs_set_denoise_stream", "rs_join_denoise_stream", "rs_set_tile_split", "rs_synchronize",
     "rs_build_bvh", "rs_build_light_table", "rs_build_alias_table", "rs_build_envmap_pdf", "rs_scene_build", "rs_scene_build_textured", "rs_scene_create",
-    "rs_scene_host_desc", "rs_scene_set_sample_sequence", "rs_scene_destroy", "rs_camera_update", "rs_trace_closest", "rs_trace_closest_wave", "rs_scene_set_ordered_tree", "rs_ordered_bvh_host_check", "rs_trace_occlusion",
+    "rs_scene_host_desc", "rs_scene_set_sample_sequence", "rs_scene_set_emission", "rs_scene_destroy", "rs_camera_update", "rs_trace_closest", "rs_trace_closest_wave", "rs_scene_set_ordered_tree", "rs_ordered_bvh_host_check", "rs_trace_occlusion",
     "rs_gbuffer_create", "rs_gbuffer_destroy", "rs_gbuffer_render", "rs_gbuffer_render_rows", "rs_gbuffer_update",
     "rs_gbuffer_get_view", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
-    "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
+    "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
     "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
     "rs_path_trace", "rs_path_trace_indirect", "rs_restir_indirect", "rs_restir_download_indirect",
     "rs_svgf_create", "rs_svgf_destroy", "rs_svgf_filter", "rs_svgf_next_frame", "rs_svgf_get_view",
@@ -166,6 +166,9 @@ def lib():
     L.rs_bake_instance.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp]
     L.rs_scene_host_desc.argtypes = [vp, C.POINTER(SceneDesc)]
     L.rs_scene_destroy.argtypes = [vp]
+    L.rs_scene_set_emission.argtypes = [vp, ci, vp, vp]
+    L.rs_restir_set_light_tracking.argtypes = [vp, ci]
+    L.rs_restir_download_light_ids.argtypes = [vp, ci, vp]
     L.rs_camera_update.argtypes = [C.POINTER(Camera)]
     L.rs_trace_closest.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.rs_trace_occlusion.argtypes = [vp, ci, vp, vp]
@@ -575,6 +578,15 @@ class Scene:
         t = np.ascontiguousarray(table, np.uint32)
         check(lib().rs_scene_set_sample_sequence(self.handle, _p(t), t.shape[0], t.shape[1]))
 
+    def set_emission(self, material_ids, radiance):
+        """rs_scene_set_emission: baseColor of the Light materials `material_ids` := rows of `radiance` ((n, 3) float32), ordered on
+        the library stream after the frames enqueued so far (no synchronisation)."""
+        ids = np.ascontiguousarray(material_ids, np.int32).reshape(-1)
+        rad = np.ascontiguousarray(radiance, np.float32).reshape(-1, 3)
+        if rad.shape[0] != ids.size:
+            raise ValueError("set_emission: one radiance row per material id")
+        check(lib().rs_scene_set_emission(self.handle, int(ids.size), _p(ids), _p(rad)))
+
     def host_desc(self):
         """numpy views of the arrays the scene was built from (for parity checks of the host build)."""
         d = SceneDesc()
@@ -797,6 +809,16 @@ class ReSTIR:
     def upload(self, which, arr):
         arr = np.ascontiguousarray(arr, RESERVOIR_DTYPE)
         check(lib().rs_restir_upload(self.handle, which, _p(arr)))
+
+    def set_light_tracking(self, on=True):
+        """rs_restir_set_light_tracking: re-evaluate the temporal candidate under the scene's current emission (off by default)."""
+        check(lib().rs_restir_set_light_tracking(self.handle, 1 if on else 0))
+
+    def download_light_ids(self, which):
+        """Light-sampler index of every reservoir's sample (which: 0 or 1 as download); -1 = none / unknown."""
+        out = np.zeros(self.width * self.height, np.int32)
+        check(lib().rs_restir_download_light_ids(self.handle, which, _p(out)))
+        return out
 
     def ray_count(self):
         n = C.c_ulonglong(0)

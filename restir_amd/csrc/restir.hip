@@ -207,8 +207,9 @@ constexpr int kRisThreads = RS_RIS_THREADS;
 constexpr int kRisLdsLights = 1024;
 constexpr int kRisAliasLdsLights = 16384;        // alias records only: 128 KB of the CU's 160 KB at most
 
-template <bool ENV, bool SOBOL, typename AliasPtr, typename LightPtr>
-__device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& sp, AliasPtr alias, LightPtr lights, int index, int looper) {
+// TRACK (rs_restir_set_light_tracking): the winner's light-sampler index goes to candId as well (-1: no winner)
+template <bool ENV, bool SOBOL, bool TRACK, typename AliasPtr, typename LightPtr>
+__device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& sp, AliasPtr alias, LightPtr lights, int index, int looper, int* candId) {
     RS_SETPRIO(RS_PRIO_RIS);
     const float4 pm = sp.posMat[index];
     const int mk = __float_as_int(pm.w);
@@ -249,7 +250,7 @@ __device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& s
         float u = rng.uniform();
         wsum += weight;                                    // Reservoir::update (restir.h:38-44)
         if (u * wsum < weight) {
-            if (ENV) { selLi = c.Li; selWi = c.wi; selDist = c.dist; }
+            if (ENV) { selLi = c.Li; selWi = c.wi; selDist = c.dist; if (TRACK) selId = c.id; }
             else { selId = c.id; selU = c.bu; selV = c.bv; }
         }
     }
@@ -257,18 +258,28 @@ __device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& s
     sp.candLi[index] = make_float4(selLi.x, selLi.y, selLi.z, selDist);
     sp.candWi[index] = make_float4(selWi.x, selWi.y, selWi.z, wsum);
     reinterpret_cast<unsigned*>(sp.rngMat + index)[0] = rng.word();
+    if (TRACK) candId[index] = selId;
 }
 
-template <bool ENV, bool SOBOL>
-__global__ void __launch_bounds__(256) k_ris(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper) {
+template <bool ENV, bool SOBOL, bool TRACK>
+__device__ __forceinline__ void ris_rows(const DevScene& s, const SurfPlanes& sp, int width, int y0, int y1, int looper, int* candId) {
     const int n0 = y0 * width, n1 = y1 * width;
     const int index = n0 + blockIdx.x * blockDim.x + threadIdx.x;
     if (index >= n1) return;
-    ris_pixel<ENV, SOBOL, const AliasRec*, const LightRec*>(s, sp, s.alias, s.lights, index, looper);
+    ris_pixel<ENV, SOBOL, TRACK, const AliasRec*, const LightRec*>(s, sp, s.alias, s.lights, index, looper, candId);
 }
 
-template <bool SOBOL>
-__global__ void __launch_bounds__(kRisThreads) k_ris_lds(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper) {
+template <bool ENV, bool SOBOL>
+__global__ void __launch_bounds__(256) k_ris(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
+    ris_rows<ENV, SOBOL, false>(s, sp, width, y0, y1, looper, candId);
+}
+template <bool ENV, bool SOBOL>
+__global__ void __launch_bounds__(256) k_ris_tracked(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
+    ris_rows<ENV, SOBOL, true>(s, sp, width, y0, y1, looper, candId);
+}
+
+template <bool SOBOL, bool TRACK>
+__global__ void __launch_bounds__(kRisThreads) k_ris_lds(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
     // The copy is laid out by quarter: the lanes of a wave read the same quarter of 64 random records, and in record order those
     // 16 bytes lie in 2 of the 8 four-bank groups whatever the light (a 4-fold bank conflict; SQ_LDS_BANK_CONFLICT was 80 % of the
     // LDS cycles); by quarter, light i's lies in group i mod 8.
@@ -283,21 +294,21 @@ __global__ void __launch_bounds__(kRisThreads) k_ris_lds(DevScene s, SurfPlanes 
     const int n0 = y0 * width, n1 = y1 * width;
     const int index = n0 + blockIdx.x * kRisThreads + threadIdx.x;
     if (index >= n1) return;
-    ris_pixel<false, SOBOL, const AliasRec*, LightQuarters<kRisLdsLights>>(s, sp, sAlias, LightQuarters<kRisLdsLights>{ sQuarters }, index, looper);
+    ris_pixel<false, SOBOL, TRACK, const AliasRec*, LightQuarters<kRisLdsLights>>(s, sp, sAlias, LightQuarters<kRisLdsLights>{ sQuarters }, index, looper, candId);
 }
 
 // More lights than the LDS copy of the whole table holds (config 5: 10 240): the alias records alone (8 B per light) still fit -- one
 // LDS read and four 16-byte gathers of the light record per candidate instead of five gathers; the light records stay in L2.
 // Dynamic LDS: numLights * 8 bytes.
-template <bool SOBOL>
-__global__ void __launch_bounds__(kRisThreads) k_ris_alias_lds(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper) {
+template <bool SOBOL, bool TRACK>
+__global__ void __launch_bounds__(kRisThreads) k_ris_alias_lds(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
     extern __shared__ AliasRec sAliasDyn[];
     for (int i = threadIdx.x; i < s.numLights; i += kRisThreads) sAliasDyn[i] = s.alias[i];
     __syncthreads();
     const int n0 = y0 * width, n1 = y1 * width;
     const int index = n0 + blockIdx.x * kRisThreads + threadIdx.x;
     if (index >= n1) return;
-    ris_pixel<false, SOBOL, const AliasRec*, const LightRec*>(s, sp, sAliasDyn, s.lights, index, looper);
+    ris_pixel<false, SOBOL, TRACK, const AliasRec*, const LightRec*>(s, sp, sAliasDyn, s.lights, index, looper, candId);
 }
 
 // ---- phase A.3: shadow ray, temporal merge, publish -------------------------------------------------
@@ -352,9 +363,22 @@ __global__ void __launch_bounds__(256, RS_WALK_WAVES) k_shadow(DevScene s, SurfP
 // were built and measured in round 4: bit-exact and THREE TIMES slower, 0.475 -> 1.38 ms.  The 64 rays of an 8x8 tile start next to each
 // other and walk in lockstep through the same cache lines; replacement desynchronises them, and what the wave then fetches per step is 64
 // different lines.  EXPERIMENTS.md, commit 5febf79, profiles/r04_ab_shadow_streaming_replacement.log.)
-template <bool SOBOL>
+// Light tracking (rs_restir_set_light_tracking): the light-sampler index of the RIS winners (cand), of the reservoirs the merge reads
+// (last) and of those it publishes (cur), and the light records of the scene's current emission
+struct LightIds {
+    const int* cand; const int* last; int* cur;
+    int* temp;                       // of the published copy the spatial pass gathers from (TempPlanes)
+    const LightRec* lights;
+    int numLights, envId;            // envId: the environment map's sampler entry, -1 = none
+};
+
+// TRACK: the temporal candidate is re-evaluated under the current emission before the merge -- its target toScalar(Li * BSDF * cos) scales
+// with luminance(Li) (the DI path evaluates the BSDF with baseColor 1, restir.cu:141), so W takes the ratio of the luminances and Li the
+// light's current radiance.  Not for an unknown light (-1), the environment map's entry or W = 0.  The published copy of a pixel that shades
+// nothing this frame keeps an older frame's reservoir (Q1) and is still a spatial tap: it is re-evaluated in place the same way.
+template <bool SOBOL, bool TRACK>
 __global__ void __launch_bounds__(256) k_temporal(SurfPlanes sp, GBufView g, ResvPlanes last, ResvPlanes cur, TempPlanes temp, const uint32_t* sampleSeq, int looper,
-                                                  int first, int reuse, int n0, int n1, unsigned long long* rayWork, unsigned long long* rayDone) {
+                                                  int first, int reuse, int n0, int n1, unsigned long long* rayWork, unsigned long long* rayDone, LightIds ids) {
     RS_SETPRIO(RS_PRIO_STREAM);
     // this call's BVH-walk counters are complete (the launch is ordered after the chain that counted): publish them and leave the
     // working slot zero for its next user, so that the chain itself needs no clearing launch
@@ -372,13 +396,31 @@ __global__ void __launch_bounds__(256) k_temporal(SurfPlanes sp, GBufView g, Res
     if (!shaded) {
         // early-exit pixels publish no reservoir (Q1: their slot keeps its stale value); only the
         // G-buffer half of the tap record is refreshed
-        if (reuse & 2) reinterpret_cast<float2*>(temp.tap + index)[1] = make_float2(__int_as_float(gid), gdepth);
+        if (reuse & 2) {
+            reinterpret_cast<float2*>(temp.tap + index)[1] = make_float2(__int_as_float(gid), gdepth);
+            if (TRACK) {
+                const int sid = ids.temp[index];
+                if (sid >= 0 && sid < ids.numLights && sid != ids.envId) {
+                    float* tw = reinterpret_cast<float*>(temp.tap + index);
+                    const float sW = *tw;
+                    const float4 li = temp.li[index];
+                    const float before = luminance(mk3(li.x, li.y, li.z));
+                    if (sW != 0.f && before > 0.f) {
+                        const float4 le = reinterpret_cast<const float4*>(ids.lights + sid)[3];
+                        const f3 Le = mk3(le.x, le.y, le.z);
+                        *tw = sW * (luminance(Le) / before);
+                        temp.li[index] = make_float4(Le.x, Le.y, Le.z, li.w);
+                    }
+                }
+            }
+        }
         return;
     }
     const float4 cl = ld_stream(sp.candLi + index), cw = ld_stream(sp.candWi + index);
     Resv r;
     r.Li = mk3(cl.x, cl.y, cl.z); r.wi = mk3(cw.x, cw.y, cw.z); r.dist = cl.w;
     r.M = kReservoirSize; r.W = cw.w;                             // 0 if the shadow ray was blocked (k_shadow)
+    int id = TRACK ? ld_stream(ids.cand + index) : -1;
 
     if (!first && (reuse & 1)) {                                  // findTemporalNeighbor, restir.cu:20-45
         const int primId = gid;
@@ -394,10 +436,20 @@ __global__ void __launch_bounds__(256) k_temporal(SurfPlanes sp, GBufView g, Res
         }
         Resv t;
         t.Li = splat(0.f); t.wi = splat(0.f); t.dist = 0.f; t.M = 0; t.W = 0.f;
+        int tid = -1;
         if (!diff) {
             const float4 a = ld_stream(last.li + lastIdx), b = ld_stream(last.wi + lastIdx);
             t.Li = mk3(a.x, a.y, a.z); t.dist = a.w; t.wi = mk3(b.x, b.y, b.z);
             t.W = ld_stream(last.w + lastIdx); t.M = ld_stream(last.m + lastIdx);
+            if (TRACK) {
+                tid = ld_stream(ids.last + lastIdx);
+                if (tid >= 0 && tid < ids.numLights && tid != ids.envId && t.W != 0.f) {
+                    const float4 le = reinterpret_cast<const float4*>(ids.lights + tid)[3];      // { Le.xyz, pdf constant }
+                    const f3 Le = mk3(le.x, le.y, le.z);
+                    const float before = luminance(t.Li);
+                    if (before > 0.f) { t.W *= luminance(Le) / before; t.Li = Le; }
+                }
+            }
         }
         if (!resv_invalid(t.W)) {
             SamplerT<SOBOL> rng = SamplerT<SOBOL>::resume(sampleSeq, rm.x, looper, kDrawsRis);
@@ -411,12 +463,14 @@ __global__ void __launch_bounds__(256) k_temporal(SurfPlanes sp, GBufView g, Res
             }
             r.W += t.W;
             r.M += t.M;
-            if (u * r.W < t.W) { r.Li = t.Li; r.wi = t.wi; r.dist = t.dist; }
+            if (u * r.W < t.W) { r.Li = t.Li; r.wi = t.wi; r.dist = t.dist; if (TRACK) id = tid; }
         }
     }
     // checkValidity (restir.h:55-59); the temp copy and the stored copy are the same value
-    if (resv_invalid(r.W)) { r.W = 0.f; r.M = 0; }
+    if (resv_invalid(r.W)) { r.W = 0.f; r.M = 0; if (TRACK) id = -1; }
+    if (TRACK) __builtin_nontemporal_store(id, ids.cur + index);
     if (reuse & 2) {
+        if (TRACK) ids.temp[index] = id;
         temp.li[index] = make_float4(r.Li.x, r.Li.y, r.Li.z, r.dist);
         temp.wi[index] = make_float4(r.wi.x, r.wi.y, r.wi.z, 0.f);
         temp.tap[index] = make_float4(r.W, __int_as_float(r.M), __int_as_float(gid), gdepth);
@@ -782,6 +836,8 @@ int rs_restir_free(rs_restir* r) {
     rs_dev_free(r->dRayCount);
     for (auto& perStream : r->split) for (auto& t : perStream) rs_tile_split_free(&t);
     rs_dev_free(r->indResv[0]); rs_dev_free(r->indResv[1]);
+    rs_dev_free(r->idCur); rs_dev_free(r->idLast); rs_dev_free(r->idTemp);
+    for (int*& p : r->candId) rs_dev_free(p);
     for (auto& e : r->ev) if (e) (void)hipEventDestroy(e);
     for (auto& pair : r->spatialEv) for (hipEvent_t& e : pair) if (e) (void)hipEventDestroy(e);
     for (auto& e : r->surfFree) if (e) (void)hipEventDestroy(e);
@@ -859,6 +915,39 @@ int rs_restir_set_probe(rs_restir* r, int enable) {
     return 0;
 }
 
+// Light tracking (include/restir_hip.h): the id planes are allocated on the first switch-on; the reservoirs published while tracking was
+// off carry no light index, so every switch-on starts from "unknown" (-1) -- ordered on the library stream like the frames around it.
+int rs_restir_set_light_tracking(rs_restir* r, int enable) {
+    RS_SCOPE(r);
+    if (!r) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_set_light_tracking: null");
+    const bool on = enable != 0;
+    if (on == r->track) return 0;
+    if (on) {
+        const size_t n = (size_t)r->width * r->height;
+        if (!r->idCur) {
+            RS_TRY(rs_dev_alloc(&r->idCur, n)); RS_TRY(rs_dev_alloc(&r->idLast, n)); RS_TRY(rs_dev_alloc(&r->idTemp, n));
+            for (int*& p : r->candId) RS_TRY(rs_dev_alloc(&p, n));
+        }
+        RS_HIP(hipMemsetAsync(r->idCur, 0xff, n * sizeof(int), rs_stream()));
+        RS_HIP(hipMemsetAsync(r->idLast, 0xff, n * sizeof(int), rs_stream()));
+        RS_HIP(hipMemsetAsync(r->idTemp, 0xff, n * sizeof(int), rs_stream()));
+        r->trackSceneId = 0;             // (the RIS winners' planes need no clearing: a frame writes its set before it reads it)
+    }
+    r->track = on;
+    return rs_after_launch("rs_restir_set_light_tracking");
+}
+
+int rs_restir_download_light_ids(const rs_restir* rc, int which, int* host) {
+    RS_SCOPE(rc);
+    rs_restir* r = const_cast<rs_restir*>(rc);
+    if (!r || !host || which < 0 || which > 2) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_download_light_ids: bad argument");
+    const size_t n = (size_t)r->width * r->height;
+    if (!r->track || !r->idCur) { for (size_t i = 0; i < n; i++) host[i] = -1; return 0; }
+    RS_HIP(hipStreamSynchronize(rs_stream()));
+    RS_HIP(hipMemcpy(host, which == 0 ? r->idCur : which == 1 ? r->idLast : r->idTemp, n * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // rs_restir_enable_timing(r, 2): the durations (ms) of the spatial pass in the last frames, oldest first, at most `capacity` and at most the
 // ring's 256; *count = how many.  Waits for the library stream.
 int rs_restir_spatial_times(rs_restir* r, float* ms, int capacity, int* count) {
@@ -881,7 +970,9 @@ int rs_restir_spatial_times(rs_restir* r, float* ms, int capacity, int* count) {
 
 namespace {
 // RIS over the light table for rows [y0, y1) on stream st; alone: nothing runs next to it (picks the alias-in-LDS form for large tables)
-int launch_ris(const rs_scene* scene, const SurfPlanes& sp, int W, int y0, int y1, int looper, bool sobol, hipStream_t st, bool alone) {
+// candId: the winners' light-sampler indices (light tracking), null = not tracked
+int launch_ris(const rs_scene* scene, const SurfPlanes& sp, int W, int y0, int y1, int looper, bool sobol, hipStream_t st, bool alone, int* candId) {
+    const bool track = candId != nullptr;
     const int npx = (y1 - y0) * W;
     // The LDS form runs one 1024-thread block per copy of the table: a launch of a few dozen blocks leaves most CUs idle and lasts as
     // long as one block.  Below 64 Ki pixels the table is read from global memory by 256-thread blocks, which spread evenly.  (Round 2
@@ -895,20 +986,33 @@ int launch_ris(const rs_scene* scene, const SurfPlanes& sp, int W, int y0, int y
     if (scene->numLights > 0 && scene->numLights <= kRisLdsLights && npx >= risGlobalBelow && scene->envMapTexId < 0)
         // (one block per CU instead of two -- half of the wave slots left to the latency-bound kernels of the other streams -- measured
         // slower: frame 1.088 -> 1.142 ms, profiles/r03_ab_ris_blocks_per_cu.log)
-        RS_LAUNCH1(k_ris_lds, sobol, dim3((npx + kRisThreads - 1) / kRisThreads), dim3(kRisThreads), st, scene->dev, sp, W, y0, y1, looper);
+    {
+        const dim3 grid((npx + kRisThreads - 1) / kRisThreads);
+        if (track) { if (sobol) hipLaunchKernelGGL((k_ris_lds<true, true>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, candId);
+                     else hipLaunchKernelGGL((k_ris_lds<false, true>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, candId); }
+        else { if (sobol) hipLaunchKernelGGL((k_ris_lds<true, false>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, candId);
+               else hipLaunchKernelGGL((k_ris_lds<false, false>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, candId); }
+    }
     else if (scene->envMapTexId < 0 && scene->numLights > kRisLdsLights && scene->numLights <= kRisAliasLdsLights && npx >= risGlobalBelow && alone) {
         const size_t lds = (size_t)scene->numLights * sizeof(AliasRec);
         static const bool ldsAllowed = []{      // more than 64 KB of dynamic LDS is opt-in
-            const bool a = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ris_alias_lds<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kRisAliasLdsLights * (int)sizeof(AliasRec)) == hipSuccess;
-            const bool b = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ris_alias_lds<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kRisAliasLdsLights * (int)sizeof(AliasRec)) == hipSuccess;
+            bool ok = true;
+            for (const void* k : { reinterpret_cast<const void*>(&k_ris_alias_lds<true, false>), reinterpret_cast<const void*>(&k_ris_alias_lds<false, false>),
+                                   reinterpret_cast<const void*>(&k_ris_alias_lds<true, true>), reinterpret_cast<const void*>(&k_ris_alias_lds<false, true>) })
+                ok = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kRisAliasLdsLights * (int)sizeof(AliasRec)) == hipSuccess && ok;
             (void)hipGetLastError();
-            return a && b; }();
+            return ok; }();
         (void)ldsAllowed;
-        if (sobol) hipLaunchKernelGGL(k_ris_alias_lds<true>, dim3((npx + kRisThreads - 1) / kRisThreads), dim3(kRisThreads), lds, st, scene->dev, sp, W, y0, y1, looper);
-        else hipLaunchKernelGGL(k_ris_alias_lds<false>, dim3((npx + kRisThreads - 1) / kRisThreads), dim3(kRisThreads), lds, st, scene->dev, sp, W, y0, y1, looper);
+        const dim3 grid((npx + kRisThreads - 1) / kRisThreads);
+        if (track) { if (sobol) hipLaunchKernelGGL((k_ris_alias_lds<true, true>), grid, dim3(kRisThreads), lds, st, scene->dev, sp, W, y0, y1, looper, candId);
+                     else hipLaunchKernelGGL((k_ris_alias_lds<false, true>), grid, dim3(kRisThreads), lds, st, scene->dev, sp, W, y0, y1, looper, candId); }
+        else { if (sobol) hipLaunchKernelGGL((k_ris_alias_lds<true, false>), grid, dim3(kRisThreads), lds, st, scene->dev, sp, W, y0, y1, looper, candId);
+               else hipLaunchKernelGGL((k_ris_alias_lds<false, false>), grid, dim3(kRisThreads), lds, st, scene->dev, sp, W, y0, y1, looper, candId); }
     }
-    else                               // the environment map is one more light (scene.h:400-403)
-        RS_LAUNCH2(k_ris, scene->envMapTexId >= 0, sobol, dim3((npx + 255) / 256), dim3(256), st, scene->dev, sp, W, y0, y1, looper);
+    else {                             // the environment map is one more light (scene.h:400-403)
+        if (track) RS_LAUNCH2(k_ris_tracked, scene->envMapTexId >= 0, sobol, dim3((npx + 255) / 256), dim3(256), st, scene->dev, sp, W, y0, y1, looper, candId);
+        else RS_LAUNCH2(k_ris, scene->envMapTexId >= 0, sobol, dim3((npx + 255) / 256), dim3(256), st, scene->dev, sp, W, y0, y1, looper, candId);
+    }
     return 0;
 }
 
@@ -1021,7 +1125,7 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     }
     mark(r, 1);
     const int npx = (y1 - y0) * W;
-    RS_TRY(launch_ris(scene, sp, W, y0, y1, looper, sobol, st, !aux || idle));
+    RS_TRY(launch_ris(scene, sp, W, y0, y1, looper, sobol, st, !aux || idle, r->track ? r->candId[r->surfSet] : nullptr));
     mark(r, 2);
     // The shadow rays of a launch that fills the chip several times over go to the library stream, behind the previous frame's
     // spatial pass: every stream then has slack against the frame period and three or four kernels are in flight at any time,
@@ -1038,8 +1142,26 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     }
     if (shadowMain) hipLaunchKernelGGL(k_shadow, dim3(tilesX * tilesY), dim3(256), 0, rs_stream(), scene->dev, sp, W, y0, y1, tilesX);
     RS_TRY(rs_gbuffer_join(g));                                 // first consumer of the G-buffer planes
-    RS_LAUNCH1(k_temporal, sobol, dim3((npx + 255) / 256), dim3(256), rs_stream(), sp, gbuf_view(g),
-               r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone);
+    if (r->track) {
+        // the light indices of another scene's reservoirs name other lights: unknown from here on
+        if (r->trackSceneId != scene->id) {
+            RS_HIP(hipMemsetAsync(r->idLast, 0xff, (size_t)W * r->height * sizeof(int), rs_stream()));
+            RS_HIP(hipMemsetAsync(r->idTemp, 0xff, (size_t)W * r->height * sizeof(int), rs_stream()));
+            r->trackSceneId = scene->id;
+        }
+        const LightIds ids{ r->candId[r->surfSet], r->idLast, r->idCur, r->idTemp, scene->dev.lights, scene->numLights, scene->envMapTexId >= 0 ? scene->numLights - 1 : -1 };
+        if (sobol) hipLaunchKernelGGL((k_temporal<true, true>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g),
+                                      r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, ids);
+        else hipLaunchKernelGGL((k_temporal<false, true>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g),
+                                r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, ids);
+    }
+    else {
+        const LightIds none{ nullptr, nullptr, nullptr, nullptr, nullptr, 0, -1 };
+        if (sobol) hipLaunchKernelGGL((k_temporal<true, false>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g),
+                                      r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, none);
+        else hipLaunchKernelGGL((k_temporal<false, false>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g),
+                                r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, none);
+    }
     mark(r, 3);
     return last ? rs_after_launch("ReSTIR Direct (phase A)") : rs_check_hip(hipGetLastError(), "ReSTIR Direct (phase A)");
 }
@@ -1106,6 +1228,7 @@ int rs_restir_end_frame(rs_restir* r) {
     RS_SCOPE(r);
     if (!r) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_end_frame: null");
     ResvPlanes t = r->cur; r->cur = r->last; r->last = t;       // std::swap(devDirectReservoir, devLastDirectReservoir)
+    int* ti = r->idCur; r->idCur = r->idLast; r->idLast = ti;   // (light tracking: the reservoirs' light indices travel with them)
     r->firstFrame = false;
     // every reader of this frame's surface planes has been enqueued: the set is free for the frame after the next one
     if (!rs_sync_enabled()) { RS_HIP(hipEventRecord(r->surfFree[r->surfSet], rs_stream())); r->surfFreeValid[r->surfSet] = true; }
@@ -1261,7 +1384,9 @@ int rs_restir_upload(rs_restir* r, int which, const rs_reservoir* host) {
         RS_HIP(hipMemcpy(p->wi, wi.data(), n * 16, hipMemcpyHostToDevice));
         RS_HIP(hipMemcpy(p->w, w.data(), n * 4, hipMemcpyHostToDevice));
         RS_HIP(hipMemcpy(p->m, m.data(), n * 4, hipMemcpyHostToDevice));
+        if (r->track) RS_HIP(hipMemset(which == 0 ? r->idCur : r->idLast, 0xff, n * sizeof(int)));     // uploaded samples: light unknown
     }
+    if (which == 2 && r->track) RS_HIP(hipMemset(r->idTemp, 0xff, n * sizeof(int)));
     return 0;
 }
 

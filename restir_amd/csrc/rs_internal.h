@@ -212,6 +212,27 @@ struct rs_scene {
     float sumLightPower = 0.f;
     int numPrims = 0, bvhSize = 0, numLights = 0;
     unsigned long long id = 0;       // unique per rs_scene_create (a freed scene's address can come back; its id cannot)
+    // Emission edits (rs_scene_set_emission): a ring of versions of { materials, light records, alias table }.  Kernels capture
+    // `dev` by value at launch, so a version is never written while a launch that captured it may still run: an edit fills the
+    // next slot (ordered before every later launch by an event) and points `dev` at it, and a slot is filled again only after the events recorded when the
+    // scene moved off it -- on the library stream and on every auxiliary stream -- have completed.  Version 0 is the arrays above.
+    static constexpr int kVersions = 8;
+    static constexpr int kVersionStreams = 1 + rs_context::kAux;
+    struct Version {
+        rs_material* materials = nullptr;
+        rs::LightRec* lights = nullptr;
+        rs::AliasRec* alias = nullptr;
+        char* staging = nullptr;                 // pinned host copy the slot is filled from
+        hipEvent_t retired[kVersionStreams] = {};
+        bool retiredValid[kVersionStreams] = {};
+    } ver[kVersions];
+    int verCur = 0;
+    bool verReady = false;                       // slots 1.. and the staging buffers allocated
+    hipEvent_t verFilled = nullptr;              // the last fill: the library stream and the auxiliary streams wait for it
+    hipStream_t verStream = nullptr;             // the fills' own stream (a free slot waits for no frame in flight)
+    std::vector<float> hLightArea;               // per light primitive, Math::triangleArea (filled on the first edit)
+    float envPower = 0.f;                        // the environment map's sampler entry (its pdf's sum)
+    bool envPowerKnown = false;
 };
 
 // ---- G-buffer (src/gbuffer.h:41-58) ------------------------------------------------------------
@@ -432,6 +453,14 @@ struct rs_restir {
     hipEvent_t spatialEv[kSpatialRing][2] = {};     // timing 2: the spatial pass of the last frames between two events each (rs_restir_spatial_times)
     int spatialNext = 0;
     bool probe = false;              // the spatial pass goes out as k_spatial_shade_probe (rs_restir_set_probe)
+    // rs_restir_set_light_tracking: the light-sampler index of every reservoir's sample, carried with cur / last (swapped with them),
+    // and of every RIS winner (one plane per surface set).  Allocated when tracking is switched on; -1 = not known.
+    bool track = false;
+    int* idCur = nullptr;
+    int* idLast = nullptr;
+    int* idTemp = nullptr;           // of the published copy (TempPlanes) the spatial pass gathers from
+    int* candId[kSurfSets] = {};
+    unsigned long long trackSceneId = 0;   // the scene whose light indices idLast holds (rs_scene::id; 0 = none yet)
 };
 
 static_assert(rs_context::kAux >= 1 + rs_restir::kChains, "one auxiliary stream for GBuffer::render and one per chain");

@@ -239,6 +239,88 @@ int build_ordered_side(rs_scene* s) {
     return 0;
 }
 
+// The light records and alias records of the scene's host arrays (hLightPrimIds, hLightRadiance, hLightProb, hLightFailId); rs_scene_create
+// and rs_scene_set_emission fill them alike.
+void light_records(const rs_scene* s, float sumInv, LightRec* rec, AliasRec* al) {
+    const size_t nl = (size_t)s->numLights, nlp = s->hLightPrimIds.size();
+    for (size_t i = 0; i < nl; i++) {
+        al[i].prob = s->hLightProb[i];
+        al[i].failId = s->hLightFailId[i];
+        if (i >= nlp) { rec[i] = LightRec{}; continue; }          // the environment map's sampler entry has no triangle
+        const float* t = &s->hVertices[(size_t)s->hLightPrimIds[i] * 9];
+        f3 v0 = ld3(t), v1 = ld3(t + 3), v2 = ld3(t + 6);
+        f3 c = cross(v1 - v0, v2 - v0);
+        f3 nrm = normalize(c);                                          // Math::triangleNormal
+        float area = length(c) * .5f;                                   // Math::triangleArea
+        f3 Le = ld3(&s->hLightRadiance[i * 3]);
+        float power = luminance(Le) / (area * 2.f * kGlmPi);
+        rec[i] = LightRec{ v0.x, v0.y, v0.z, nrm.x, v1.x, v1.y, v1.z, nrm.y, v2.x, v2.y, v2.z, nrm.z,
+                           Le.x, Le.y, Le.z, power * sumInv };
+    }
+}
+
+// Byte offsets of one version's three tables in its staging buffer (each 64-byte aligned)
+struct VersionLayout { size_t mat, light, alias, total; };
+VersionLayout version_layout(const rs_scene* s) {
+    auto up = [](size_t b) { return (b + 63) & ~(size_t)63; };
+    VersionLayout l;
+    l.mat = 0;
+    l.light = up(s->hMaterials.size() * sizeof(rs_material));
+    l.alias = l.light + up((size_t)s->numLights * sizeof(LightRec));
+    l.total = l.alias + up((size_t)s->numLights * sizeof(AliasRec));
+    return l;
+}
+
+// First edit: slots 1.. of the version ring, every slot's staging buffer and events, the per-light areas and the environment map's power
+int versions_prepare(rs_scene* s) {
+    if (s->verReady) return 0;
+    const VersionLayout l = version_layout(s);
+    const size_t nm = s->hMaterials.size(), nl = (size_t)s->numLights;
+    s->ver[0].materials = s->dMaterials; s->ver[0].lights = s->dLights; s->ver[0].alias = s->dAlias;
+    for (int v = 0; v < rs_scene::kVersions; v++) {
+        rs_scene::Version& x = s->ver[v];
+        if (v > 0) {
+            RS_TRY(rs_dev_alloc(&x.materials, nm));
+            RS_TRY(rs_dev_alloc(&x.lights, nl));
+            RS_TRY(rs_dev_alloc(&x.alias, nl));
+        }
+        RS_HIP(hipHostMalloc((void**)&x.staging, l.total, hipHostMallocDefault));
+        for (hipEvent_t& e : x.retired) RS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    RS_HIP(hipEventCreateWithFlags(&s->verFilled, hipEventDisableTiming));
+    RS_HIP(hipStreamCreateWithFlags(&s->verStream, hipStreamNonBlocking));
+    // Math::triangleArea of every light primitive, as rs_build_light_table computes it (scene_build.cpp)
+    s->hLightArea.resize(s->hLightPrimIds.size());
+    for (size_t i = 0; i < s->hLightArea.size(); i++) {
+        const float* t = &s->hVertices[(size_t)s->hLightPrimIds[i] * 9];
+        f3 v0 = ld3(t), v1 = ld3(t + 3), v2 = ld3(t + 6);
+        s->hLightArea[i] = length(cross(v1 - v0, v2 - v0)) * .5f;
+    }
+    // the environment map's sampler entry keeps its power: the sum of its pdf, as rs_scene_build_textured passes it on (a scene made by
+    // rs_scene_create from a description does not carry it)
+    if (s->envMapTexId >= 0 && !s->envPowerKnown) {
+        const rs_texture& env = s->hTextures[(size_t)s->envMapTexId];
+        std::vector<float> pdf((size_t)env.width * env.height);
+        RS_TRY(rs_build_envmap_pdf(env.width, env.height, env.data, pdf.data()));
+        float total = 0.f;
+        for (float p : pdf) total += p;                           // rs_build_alias_table's sum, in its order
+        s->envPower = total; s->envPowerKnown = true;
+    }
+    s->verReady = true;
+    return 0;
+}
+
+void versions_free(rs_scene* s) {
+    for (int v = 0; v < rs_scene::kVersions; v++) {
+        rs_scene::Version& x = s->ver[v];
+        if (v > 0) { rs_dev_free(x.materials); rs_dev_free(x.lights); rs_dev_free(x.alias); }
+        if (x.staging) { (void)hipHostFree(x.staging); x.staging = nullptr; }
+        for (hipEvent_t& e : x.retired) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    }
+    if (s->verFilled) { (void)hipEventDestroy(s->verFilled); s->verFilled = nullptr; }
+    if (s->verStream) { (void)hipStreamDestroy(s->verStream); s->verStream = nullptr; }
+}
+
 }  // namespace
 
 extern "C" int rs_scene_destroy(rs_scene* s) {
@@ -251,6 +333,7 @@ extern "C" int rs_scene_destroy(rs_scene* s) {
     rs_dev_free(s->dMaterialIds); rs_dev_free(s->dMaterials); rs_dev_free(s->dLights); rs_dev_free(s->dAlias);
     rs_dev_free(s->dTextures); rs_dev_free(s->dEnvAlias); rs_dev_free(s->dTexcoords); rs_dev_free(s->dSampleSeq);
     for (float*& p : s->dTexData) rs_dev_free(p);
+    versions_free(s);
     delete s;
     return 0;
 }
@@ -276,6 +359,94 @@ extern "C" int rs_scene_set_sample_sequence(rs_scene* s, const uint32_t* data, i
     RS_HIP(hipMemset(s->dSampleSeq + n, 0, kSobolGuard * sizeof(uint32_t)));
     s->dev.sampleSeq = s->dSampleSeq; s->dev.sampleCount = numSamples;
     return 0;
+}
+
+// Emission of Light-type materials, stream-ordered (include/restir_hip.h).  The host tables are rebuilt as rs_scene_build_textured builds
+// them (rs_build_light_table's powers over the scene's light primitives, the environment map's entry last, rs_build_alias_table), so
+// that the scene equals, bit for bit, one built afresh from the edited materials.  The device tables go to the next slot of the version
+// ring (rs_internal.h rs_scene::Version): launches enqueued before the call keep reading the slot they captured.
+extern "C" int rs_scene_set_emission(rs_scene* s, int count, const int* materialIds, const float* radiance) {
+    RS_SCOPE(s);
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_emission: null scene");
+    if (count < 0 || (count > 0 && (!materialIds || !radiance))) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_emission: count < 0 or null arrays");
+    const int nm = (int)s->hMaterials.size();
+    for (int i = 0; i < count; i++) {
+        const int m = materialIds[i];
+        if (m < 0 || m >= nm || s->hMaterials[(size_t)m].type != 4)
+            return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_emission: a material id out of range or of a material that is not a Light");
+        for (int k = 0; k < 3; k++) {
+            const float x = radiance[(size_t)i * 3 + k];
+            if (!(x >= 0.f) || std::isinf(x)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_emission: radiance must be finite and >= 0");
+        }
+    }
+    {
+        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(rs_stream(), &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
+        if (capturing != hipStreamCaptureStatusNone) return rs_fail(RS_ERR_UNSUPPORTED, "rs_scene_set_emission: the library stream is being captured into a graph");
+    }
+    RS_TRY(versions_prepare(s));
+
+    // the new host tables (nothing of the scene changes before all of them have been built and checked)
+    std::vector<rs_material> mats = s->hMaterials;
+    for (int i = 0; i < count; i++) std::memcpy(mats[(size_t)materialIds[i]].baseColor, radiance + (size_t)i * 3, 3 * sizeof(float));
+    const size_t nl = (size_t)s->numLights, nlp = s->hLightPrimIds.size();
+    std::vector<float> rad(nlp * 3), power(nl), prob(nl);
+    std::vector<int> fail(nl);
+    for (size_t i = 0; i < nlp; i++) {
+        const f3 Le = ld3(mats[(size_t)s->hMaterialIds[(size_t)s->hLightPrimIds[i]]].baseColor);
+        st3(&rad[i * 3], Le);
+        const float perArea = luminance(Le) * 2.f * kGlmPi;            // rs_build_light_table (scene.cpp:164)
+        power[i] = perArea * s->hLightArea[i];
+    }
+    if (nlp < nl) power[nlp] = s->envPower;
+    float sumAll = 0.f;
+    if (nl) {
+        RS_TRY(rs_build_alias_table((int)nl, power.data(), prob.data(), fail.data(), &sumAll));
+        if (!(sumAll > 0.f) || std::isinf(sumAll))
+            return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_emission: the edit leaves the light sampler without a finite, positive total power");
+    }
+
+    // frames in flight: a render that has only been recorded captures `dev` when it is launched -- launch it now, with the old tables
+    RS_TRY(rs_gbuffer_release_scene(s));
+    const int next = (s->verCur + 1) % rs_scene::kVersions;
+    rs_scene::Version& nv = s->ver[next];
+    for (int k = 0; k < rs_scene::kVersionStreams; k++)          // the ring has run out only if a launch that captured the slot still runs
+        if (nv.retiredValid[k]) { RS_HIP(hipEventSynchronize(nv.retired[k])); nv.retiredValid[k] = false; }
+
+    s->hMaterials.swap(mats);
+    s->hLightRadiance.swap(rad);
+    s->hLightProb.swap(prob);
+    s->hLightFailId.swap(fail);
+    s->sumLightPower = sumAll;
+    const VersionLayout l = version_layout(s);
+    std::memcpy(nv.staging + l.mat, s->hMaterials.data(), s->hMaterials.size() * sizeof(rs_material));
+    light_records(s, 1.f / sumAll, reinterpret_cast<LightRec*>(nv.staging + l.light), reinterpret_cast<AliasRec*>(nv.staging + l.alias));
+
+    // the current slot is retired by what has been enqueued so far on the library stream and on every auxiliary stream
+    rs_context* c = rs_ctx();
+    const hipStream_t st = rs_stream();
+    rs_scene::Version& ov = s->ver[s->verCur];
+    RS_HIP(hipEventRecord(ov.retired[0], st)); ov.retiredValid[0] = true;
+    for (int i = 0; i < rs_context::kAux; i++)
+        if (c->aux[i]) { RS_HIP(hipEventRecord(ov.retired[1 + i], c->aux[i])); ov.retiredValid[1 + i] = true; }
+    // The slot is free (no launch reads it), so its fill waits for nothing: it goes to a stream of the scene's own and the library and
+    // auxiliary streams wait for that copy alone.  (Filled on the library stream, the edit would order the auxiliary streams after the
+    // frames in flight there and end the overlap of consecutive frames: config 5 with an edit per frame 1.69 -> 3.12 ms.)
+    RS_HIP(hipMemcpyAsync(nv.materials, nv.staging + l.mat, s->hMaterials.size() * sizeof(rs_material), hipMemcpyHostToDevice, s->verStream));
+    if (nl) {
+        RS_HIP(hipMemcpyAsync(nv.lights, nv.staging + l.light, nl * sizeof(LightRec), hipMemcpyHostToDevice, s->verStream));
+        RS_HIP(hipMemcpyAsync(nv.alias, nv.staging + l.alias, nl * sizeof(AliasRec), hipMemcpyHostToDevice, s->verStream));
+    }
+    RS_HIP(hipEventRecord(s->verFilled, s->verStream));
+    RS_HIP(hipStreamWaitEvent(st, s->verFilled, 0));             // launches from now on see the new tables
+    for (int i = 0; i < rs_context::kAux; i++)
+        if (c->aux[i]) RS_HIP(hipStreamWaitEvent(c->aux[i], s->verFilled, 0));
+    s->dev.materials = nv.materials;
+    s->dev.lights = nv.lights;
+    s->dev.alias = nv.alias;
+    s->dev.sumLightPowerInv = 1.f / sumAll;                              // scene.cpp:489
+    s->verCur = next;
+    return rs_after_launch("rs_scene_set_emission");
 }
 
 int rs_check_looper(const rs_scene* scene, int looper, const char* what) {
@@ -398,21 +569,7 @@ extern "C" int rs_scene_create(const rs_scene_desc* d, rs_scene** out) {
     {
         std::vector<LightRec> rec(nl);
         std::vector<AliasRec> al(nl);
-        const float sumInv = 1.f / d->sumLightPower;                       // scene.cpp:489
-        for (size_t i = 0; i < nl; i++) {
-            al[i].prob = s->hLightProb[i];
-            al[i].failId = s->hLightFailId[i];
-            if (i >= nlp) { rec[i] = LightRec{}; continue; }          // the environment map's sampler entry has no triangle
-            const float* t = &s->hVertices[(size_t)s->hLightPrimIds[i] * 9];
-            f3 v0 = ld3(t), v1 = ld3(t + 3), v2 = ld3(t + 6);
-            f3 c = cross(v1 - v0, v2 - v0);
-            f3 nrm = normalize(c);                                          // Math::triangleNormal
-            float area = length(c) * .5f;                                   // Math::triangleArea
-            f3 Le = ld3(&s->hLightRadiance[i * 3]);
-            float power = luminance(Le) / (area * 2.f * kGlmPi);
-            rec[i] = LightRec{ v0.x, v0.y, v0.z, nrm.x, v1.x, v1.y, v1.z, nrm.y, v2.x, v2.y, v2.z, nrm.z,
-                               Le.x, Le.y, Le.z, power * sumInv };
-        }
+        light_records(s, 1.f / d->sumLightPower, rec.data(), al.data());       // scene.cpp:489
         if (int e = upload(&s->dLights, rec)) { rs_scene_destroy(s); return e; }
         if (int e = upload(&s->dAlias, al)) { rs_scene_destroy(s); return e; }
     }
@@ -588,7 +745,9 @@ extern "C" int rs_scene_build_textured(int numPrims, const float* vertices, cons
     d.lightProb = prob.data(); d.lightFailId = fail.data(); d.sumLightPower = sumAll;
     d.numTextures = numTextures; d.textures = textures; d.envMapTexId = envMapTexId;
     d.envMapProb = envProb.empty() ? nullptr : envProb.data(); d.envMapFailId = envFail.empty() ? nullptr : envFail.data();
-    return rs_scene_create(&d, out);
+    RS_TRY(rs_scene_create(&d, out));
+    if (envMapTexId >= 0) { (*out)->envPower = lightPower[(size_t)numLights - 1]; (*out)->envPowerKnown = true; }     // (rs_scene_set_emission)
+    return 0;
 }
 
 extern "C" int rs_scene_host_desc(const rs_scene* s, rs_scene_desc* d) {

@@ -455,6 +455,7 @@ int rs_strips_frame(rs_strips* s, rs_restir* r, const rs_scene* scene, const rs_
                     float* devDirectIllum, int iter, int looper, int reuse) {
     RS_SCOPE(s);
     if (!s || !r || !scene || !cam || !g || !devDirectIllum) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_frame: null argument");
+    if (r->track) return rs_fail(RS_ERR_UNSUPPORTED, "rs_strips_frame: light tracking (rs_restir_set_light_tracking) is not supported by the strip driver");
     if (g->width != s->width || g->height != s->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_frame: G-buffer size differs from the strips' frame");
     const int y0 = s->y0, y1 = s->y1;
     const rs_comm* c = s->comm;
@@ -616,6 +617,7 @@ int rs_strips_exchange_svgf_history(rs_strips* s, rs_svgf* f) {
 int rs_strips_exchange_history(rs_strips* s, rs_restir* r, rs_gbuffer* g) {
     RS_SCOPE(s);
     if (!s || !r || !g) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_exchange_history: null argument");
+    if (r->track) return rs_fail(RS_ERR_UNSUPPORTED, "rs_strips_exchange_history: light tracking (rs_restir_set_light_tracking) is not supported by the strip driver");
     if (g->width != s->width || g->height != s->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_exchange_history: G-buffer size differs from the strips' frame");
     const rs_comm* c = s->comm;
     if (c->world == 1) return 0;
