@@ -5,12 +5,13 @@ TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.
 leg -- never by restir_amd/ (the product).
 """
 import ctypes as C
+import itertools
 import os
 import subprocess
 
 import numpy as np
 
-from restir_amd.ctypes_structs import Camera, Material, Reservoir, MATERIAL_DTYPE, RESERVOIR_DTYPE, INDIRECT_RESERVOIR_DTYPE
+from restir_amd.ctypes_structs import Camera, Material, Reservoir, LIGHT, MATERIAL_DTYPE, RESERVOIR_DTYPE, INDIRECT_RESERVOIR_DTYPE
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liboracle.so")
@@ -127,6 +128,7 @@ def lib():
         C.POINTER(OrcScene), C.POINTER(Camera), C.POINTER(OrcGBuffer), f32p,
         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong),
     ]
+    L.orc_restir_direct_tracked.argtypes = L.orc_restir_direct.argtypes + [C.c_void_p, C.c_void_p, C.c_void_p]
     L.orc_path_trace.argtypes = [C.POINTER(OrcScene), C.POINTER(Camera), f32p, f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]
     L.orc_pt_indirect.argtypes = [C.POINTER(OrcScene), C.POINTER(Camera), f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]
     L.orc_restir_indirect.argtypes = [C.POINTER(OrcScene), C.POINTER(Camera), C.POINTER(OrcGBuffer), f32p, C.c_void_p, C.c_void_p,
@@ -138,6 +140,7 @@ def lib():
         C.c_void_p, C.POINTER(OrcScene), C.POINTER(Camera), C.POINTER(OrcGBuffer), C.c_void_p, C.c_void_p, C.c_void_p,
         C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong),
     ]
+    L.orc_restir_phase_a_tracked.argtypes = L.orc_restir_phase_a.argtypes + [C.c_void_p, C.c_void_p, C.c_void_p]
     L.orc_restir_phase_b.argtypes = [
         C.c_void_p, C.POINTER(OrcScene), C.POINTER(Camera), C.POINTER(OrcGBuffer), f32p, C.c_void_p,
         C.c_int, C.c_int, C.c_int, C.c_int,
@@ -265,10 +268,14 @@ def light_table(vertices, material_ids, materials):
     return ids[:k].copy(), rad[:k].copy(), power[:k].copy()
 
 
+_scene_ids = itertools.count(1)
+
+
 class Scene:
     """Host image of DevScene, built the way Scene::buildDevData does (scene.cpp:159-215)."""
 
     def __init__(self, vertices, normals, texcoords, material_ids, materials, prebuilt=None, textures=(), env_map_tex=-1):
+        self.uid = next(_scene_ids)                         # rs_scene::id: light tracking forgets another scene's light indices
         # textures: list of (H, W, 3) float32 linear-RGB arrays; env_map_tex: index of the environment map or -1
         self.textures = [np.ascontiguousarray(t, np.float32) for t in textures]
         self.env_map_tex = int(env_map_tex)
@@ -328,6 +335,45 @@ class Scene:
         s.envMapFailId = self.env_fail.ctypes.data
         self.c = s
         self.sample_sequence = None
+
+    def set_emission(self, material_ids, radiance):
+        """rs_scene_set_emission in place: baseColor of the Light materials `material_ids` := rows of `radiance`, then the light
+        radiance, the powers, the alias table and sumLightPower rebuilt as the constructor builds them (the environment map's entry
+        keeps its power).  The scene stays the same object (its uid too), as an edited rs_scene stays the same scene.  Refuses
+        (ValueError, the scene unchanged) what the product refuses: an id out of range or of a material that is not a Light, a
+        negative, NaN or infinite radiance, an edit that leaves the light sampler without a positive total power."""
+        ids = np.ascontiguousarray(material_ids, np.int32).reshape(-1)
+        rad = np.ascontiguousarray(radiance, np.float32).reshape(-1, 3)
+        if rad.shape[0] != ids.size:
+            raise ValueError("set_emission: one radiance row per material id")
+        if ids.size and (ids.min() < 0 or ids.max() >= len(self.materials)):
+            raise ValueError("set_emission: material id out of range")
+        if ids.size and (self.materials["type"][ids] != LIGHT).any():
+            raise ValueError("set_emission: not a Light material")
+        if not np.isfinite(rad).all() or (rad < 0).any():
+            raise ValueError("set_emission: radiance must be finite and non-negative")
+        mats = self.materials.copy()
+        mats["baseColor"][ids] = rad
+        prim_ids, radiance_, power = light_table(self.vertices, self.material_ids, mats)
+        if self.env_map_tex >= 0:
+            power = np.concatenate([power, self.light_power[-1:]])
+        if len(power) == 0:
+            return
+        prob, fail, sum_power = alias_build(power)
+        if not sum_power > 0:
+            raise ValueError("set_emission: no power left in the light sampler")
+        assert np.array_equal(prim_ids, self.light_prim_ids)     # the emitters themselves do not change
+        self.materials = mats                                   # a new array: the caller's materials (often shared) stay as they were
+        self.light_radiance, self.light_power = radiance_, power
+        self.light_prob, self.light_fail, self.sum_power = prob, fail, sum_power
+        s = self.c
+        s.materials = self.materials.ctypes.data
+        s.lightPrimIds = self.light_prim_ids.ctypes.data
+        s.lightUnitRadiance = self.light_radiance.ctypes.data
+        s.lightProb = self.light_prob.ctypes.data
+        s.lightFailId = self.light_fail.ctypes.data
+        with np.errstate(divide="ignore"):
+            s.sumLightPowerInv = np.float32(1.0) / np.float32(self.sum_power)
 
     def set_sample_sequence(self, table):
         """DevScene::sampleSequence (scene.cpp:500-506): the Sobol table as uint32 [SobolSampleNum, SobolSampleDim]; None selects the
@@ -415,6 +461,41 @@ class ReSTIR:
         self.ind_last = np.zeros(n, INDIRECT_RESERVOIR_DTYPE)        # devIndLastTemporalReservoir
         self.first = True
         self.rays = 0
+        self.track = False
+        self.ids = self.ids_last = self.ids_temp = None      # light tracking: beside reservoir / last / temp
+        self.track_scene = 0
+
+    def set_light_tracking(self, on=True):
+        """rs_restir_set_light_tracking: on switch-on every reservoir's light is unknown (-1)."""
+        on = bool(on)
+        if on and not self.track:
+            self.ids = np.full(self.n, -1, np.int32)
+            self.ids_last = np.full(self.n, -1, np.int32)
+            self.ids_temp = np.full(self.n, -1, np.int32)
+            self.track_scene = 0
+        self.track = on
+
+    def light_ids(self, which):
+        """rs_restir_download_light_ids: which 0 = the buffer written next, 1 = the last written, 2 = the published copy;
+        all -1 while tracking is off."""
+        if not self.track:
+            return np.full(self.n, -1, np.int32)
+        return (self.ids, self.ids_last, self.ids_temp)[which].copy()
+
+    def upload(self, which, arr):
+        """rs_restir_upload: which 0 / 1 / 2 as light_ids; the uploaded samples' lights are unknown."""
+        dst = (self.reservoir, self.last, self.temp)[which]
+        dst[:] = np.ascontiguousarray(arr, RESERVOIR_DTYPE)
+        if self.track:
+            (self.ids, self.ids_last, self.ids_temp)[which][:] = -1
+
+    def _id_planes(self, scene):
+        """The tracked entry point's id planes (tracking on only)."""
+        if self.track_scene != scene.uid:                 # another scene's light indices name other lights (phase_a_impl)
+            self.ids_last[:] = -1
+            self.ids_temp[:] = -1
+            self.track_scene = scene.uid
+        return _ptr(self.ids), _ptr(self.ids_last), _ptr(self.ids_temp)
 
     def indirect(self, scene, cam, gbuf, indirect_illum, iter_, looper, reuse, max_depth):
         """ReSTIRIndirect (restir.cu:448-476); shares ReSTIRFirstFrame with direct()."""
@@ -434,25 +515,36 @@ class ReSTIR:
         if getattr(self, "_state", None) is None:
             self._state = lib().orc_restir_state_create(gbuf.width, gbuf.height)
         rays = C.c_ulonglong(0)
-        lib().orc_restir_phase_a(self._state, C.byref(scene.c), C.byref(cam), C.byref(gbuf.c), _ptr(self.reservoir),
-                                 _ptr(self.last), _ptr(self.temp), looper, int(self.first), reuse, y0, y1, C.byref(rays))
+        args = (self._state, C.byref(scene.c), C.byref(cam), C.byref(gbuf.c), _ptr(self.reservoir), _ptr(self.last), _ptr(self.temp),
+                looper, int(self.first), reuse, y0, y1, C.byref(rays))
+        if self.track:
+            lib().orc_restir_phase_a_tracked(*args, *self._id_planes(scene))
+        else:
+            lib().orc_restir_phase_a(*args)
         self.rays = rays.value
 
     def phase_b(self, scene, cam, gbuf, direct_illum, iter_, reuse, y0, y1):
         lib().orc_restir_phase_b(self._state, C.byref(scene.c), C.byref(cam), C.byref(gbuf.c), direct_illum.reshape(-1),
                                  _ptr(self.temp), iter_, reuse, y0, y1)
 
-    def end_frame(self):
+    def _swap(self):
         self.reservoir, self.last = self.last, self.reservoir
+        if self.ids is not None:
+            self.ids, self.ids_last = self.ids_last, self.ids      # the light indices travel with their reservoirs
         self.first = False
+
+    def end_frame(self):
+        self._swap()
 
     def direct(self, scene, cam, gbuf, direct_illum, iter_, looper, reuse):
         rays = C.c_ulonglong(0)
-        lib().orc_restir_direct(C.byref(scene.c), C.byref(cam), C.byref(gbuf.c), direct_illum.reshape(-1),
-                                _ptr(self.reservoir), _ptr(self.last), _ptr(self.temp),
-                                looper, iter_, int(self.first), reuse, C.byref(rays))
-        self.reservoir, self.last = self.last, self.reservoir
-        self.first = False
+        args = (C.byref(scene.c), C.byref(cam), C.byref(gbuf.c), direct_illum.reshape(-1), _ptr(self.reservoir), _ptr(self.last),
+                _ptr(self.temp), looper, iter_, int(self.first), reuse, C.byref(rays))
+        if self.track:
+            lib().orc_restir_direct_tracked(*args, *self._id_planes(scene))
+        else:
+            lib().orc_restir_direct(*args)
+        self._swap()
         self.rays = rays.value
         return rays.value
 

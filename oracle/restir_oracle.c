@@ -835,12 +835,14 @@ static inline int light_sampler_sample(const orc_scene* s, float r1, float r2) {
     return (r2 < s->lightProb[passId]) ? passId : s->lightFailId[passId];
 }
 
-/* scene.h:394-425 */
-static float sample_direct_light_nv(const orc_scene* s, v3 pos, v4 r, v3* radiance, v3* wi, float* dist) {
+/* scene.h:394-425.  *id: the light-sampler index drawn (left alone without lights), for light tracking (LightSample::id,
+ * rs_surface.h sample_light_nv) */
+static float sample_direct_light_nv(const orc_scene* s, v3 pos, v4 r, v3* radiance, v3* wi, float* dist, int* id) {
     if (s->numLights == 0) {
         return INVALID_PDF;
     }
     int lightId = light_sampler_sample(s, r.x, r.y);
+    *id = lightId;
     if (lightId == s->numLights - 1 && s->envMapSamplerLength != 0) {     /* :400-403 */
         *dist = 1e10f;
         v2 r2 = { r.z, r.w };
@@ -918,12 +920,15 @@ static inline void resv_store(orc_reservoir* p, const resv_t* r) {
     st3(p->Li, r->sample.Li); st3(p->wi, r->sample.wi); p->dist = r->sample.dist;
     p->numSamples = r->numSamples; p->weight = r->weight;
 }
-static inline void resv_update(resv_t* r, const li_sample_t* ns, float newWeight, float rnd) { /* :38-44 */
+/* update / merge return whether the new sample was selected (light tracking carries its light index along) */
+static inline int resv_update(resv_t* r, const li_sample_t* ns, float newWeight, float rnd) { /* :38-44 */
     r->weight += newWeight;
     r->numSamples++;
     if (rnd * r->weight < newWeight) {
         r->sample = *ns;
+        return 1;
     }
+    return 0;
 }
 static inline int resv_invalid(const resv_t* r) {             /* :51-53 */
     return is_nan_or_inf(r->weight) || r->weight < 0.f;
@@ -934,12 +939,14 @@ static inline void resv_check_validity(resv_t* r) {           /* :55-59, clear :
         r->numSamples = 0;
     }
 }
-static inline void resv_merge(resv_t* r, const resv_t* rhs, float rnd) { /* :61-68 */
+static inline int resv_merge(resv_t* r, const resv_t* rhs, float rnd) { /* :61-68 */
     r->weight += rhs->weight;
     r->numSamples += rhs->numSamples;
     if (rnd * r->weight < rhs->weight) {
         r->sample = rhs->sample;
+        return 1;
     }
+    return 0;
 }
 static inline void resv_clamp(resv_t* r, int val) {            /* :88-93 */
     if (r->numSamples > val) {
@@ -947,11 +954,11 @@ static inline void resv_clamp(resv_t* r, int val) {            /* :88-93 */
         r->numSamples = val;
     }
 }
-static inline void resv_pre_clamped_merge(resv_t* r, resv_t rhs, int M, float rnd) { /* :95-102 */
+static inline int resv_pre_clamped_merge(resv_t* r, resv_t rhs, int M, float rnd) { /* :95-102 */
     if (r->numSamples > 0) {
         resv_clamp(&rhs, (M - 1) * r->numSamples);
     }
-    resv_merge(r, &rhs, rnd);
+    return resv_merge(r, &rhs, rnd);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -1272,12 +1279,6 @@ void orc_pt_indirect(const orc_scene* s, const orc_camera* cam, float* indirectI
 /* ------------------------------------------------------------------------------------------
  * ReSTIRDirectKernel (restir.cu:20-100,111-231), two-phase contract
  * ---------------------------------------------------------------------------------------- */
-/* restir.cu:20-45 */
-static int temporal_neighbor_index(int idx, const orc_gbuffer* g);
-static resv_t find_temporal_neighbor(const orc_reservoir* reservoir, int idx, const orc_gbuffer* g) {
-    int lastIdx = temporal_neighbor_index(idx, g);
-    return lastIdx < 0 ? resv_default() : resv_load(&reservoir[lastIdx]);
-}
 /* the neighbour test of findTemporalNeighbor (restir.cu:20-45): the index to reuse, or -1 for `T()` */
 static int temporal_neighbor_index(int idx, const orc_gbuffer* g) {
     const int cur = g->frameIdx, last = g->frameIdx ^ 1;
@@ -1341,6 +1342,28 @@ static resv_t find_spatial_neighbor_disk(const orc_reservoir* reservoir, int x, 
     return diff ? resv_default() : resv_load(&reservoir[pidx]);
 }
 
+/* Light tracking (rs_restir_set_light_tracking, include/restir_hip.h): a reused sample of light `id` re-evaluated under the scene's
+ * current emission, W *= luminance(Le) / luminance(Li) (the division first) and Li = Le.  Not for an unknown light (-1), the
+ * environment map's entry or W = 0, nor when luminance(Li) is not positive (restir.hip k_temporal, the TRACK blocks of the merge
+ * and of the `!shaded` branch). */
+static void rescale_to_emission(const orc_scene* s, int id, float* W, v3* Li) {
+    const int envId = s->envMapSamplerLength != 0 ? s->numLights - 1 : -1;
+    if (id < 0 || id >= s->numLights || id == envId || *W == 0.f) return;
+    const float before = luminance(*Li);
+    if (!(before > 0.f)) return;
+    const v3 Le = ld3(s->lightUnitRadiance + (size_t)id * 3);
+    *W *= luminance(Le) / before;
+    *Li = Le;
+}
+
+/* A pixel that shades nothing publishes no reservoir (Q1); with spatial reuse its published copy is still a spatial tap and is
+ * re-evaluated in place (restir.hip k_temporal, `!shaded`), dist kept */
+static void rescale_published(const orc_scene* s, orc_reservoir* p, int id) {
+    v3 Li = ld3(p->Li);
+    rescale_to_emission(s, id, &p->weight, &Li);
+    st3(p->Li, Li);
+}
+
 typedef struct {
     int   kind;          /* 0 = early exit (miss / light), 1 = shaded */
     v3    direct;        /* early-exit radiance */
@@ -1358,11 +1381,13 @@ void* orc_restir_state_create(int width, int height) {
 void orc_restir_state_destroy(void* st) { free(st); }
 
 /* ---- phase A: restir.cu:119-194 (everything before the barrier) + :211-212, rows [y0,y1) ---- */
-void orc_restir_phase_a(void* state, const orc_scene* s, const orc_camera* cam, const orc_gbuffer* g,
-                        orc_reservoir* reservoirOut, const orc_reservoir* reservoirIn,
-                        orc_reservoir* reservoirTemp, int looper, int first, int reuse,
-                        int y0, int y1, unsigned long long* rays) {
+void orc_restir_phase_a_tracked(void* state, const orc_scene* s, const orc_camera* cam, const orc_gbuffer* g,
+                                orc_reservoir* reservoirOut, const orc_reservoir* reservoirIn,
+                                orc_reservoir* reservoirTemp, int looper, int first, int reuse,
+                                int y0, int y1, unsigned long long* rays,
+                                int* idsOut, const int* idsIn, int* idsTemp) {
     const int W = cam->resolution[0], H = cam->resolution[1];
+    const int track = idsOut != NULL;
     pixel_state_t* st = (pixel_state_t*)state;
     unsigned long long total = 0;
     if (y0 < 0) y0 = 0;
@@ -1386,6 +1411,7 @@ void orc_restir_phase_a(void* state, const orc_scene* s, const orc_camera* cam, 
                 if (scene_has_env(s)) {         /* restir.cu:134-136 */
                     ps->direct = env_radiance(s, ray.direction);
                 }
+                if (track && (reuse & 2)) rescale_published(s, &reservoirTemp[index], idsTemp[index]);
                 continue;
             }
             orc_material material = textured_material_and_surface(s, &it);   /* restir.cu:140 */
@@ -1393,6 +1419,7 @@ void orc_restir_phase_a(void* state, const orc_scene* s, const orc_camera* cam, 
 
             if (material.type == MAT_LIGHT) {
                 ps->direct = ld3(material.baseColor);
+                if (track && (reuse & 2)) rescale_published(s, &reservoirTemp[index], idsTemp[index]);
                 continue;
             }
             it.wo = neg(ray.direction);
@@ -1402,34 +1429,47 @@ void orc_restir_phase_a(void* state, const orc_scene* s, const orc_camera* cam, 
             }
 
             resv_t reservoir = resv_default();
+            int id = -1;                        /* light tracking: the winner's light-sampler index (restir.hip ris_pixel) */
             for (int i = 0; i < RESERVOIR_SIZE; i++) {
                 li_sample_t cand;
                 cand.Li = v3s(0.f); cand.wi = v3s(0.f); cand.dist = 0.f;  /* dist: indeterminate in the reference when p<=0; never selected */
+                int candId = -1;
                 v4 rl = sample4D(&rng);
-                float p = sample_direct_light_nv(s, it.pos, rl, &cand.Li, &cand.wi, &cand.dist);
+                float p = sample_direct_light_nv(s, it.pos, rl, &cand.Li, &cand.wi, &cand.dist, &candId);
                 v3 gg = scl(mul(cand.Li, material_bsdf(&material, it.norm, it.wo, cand.wi)), sat_dot(it.norm, cand.wi));
                 float weight = luminance(dvs(gg, p));
                 if (is_nan_or_inf(weight) || p <= 0.f) {
                     weight = 0.f;
                 }
                 float ru = sample1D(&rng);
-                resv_update(&reservoir, &cand, weight, ru);
+                if (resv_update(&reservoir, &cand, weight, ru)) id = candId;
             }
             li_sample_t sample = reservoir.sample;
 
             total++;
             if (scene_test_occlusion(s, it.pos, add(it.pos, scl(sample.wi, sample.dist)))) {
-                reservoir.weight = 0.f;
+                reservoir.weight = 0.f;         /* a blocked winner keeps its light index */
             }
 
-            if (!first && (reuse & 1)) {
-                resv_t temporal = find_temporal_neighbor(reservoirIn, index, g);
+            if (!first && (reuse & 1)) {        /* findTemporalNeighbor (restir.cu:20-45) */
+                int lastIdx = temporal_neighbor_index(index, g);
+                resv_t temporal = lastIdx < 0 ? resv_default() : resv_load(&reservoirIn[lastIdx]);
+                int tid = -1;
+                if (track && lastIdx >= 0) {    /* re-evaluated before the validity test and the clamp (restir.hip k_temporal) */
+                    tid = idsIn[lastIdx];
+                    rescale_to_emission(s, tid, &temporal.weight, &temporal.sample.Li);
+                }
                 if (!resv_invalid(&temporal)) {
                     float ru = sample1D(&rng);
-                    resv_pre_clamped_merge(&reservoir, temporal, 20, ru);
+                    if (resv_pre_clamped_merge(&reservoir, temporal, 20, ru)) id = tid;
                 }
             }
 
+            if (track) {                        /* checkValidity clears the light too; published with the reservoir */
+                if (resv_invalid(&reservoir)) id = -1;
+                idsOut[index] = id;
+                if (reuse & 2) idsTemp[index] = id;
+            }
             resv_t tempReservoir = reservoir;
             if (reuse & 2) {
                 resv_check_validity(&reservoir);
@@ -1502,15 +1542,33 @@ void orc_restir_phase_b(void* state, const orc_scene* s, const orc_camera* cam, 
     }
 }
 
+void orc_restir_phase_a(void* state, const orc_scene* s, const orc_camera* cam, const orc_gbuffer* g,
+                        orc_reservoir* reservoirOut, const orc_reservoir* reservoirIn,
+                        orc_reservoir* reservoirTemp, int looper, int first, int reuse,
+                        int y0, int y1, unsigned long long* rays) {
+    orc_restir_phase_a_tracked(state, s, cam, g, reservoirOut, reservoirIn, reservoirTemp, looper, first, reuse, y0, y1, rays,
+                               NULL, NULL, NULL);
+}
+
+void orc_restir_direct_tracked(const orc_scene* s, const orc_camera* cam, const orc_gbuffer* g,
+                               float* directIllum, orc_reservoir* reservoirOut,
+                               const orc_reservoir* reservoirIn, orc_reservoir* reservoirTemp,
+                               int looper, int iter, int first, int reuse, unsigned long long* rays,
+                               int* idsOut, const int* idsIn, int* idsTemp) {
+    const int W = cam->resolution[0], H = cam->resolution[1];
+    void* st = orc_restir_state_create(W, H);
+    orc_restir_phase_a_tracked(st, s, cam, g, reservoirOut, reservoirIn, reservoirTemp, looper, first, reuse, 0, H, rays,
+                               idsOut, idsIn, idsTemp);
+    orc_restir_phase_b(st, s, cam, g, directIllum, reservoirTemp, iter, reuse, 0, H);
+    orc_restir_state_destroy(st);
+}
+
 void orc_restir_direct(const orc_scene* s, const orc_camera* cam, const orc_gbuffer* g,
                        float* directIllum, orc_reservoir* reservoirOut,
                        const orc_reservoir* reservoirIn, orc_reservoir* reservoirTemp,
                        int looper, int iter, int first, int reuse, unsigned long long* rays) {
-    const int W = cam->resolution[0], H = cam->resolution[1];
-    void* st = orc_restir_state_create(W, H);
-    orc_restir_phase_a(st, s, cam, g, reservoirOut, reservoirIn, reservoirTemp, looper, first, reuse, 0, H, rays);
-    orc_restir_phase_b(st, s, cam, g, directIllum, reservoirTemp, iter, reuse, 0, H);
-    orc_restir_state_destroy(st);
+    orc_restir_direct_tracked(s, cam, g, directIllum, reservoirOut, reservoirIn, reservoirTemp, looper, iter, first, reuse, rays,
+                              NULL, NULL, NULL);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -2440,9 +2498,9 @@ void orc_test_occlusion(const orc_scene* s, int n, const float* seg, int* occlud
 void orc_sample_direct_light_nv(const orc_scene* s, int n, const float* pos, const float* r,
                                 float* pdf, float* Li, float* wi, float* dist) {
     for (int i = 0; i < n; i++) {
-        v3 L = v3s(0.f), w = v3s(0.f); float d = 0.f;
+        v3 L = v3s(0.f), w = v3s(0.f); float d = 0.f; int id = -1;
         v4 r4 = { r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3] };
-        pdf[i] = sample_direct_light_nv(s, ld3(pos + 3 * i), r4, &L, &w, &d);
+        pdf[i] = sample_direct_light_nv(s, ld3(pos + 3 * i), r4, &L, &w, &d, &id);
         st3(Li + 3 * i, L); st3(wi + 3 * i, w); dist[i] = d;
     }
 }

@@ -252,6 +252,15 @@ void orc_restir_direct(const orc_scene* s, const orc_camera* cam, const orc_gbuf
                        float* directIllum, orc_reservoir* reservoirOut,
                        const orc_reservoir* reservoirIn, orc_reservoir* reservoirTemp,
                        int looper, int iter, int first, int reuse, unsigned long long* rays);
+/* The same with light tracking (rs_restir_set_light_tracking): idsOut / idsIn / idsTemp hold the light-sampler index of each
+ * reservoir's sample beside reservoirOut / reservoirIn / reservoirTemp (-1 = none or unknown).  The temporal candidate and the
+ * published copy of a pixel that shades nothing are re-evaluated under the scene's current lightUnitRadiance
+ * (include/restir_hip.h).  All three NULL = orc_restir_direct, the reference's merge. */
+void orc_restir_direct_tracked(const orc_scene* s, const orc_camera* cam, const orc_gbuffer* g,
+                               float* directIllum, orc_reservoir* reservoirOut,
+                               const orc_reservoir* reservoirIn, orc_reservoir* reservoirTemp,
+                               int looper, int iter, int first, int reuse, unsigned long long* rays,
+                               int* idsOut, const int* idsIn, int* idsTemp);
 
 /* The same pass split at the barrier, on a row range, with the per-pixel carried state (RNG, surface,
  * post-temporal reservoir) kept in an opaque buffer: the decomposition the multi-GPU row-strip tiling
@@ -262,6 +271,11 @@ void  orc_restir_phase_a(void* state, const orc_scene* s, const orc_camera* cam,
                          orc_reservoir* reservoirOut, const orc_reservoir* reservoirIn,
                          orc_reservoir* reservoirTemp, int looper, int first, int reuse,
                          int y0, int y1, unsigned long long* rays);
+void  orc_restir_phase_a_tracked(void* state, const orc_scene* s, const orc_camera* cam, const orc_gbuffer* g,
+                                 orc_reservoir* reservoirOut, const orc_reservoir* reservoirIn,
+                                 orc_reservoir* reservoirTemp, int looper, int first, int reuse,
+                                 int y0, int y1, unsigned long long* rays,
+                                 int* idsOut, const int* idsIn, int* idsTemp);
 void  orc_restir_phase_b(void* state, const orc_scene* s, const orc_camera* cam, const orc_gbuffer* g,
                          float* directIllum, const orc_reservoir* reservoirTemp, int iter, int reuse,
                          int y0, int y1);

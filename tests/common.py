@@ -13,6 +13,11 @@ from restir_amd import scenes
 from restir_amd.ctypes_structs import RESERVOIR_DTYPE, copy_camera
 
 
+# rs_set_ris_table_pixels: the library's own threshold (rs_ris_global_below, api_common.hip).  A test that moves it restores this value,
+# so that which RIS form a later launch takes does not depend on the order the tests run in.
+RIS_TABLE_PIXELS_DEFAULT = 64 * 1024
+
+
 def bits_equal(a, b):
     a = np.ascontiguousarray(a); b = np.ascontiguousarray(b)
     if a.dtype == np.float32:
@@ -117,8 +122,9 @@ def next_looper(looper, sobol_num):
 class OracleRenderer:
     """runCuda on the CPU oracle."""
 
-    def __init__(self, sd, width, height, scene=None, sobol=None):
-        """sobol: the Sobol table (uint32 [SobolSampleNum, 200]) = a build with SAMPLER_USE_SOBOL true; None = the default engine."""
+    def __init__(self, sd, width, height, scene=None, sobol=None, track=False):
+        """sobol: the Sobol table (uint32 [SobolSampleNum, 200]) = a build with SAMPLER_USE_SOBOL true; None = the default engine.
+        track: light tracking (rs_restir_set_light_tracking) on from the first frame."""
         self.sd = sd
         self.scene = scene or oracle_scene(sd)
         if sobol is not None or scene is None:
@@ -128,9 +134,17 @@ class OracleRenderer:
         self.cam = ob.camera_update(sd.camera(width, height))
         self.gbuf = ob.GBuffer(width, height)
         self.restir = ob.ReSTIR(width, height)
+        if track:
+            self.restir.set_light_tracking(True)
         self.image = np.zeros((width * height, 3), np.float32)
         self.looper = 0
         self.rays = 0
+
+    def set_emission(self, material_ids, radiance):
+        self.scene.set_emission(material_ids, radiance)
+
+    def light_ids(self, which):
+        return self.restir.light_ids(which)
 
     def set_camera_position(self, pos):
         for i in range(3):
@@ -151,7 +165,7 @@ class OracleRenderer:
 class HipRenderer:
     """runCuda on librestir_hip through the C ABI."""
 
-    def __init__(self, capi, sd, width, height, scene=None, sobol=None):
+    def __init__(self, capi, sd, width, height, scene=None, sobol=None, track=False):
         import torch
         self.torch = torch
         self.capi = capi
@@ -164,8 +178,16 @@ class HipRenderer:
         self.cam = capi.camera_update(sd.camera(width, height))
         self.gbuf = capi.GBuffer(width, height)
         self.restir = capi.ReSTIR(width, height)
+        if track:
+            self.restir.set_light_tracking(True)
         self.image = torch.zeros((width * height, 3), dtype=torch.float32, device="cuda")
         self.looper = 0
+
+    def set_emission(self, material_ids, radiance):
+        self.scene.set_emission(material_ids, radiance)
+
+    def light_ids(self, which):
+        return self.restir.download_light_ids(which)
 
     def set_camera_position(self, pos):
         for i in range(3):
@@ -182,6 +204,37 @@ class HipRenderer:
         self.looper = next_looper(self.looper, self.sobol_num)
         self.gbuf.update(self.cam)
         return self.image.cpu().numpy()
+
+
+class EmissionEdits:
+    """Random non-uniform edits of a scene's lamps (rs_scene_set_emission): each edit recolours a subset with per-channel ratios (so
+    the luminance ratios and the hues differ from lamp to lamp), switches some of them off and switches some lamps that an earlier
+    edit switched off back on.  One lamp stays lit where no environment map keeps the light sampler's power positive."""
+
+    def __init__(self, sd, seed):
+        from restir_amd.ctypes_structs import LIGHT
+        self.rng = np.random.default_rng(seed)
+        self.lamps = np.nonzero(sd.materials["type"] == LIGHT)[0].astype(np.int32)
+        self.base = sd.materials["baseColor"][self.lamps].astype(np.float32)
+        self.now = self.base.copy()
+        self.env = sd.env_map_tex >= 0
+
+    def next(self):
+        rng, n = self.rng, len(self.lamps)
+        pick = rng.choice(n, max(1, n // 4), replace=False)
+        rad = (self.base[pick] * rng.uniform(0.25, 4.0, (len(pick), 3))).astype(np.float32)
+        rad[: len(pick) // 3] = 0.0
+        dark = np.setdiff1d(np.nonzero(~self.now.any(axis=1))[0], pick)
+        back = rng.permutation(dark)[: (len(dark) + 1) // 2]
+        pick = np.concatenate([pick, back])
+        rad = np.concatenate([rad, (self.base[back] * rng.uniform(0.5, 2.0, (len(back), 1))).astype(np.float32)])
+        now = self.now.copy()
+        now[pick] = rad
+        if not self.env and not now.any():
+            rad[0] = self.base[pick[0]]
+            now[pick[0]] = rad[0]
+        self.now = now
+        return self.lamps[pick], rad
 
 
 def radiance_stats(a, b):

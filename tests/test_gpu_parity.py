@@ -18,7 +18,7 @@ import pytest
 
 from oracle import binding as ob
 from restir_amd.ctypes_structs import RESERVOIR_DTYPE
-from tests.common import (HipRenderer, OracleRenderer, bits_equal, get_scene, hip_scene, mismatch_fraction, oracle_scene,
+from tests.common import (RIS_TABLE_PIXELS_DEFAULT, HipRenderer, OracleRenderer, bits_equal, get_scene, hip_scene, mismatch_fraction, oracle_scene,
                           radiance_stats)
 
 pytestmark = pytest.mark.gpu
@@ -194,7 +194,7 @@ def _compare_reservoirs(a, b):
 @pytest.mark.parametrize("table", ["lds", "global"])
 def test_restir_no_spatial_bit_exact(hip, name, reuse, table):
     """RIS-only (config 2 semantics) and temporal reuse: bit-exact radiance and reservoirs over 4 frames, with the RIS light table
-    in LDS (what a full frame uses) and read from global memory (what a launch below 384 Ki pixels uses by default)."""
+    in LDS (what a full frame uses) and read from global memory (what a launch below 64 Ki pixels uses by default)."""
     sd = get_scene(name)
     W, H = SCENES[name]
     o = OracleRenderer(sd, W, H)
@@ -207,7 +207,7 @@ def test_restir_no_spatial_bit_exact(hip, name, reuse, table):
             assert bits_equal(a, b), (frame, radiance_stats(a, b))
             _compare_reservoirs(o.restir.last, h.restir.download(1))      # the buffer written this frame
     finally:
-        hip.set_ris_table_pixels(384 * 1024)
+        hip.set_ris_table_pixels(RIS_TABLE_PIXELS_DEFAULT)
 
 
 @pytest.mark.parametrize("name", list(SCENES))

@@ -10,7 +10,7 @@ import pytest
 
 from oracle import binding as ob
 from restir_amd import sobol
-from tests.common import HipRenderer, OracleRenderer, bits_equal, get_scene, hip_scene, radiance_stats
+from tests.common import RIS_TABLE_PIXELS_DEFAULT, HipRenderer, OracleRenderer, bits_equal, get_scene, hip_scene, radiance_stats
 from tests.test_gpu_parity import SCENES, _compare_reservoirs, _gi_scene
 
 pytestmark = pytest.mark.gpu
@@ -72,7 +72,7 @@ def test_sobol_both_ris_table_locations(hip, table, table_in):
             a = o.frame(3); b = h.frame(3)
             assert bits_equal(a, b), (frame, radiance_stats(a, b))
     finally:
-        hip.set_ris_table_pixels(384 * 1024)
+        hip.set_ris_table_pixels(RIS_TABLE_PIXELS_DEFAULT)
 
 
 def test_sobol_textured_and_environment_lit_scene(hip, table):
