@@ -613,7 +613,8 @@ int  rs_eaw_set_fused(rs_eaw* f, int fused);
 int  rs_eaw_filter(rs_eaw* f, float** devColorOut, const float* devColorIn, const rs_gbuffer* g, const rs_camera* cam);
 /* Row-strip form for framebuffer tiling: positions of rows [y0, y1) (EAWaveletFilter's cam.getPosition per tap, computed once),
  * then one wavelet level (src/denoiser.cu:64-134) on rows [y0, y1).  Level l reads rows up to 2 << l outside the strip from
- * devColorIn, the G-buffer and the positions; the caller exchanges those colour rows between the levels and owns the buffers. */
+ * devColorIn, the G-buffer and the positions; the caller exchanges those colour rows between the levels and owns the buffers.
+ * 0 <= level <= 29 (a tap lies 2 << level pixels away, which must stay an int); rows are clamped to the frame. */
 int  rs_eaw_positions_rows(rs_eaw* f, const rs_gbuffer* g, const rs_camera* cam, int y0, int y1);
 int  rs_eaw_level_rows(rs_eaw* f, float* devColorOut, const float* devColorIn, const rs_gbuffer* g, int level, int y0, int y1);
 /* ---- SVGF (src/denoiser.h:45-70) ---------------------------------------------------------- */
@@ -624,7 +625,9 @@ int  rs_svgf_destroy(rs_svgf* f);
  * (src/denoiser.cu:488).  As in the reference the filter always runs five levels. */
 int  rs_svgf_set_params(rs_svgf* f, float sigLumin, float sigNormal, float sigDepth, int level);
 int  rs_svgf_get_params(const rs_svgf* f, float* sigLumin, float* sigNormal, float* sigDepth, int* level);
-/* 1 (default): the a-trous levels read their taps from an LDS tile (the reference's default sigmas only); 0: plain gathers.  Same bits. */
+/* 1 (default): the a-trous levels read their taps from an LDS tile -- with sigNormal 128 (the reference's default), a sigDepth that is a
+ * power of two and any sigLumin; other sigmas gather from memory whatever this switch says.  0: plain gathers.  Same bits
+ * (tests/test_gpu_denoise_edges.py, tests/test_gpu_parity.py test_svgf_tiled_levels_equal_plain_gathers). */
 int  rs_svgf_set_tiled(rs_svgf* f, int tiled);
 /* The arithmetic of a tap, as rs_eaw_set_fused: fused dot products and accumulation, one multiplication per exponent (the colour
  * weight's -log2(e) / denominator and the luminance staged once per pixel).  Acts with the reference's defaults sigNormal 128 and a

@@ -151,6 +151,9 @@ def lib():
     L.orc_svgf_destroy.argtypes = [C.c_void_p]
     L.orc_svgf_filter.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(OrcGBuffer), C.POINTER(Camera)]
     L.orc_svgf_next_frame.argtypes = [C.c_void_p]
+    L.orc_svgf_set_params.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float]
+    L.orc_svgf_branches.argtypes = [C.c_void_p]
+    L.orc_svgf_branches.restype = C.POINTER(C.c_ubyte)
     for _n in ("orc_svgf_variance", "orc_svgf_accum_color", "orc_svgf_accum_moment"):
         getattr(L, _n).argtypes = [C.c_void_p]
     L.orc_eaw_level.argtypes = [C.POINTER(OrcGBuffer), C.POINTER(Camera), f32p, f32p, C.c_float, C.c_float, C.c_float, C.c_int]
@@ -603,6 +606,14 @@ class SVGF:
 
     def next_frame(self):
         lib().orc_svgf_next_frame(self.h)
+
+    def set_params(self, sig_lumin=4.0, sig_normal=128.0, sig_depth=1.0):
+        """waveletFilter.sig* of SpatioTemporalFilter (src/preview.cpp:278-286); the defaults are the reference's (src/denoiser.cu:488)."""
+        lib().orc_svgf_set_params(self.h, sig_lumin, sig_normal, sig_depth)
+
+    def branches(self):
+        """(5, n) uint8: per level of the last filter() call, bit 0 = colour kept (sumWeight < FLT_EPSILON), bit 1 = variance kept."""
+        return np.ctypeslib.as_array(lib().orc_svgf_branches(self.h), (5 * self.n,)).copy().reshape(5, self.n)
 
     def state(self):
         L = lib()

@@ -1841,6 +1841,8 @@ typedef struct {
     float* variance; float* tempColor; float* tempVariance; float* filteredVariance;
     float* colorOut;     /* the caller's `devColorOut` of the reference: swapped with the filter's buffers by filter() */
     int firstTime, frameIdx;
+    float sigLumin, sigNormal, sigDepth;          /* waveletFilter.sig*, the members the viewer edits (preview.cpp:278-286) */
+    unsigned char* branches;                      /* per level and pixel: bit 0 sumWeight < FLT_EPSILON, bit 1 sumWeight2 < FLT_EPSILON */
 } svgf_t;
 
 void* orc_svgf_create(int width, int height) {        /* :479-493 */
@@ -1851,6 +1853,8 @@ void* orc_svgf_create(int width, int height) {        /* :479-493 */
     f->variance = (float*)calloc(n, 4); f->tempVariance = (float*)calloc(n, 4); f->filteredVariance = (float*)calloc(n, 4);
     f->tempColor = (float*)calloc(n * 3, 4); f->colorOut = (float*)calloc(n * 3, 4);
     f->firstTime = 1; f->frameIdx = 0;
+    f->sigLumin = 4.f; f->sigNormal = 128.f; f->sigDepth = 1.f;          /* :488 */
+    f->branches = (unsigned char*)calloc(n * 5, 1);
     return f;
 }
 void orc_svgf_destroy(void* p) {
@@ -1858,12 +1862,19 @@ void orc_svgf_destroy(void* p) {
     if (!f) return;
     for (int i = 0; i < 2; i++) { free(f->accumColor[i]); free(f->accumMoment[i]); }
     free(f->variance); free(f->tempVariance); free(f->filteredVariance); free(f->tempColor); free(f->colorOut);
+    free(f->branches);
     free(f);
 }
 void orc_svgf_next_frame(void* p) { ((svgf_t*)p)->frameIdx ^= 1; }          /* :566-568 */
 const float* orc_svgf_variance(void* p) { return ((svgf_t*)p)->variance; }
 const float* orc_svgf_accum_color(void* p) { svgf_t* f = (svgf_t*)p; return f->accumColor[f->frameIdx]; }
 const float* orc_svgf_accum_moment(void* p) { svgf_t* f = (svgf_t*)p; return f->accumMoment[f->frameIdx]; }
+void orc_svgf_set_params(void* p, float sigLumin, float sigNormal, float sigDepth) {
+    svgf_t* f = (svgf_t*)p;
+    f->sigLumin = sigLumin; f->sigNormal = sigNormal; f->sigDepth = sigDepth;
+}
+/* which of the two fall-backs of the last filter call's levels every pixel took: 5 planes of width * height bytes, level-major */
+const unsigned char* orc_svgf_branches(void* p) { return ((svgf_t*)p)->branches; }
 
 /* temporalAccumulate (:250-305).  lastColor / lastMoment are read at lastIdx before `diff` is looked at in the
  * reference (also at lastIdx = -1); they only matter when !diff. */
@@ -1950,7 +1961,8 @@ static void svgf_filter_variance(float* out, const float* in, int width, int hei
 
 /* waveletFilter, SVGF form (:139-216) */
 static void svgf_wavelet(float* colorOut, const float* colorIn, float* varOut, const float* varIn, const float* varFiltered,
-                         const orc_gbuffer* g, const orc_camera* cam, float sigDepth, float sigNormal, float sigLuminance, int level) {
+                         const orc_gbuffer* g, const orc_camera* cam, float sigDepth, float sigNormal, float sigLuminance, int level,
+                         unsigned char* branches) {
     const int W = cam->resolution[0], H = cam->resolution[1];
     const int step = 1 << level;
     const int* primIdPlane = g->primId[g->frameIdx];
@@ -1964,6 +1976,7 @@ static void svgf_wavelet(float* colorOut, const float* colorIn, float* varOut, c
             if (primIdP <= NULL_PRIM) {
                 st3(colorOut + (size_t)idxP * 3, ld3(colorIn + (size_t)idxP * 3));
                 varOut[idxP] = varIn[idxP];
+                branches[idxP] = 0;
                 continue;
             }
             v3 normP = ld3(normal + (size_t)idxP * 3);
@@ -1997,6 +2010,7 @@ static void svgf_wavelet(float* colorOut, const float* colorIn, float* varOut, c
             }
             st3(colorOut + (size_t)idxP * 3, (sumWeight < FLT_EPSILON) ? ld3(colorIn + (size_t)idxP * 3) : dvs(sumColor, sumWeight));
             varOut[idxP] = (sumWeight2 < FLT_EPSILON) ? varIn[idxP] : sumVariance / sumWeight2;
+            branches[idxP] = (unsigned char)((sumWeight < FLT_EPSILON ? 1 : 0) | (sumWeight2 < FLT_EPSILON ? 2 : 0));
         }
     }
 }
@@ -2007,24 +2021,25 @@ static void svgf_wavelet(float* colorOut, const float* colorIn, float* varOut, c
  * carried from call to call.  Returns the buffer that holds the result. */
 const float* orc_svgf_filter(void* p, const float* colorIn, const orc_gbuffer* g, const orc_camera* cam) {
     svgf_t* f = (svgf_t*)p;
-    const float sigLumin = 4.f, sigNormal = 128.f, sigDepth = 1.f;          /* :488 */
+    const float sigLumin = f->sigLumin, sigNormal = f->sigNormal, sigDepth = f->sigDepth;
     const int W = f->width, H = f->height, fi = f->frameIdx;
+    const size_t n = (size_t)W * H;
     svgf_temporal(f->accumColor[fi], f->accumColor[fi ^ 1], f->accumMoment[fi], f->accumMoment[fi ^ 1], colorIn, g, f->firstTime);
     f->firstTime = 0;
     svgf_estimate_variance(f->variance, f->accumMoment[fi], W, H);
 
     svgf_filter_variance(f->filteredVariance, f->variance, W, H);
-    svgf_wavelet(f->colorOut, f->accumColor[fi], f->tempVariance, f->variance, f->filteredVariance, g, cam, sigDepth, sigNormal, sigLumin, 0);
+    svgf_wavelet(f->colorOut, f->accumColor[fi], f->tempVariance, f->variance, f->filteredVariance, g, cam, sigDepth, sigNormal, sigLumin, 0, f->branches);
     SWAP_PTR(f->colorOut, f->accumColor[fi]);
     SWAP_PTR(f->tempVariance, f->variance);
 
     svgf_filter_variance(f->filteredVariance, f->variance, W, H);
-    svgf_wavelet(f->colorOut, f->accumColor[fi], f->tempVariance, f->variance, f->filteredVariance, g, cam, sigDepth, sigNormal, sigLumin, 1);
+    svgf_wavelet(f->colorOut, f->accumColor[fi], f->tempVariance, f->variance, f->filteredVariance, g, cam, sigDepth, sigNormal, sigLumin, 1, f->branches + n);
     SWAP_PTR(f->tempVariance, f->variance);
 
     for (int level = 2; level <= 4; level++) {
         svgf_filter_variance(f->filteredVariance, f->variance, W, H);
-        svgf_wavelet(f->tempColor, f->colorOut, f->tempVariance, f->variance, f->filteredVariance, g, cam, sigDepth, sigNormal, sigLumin, level);
+        svgf_wavelet(f->tempColor, f->colorOut, f->tempVariance, f->variance, f->filteredVariance, g, cam, sigDepth, sigNormal, sigLumin, level, f->branches + n * level);
         SWAP_PTR(f->tempColor, f->colorOut);
         SWAP_PTR(f->tempVariance, f->variance);
     }

@@ -304,6 +304,11 @@ void  orc_svgf_next_frame(void* f);
 const float* orc_svgf_variance(void* f);
 const float* orc_svgf_accum_color(void* f);
 const float* orc_svgf_accum_moment(void* f);
+/* waveletFilter.sigLumin / sigNormal / sigDepth of the filter, which the viewer edits (src/preview.cpp:278-286); 4 / 128 / 1 until set */
+void  orc_svgf_set_params(void* f, float sigLumin, float sigNormal, float sigDepth);
+/* the fall-backs the levels of the last orc_svgf_filter took: 5 planes (level-major) of width * height bytes, bit 0 = the weights summed
+ * to less than FLT_EPSILON (colour kept), bit 1 = their squares did (variance kept) */
+const unsigned char* orc_svgf_branches(void* f);
 
 /* src/denoiser.cu:218-248 */
 void orc_modulate(int w, int h, float* image, const float* albedo);

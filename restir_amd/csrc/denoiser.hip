@@ -46,7 +46,10 @@ __device__ __forceinline__ float div_sigma(float x, float sigma, float rsigma) {
     if (POW2) return x * rsigma;
     const float q0 = x * rsigma;
     const float rem = __builtin_fmaf(-q0, sigma, x);
-    return __builtin_fmaf(rem, rsigma, q0);
+    // An infinite x (an Inf sample's distance) or an infinite sigma (SVGF's denominator over an Inf variance) makes the residual
+    // Inf - Inf: the quotient is then q0 itself -- Inf, 0 or NaN as the IEEE division gives -- instead of a NaN that would spread to the
+    // tap's finite channels (tests/test_gpu_denoise_edges.py, the non-finite cases).  Finite arguments never take this branch.
+    return rem == rem ? __builtin_fmaf(rem, rsigma, q0) : q0;
 }
 // exp(-e) for e >= 0 (or NaN, which passes through).  The reference's three factors min(1, exp(-a)) * min(1, exp(-b)) * min(1, exp(-c))
 // share one exponential (the min() never acts on arguments <= 0): 1e-7-relative rounding differences in w.  The exponential itself is
@@ -313,7 +316,7 @@ __global__ void __launch_bounds__(256) k_svgf_filter_variance(float* __restrict_
 // The denominator of wColor depends on the tap's pixel only: `denomQ` and its correctly rounded reciprocal are evaluated once per
 // pixel where the kernel stages its tile (the same expressions, so the same values as evaluating them per tap), and the division
 // takes Markstein's form (div_sigma).  Exponentials as in the EAW filter (exp_neg).  Stated tolerance against the oracle: rtol 3e-5.
-// FUSED (rs_svgf_set_fused, the reference's default sigmas only): as for the EAW taps (kFusedTaps) -- |dp|^2 as a fused dot product, each
+// FUSED (rs_svgf_set_fused; sigNormal 128 and a power-of-two sigDepth only): as for the EAW taps (kFusedTaps) -- |dp|^2 as a fused dot product, each
 // exponent one multiplication by a coefficient that holds -log2(e): `rDepth` is -log2(e) / sigDepth and `rdenomQ` is -log2(e) / denomQ, the
 // latter staged per pixel like the luminances; the caller accumulates with fused operations.  What stays separately rounded, because
 // the weight amplifies its last bit: the luminances (their DIFFERENCE is divided by a denominator that can be 1e-4: fusing them put the
@@ -647,7 +650,8 @@ int rs_eaw_positions_rows(rs_eaw* f, const rs_gbuffer* g, const rs_camera* cam, 
 int rs_eaw_level_rows(rs_eaw* f, float* devColorOut, const float* devColorIn, const rs_gbuffer* g, int level, int y0, int y1) {
     RS_SCOPE(f);
     RS_TRY(rs_gbuffer_join(g));
-    if (!f || !devColorOut || !devColorIn || !g || level < 0 || level > 30) return rs_fail(RS_ERR_INVALID_ARGUMENT, "EAW level: bad argument");
+    // level <= 29: the taps lie +-2 << level pixels away, and x + 2 * (1 << 30) leaves the int range
+    if (!f || !devColorOut || !devColorIn || !g || level < 0 || level > 29) return rs_fail(RS_ERR_INVALID_ARGUMENT, "EAW level: bad argument");
     if (g->width != f->width || g->height != f->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, "EAW filter: size mismatch");
     if (y0 < 0) y0 = 0;
     if (y1 > f->height) y1 = f->height;
@@ -778,7 +782,7 @@ int rs_svgf_filter_rows(rs_svgf* f, float** devColorOut, const float* devColorIn
         hipLaunchKernelGGL(k_svgf_filter_variance, grid_rows(va, vb), dim3(256), 0, rs_stream(), f->devFilteredVariance, f->devVariance, W, H, va, vb);
 #define RS_SVGF_WAVELET(N, D) hipLaunchKernelGGL((k_svgf_wavelet<N, D>), grid_rows(y0, y1), dim3(256), 0, rs_stream(), out, in, f->devTempVariance, f->devVariance, \
                                                 f->devFilteredVariance, gv.primId, gv.normal, f->devPos, W, H, f->sigDepth, f->sigNormal, f->sigLumin, lv, y0, y1)
-        // the reference's defaults (sigNormal 128, sigDepth 1) from the LDS tile; edited sigmas keep the plain gathers
+        // sigNormal 128 (the reference's default) with a power-of-two sigDepth and any sigLumin from the LDS tile; other sigmas keep the plain gathers
         if (f->tiled && f->sigNormal == 128.f && depthPow2 && lv <= 4) {
             const dim3 gridT((W + kTileW - 1) / kTileW, ((y1 - y0 + kTileH * step - 1) / (kTileH * step)) * step);
 #define RS_SVGF_TILED_ARGS gridT, dim3(kTileThreads), 0, rs_stream(), out, in, f->devTempVariance, f->devVariance, \
