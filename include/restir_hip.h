@@ -338,6 +338,19 @@ int  rs_gbuffer_render_rows(rs_gbuffer* g, const rs_scene* scene, const rs_camer
 /* GBuffer::update (src/gbuffer.cu:75-78): lastCamera = cam; frameIdx ^= 1 */
 int  rs_gbuffer_update(rs_gbuffer* g, const rs_camera* cam);
 int  rs_gbuffer_get_view(const rs_gbuffer* g, rs_gbuffer_view* view);
+/* GBuffer::render (src/gbuffer.cu:80-86) reads the scene, the camera, lastCamera and the row range and nothing else.  A frame's
+ * first render request that equals those of the two previous frames in all of them (same scene and no rs_scene_set_emission since,
+ * every byte of both cameras, same rows) launches nothing: the G-buffer hands out the planes it already holds, which are the bits a
+ * render would have written.  That is the reference's default (a camera that stands still).  Anything else renders: a second
+ * render within a frame, a frame that had none, rs_gbuffer_rows_unpack into the rendered rows, rs_set_denoise_stream(1), a stream
+ * that is being captured.  The planes of rs_gbuffer_get_view are therefore read-only for the caller, unless it calls
+ * rs_gbuffer_invalidate afterwards (or renders again).  on = 1 is the default; the environment variable RS_GBUFFER_REUSE=0 makes 0
+ * the default (A/B measurements). */
+int  rs_gbuffer_set_reuse(rs_gbuffer* g, int on);
+/* GBuffer::render (src/gbuffer.cu:80-86) requests so far that launched the walk / that were answered from retained planes */
+int  rs_gbuffer_reuse_stats(const rs_gbuffer* g, unsigned long long* rendered, unsigned long long* reused);
+/* for a caller that wrote planes through the pointers of the view: the next GBuffer::render requests (src/gbuffer.cu:80-86) walk again */
+int  rs_gbuffer_invalidate(rs_gbuffer* g);
 /* Rows [y0,y0+rows) of the id / normal / depth planes as one packed device buffer (20 B/px); sel 0 =
  * planes of the current frame index, 1 = the "last" planes.  Used by the multi-GPU tiling to share
  * G-buffer history when the camera moves (findTemporalNeighbor reads lastPrimId/lastNormal/lastDepth

@@ -112,7 +112,7 @@ EXPORTS = [
     "rs_build_bvh", "rs_build_light_table", "rs_build_alias_table", "rs_build_envmap_pdf", "rs_scene_build", "rs_scene_build_textured", "rs_scene_create",
     "rs_scene_host_desc", "rs_scene_set_sample_sequence", "rs_scene_set_emission", "rs_scene_destroy", "rs_camera_update", "rs_trace_closest", "rs_trace_closest_wave", "rs_scene_set_ordered_tree", "rs_ordered_bvh_host_check", "rs_trace_occlusion",
     "rs_gbuffer_create", "rs_gbuffer_destroy", "rs_gbuffer_render", "rs_gbuffer_render_rows", "rs_gbuffer_update",
-    "rs_gbuffer_get_view", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
+    "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
     "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
     "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
@@ -180,6 +180,9 @@ def lib():
     L.rs_gbuffer_render_rows.argtypes = [vp, vp, C.POINTER(Camera), ci, ci]
     L.rs_gbuffer_update.argtypes = [vp, C.POINTER(Camera)]
     L.rs_gbuffer_get_view.argtypes = [vp, C.POINTER(GBufferView)]
+    L.rs_gbuffer_set_reuse.argtypes = [vp, ci]
+    L.rs_gbuffer_reuse_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    L.rs_gbuffer_invalidate.argtypes = [vp]
     L.rs_restir_init.argtypes = [ci, ci, C.POINTER(vp)]
     L.rs_restir_free.argtypes = [vp]
     L.rs_restir_reset.argtypes = [vp]
@@ -655,6 +658,20 @@ class GBuffer:
         v = GBufferView()
         check(lib().rs_gbuffer_get_view(self.handle, C.byref(v)))
         return v
+
+    def set_reuse(self, on):
+        """Render requests whose inputs equal the two previous frames' are answered from the retained planes (rs_gbuffer_set_reuse; default on)."""
+        check(lib().rs_gbuffer_set_reuse(self.handle, 1 if on else 0))
+
+    def reuse_stats(self):
+        """(rendered, reused): render requests that launched the walk / that were answered from retained planes (rs_gbuffer_reuse_stats)."""
+        a, b = C.c_ulonglong(0), C.c_ulonglong(0)
+        check(lib().rs_gbuffer_reuse_stats(self.handle, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def invalidate(self):
+        """After writing planes through the view's pointers: the next render requests walk again (rs_gbuffer_invalidate)."""
+        check(lib().rs_gbuffer_invalidate(self.handle))
 
     def download(self):
         """Copies every plane to host numpy arrays (torch is only used for the D2H copy)."""

@@ -6,6 +6,8 @@
 // coalesced in 8-pixel row segments).  HBM per pixel: write albedo 12 + normal 12 + id 4 + depth 4
 // + motion 4 = 36 B; BVH node/triangle reads are data dependent and mostly served by L2 / MALL.
 #include <algorithm>
+#include <cstdlib>
+#include <cstring>
 #include <mutex>
 
 #include "rs_internal.h"
@@ -91,7 +93,31 @@ int flush_deferred(const rs_gbuffer* g) {
     return 0;
 }
 
+// ---- reuse of retained planes (rs_internal.h, struct rs_gbuffer) ----
+bool same_key(const rs_gbuffer::Key& a, const rs_gbuffer::Key& b) {
+    return a.valid && b.valid && a.sceneId == b.sceneId && a.edits == b.edits && a.y0 == b.y0 && a.y1 == b.y1 &&
+           std::memcmp(&a.cam, &b.cam, sizeof(rs_camera)) == 0 && std::memcmp(&a.lastCam, &b.lastCam, sizeof(rs_camera)) == 0;
+}
+// a launch that is being captured into a graph does not run now: what it would write is not there to be reused, and a request
+// answered without a launch would be missing from the graph.  (The legacy default stream cannot be captured.)  An error: assume it is.
+bool library_stream_capturing() {
+    const hipStream_t st = rs_stream();
+    if (!st) return false;
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &status) != hipSuccess) { (void)hipGetLastError(); return true; }
+    return status != hipStreamCaptureStatusNone;
+}
+void drop_keys(rs_gbuffer* g) {
+    for (rs_gbuffer::Key& k : g->key) k.valid = false;
+    for (bool& b : g->posKeyed) b = false;
+}
+
 }  // namespace
+
+void rs_gbuffer_note_write(rs_gbuffer* g, int set, int y0, int rows) {
+    rs_gbuffer::Key& k = g->key[set];
+    if (k.valid && rows > 0 && y0 < k.y1 && y0 + rows > k.y0) k.valid = false;
+}
 
 // Nothing that runs before the temporal pass of a frame reads the G-buffer, and the set written is not the one the previous
 // frame's passes read: the render is ordered after the last readers of its set (or, for a second render without an update in
@@ -172,6 +198,7 @@ int rs_gbuffer_create(int width, int height, rs_gbuffer** out) {
     g->ctx = rs_ctx();
     rs_ctx_scope scope(g->ctx);
     g->width = width; g->height = height;
+    if (const char* e = std::getenv("RS_GBUFFER_REUSE")) g->reuse = std::atoi(e) != 0;     // A/B switch for measurements: the default of rs_gbuffer_set_reuse
     const size_t n = (size_t)width * height;
     int e = 0;
     // The reference leaves the planes uninitialised (cudaMalloc only).  They are zeroed here so that
@@ -207,6 +234,56 @@ int rs_gbuffer_render_rows(rs_gbuffer* g, const rs_scene* scene, const rs_camera
     if (y0 < 0) y0 = 0;
     if (y1 > g->height) y1 = g->height;
     if (y1 <= y0) return 0;
+    // The planes depend on the scene, the camera, lastCamera and the rows alone.  The first request of a frame whose key equals those
+    // of the two previous frames' sets is answered from them: this frame's position shows the set of the frame before the previous one
+    // and prev() is the previous frame's, bit for bit what a render would write and what it would leave as "last" planes.  Nothing is
+    // launched, recorded or ordered.
+    // A set takes a key only from the single render of its frame, and not at all while a filter may still use it on the denoise stream
+    // after the library stream has moved on (rs_set_denoise_stream(1): that mode always renders) or while the stream is being captured.
+    const bool first = !g->renderedSinceUpdate;
+    rs_gbuffer::Key k;
+    k.valid = g->reuse && first && rs_ctx()->denoiseMode != 1 && !library_stream_capturing();
+    k.sceneId = scene->id; k.edits = scene->edits; k.cam = *cam; k.lastCam = g->lastCamera; k.y0 = y0; k.y1 = y1;
+    const int p1 = g->pos(1), p2 = g->pos(2);
+    if (k.valid && !g->deferred.valid && !g->pending && g->posKeyed[p1] && g->posKeyed[p2] && same_key(k, g->key[g->phys[p1]]) &&
+        same_key(k, g->key[g->phys[p2]]) && g->phys[p1] != g->phys[p2]) {
+        g->phys[g->ring] = g->phys[p2];
+        g->posKeyed[g->ring] = true;
+        g->renderedSinceUpdate = true;
+        g->reusedFrame = true;
+        g->numReused++;
+        return 0;
+    }
+    // The set this render writes: one that no other position shows (of five sets, four other positions leave at least one).  After
+    // requests answered from retained planes this position shows a set it shares with others: the render takes a free one.  (Rows
+    // outside [y0, y1) are nobody's: a strip's neighbour rows are written before they are read, in every frame.)  Only a SECOND render
+    // of a frame whose first request was answered from the planes builds on them: the free set receives them first.
+    {
+        bool shown[rs_gbuffer::kSets] = {};
+        for (int q = 0; q < rs_gbuffer::kSets; q++) if (q != g->ring) shown[g->phys[q]] = true;
+        const int from = g->phys[g->ring];
+        if (shown[from]) {
+            int to = from;
+            for (int s = 0; s < rs_gbuffer::kSets; s++) if (!shown[s]) { to = s; break; }
+            if (g->reusedFrame && (y0 > 0 || y1 < g->height)) {
+                // on the library stream: every reader of the free set was enqueued there or has been joined to it (a filter on the denoise
+                // stream: by its event); the render itself is ordered after everything enqueued so far (Deferred::rerender)
+                const hipStream_t st = rs_stream();
+                if (g->denoiseValid[to]) RS_HIP(hipStreamWaitEvent(st, g->denoiseEv[to], 0));
+                const size_t n = (size_t)g->width * g->height;
+                RS_HIP(hipMemcpyAsync(g->albedo[to], g->albedo[from], n * 12, hipMemcpyDeviceToDevice, st));
+                RS_HIP(hipMemcpyAsync(g->motion[to], g->motion[from], n * 4, hipMemcpyDeviceToDevice, st));
+                RS_HIP(hipMemcpyAsync(g->normal[to], g->normal[from], n * 12, hipMemcpyDeviceToDevice, st));
+                RS_HIP(hipMemcpyAsync(g->primId[to], g->primId[from], n * 4, hipMemcpyDeviceToDevice, st));
+                RS_HIP(hipMemcpyAsync(g->depth[to], g->depth[from], n * 4, hipMemcpyDeviceToDevice, st));
+            }
+            g->phys[g->ring] = to;
+        }
+    }
+    g->key[g->cur()] = k;                                       // (a second render of a frame: no key)
+    g->posKeyed[g->ring] = k.valid;
+    g->reusedFrame = false;
+    g->numRendered++;
     // Asynchronous mode: the render is only recorded here.  ReSTIRDirect launches it together with its primary rays (the two rays
     // of a pixel in one packet walk); any other reader of the planes launches it on the auxiliary stream first, where it is
     // ordered after the last readers of the set it writes and overlaps the other frame's passes (rs_gbuffer_join).
@@ -244,6 +321,8 @@ int rs_gbuffer_update(rs_gbuffer* g, const rs_camera* cam) {
         g->useOf[c] = g->useOf[l] = k;
     }
     else g->useOf[c] = g->useOf[l] = -1;                // synchronous mode: those readers have finished
+    if (!g->renderedSinceUpdate) g->posKeyed[g->ring] = false;   // a frame without a render: what its position shows is not "the previous frame's planes"
+    g->reusedFrame = false;
     g->updates++;
     g->ring = (g->ring + 1) % rs_gbuffer::kSets;
     g->frameIdx ^= 1;
@@ -273,6 +352,7 @@ int rs_gbuffer_rows_unpack(rs_gbuffer* g, int sel, int y0, int rows, const void*
     if (!g || !devBuffer || (sel != 0 && sel != 1) || y0 < 0 || rows < 0 || y0 + rows > g->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_gbuffer_rows_unpack: bad argument");
     RS_TRY(rs_gbuffer_join(g));
     const int f = sel ? g->prev() : g->cur();
+    rs_gbuffer_note_write(g, f, y0, rows);
     const size_t n = (size_t)g->width * rows, off = (size_t)y0 * g->width;
     const char* b = (const char*)devBuffer;
     RS_HIP(hipMemcpyAsync(g->primId[f] + off, b, n * 4, hipMemcpyDeviceToDevice, rs_stream()));
@@ -291,6 +371,33 @@ int rs_gbuffer_get_view(const rs_gbuffer* g, rs_gbuffer_view* v) {
     v->devPrimId[f] = g->primId[c]; v->devPrimId[f ^ 1] = g->primId[l];
     v->devDepth[f] = g->depth[c]; v->devDepth[f ^ 1] = g->depth[l];
     v->frameIdx = g->frameIdx; v->width = g->width; v->height = g->height;
+    return 0;
+}
+
+// GBuffer::render (src/gbuffer.cu:80-86) answered from the planes the G-buffer already holds when nothing it reads has changed: on (the
+// default) or off.  Switching it off also forgets what the sets hold.
+int rs_gbuffer_set_reuse(rs_gbuffer* g, int on) {
+    RS_SCOPE(g);
+    if (!g) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_gbuffer_set_reuse: null argument");
+    g->reuse = on != 0;
+    if (!g->reuse) drop_keys(g);
+    return 0;
+}
+
+// requests of GBuffer::render (src/gbuffer.cu:80-86) that launched the walk / that were answered from retained planes
+int rs_gbuffer_reuse_stats(const rs_gbuffer* g, unsigned long long* rendered, unsigned long long* reused) {
+    RS_SCOPE(g);
+    if (!g) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_gbuffer_reuse_stats: null argument");
+    if (rendered) *rendered = g->numRendered;
+    if (reused) *reused = g->numReused;
+    return 0;
+}
+
+// the caller has written planes through the pointers of rs_gbuffer_get_view: the next GBuffer::render (src/gbuffer.cu:80-86) walks again
+int rs_gbuffer_invalidate(rs_gbuffer* g) {
+    RS_SCOPE(g);
+    if (!g) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_gbuffer_invalidate: null argument");
+    drop_keys(g);
     return 0;
 }
 

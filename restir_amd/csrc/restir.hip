@@ -1063,7 +1063,14 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     }
     int kThreeStreams[rs_restir::kSmallChains];                 // the chain streams first, the render's stream (idle after a fused launch) last
     for (int i = 0; i < rs_restir::kSmallChains; i++) kThreeStreams[i] = i < 2 ? 1 + i : i == 2 ? 0 : i;
-    const bool three = fuse && parityStreams && r->phaseACalls == 0;
+    // A frame whose render request was answered from retained planes (rs_gbuffer_render_rows) launched nothing on the render's stream
+    // either: it is idle for the same reason, and the frame's chain is one of three as well.  (RS_REUSE_CHAINS=2: A/B switch, two chains.)
+    static const bool reusedThree = [] { const char* e = std::getenv("RS_REUSE_CHAINS"); return !(e && std::atoi(e) == 2); }();
+    const bool reused = asyncMode && g->reusedFrame && !d.valid && !denoiseStream && y1 > y0;
+    const bool three = (fuse || (reused && reusedThree)) && parityStreams && r->phaseACalls == 0;
+    // The measured choice compares spans of consecutive frames that each had a render to fuse: a reused frame in between is not
+    // one of them, so a measurement under way starts again with the next real render.  (A still camera never decides it.)
+    if (reused && r->phaseACalls == 0 && r->tuneChoice < 0) r->tuneFrame = 0;
     // (a context that keeps another stream busy next to the frames -- the strip driver with its transfers on a stream of their own, the
     // denoise stream -- leaves room for two chains, or one: four streams that hand events to each other is what the device runs side by
     // side, rs_chains_in_flight)

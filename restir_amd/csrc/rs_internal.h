@@ -212,6 +212,7 @@ struct rs_scene {
     float sumLightPower = 0.f;
     int numPrims = 0, bvhSize = 0, numLights = 0;
     unsigned long long id = 0;       // unique per rs_scene_create (a freed scene's address can come back; its id cannot)
+    unsigned long long edits = 0;    // counts the edits that change what GBuffer::render writes (rs_scene_set_emission: baseColor, hence the albedo plane); part of a G-buffer set's content key
     // Emission edits (rs_scene_set_emission): a ring of versions of { materials, light records, alias table }.  Kernels capture
     // `dev` by value at launch, so a version is never written while a launch that captured it may still run: an edit fills the
     // next slot (ordered before every later launch by an event) and points `dev` at it, and a slot is filled again only after the events recorded when the
@@ -241,6 +242,14 @@ struct rs_scene {
 // three frames whose renders run ahead on the auxiliary streams (a strip has three chains in flight, each with the frame's render
 // in its first launch), so that no render writes what an earlier frame's temporal pass still reads.  frameIdx is still toggled
 // and reported by rs_gbuffer_get_view, whose devNormal[frameIdx] / [frameIdx ^ 1] are the current / last sets.
+//
+// Reuse (GBuffer::render, src/gbuffer.cu:80-86, reads the scene, the camera, lastCamera and the row range and nothing else): the ring
+// is one of POSITIONS, and phys[] says which set of planes a position shows.  Every set carries the key of the one render that wrote it
+// during its frame.  A frame's first render request whose key equals the keys of the two previous frames' sets launches nothing: its
+// position takes the set of the frame before the previous one -- the bits a render would have written -- and prev() stays the previous
+// frame's set, the bits it would have left as "last" planes.  A still camera so alternates between two sets, read and never written by
+// all frames in flight.  The ring itself advances as always, so every position shows what it would show without reuse (also the stale
+// planes a frame without a render looks at).  A request that differs renders into a set that no other position shows.
 struct rs_gbuffer {
     rs_context* ctx = nullptr;
     static constexpr int kSets = RS_GBUF_SETS;
@@ -249,7 +258,9 @@ struct rs_gbuffer {
     float* normal[kSets] = {};
     int* primId[kSets] = {};
     float* depth[kSets] = {};
-    int ring = 0;                // set of the current frame; the previous frame's is (ring + kSets - 1) % kSets
+    int ring = 0;                // position of the current frame; the previous frame's is (ring + kSets - 1) % kSets
+    int phys[kSets];             // the set each position shows (the identity until a request is answered from retained planes)
+    bool posKeyed[kSets] = {};   // the frame at that position had exactly one render request, and its set took (or matched) that request's key
     int frameIdx = 0;
     rs_camera lastCamera{};      // uninitialised in the reference until the first update (Q14); zero here
     int width = 0, height = 0;
@@ -258,7 +269,7 @@ struct rs_gbuffer {
     hipEvent_t doneEv = nullptr;             // the render
     hipEvent_t useEv[kSets] = {};   // recorded by update(): the frame that ended there has been enqueued
     int useOf[kSets];       // per set: which useEv covers its last readers (-1: none outstanding)
-    rs_gbuffer() { for (int i = 0; i < kSets; i++) useOf[i] = -1; }
+    rs_gbuffer() { for (int i = 0; i < kSets; i++) { useOf[i] = -1; phys[i] = i; } }
     // a filter on the denoise stream reads (a strip's: also writes the rows just outside the strip of) the current set after the library
     // stream has moved on: the next render into that set waits for this event as well (rs_gbuffer_order_before_render)
     mutable hipEvent_t denoiseEv[kSets] = {};
@@ -277,8 +288,20 @@ struct rs_gbuffer {
     };
     mutable Deferred deferred;
     mutable rs_tile_split split[2];          // k_render_gbuffer on the library stream / on the auxiliary stream
-    int cur() const { return ring; }
-    int prev() const { return (ring + kSets - 1) % kSets; }
+    // content keys (see above).  valid: exactly one render wrote the set during its frame and nothing has written its keyed rows since
+    struct Key {
+        bool valid = false;
+        unsigned long long sceneId = 0, edits = 0;
+        rs_camera cam{}, lastCam{};
+        int y0 = 0, y1 = 0;
+    };
+    Key key[kSets];
+    bool reuse = true;                       // rs_gbuffer_set_reuse (RS_GBUFFER_REUSE=0: off from the start)
+    bool reusedFrame = false;                // this frame's render request was answered from the retained planes (cleared by update and by a second render)
+    unsigned long long numRendered = 0, numReused = 0;   // rs_gbuffer_reuse_stats
+    int pos(int back) const { return (ring + kSets - back) % kSets; }   // the position of the frame `back` frames ago
+    int cur() const { return phys[ring]; }
+    int prev() const { return phys[pos(1)]; }
     // albedo / motion are single planes in the reference: they show the most recent render, also after update()
     int latest() const { return (renderedSinceUpdate || updates == 0) ? cur() : prev(); }
 };
@@ -293,6 +316,9 @@ int rs_gbuffer_release_scene(const rs_scene* scene);
 int rs_gbuffer_order_before_render(const rs_gbuffer* g, hipStream_t stream);
 // inside an rs_denoise_scope: the current set is in use on the denoise stream up to here
 int rs_gbuffer_denoise_mark(const rs_gbuffer* g);
+// somebody other than a render writes rows [y0, y0 + rows) of set `set` (rs_gbuffer_rows_unpack, a strip's halo copies): a content key
+// whose rows they overlap no longer describes the set
+void rs_gbuffer_note_write(rs_gbuffer* g, int set, int y0, int rows);
 bool rs_fuse_enabled();
 int rs_ris_global_below();
 const rs_context* rs_stream_plan();   // the current context with chainStreams / smallChains / shadowOnMain resolved

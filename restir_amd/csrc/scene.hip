@@ -446,6 +446,7 @@ extern "C" int rs_scene_set_emission(rs_scene* s, int count, const int* material
     s->dev.alias = nv.alias;
     s->dev.sumLightPowerInv = 1.f / sumAll;                              // scene.cpp:489
     s->verCur = next;
+    s->edits++;                                                          // baseColor feeds the albedo plane: retained G-buffer planes are not this scene's any more
     return rs_after_launch("rs_scene_set_emission");
 }
 

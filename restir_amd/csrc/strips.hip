@@ -224,8 +224,8 @@ int exchange_gbuffer_rows(rs_strips* s, rs_gbuffer* g, int reach) {
     RS_TRY(join(s, false));
     {
         SegList l;
-        if (up) segments(l, y0 - reach, s->eawRecv[0]);
-        if (down) segments(l, y1, s->eawRecv[1]);
+        if (up) { segments(l, y0 - reach, s->eawRecv[0]); rs_gbuffer_note_write(g, cur, y0 - reach, reach); }
+        if (down) { segments(l, y1, s->eawRecv[1]); rs_gbuffer_note_write(g, cur, y1, reach); }
         RS_TRY(copy_segments(l, false));
     }
     return 0;
@@ -488,8 +488,8 @@ int rs_strips_frame(rs_strips* s, rs_restir* r, const rs_scene* scene, const rs_
         // and two 5-row bands would only buy two more launches -- and the bands are 5 rows in 16-row tiles.  Unpack, then ONE launch over
         // the strip (a 1/8 strip of 1080p: three launches of 14.6 + 8.5 + 8.8 us -> one of 15; results do not depend on the partition).
         SegList l;
-        if (up) halo_segments(l, r, g, y0 - kHalo, y0 - s->gReach, s->gReach, s->recvUp);
-        if (down) halo_segments(l, r, g, y1, y1, s->gReach, s->recvDown);
+        if (up) { halo_segments(l, r, g, y0 - kHalo, y0 - s->gReach, s->gReach, s->recvUp); rs_gbuffer_note_write(g, g->cur(), y0 - s->gReach, s->gReach); }
+        if (down) { halo_segments(l, r, g, y1, y1, s->gReach, s->recvDown); rs_gbuffer_note_write(g, g->cur(), y1, s->gReach); }
         s->gbufFresh = true;
         RS_TRY(copy_segments(l, false));
         RS_TRY(rs_restir_phase_b(r, scene, cam, g, devDirectIllum, iter, reuse, y0, y1));
@@ -502,8 +502,8 @@ int rs_strips_frame(rs_strips* s, rs_restir* r, const rs_scene* scene, const rs_
     RS_TRY(join(s, true));
     {
         SegList l;
-        if (up) halo_segments(l, r, g, y0 - kHalo, y0 - s->gReach, s->gReach, s->recvUp);
-        if (down) halo_segments(l, r, g, y1, y1, s->gReach, s->recvDown);
+        if (up) { halo_segments(l, r, g, y0 - kHalo, y0 - s->gReach, s->gReach, s->recvUp); rs_gbuffer_note_write(g, g->cur(), y0 - s->gReach, s->gReach); }
+        if (down) { halo_segments(l, r, g, y1, y1, s->gReach, s->recvDown); rs_gbuffer_note_write(g, g->cur(), y1, s->gReach); }
         s->gbufFresh = true;
         RS_TRY(copy_segments(l, false));
     }

@@ -14,7 +14,11 @@
 // for a static and an orbiting camera, with the transfers on the library stream (the default: deferred gathers ride in the next
 // frame's group) and on the driver's own stream (rs_strips_set_comm_stream), without and with the EAW filter.
 //
-//     strips_loopback_ranks [N [SECONDS]]     N ranks (default 3, at most 8: the split BASELINE's multi-GPU configs name); the process ends itself after SECONDS (default 240)
+// A static camera's render requests are answered from the planes the G-buffer retains (rs_gbuffer_set_reuse, the default): every rank
+// checks its counts -- three renders, then hits only; an orbit and the denoise stream never hit -- and prints them.
+//
+//     strips_loopback_ranks [N [SECONDS [static-halo]]]     N ranks (default 3, at most 8: the split BASELINE's multi-GPU configs name); the process ends itself after SECONDS (default 240);
+//                                                           static-halo: the filter modes with a static camera take rs_strips_set_gbuffer_halo(32) as well
 #include <condition_variable>
 #include <deque>
 
@@ -88,6 +92,7 @@ int lb_recv(void* ctx, void* buf, size_t bytes, int peer, void* stream) {
 }
 
 std::atomic<int> mismatches{ 0 };
+bool staticHalo = false;
 #define CHECK(x) RANKS_CHECK(x)
 
 void run_rank(int rank, int world, Mailbox* box) {
@@ -116,7 +121,7 @@ void run_rank(int rank, int world, Mailbox* box) {
         rs_strips* strips = nullptr;
         CHECK(rs_strips_create(comm, W, H, nullptr, &strips));
         CHECK(rs_strips_set_comm_stream(strips, ownStream ? 1 : 0));
-        if (denoise && orbit) CHECK(rs_strips_set_gbuffer_halo(strips, 32));      // (half of the filter modes: its 32 G-buffer rows travel with the reservoir rows)
+        if (denoise && (orbit || staticHalo)) CHECK(rs_strips_set_gbuffer_halo(strips, 32));      // (half of the filter modes: its 32 G-buffer rows travel with the reservoir rows)
         int y0 = 0, y1 = 0;
         CHECK(rs_strips_rows(strips, &y0, &y1));
         const int sets = rank == 0 ? 2 : 1;                        // rank 0: the strips' objects and a full-frame renderer of its own
@@ -187,6 +192,15 @@ void run_rank(int rank, int world, Mailbox* box) {
         }
         CHECK(rs_synchronize());
         RANKS_HIP(hipStreamSynchronize(lib));
+        for (int k = 0; k < sets; k++) {                            // the strip's G-buffer (and rank 0's full-frame one): which requests walked
+            unsigned long long rendered = 0, reused = 0;
+            CHECK(rs_gbuffer_reuse_stats(g[k], &rendered, &reused));
+            const unsigned long long wantReused = (orbit || denoiseStream) ? 0 : kFrames - 3;
+            const bool ok = reused == wantReused && rendered == kFrames - wantReused;
+            std::printf("rank %d, mode %d, %s G-buffer: rendered %llu, reused %llu: %s\n", rank, mode, k == 0 ? "strip" : "full-frame", rendered, reused, ok ? "as expected" : "UNEXPECTED");
+            std::fflush(stdout);
+            if (!ok) mismatches++;
+        }
         if (rank == 0) {
             std::vector<unsigned char> got(px * 4);
             for (int frame = 0; frame < kFrames; frame++) {
@@ -225,6 +239,7 @@ int main(int argc, char** argv) {
     if (world > 6) H = 36 * world;                                 // eight ranks: 288 rows, 36 per strip (the EAW levels reach 32 rows into the neighbours)
     if (H / world < 32) { std::fprintf(stderr, "strips of fewer than 32 rows (the EAW levels reach that far)\n"); return 2; }
     start_watchdog(argc > 2 ? std::atoi(argv[2]) : 240);
+    staticHalo = argc > 3 && std::strcmp(argv[3], "static-halo") == 0;
     static Mailbox box;
     if (hipSetDevice(0) != hipSuccess) return 1;
     for (int a = 0; a < world; a++) for (int b = 0; b < world; b++) {
