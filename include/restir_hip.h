@@ -390,6 +390,40 @@ int  rs_restir_launch_choice(const rs_restir* r, int* choice);
  * launch, 0 its own launch (-1 before the first call); *chains = how many internal streams the frames' chains take in turn (0 in
  * synchronous mode).  A launch below three rounds of wave slots (a strip) is fused and on three chains without a measurement. */
 int  rs_restir_last_launch(const rs_restir* r, int* fused, int* chains);
+/* What a phase-A call decides before it launches anything, as a function of plain integers (restir_amd/csrc/rs_frame_plan.h; the
+ * rules and the measurements behind them are written there, DESIGN.md section 4 lists them).  Flags are 0 / 1. */
+typedef struct rs_phase_a_inputs {
+    int async;              /* launches of this call are asynchronous (overlapped mode, no per-pass timing) */
+    int chainStreams, smallChains, shadowOnMain;   /* rs_set_stream_plan, resolved: 1 / 2, 0 / 1, 0 / 1 / 2 */
+    int fuseMode;           /* 0 never, 1 always (large launches), 2 always, 3 measured (rs_set_side_stream's 1 .. 4) */
+    int denoiseStream;      /* rs_set_denoise_stream(1) */
+    int chainsInFlight;     /* 3, less one per other stream of the context with work in flight */
+    int reusedThree;        /* a frame answered from retained G-buffer planes takes one of three chains (0: RS_REUSE_CHAINS=2) */
+    int phaseACalls;        /* phase-A calls of this frame before this one */
+    int width, y0, y1;      /* rows clamped to the image */
+    int deferredValid, deferredMatches, deferredY0, deferredY1;   /* the deferred GBuffer::render: there is one; same scene and camera; its rows */
+    int reusedFrame;        /* this frame's render request was answered from retained planes */
+    int tuneChoice, tuneFrame;   /* the measurement for this scene: -1 measuring / 0 two launches / 1 one; frames counted so far */
+    int chain, smallChain;  /* the frame's turn among two / three chains */
+    int idle;               /* the previous frames had finished when this frame began (twice in a row) */
+    int numLights, envMap, risGlobalBelow;   /* light table entries; the scene has an environment map; rs_set_ris_table_pixels */
+} rs_phase_a_inputs;
+#define RS_RIS_GLOBAL    0  /* light table read from global memory */
+#define RS_RIS_LDS       1  /* whole table in LDS */
+#define RS_RIS_ALIAS_LDS 2  /* alias records in LDS */
+typedef struct rs_phase_a_plan {
+    int fuse;               /* GBuffer::render rides in the primary rays' launch (rs_restir_last_launch's *fused) */
+    int tuneCounted;        /* this launch is one the fused / separate measurement applies to */
+    int tuneRestart;        /* a measurement under way starts again */
+    int stream;             /* -1 the library stream, else the internal stream 0 .. 2 of the chain primary rays -> RIS -> shadow rays */
+    int lastChains;         /* rs_restir_last_launch's *chains */
+    int splitSlot, splitCall, splitMode;   /* tile-split hints: per stream (0 library, 1 + stream), per call of the frame (at most 2); mode 1 alone / 0 large / 2 small */
+    int shadowOnLibrary;    /* the shadow rays go to the library stream, not to the chain's */
+    int risForm;            /* RS_RIS_* */
+    int tilesX, tilesY, fusedTilesY;   /* blocks of 32 x 8 pixels over the rows; of 32 x 4 over the deferred render's rows when fused */
+} rs_phase_a_plan;
+/* Test hook: evaluates that function; needs no device. */
+int  rs_debug_phase_a_plan(const rs_phase_a_inputs* in, rs_phase_a_plan* out);
 #define RS_SPATIAL_HALO_ROWS 5           /* taps reach y-4..y+5 (src/restir.cu:49-56) */
 /* bytes needed for `rows` rows of published reservoirs */
 size_t rs_restir_halo_bytes(const rs_restir* r, int rows);

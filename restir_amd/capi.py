@@ -106,6 +106,24 @@ class GBufferView(C.Structure):
     ]
 
 
+class PhaseAInputs(C.Structure):
+    """rs_phase_a_inputs (include/restir_hip.h): what a phase-A call of ReSTIRDirect decides from."""
+    _fields_ = [(n, C.c_int) for n in (
+        "async_", "chainStreams", "smallChains", "shadowOnMain", "fuseMode", "denoiseStream", "chainsInFlight", "reusedThree", "phaseACalls",
+        "width", "y0", "y1", "deferredValid", "deferredMatches", "deferredY0", "deferredY1", "reusedFrame", "tuneChoice", "tuneFrame",
+        "chain", "smallChain", "idle", "numLights", "envMap", "risGlobalBelow")]
+
+
+class PhaseAPlan(C.Structure):
+    """rs_phase_a_plan (include/restir_hip.h): what it decides."""
+    _fields_ = [(n, C.c_int) for n in (
+        "fuse", "tuneCounted", "tuneRestart", "stream", "lastChains", "splitSlot", "splitCall", "splitMode", "shadowOnLibrary", "risForm",
+        "tilesX", "tilesY", "fusedTilesY")]
+
+
+RIS_GLOBAL, RIS_LDS, RIS_ALIAS_LDS = 0, 1, 2
+
+
 # every symbol include/restir_hip.h declares; tests check that the library exports all of them
 EXPORTS = [
     "rs_last_error", "rs_context_create", "rs_context_destroy", "rs_context_set_current", "rs_init", "rs_set_stream", "rs_set_sync", "rs_set_side_stream", "rs_set_ris_table_pixels", "rs_set_internal_stream_priority", "rs_internal_streams_info", "rs_choose_internal_streams_again", "rs_prepare_streams", "rs_set_stream_plan", "rs_set_denoise_stream", "rs_join_denoise_stream", "rs_set_tile_split", "rs_synchronize",
@@ -115,7 +133,7 @@ EXPORTS = [
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
     "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
-    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
+    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
     "rs_path_trace", "rs_path_trace_indirect", "rs_restir_indirect", "rs_restir_download_indirect",
     "rs_svgf_create", "rs_svgf_destroy", "rs_svgf_filter", "rs_svgf_next_frame", "rs_svgf_get_view",
     "rs_copy_image_to_pbo", "rs_copy_image2_to_pbo", "rs_copy_imagef_to_pbo", "rs_copy_imagei_to_pbo", "rs_eaw_create", "rs_eaw_destroy", "rs_eaw_set_params", "rs_eaw_get_params", "rs_eaw_set_tiled", "rs_eaw_set_fused", "rs_svgf_set_params", "rs_svgf_get_params", "rs_svgf_set_tiled", "rs_svgf_set_fused", "rs_eaw_filter", "rs_eaw_positions_rows", "rs_eaw_level_rows", "rs_modulate_albedo",
@@ -199,6 +217,7 @@ def lib():
     L.rs_restir_rows_bytes.restype = C.c_size_t
     L.rs_debug_tap_estimate_error.argtypes = [ci, C.POINTER(cf)]
     L.rs_restir_last_launch.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+    L.rs_debug_phase_a_plan.argtypes = [C.POINTER(PhaseAInputs), C.POINTER(PhaseAPlan)]
     L.rs_pbo_register.argtypes = [C.c_uint, C.POINTER(vp)]
     L.rs_pbo_map.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rs_pbo_unmap.argtypes = [vp]
@@ -348,6 +367,13 @@ def choose_internal_streams_again():
 def set_ris_table_pixels(pixels):
     """Launches of fewer pixels read the RIS light table from global memory instead of LDS (rs_set_ris_table_pixels); 0 = always LDS."""
     check(lib().rs_set_ris_table_pixels(int(pixels)))
+
+
+def phase_a_plan(**inputs):
+    """The plan of a phase-A call for these inputs (rs_debug_phase_a_plan; fields of PhaseAInputs, the rest 0): needs no device."""
+    i, o = PhaseAInputs(**inputs), PhaseAPlan()
+    check(lib().rs_debug_phase_a_plan(C.byref(i), C.byref(o)))
+    return o
 
 
 def prepare_streams():

@@ -424,12 +424,9 @@ int launch_path(const rs_scene* scene, const rs_camera* cam, float* direct, floa
         if (6 + 7LL * maxDepth > kSobolSampleDim + kSobolGuard) return rs_fail(RS_ERR_INVALID_ARGUMENT, "pathTrace / ReSTIRIndirect: trace depth too large for the Sobol table's guard");
     }
     const dim3 grid(tilesX * tilesY), block(256);
-#define RS_PATH_ARGS scene->dev, cp, direct, indirect, out, in, g, looper, iter, maxDepth, first, reuse, tilesX, g_giRayCount
-    if (scene->textured) { if (sobol) hipLaunchKernelGGL((k_path<MODE, true, true>), grid, block, 0, rs_stream(), RS_PATH_ARGS);
-                           else       hipLaunchKernelGGL((k_path<MODE, true, false>), grid, block, 0, rs_stream(), RS_PATH_ARGS); }
-    else                 { if (sobol) hipLaunchKernelGGL((k_path<MODE, false, true>), grid, block, 0, rs_stream(), RS_PATH_ARGS);
-                           else       hipLaunchKernelGGL((k_path<MODE, false, false>), grid, block, 0, rs_stream(), RS_PATH_ARGS); }
-#undef RS_PATH_ARGS
+    rs_dispatch([&](auto TEX, auto SOBOL) {
+        hipLaunchKernelGGL((k_path<MODE, TEX(), SOBOL()>), grid, block, 0, rs_stream(), scene->dev, cp, direct, indirect, out, in, g, looper, iter, maxDepth, first, reuse, tilesX, g_giRayCount);
+    }, scene->textured, sobol);
     return 0;
 }
 

@@ -171,8 +171,10 @@ int rs_path_trace_direct(const rs_scene* scene, const rs_camera* cam, float* dev
     RS_HIP(hipMemsetAsync(rs_ctx()->ptRayCount, 0, 8, rs_stream()));
     const int W = cam->resolution[0], H = cam->resolution[1];
     const int tilesX = (W + 31) / 32, tilesY = (H + 7) / 8;
-    RS_LAUNCH2(k_pt_direct, scene->textured, scene->dev.sampleSeq != nullptr, dim3(tilesX * tilesY), dim3(256), rs_stream(), scene->dev,
-               rs_make_cam_params(cam), devDirectIllum, looper, iter, tilesX, rs_ctx()->ptRayCount);
+    rs_dispatch([&](auto TEX, auto SOBOL) {
+        hipLaunchKernelGGL((k_pt_direct<TEX(), SOBOL()>), dim3(tilesX * tilesY), dim3(256), 0, rs_stream(), scene->dev,
+                           rs_make_cam_params(cam), devDirectIllum, looper, iter, tilesX, rs_ctx()->ptRayCount);
+    }, scene->textured, scene->dev.sampleSeq != nullptr);
     RS_TRY(rs_after_launch("pathTrace"));
     if (rays) {
         RS_HIP(hipStreamSynchronize(rs_stream()));
@@ -191,10 +193,9 @@ int rs_copy_image_to_pbo(void* devPBO, const float* devImage, int width, int hei
     rs_denoise_scope onDenoiseStream(!rs_denoise_owns(devPBO), rs_denoise_owns(devImage));      // (fork for a display buffer that stream has never written: after its last use on the library stream)
     RS_TRY(onDenoiseStream.err);
     if (!onDenoiseStream.active) { RS_TRY(rs_denoise_order(devImage, false)); RS_TRY(rs_denoise_order(devPBO)); }
-    if (std::getenv("RS_EXACT_GAMMA"))      // test switch: every pixel through the double-precision power
-        hipLaunchKernelGGL(k_send_image_to_pbo<true>, dim3((n + 255) / 256), dim3(256), 0, rs_stream(), (uchar4*)devPBO, devImage, n, toneMapping, scale);
-    else
-        hipLaunchKernelGGL(k_send_image_to_pbo<false>, dim3((n + 255) / 256), dim3(256), 0, rs_stream(), (uchar4*)devPBO, devImage, n, toneMapping, scale);
+    rs_dispatch([&](auto EXACT) {
+        hipLaunchKernelGGL(k_send_image_to_pbo<EXACT()>, dim3((n + 255) / 256), dim3(256), 0, rs_stream(), (uchar4*)devPBO, devImage, n, toneMapping, scale);
+    }, std::getenv("RS_EXACT_GAMMA") != nullptr);      // test switch: every pixel through the double-precision power
     if (onDenoiseStream.active) RS_TRY(rs_denoise_mark(devPBO, (size_t)n * 4, false));
     return rs_after_launch("copyImageToPBO");
 }

@@ -140,13 +140,7 @@ __global__ void __launch_bounds__(256, RS_WALK_WAVES) k_primary_split(DevScene s
 
 // GBuffer::render and the primary rays of ReSTIRDirect in one launch (asynchronous mode, when the render of this frame is
 // still pending -- rs_gbuffer_render_rows defers it), each ray stored as k_render_gbuffer / k_primary store it.
-// Frames at which the measured launch choice takes its time stamps: two launches until kTuneB, one fused launch from there to kTuneD; the
-// first span is frames kTuneA..kTuneB, the second kTuneC..kTuneD -- twelve frames each, and the four frames after every switch are not
-// timed: chains run up to four frames ahead of the library stream, so the frames around a switch carry the other form's kernels next to
-// them.  (Rounds 1-5 timed 2..8 against 8..14: on the Bistro-class scene, where the forms differ by 18 %, one run in four took the
-// slower one -- 2.10 instead of 1.78 ms per frame, profiles/r06_fuse_tuner_flips.log.)
-constexpr int kTuneA = 6, kTuneB = 18, kTuneC = 22, kTuneD = 34;
-constexpr long long kFuseMinWaves = kSmallLaunchWaves;     // three rounds of the chip's 8 192 wave slots (256 CUs x 4 SIMDs x 8 waves)
+// (when a frame takes this launch: rs_frame_plan.h)
 
 // The two rays of a pixel sit in two LANES: a wave takes an 8x4 block of pixels, lanes 0-31 walk their pixel-centre rays and lanes
 // 32-63 their jittered rays -- 64 rays in the ordinary one-ray-per-lane packet walk.  The two rays of a pixel visit almost the same
@@ -204,8 +198,7 @@ __global__ void __launch_bounds__(256, RS_WALK_WAVES) k_gbuffer_primary_split(De
 #define RS_RIS_THREADS 1024
 #endif
 constexpr int kRisThreads = RS_RIS_THREADS;
-constexpr int kRisLdsLights = 1024;
-constexpr int kRisAliasLdsLights = 16384;        // alias records only: 128 KB of the CU's 160 KB at most
+// (kRisLdsLights, kRisAliasLdsLights: rs_frame_plan.h, with the rule that picks the form)
 
 // TRACK (rs_restir_set_light_tracking): the winner's light-sampler index goes to candId as well (-1: no winner)
 template <bool ENV, bool SOBOL, bool TRACK, typename AliasPtr, typename LightPtr>
@@ -269,13 +262,9 @@ __device__ __forceinline__ void ris_rows(const DevScene& s, const SurfPlanes& sp
     ris_pixel<ENV, SOBOL, TRACK, const AliasRec*, const LightRec*>(s, sp, s.alias, s.lights, index, looper, candId);
 }
 
-template <bool ENV, bool SOBOL>
+template <bool ENV, bool SOBOL, bool TRACK>
 __global__ void __launch_bounds__(256) k_ris(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
-    ris_rows<ENV, SOBOL, false>(s, sp, width, y0, y1, looper, candId);
-}
-template <bool ENV, bool SOBOL>
-__global__ void __launch_bounds__(256) k_ris_tracked(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
-    ris_rows<ENV, SOBOL, true>(s, sp, width, y0, y1, looper, candId);
+    ris_rows<ENV, SOBOL, TRACK>(s, sp, width, y0, y1, looper, candId);
 }
 
 template <bool SOBOL, bool TRACK>
@@ -841,7 +830,7 @@ int rs_restir_free(rs_restir* r) {
     for (auto& e : r->ev) if (e) (void)hipEventDestroy(e);
     for (auto& pair : r->spatialEv) for (hipEvent_t& e : pair) if (e) (void)hipEventDestroy(e);
     for (auto& e : r->surfFree) if (e) (void)hipEventDestroy(e);
-    for (auto& e : r->tuneEv) if (e) (void)hipEventDestroy(e);
+    for (auto& e : r->tune.ev) if (e) (void)hipEventDestroy(e);
     if (r->auxFork) (void)hipEventDestroy(r->auxFork);
     if (r->auxDone) (void)hipEventDestroy(r->auxDone);
     delete r;
@@ -875,7 +864,7 @@ int rs_restir_init(int width, int height, rs_restir** out) {
         if (!e) e = rs_check_hip(hipMemset(f.rngMat, 0, n * 8), "memset");
     }
     for (auto& ev : r->surfFree) if (!e) e = rs_check_hip(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-    for (auto& ev : r->tuneEv) if (!e) e = rs_check_hip(hipEventCreate(&ev), "hipEventCreate");
+    for (auto& ev : r->tune.ev) if (!e) e = rs_check_hip(hipEventCreate(&ev), "hipEventCreate");
     if (!e) e = rs_check_hip(hipEventCreateWithFlags(&r->auxFork, hipEventDisableTiming), "hipEventCreate");
     if (!e) e = rs_check_hip(hipEventCreateWithFlags(&r->auxDone, hipEventDisableTiming), "hipEventCreate");
     if (!e) e = rs_dev_alloc(&r->dRayCount, 2 * (size_t)kRaySlots * kRaySub * kRayStride);     // working slots, then published slots
@@ -969,31 +958,17 @@ int rs_restir_spatial_times(rs_restir* r, float* ms, int capacity, int* count) {
 }  // extern "C"
 
 namespace {
-// RIS over the light table for rows [y0, y1) on stream st; alone: nothing runs next to it (picks the alias-in-LDS form for large tables)
+// RIS over the light table for rows [y0, y1) on stream st in the form the plan names (RS_RIS_*, rs_frame_plan.h)
 // candId: the winners' light-sampler indices (light tracking), null = not tracked
-int launch_ris(const rs_scene* scene, const SurfPlanes& sp, int W, int y0, int y1, int looper, bool sobol, hipStream_t st, bool alone, int* candId) {
+int launch_ris(const rs_scene* scene, const SurfPlanes& sp, int W, int y0, int y1, int looper, bool sobol, hipStream_t st, int form, int* candId) {
     const bool track = candId != nullptr;
     const int npx = (y1 - y0) * W;
-    // The LDS form runs one 1024-thread block per copy of the table: a launch of a few dozen blocks leaves most CUs idle and lasts as
-    // long as one block.  Below 64 Ki pixels the table is read from global memory by 256-thread blocks, which spread evenly.  (Round 2
-    // drew the line at 384 Ki pixels -- a 1/8 strip of 1080p 0.241 -> 0.231 ms per frame with the global table; measured again in round 5
-    // through rs_strips_frame the LDS form wins on every rank of that split, 0.193 -> 0.191 ms on the heaviest strip and 0.149 -> 0.130 on
-    // the lightest, whose chain is mostly RIS: profiles/r05_ab_strip_knobs.log.)
-    // Alone the alias-in-LDS form is a third faster (config 5: 645 -> 455 us); inside overlapped frames it is slower (1.88 -> 1.95 ms per
-    // frame: one 1024-thread block with 82 KB of LDS per CU keeps the other streams' kernels off that CU), so it is taken when the
-    // kernels run one after the other on the library stream only (`alone`; A/B in profiles/r03_ab_config5_ris_alias_lds.log).
-    const int risGlobalBelow = rs_ris_global_below();           // 64 Ki pixels unless rs_set_ris_table_pixels says otherwise
-    if (scene->numLights > 0 && scene->numLights <= kRisLdsLights && npx >= risGlobalBelow && scene->envMapTexId < 0)
+    const dim3 grid((npx + kRisThreads - 1) / kRisThreads);
+    if (form == RS_RIS_LDS)
         // (one block per CU instead of two -- half of the wave slots left to the latency-bound kernels of the other streams -- measured
         // slower: frame 1.088 -> 1.142 ms, profiles/r03_ab_ris_blocks_per_cu.log)
-    {
-        const dim3 grid((npx + kRisThreads - 1) / kRisThreads);
-        if (track) { if (sobol) hipLaunchKernelGGL((k_ris_lds<true, true>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, candId);
-                     else hipLaunchKernelGGL((k_ris_lds<false, true>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, candId); }
-        else { if (sobol) hipLaunchKernelGGL((k_ris_lds<true, false>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, candId);
-               else hipLaunchKernelGGL((k_ris_lds<false, false>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, candId); }
-    }
-    else if (scene->envMapTexId < 0 && scene->numLights > kRisLdsLights && scene->numLights <= kRisAliasLdsLights && npx >= risGlobalBelow && alone) {
+        rs_dispatch([&](auto SOBOL, auto TRACK) { hipLaunchKernelGGL((k_ris_lds<SOBOL(), TRACK()>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, candId); }, sobol, track);
+    else if (form == RS_RIS_ALIAS_LDS) {
         const size_t lds = (size_t)scene->numLights * sizeof(AliasRec);
         static const bool ldsAllowed = []{      // more than 64 KB of dynamic LDS is opt-in
             bool ok = true;
@@ -1003,16 +978,11 @@ int launch_ris(const rs_scene* scene, const SurfPlanes& sp, int W, int y0, int y
             (void)hipGetLastError();
             return ok; }();
         (void)ldsAllowed;
-        const dim3 grid((npx + kRisThreads - 1) / kRisThreads);
-        if (track) { if (sobol) hipLaunchKernelGGL((k_ris_alias_lds<true, true>), grid, dim3(kRisThreads), lds, st, scene->dev, sp, W, y0, y1, looper, candId);
-                     else hipLaunchKernelGGL((k_ris_alias_lds<false, true>), grid, dim3(kRisThreads), lds, st, scene->dev, sp, W, y0, y1, looper, candId); }
-        else { if (sobol) hipLaunchKernelGGL((k_ris_alias_lds<true, false>), grid, dim3(kRisThreads), lds, st, scene->dev, sp, W, y0, y1, looper, candId);
-               else hipLaunchKernelGGL((k_ris_alias_lds<false, false>), grid, dim3(kRisThreads), lds, st, scene->dev, sp, W, y0, y1, looper, candId); }
+        rs_dispatch([&](auto SOBOL, auto TRACK) { hipLaunchKernelGGL((k_ris_alias_lds<SOBOL(), TRACK()>), grid, dim3(kRisThreads), lds, st, scene->dev, sp, W, y0, y1, looper, candId); }, sobol, track);
     }
-    else {                             // the environment map is one more light (scene.h:400-403)
-        if (track) RS_LAUNCH2(k_ris_tracked, scene->envMapTexId >= 0, sobol, dim3((npx + 255) / 256), dim3(256), st, scene->dev, sp, W, y0, y1, looper, candId);
-        else RS_LAUNCH2(k_ris, scene->envMapTexId >= 0, sobol, dim3((npx + 255) / 256), dim3(256), st, scene->dev, sp, W, y0, y1, looper, candId);
-    }
+    else                               // the environment map is one more light (scene.h:400-403)
+        rs_dispatch([&](auto ENV, auto SOBOL, auto TRACK) { hipLaunchKernelGGL((k_ris<ENV(), SOBOL(), TRACK()>), dim3((npx + 255) / 256), dim3(256), 0, st, scene->dev, sp, W, y0, y1, looper, candId); },
+                    scene->envMapTexId >= 0, sobol, track);
     return 0;
 }
 
@@ -1032,68 +1002,44 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     // frame's own set of surface planes: in asynchronous mode they go to an auxiliary stream, ordered after the frame
     // that last used the set (or, for a second call within one frame, after everything enqueued so far), and the library
     // stream joins them before the temporal pass.  Their heavy-tile tails then overlap the other frame's passes.
+    // Which stream, which launches and which forms is rs_plan_phase_a's answer (rs_frame_plan.h) to what is gathered here.
     const rs_context* plan = rs_stream_plan();                  // rs_set_stream_plan (defaults: two chain streams, small launches on three, shadow rays of large launches on the library stream)
-    const bool parityStreams = plan->chainStreams == 2;
-    const bool asyncMode = r->timing != 1 && rs_aux_stream(1) != nullptr;
-    const int W = r->width;
-    const int tilesX = (W + 31) / 32, tilesY = (y1 > y0 ? y1 - y0 + 7 : 0) / 8;
-    // A render of this frame that rs_gbuffer_render_rows deferred (asynchronous mode) can be launched here, in ONE launch with the
-    // primary rays (k_gbuffer_primary): same scene and camera, rows that contain the rows shaded here.
-    //  * A launch that fills the chip at least three times over: ~5 % less work than two launches, longer waves; the frame period is
-    //    measured both ways once per scene and the faster form kept (full 1080p frame: the fused launch, by 0.5 %).
-    //  * A smaller launch -- a strip -- lasts as long as its slowest wave, and what bounds its frame rate is the length of the chain
-    //    primary rays -> RIS -> shadow rays over the number of chains in flight.  With two chains the fused launch loses (its slowest
-    //    wave: 0.25 ms against 0.18 on a 1/8 strip), but it leaves the render's stream idle, and with that stream as a THIRD chain
-    //    it wins: 8 strips of 1080p 5.96x -> 6.5x (rs_set_stream_plan(-1, 0, -1): two chains and a separate render).
-    // Whenever the launch is fused the frame's chain is one of three (a full frame gains another 0.9 % from the third).
-    const bool smallChains = plan->smallChains != 0;
     const rs_gbuffer::Deferred& d = g->deferred;
-    const int fuseMode = rs_fuse_mode();
-    const bool fusable = asyncMode && fuseMode != 0 && y1 > y0 && d.valid && d.scene == scene && std::memcmp(&d.cam, cam, sizeof(rs_camera)) == 0 &&
-                         d.y0 <= y0 && d.y1 >= y1;
-    const bool large = fusable && (long long)tilesX * ((d.y1 - d.y0 + 7) / 8) * 4 >= kFuseMinWaves;
-    const bool small = fusable && !large && smallChains && parityStreams && fuseMode == 3 && r->phaseACalls == 0;
-    bool fuse = fusable && (small || large || fuseMode == 2);
-    // (with a denoise stream the render's own stream is that stream: a separate render would queue behind the previous frame's filter)
-    const bool denoiseStream = asyncMode && rs_ctx()->denoiseMode == 1;
-    if (fuse && large && fuseMode == 3 && !denoiseStream) {        // measured choice (end_frame advances the measurement)
-        if (r->tuneSceneId != scene->id) { r->tuneSceneId = scene->id; r->tuneFrame = 0; r->tuneChoice = -1; }
-        r->tuneCounted = true;
-        fuse = r->tuneChoice >= 0 ? r->tuneChoice == 1 : (r->tuneFrame >= kTuneB && r->tuneFrame < kTuneD);
-    }
-    int kThreeStreams[rs_restir::kSmallChains];                 // the chain streams first, the render's stream (idle after a fused launch) last
-    for (int i = 0; i < rs_restir::kSmallChains; i++) kThreeStreams[i] = i < 2 ? 1 + i : i == 2 ? 0 : i;
-    // A frame whose render request was answered from retained planes (rs_gbuffer_render_rows) launched nothing on the render's stream
-    // either: it is idle for the same reason, and the frame's chain is one of three as well.  (RS_REUSE_CHAINS=2: A/B switch, two chains.)
     static const bool reusedThree = [] { const char* e = std::getenv("RS_REUSE_CHAINS"); return !(e && std::atoi(e) == 2); }();
-    const bool reused = asyncMode && g->reusedFrame && !d.valid && !denoiseStream && y1 > y0;
-    const bool three = (fuse || (reused && reusedThree)) && parityStreams && r->phaseACalls == 0;
-    // The measured choice compares spans of consecutive frames that each had a render to fuse: a reused frame in between is not
-    // one of them, so a measurement under way starts again with the next real render.  (A still camera never decides it.)
-    if (reused && r->phaseACalls == 0 && r->tuneChoice < 0) r->tuneFrame = 0;
-    // (a context that keeps another stream busy next to the frames -- the strip driver with its transfers on a stream of their own, the
-    // denoise stream -- leaves room for two chains, or one: four streams that hand events to each other is what the device runs side by
-    // side, rs_chains_in_flight)
-    const int inFlight = rs_chains_in_flight();
-    const int chainSlot = three ? kThreeStreams[inFlight >= rs_restir::kSmallChains ? r->smallChain : inFlight == 2 ? r->chain : 0] : 0;
-    const hipStream_t aux = asyncMode ? rs_aux_stream(three ? chainSlot : (parityStreams && inFlight >= 2) ? 1 + r->chain : 1) : nullptr;
-    r->lastFused = fuse ? 1 : 0;
-    r->lastChains = !aux ? 0 : three ? (inFlight < rs_restir::kSmallChains ? inFlight : rs_restir::kSmallChains) : (parityStreams && inFlight >= 2) ? rs_restir::kChains : 1;
-    const hipStream_t st = aux ? aux : rs_stream();
-    const int splitSlot = !aux ? 0 : 1 + (three ? chainSlot : (parityStreams && inFlight >= 2) ? 1 + r->chain : 1);     // the hints of the stream this launch goes to (rs_tilesplit.h)
-    const int splitCall = r->phaseACalls < 2 ? r->phaseACalls : 2;
-    // One frame at a time -- a caller that waits for every frame before it enqueues the next (preview.cpp:337-361) -- has nothing running
-    // next to this frame's kernels, like the synchronous mode: a launch lasts as long as its longest tile and RIS has the CUs to itself, so
-    // it takes that mode's forms (heavy tiles split four ways, the alias table in LDS for large light sets).  Asked of the previous frame's
-    // end event, never waited for: config 5 one frame in flight 3.34 -> 2.6 ms (synchronous 2.84).
-    bool idle = false;
-    if (aux && r->phaseACalls == 0) {
+    const int W = r->width;
+    rs_phase_a_inputs in{};
+    in.async = r->timing != 1 && rs_aux_stream(1) != nullptr;
+    in.chainStreams = plan->chainStreams; in.smallChains = plan->smallChains; in.shadowOnMain = plan->shadowOnMain;
+    in.fuseMode = rs_fuse_mode();
+    in.denoiseStream = rs_ctx()->denoiseMode == 1;
+    in.chainsInFlight = rs_chains_in_flight();
+    in.reusedThree = reusedThree;
+    in.phaseACalls = r->phaseACalls;
+    in.width = W; in.y0 = y0; in.y1 = y1;
+    in.deferredValid = d.valid;
+    in.deferredMatches = d.valid && d.scene == scene && std::memcmp(&d.cam, cam, sizeof(rs_camera)) == 0;
+    in.deferredY0 = d.y0; in.deferredY1 = d.y1;
+    in.reusedFrame = g->reusedFrame;
+    in.tuneChoice = r->tune.choice_for(scene->id); in.tuneFrame = r->tune.frame_for(scene->id);
+    in.chain = r->chain; in.smallChain = r->smallChain;
+    // one frame at a time?  (two frames in a row: a pipelined caller whose device catches up once keeps its forms)
+    if (in.async && r->phaseACalls == 0) {
         const int prevSet = (r->surfSet + rs_restir::kSurfSets - 1) % rs_restir::kSurfSets;
         const bool finished = !r->surfFreeValid[prevSet] || hipEventQuery(r->surfFree[prevSet]) == hipSuccess;
-        r->idleStreak = finished ? (r->idleStreak < 2 ? r->idleStreak + 1 : 2) : 0;      // (two frames in a row: a pipelined caller whose device catches up once keeps its forms)
-        r->idleFrame = idle = r->idleStreak >= 2;
+        r->idleStreak = finished ? (r->idleStreak < 2 ? r->idleStreak + 1 : 2) : 0;
+        r->idleFrame = r->idleStreak >= 2;
     }
-    else if (aux) idle = r->idleFrame;
+    in.idle = in.async && r->idleFrame;
+    in.numLights = scene->numLights; in.envMap = scene->envMapTexId >= 0; in.risGlobalBelow = rs_ris_global_below();
+    rs_phase_a_plan p;
+    rs_plan_phase_a(in, p);
+    hipStream_t aux = p.stream >= 0 ? rs_aux_stream(p.stream) : nullptr;
+    if (p.stream >= 0 && !aux) { in.async = in.idle = 0; rs_plan_phase_a(in, p); }      // (that stream could not be created: the synchronous forms)
+    if (p.tuneCounted) r->tune.count(scene->id);
+    if (p.tuneRestart) r->tune.restart();
+    r->lastFused = p.fuse; r->lastChains = p.lastChains;
+    const hipStream_t st = aux ? aux : rs_stream();
+    const int tilesX = p.tilesX, tilesY = p.tilesY;
     if (aux) {
         if (r->phaseACalls > 0) {
             RS_HIP(hipEventRecord(r->auxFork, rs_stream()));
@@ -1109,46 +1055,47 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     }
     const SurfPlanes sp = surf_of(r);
     const CamParams cp = rs_make_cam_params(cam);
+    const bool tex = scene->textured;
+    rs_tile_split* hints = &r->split[p.splitSlot][p.splitCall];
     mark(r, 0);
-    if (fuse) {
+    if (p.fuse) {
         RS_TRY(rs_gbuffer_order_before_render(g, aux));
         rs_gbuffer_deferred_taken(g);
         const int c = g->cur();
         const GBufWrite gw{ g->albedo[c], g->motion[c], g->normal[c], g->primId[c], g->depth[c] };
-        const int gTilesY = (d.y1 - d.y0 + 3) / 4;                // 8x4-pixel tiles: two rays per pixel fill the wave
+        const int gTilesY = p.fusedTilesY;
         const CamParams lp = rs_make_cam_params(&d.lastCam);
         TileSplit ts; int helpers = 0;
-        RS_TRY(rs_tile_split_prepare(&r->split[splitSlot][splitCall], ((((long long)1 << 20 | d.y0) << 20 | d.y1) << 12 | tilesX) ^ ((long long)(y0 * 4099 + y1) << 44), tilesX * 4 * gTilesY, tilesX * gTilesY, (!aux || idle) ? 1 : ((long long)tilesX * gTilesY * 4 < kSplitSmallWaves ? 2 : 0), st, &ts, &helpers));
-        if (ts.base) RS_LAUNCH2(k_gbuffer_primary_split, scene->textured, sobol, dim3(helpers + tilesX * gTilesY), dim3(256), st, scene->dev, cp, lp, gw, sp, looper, d.y0, d.y1, y0, y1, tilesX, rayCounter, ts);
-        else RS_LAUNCH2(k_gbuffer_primary, scene->textured, sobol, dim3(tilesX * gTilesY), dim3(256), st, scene->dev, cp, lp, gw, sp, looper, d.y0, d.y1, y0, y1, tilesX, rayCounter);
+        RS_TRY(rs_tile_split_prepare(hints, ((((long long)1 << 20 | d.y0) << 20 | d.y1) << 12 | tilesX) ^ ((long long)(y0 * 4099 + y1) << 44), tilesX * 4 * gTilesY, tilesX * gTilesY, p.splitMode, st, &ts, &helpers));
+        rs_dispatch([&](auto TEX, auto SOBOL) {
+            if (ts.base) hipLaunchKernelGGL((k_gbuffer_primary_split<TEX(), SOBOL()>), dim3(helpers + tilesX * gTilesY), dim3(256), 0, st, scene->dev, cp, lp, gw, sp, looper, d.y0, d.y1, y0, y1, tilesX, rayCounter, ts);
+            else hipLaunchKernelGGL((k_gbuffer_primary<TEX(), SOBOL()>), dim3(tilesX * gTilesY), dim3(256), 0, st, scene->dev, cp, lp, gw, sp, looper, d.y0, d.y1, y0, y1, tilesX, rayCounter);
+        }, tex, sobol);
         RS_HIP(hipEventRecord(g->doneEv, aux));              // the planes are ready when this kernel is
         g->pending = true;
     }
     else {
         TileSplit ts; int helpers = 0;
-        RS_TRY(rs_tile_split_prepare(&r->split[splitSlot][splitCall], (((long long)y0 << 20 | y1) << 12 | tilesX), tilesX * 4 * tilesY, tilesX * tilesY, (!aux || idle) ? 1 : ((long long)tilesX * tilesY * 4 < kSplitSmallWaves ? 2 : 0), st, &ts, &helpers));
-        if (ts.base) RS_LAUNCH2(k_primary_split, scene->textured, sobol, dim3(helpers + tilesX * tilesY), dim3(256), st, scene->dev, cp, sp, looper, y0, y1, tilesX, rayCounter, ts);
-        else RS_LAUNCH2(k_primary, scene->textured, sobol, dim3(tilesX * tilesY), dim3(256), st, scene->dev, cp, sp, looper, y0, y1, tilesX, rayCounter);
+        RS_TRY(rs_tile_split_prepare(hints, (((long long)y0 << 20 | y1) << 12 | tilesX), tilesX * 4 * tilesY, tilesX * tilesY, p.splitMode, st, &ts, &helpers));
+        rs_dispatch([&](auto TEX, auto SOBOL) {
+            if (ts.base) hipLaunchKernelGGL((k_primary_split<TEX(), SOBOL()>), dim3(helpers + tilesX * tilesY), dim3(256), 0, st, scene->dev, cp, sp, looper, y0, y1, tilesX, rayCounter, ts);
+            else hipLaunchKernelGGL((k_primary<TEX(), SOBOL()>), dim3(tilesX * tilesY), dim3(256), 0, st, scene->dev, cp, sp, looper, y0, y1, tilesX, rayCounter);
+        }, tex, sobol);
     }
     mark(r, 1);
     const int npx = (y1 - y0) * W;
-    RS_TRY(launch_ris(scene, sp, W, y0, y1, looper, sobol, st, !aux || idle, r->track ? r->candId[r->surfSet] : nullptr));
+    RS_TRY(launch_ris(scene, sp, W, y0, y1, looper, sobol, st, p.risForm, r->track ? r->candId[r->surfSet] : nullptr));
     mark(r, 2);
-    // The shadow rays of a launch that fills the chip several times over go to the library stream, behind the previous frame's
-    // spatial pass: every stream then has slack against the frame period and three or four kernels are in flight at any time,
-    // which is what a frame bound by VALU issue needs (1080p: 1.277 -> 1.245 ms).  A small launch -- a strip -- lasts as long as its
-    // slowest wave, and there the library stream is the one chain that links consecutive frames: its shadow rays stay on the
-    // frame's own chain (8 strips of 1080p: 0.235 ms against 0.270).  rs_set_stream_plan(-1, -1, 0 / 1): never / always.
-    const int shadowOnMain = plan->shadowOnMain;
-    const bool shadowMain = aux && (shadowOnMain == 1 || (shadowOnMain == 2 && (long long)tilesX * tilesY * 4 >= kFuseMinWaves));
-    if (!shadowMain) hipLaunchKernelGGL(k_shadow, dim3(tilesX * tilesY), dim3(256), 0, st, scene->dev, sp, W, y0, y1, tilesX);
+    // (the shadow rays of a launch that fills the chip several times over go to the library stream: rs_frame_plan.h)
+    if (!p.shadowOnLibrary) hipLaunchKernelGGL(k_shadow, dim3(tilesX * tilesY), dim3(256), 0, st, scene->dev, sp, W, y0, y1, tilesX);
     if (aux) {
         RS_TRY(rs_check_hip(hipGetLastError(), "ReSTIR Direct (primary / RIS / shadow rays)"));
         RS_HIP(hipEventRecord(r->auxDone, aux));
         RS_HIP(hipStreamWaitEvent(rs_stream(), r->auxDone, 0));
     }
-    if (shadowMain) hipLaunchKernelGGL(k_shadow, dim3(tilesX * tilesY), dim3(256), 0, rs_stream(), scene->dev, sp, W, y0, y1, tilesX);
+    if (p.shadowOnLibrary) hipLaunchKernelGGL(k_shadow, dim3(tilesX * tilesY), dim3(256), 0, rs_stream(), scene->dev, sp, W, y0, y1, tilesX);
     RS_TRY(rs_gbuffer_join(g));                                 // first consumer of the G-buffer planes
+    LightIds ids{ nullptr, nullptr, nullptr, nullptr, nullptr, 0, -1 };
     if (r->track) {
         // the light indices of another scene's reservoirs name other lights: unknown from here on
         if (r->trackSceneId != scene->id) {
@@ -1156,19 +1103,12 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
             RS_HIP(hipMemsetAsync(r->idTemp, 0xff, (size_t)W * r->height * sizeof(int), rs_stream()));
             r->trackSceneId = scene->id;
         }
-        const LightIds ids{ r->candId[r->surfSet], r->idLast, r->idCur, r->idTemp, scene->dev.lights, scene->numLights, scene->envMapTexId >= 0 ? scene->numLights - 1 : -1 };
-        if (sobol) hipLaunchKernelGGL((k_temporal<true, true>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g),
-                                      r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, ids);
-        else hipLaunchKernelGGL((k_temporal<false, true>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g),
-                                r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, ids);
+        ids = LightIds{ r->candId[r->surfSet], r->idLast, r->idCur, r->idTemp, scene->dev.lights, scene->numLights, scene->envMapTexId >= 0 ? scene->numLights - 1 : -1 };
     }
-    else {
-        const LightIds none{ nullptr, nullptr, nullptr, nullptr, nullptr, 0, -1 };
-        if (sobol) hipLaunchKernelGGL((k_temporal<true, false>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g),
-                                      r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, none);
-        else hipLaunchKernelGGL((k_temporal<false, false>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g),
-                                r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, none);
-    }
+    rs_dispatch([&](auto SOBOL, auto TRACK) {
+        hipLaunchKernelGGL((k_temporal<SOBOL(), TRACK()>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g),
+                           r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, ids);
+    }, sobol, r->track);
     mark(r, 3);
     return last ? rs_after_launch("ReSTIR Direct (phase A)") : rs_check_hip(hipGetLastError(), "ReSTIR Direct (phase A)");
 }
@@ -1187,17 +1127,41 @@ int phase_b_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     // timing 2: the pass of every frame between two events of a ring, never waited for here (rs_restir_spatial_times reads them later)
     const int slot = r->timing == 2 ? r->spatialNext % rs_restir::kSpatialRing : -1;
     if (slot >= 0) RS_HIP(hipEventRecord(r->spatialEv[slot][0], rs_stream()));
-    if (r->probe)
-        RS_LAUNCH1(k_spatial_shade_probe, scene->dev.sampleSeq != nullptr, dim3(numTiles), dim3(kBThreads), rs_stream(), scene->dev, surf_of(r), gbuf_view(g),
-                   r->cur, r->temp, devDirectIllum, iter, r->looper, reuse, y0, y1, tilesX, numTiles);
-    else
-        RS_LAUNCH1(k_spatial_shade, scene->dev.sampleSeq != nullptr, dim3(numTiles), dim3(kBThreads), rs_stream(), scene->dev, surf_of(r), gbuf_view(g),
-                   r->cur, r->temp, devDirectIllum, iter, r->looper, reuse, y0, y1, tilesX, numTiles);
+    rs_dispatch([&](auto SOBOL) {
+        if (r->probe) hipLaunchKernelGGL((k_spatial_shade_probe<SOBOL()>), dim3(numTiles), dim3(kBThreads), 0, rs_stream(), scene->dev, surf_of(r), gbuf_view(g),
+                                         r->cur, r->temp, devDirectIllum, iter, r->looper, reuse, y0, y1, tilesX, numTiles);
+        else hipLaunchKernelGGL((k_spatial_shade<SOBOL()>), dim3(numTiles), dim3(kBThreads), 0, rs_stream(), scene->dev, surf_of(r), gbuf_view(g),
+                                r->cur, r->temp, devDirectIllum, iter, r->looper, reuse, y0, y1, tilesX, numTiles);
+    }, scene->dev.sampleSeq != nullptr);
     if (slot >= 0) { RS_HIP(hipEventRecord(r->spatialEv[slot][1], rs_stream())); r->spatialNext++; }
     mark(r, 4);
     return last ? rs_after_launch("ReSTIR Direct (phase B)") : rs_check_hip(hipGetLastError(), "ReSTIR Direct (phase B)");
 }
 }  // namespace
+
+// the measurement of rs_fuse_mode() == 3: time stamps on the library stream where frames kTuneA .. kTuneD end (two launches up to
+// kTuneB, one fused launch from there to kTuneD; the spans kTuneA-kTuneB and kTuneC-kTuneD are compared); from frame kTuneD on every
+// frame end asks (hipEventQuery, no wait) whether the last stamp has been reached, and the shorter span decides; until then frames take
+// two launches.  A caller that times frames runs kTuneD + 2 frames and a synchronisation first (bench.py does, before its warm-up) and
+// then sees one launch form only.
+int rs_fuse_tuner::end_frame(hipStream_t st) {
+    if (counted && choice < 0) {
+        const int f = ++frame;
+        if (f == kTuneA || f == kTuneB || f == kTuneC || f == kTuneD) RS_HIP(hipEventRecord(ev[f == kTuneA ? 0 : f == kTuneB ? 1 : f == kTuneC ? 2 : 3], st));
+        if (f >= kTuneD) {                                          // never a host wait: the stamp is asked for at every frame end until it is there
+            float separate = 0.f, fused = 0.f;
+            const hipError_t q = hipEventQuery(ev[3]);
+            if (q == hipSuccess) {
+                if (hipEventElapsedTime(&separate, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&fused, ev[2], ev[3]) == hipSuccess)
+                    choice = fused < separate ? 1 : 0;
+                else { (void)hipGetLastError(); choice = 0; }
+            }
+            else if (q != hipErrorNotReady) { (void)hipGetLastError(); choice = 0; }
+        }
+    }
+    counted = false;
+    return 0;
+}
 
 extern "C" {
 
@@ -1222,12 +1186,19 @@ int rs_restir_last_launch(const rs_restir* r, int* fused, int* chains) {
     return 0;
 }
 
+// the plan of a phase-A call (rs_frame_plan.h) for inputs the caller fills in: no device, no context, no object
+int rs_debug_phase_a_plan(const rs_phase_a_inputs* in, rs_phase_a_plan* out) {
+    if (!in || !out) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_phase_a_plan: null argument");
+    rs_plan_phase_a(*in, *out);
+    return 0;
+}
+
 // 0 two launches, 1 one fused launch, -1 still measuring, -2 nothing measured (no frame so far had a launch the measurement applies
 // to: synchronous launches, a forced mode, launches below three rounds of wave slots -- those are fused without one)
 int rs_restir_launch_choice(const rs_restir* r, int* choice) {
     RS_SCOPE(r);
     if (!r || !choice) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_launch_choice: null argument");
-    *choice = r->tuneChoice >= 0 ? r->tuneChoice : (r->tuneFrame > 0 || r->tuneCounted) ? -1 : -2;
+    *choice = r->tune.reported();
     return 0;
 }
 
@@ -1244,27 +1215,7 @@ int rs_restir_end_frame(rs_restir* r) {
     r->chain = (r->chain + 1) % rs_restir::kChains;
     r->smallChain = (r->smallChain + 1) % rs_restir::kSmallChains;
     r->phaseACalls = 0;
-    // the measurement of rs_fuse_mode() == 3: time stamps on the library stream where frames kTuneA .. kTuneD end (two launches up to
-    // kTuneB, one fused launch from there to kTuneD; the spans kTuneA-kTuneB and kTuneC-kTuneD are compared); from frame kTuneD on every
-    // frame end asks (hipEventQuery, no wait) whether the last stamp has been reached, and the shorter span decides; until then frames take
-    // two launches.  A caller that times frames runs kTuneD + 2 frames and a synchronisation first (bench.py does, before its warm-up) and
-    // then sees one launch form only.
-    if (r->tuneCounted && r->tuneChoice < 0) {
-        const int f = ++r->tuneFrame;
-        if (f == kTuneA || f == kTuneB || f == kTuneC || f == kTuneD) RS_HIP(hipEventRecord(r->tuneEv[f == kTuneA ? 0 : f == kTuneB ? 1 : f == kTuneC ? 2 : 3], rs_stream()));
-        if (f >= kTuneD) {                                          // never a host wait: the stamp is asked for at every frame end until it is there
-            float separate = 0.f, fused = 0.f;
-            const hipError_t q = hipEventQuery(r->tuneEv[3]);
-            if (q == hipSuccess) {
-                if (hipEventElapsedTime(&separate, r->tuneEv[0], r->tuneEv[1]) == hipSuccess && hipEventElapsedTime(&fused, r->tuneEv[2], r->tuneEv[3]) == hipSuccess)
-                    r->tuneChoice = fused < separate ? 1 : 0;
-                else { (void)hipGetLastError(); r->tuneChoice = 0; }
-            }
-            else if (q != hipErrorNotReady) { (void)hipGetLastError(); r->tuneChoice = 0; }
-        }
-    }
-    r->tuneCounted = false;
-    return 0;
+    return r->tune.end_frame(rs_stream());
 }
 
 // (A synchronous ReSTIRDirect as a software pipeline over bands of rows -- primary rays / RIS / shadow rays of consecutive bands on three

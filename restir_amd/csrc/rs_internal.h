@@ -4,9 +4,14 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <type_traits>
 #ifndef RS_AUX_STREAMS
 #define RS_AUX_STREAMS 3
 #endif
+#ifndef RS_SPLIT_SMALL_ROUNDS
+#define RS_SPLIT_SMALL_ROUNDS 3
+#endif
+#include "rs_frame_plan.h"
 #ifndef RS_GBUF_SETS
 #define RS_GBUF_SETS (RS_AUX_STREAMS + 2)
 #endif
@@ -120,19 +125,15 @@ static inline void rs_dev_free(T*& p) {
     if (p) { (void)hipFree((void*)p); p = nullptr; }
 }
 
-// kernel<A, B> for two run-time booleans (TEX / ENV x SOBOL variants)
-#define RS_LAUNCH2(kernel, a, b, grid, block, stream, ...)                                                          \
-    do {                                                                                                            \
-        if (a) { if (b) hipLaunchKernelGGL((kernel<true, true>), grid, block, 0, stream, __VA_ARGS__);              \
-                 else   hipLaunchKernelGGL((kernel<true, false>), grid, block, 0, stream, __VA_ARGS__); }           \
-        else   { if (b) hipLaunchKernelGGL((kernel<false, true>), grid, block, 0, stream, __VA_ARGS__);             \
-                 else   hipLaunchKernelGGL((kernel<false, false>), grid, block, 0, stream, __VA_ARGS__); }          \
-    } while (0)
-#define RS_LAUNCH1(kernel, a, grid, block, stream, ...)                                                             \
-    do {                                                                                                            \
-        if (a) hipLaunchKernelGGL((kernel<true>), grid, block, 0, stream, __VA_ARGS__);                             \
-        else   hipLaunchKernelGGL((kernel<false>), grid, block, 0, stream, __VA_ARGS__);                            \
-    } while (0)
+// Run-time booleans as template arguments: f is called once, with a std::true_type / std::false_type per boolean --
+//   rs_dispatch([&](auto TEX, auto SOBOL) { hipLaunchKernelGGL((kernel<TEX(), SOBOL()>), grid, block, 0, stream, args...); }, tex, sobol);
+template <typename F>
+inline void rs_dispatch(F&& f) { f(); }
+template <typename F, typename... Bools>
+inline void rs_dispatch(F&& f, bool b, Bools... rest) {
+    if (b) rs_dispatch([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else rs_dispatch([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
 // The Sobol branch indexes its table by the caller's looper (State::looper, kept below SobolSampleNum by the reference's
 // `(looper + 1) % SobolSampleNum`, restir.cu:441-445): a looper outside the table is refused instead of read.
 int rs_check_looper(const struct rs_scene* scene, int looper, const char* what);
@@ -163,12 +164,8 @@ struct rs_tile_split {
 //      -> 1024: measured better than 768 on strips), and only while it finds heavy tiles: the kernels that count cost a scene
 //      without any (the Sponza-class strips) 1.3 %, so a site whose last fresh report says "none" runs the plain kernels for
 //      kTileSplitSleep launches before it looks again.
+// (which mode a launch takes: rs_split_mode, rs_frame_plan.h)
 int rs_tile_split_prepare(rs_tile_split* t, long long key, int numTiles, int regularBlocks, int mode, hipStream_t st, rs::TileSplit* ts, int* helperBlocks);
-constexpr long long kSmallLaunchWaves = 3 * 8192;   // three rounds of the chip's 8 192 wave slots (256 CUs x 4 SIMDs x 8 waves)
-#ifndef RS_SPLIT_SMALL_ROUNDS
-#define RS_SPLIT_SMALL_ROUNDS 3
-#endif
-constexpr long long kSplitSmallWaves = (long long)RS_SPLIT_SMALL_ROUNDS * 8192;   // launches below this many waves split their heavy tiles also when other kernels run next to them
 void rs_tile_split_free(rs_tile_split* t);
 int rs_tile_split_threshold();                      // of the current context
 
@@ -425,6 +422,23 @@ struct TempPlanes {
     float4* tap = nullptr;
 };
 
+// one traversal for the G-buffer ray and the shading ray of a pixel, or two?  Measured once per scene (rs_fuse_mode() == 3):
+// frames 6..17 with two launches against 22..33 with one (the four frames after each switch are not timed), by events on the library stream at the frame ends
+struct rs_fuse_tuner {
+    unsigned long long sceneId = 0;
+    int frame = 0;                   // frames with a fusable launch since tuning began
+    int choice = -1;                 // -1 measuring, 0 separate, 1 fused
+    bool counted = false;            // this frame had a launch the choice applies to
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    // what a frame of `scene` sees of the measurement (another scene's: one that has not begun), rs_tuned_fuse() of which is the form it takes
+    int choice_for(unsigned long long scene) const { return sceneId == scene ? choice : -1; }
+    int frame_for(unsigned long long scene) const { return sceneId == scene ? frame : 0; }
+    void count(unsigned long long scene) { if (sceneId != scene) { sceneId = scene; frame = 0; choice = -1; } counted = true; }
+    void restart() { if (choice < 0) frame = 0; }    // a measurement under way starts again
+    int end_frame(hipStream_t st);                   // a frame ended: the time stamps, and the decision once the last one has been reached (restir.hip)
+    int reported() const { return choice >= 0 ? choice : (frame > 0 || counted) ? -1 : -2; }     // rs_restir_launch_choice
+};
+
 struct rs_restir {
     rs_context* ctx = nullptr;
     // The chain primary rays -> RIS -> shadow rays of a frame depends on no other frame.  Frames put theirs on kChains auxiliary
@@ -434,8 +448,8 @@ struct rs_restir {
     // starts as soon as its stream is free.  A third chain next to the render's stream would be a fifth stream on the runtime's
     // four hardware queues (slower).  A small launch -- a strip, whose kernels last as long as their slowest wave -- therefore
     // takes the fused launch (render + primary rays, k_gbuffer_primary), after which nothing runs on the render's stream, and
-    // gives that stream to a third chain (kSmallChains; restir.hip phase_a_impl): 8 strips of 1080p 5.96x -> 6.5x.
-    static constexpr int kChains = 2, kSmallChains = rs_context::kAux, kSurfSets = RS_SURF_SETS;
+    // gives that stream to a third chain (kSmallChains; rs_frame_plan.h): 8 strips of 1080p 5.96x -> 6.5x.
+    static constexpr int kChains = kPlanChains, kSmallChains = kPlanSmallChains, kSurfSets = RS_SURF_SETS;
     int width = 0, height = 0;
     ResvPlanes cur;      // devDirectReservoir      (written this frame)
     ResvPlanes last;     // devLastDirectReservoir  (read by the temporal merge)
@@ -461,14 +475,8 @@ struct rs_restir {
     int phaseACalls = 0;             // since the last end_frame
     bool idleFrame = false;          // this frame's first phase-A call found the previous frames finished (restir.hip phase_a_impl)
     int idleStreak = 0;
-    // one traversal for the G-buffer ray and the shading ray of a pixel, or two?  Measured once per scene (rs_fuse_mode() == 3):
-    // frames 6..17 with two launches against 22..33 with one (the four frames after each switch are not timed), by events on the library stream at the frame ends
-    unsigned long long tuneSceneId = 0;
-    int tuneFrame = 0;               // frames with a fusable launch since tuning began
-    int tuneChoice = -1;             // -1 measuring, 0 separate, 1 fused
-    int lastFused = -1, lastChains = 0;   // form of the last phase-A launch: render fused with the primary rays? how many chain streams in turn? (rs_restir_launch_choice)
-    bool tuneCounted = false;        // this frame had a launch the choice applies to
-    hipEvent_t tuneEv[4] = { nullptr, nullptr, nullptr, nullptr };
+    rs_fuse_tuner tune;
+    int lastFused = -1, lastChains = 0;   // form of the last phase-A launch: render fused with the primary rays? how many chain streams in turn? (rs_restir_last_launch)
     unsigned long long* dRayCount = nullptr;   // ring of per-frame counters (1024 slots)
     rs_tile_split split[1 + rs_context::kAux][3];   // primary-ray launches: per stream (library, auxiliary 0..2) and per call within a frame (strips: interior rows, border rows)
     int raySlot = 0;
@@ -490,6 +498,7 @@ struct rs_restir {
 };
 
 static_assert(rs_context::kAux >= 1 + rs_restir::kChains, "one auxiliary stream for GBuffer::render and one per chain");
+static_assert(kPlanSmallChains == rs_context::kAux, "the plan's three chains are the context's auxiliary streams");
 
 struct rs_eaw {
     rs_context* ctx = nullptr;

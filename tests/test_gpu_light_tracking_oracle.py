@@ -99,10 +99,10 @@ def run_edited(hip, sd, W, H, reuse, sobol=None, track=True, seed=0, frames=8):
 # ---- a. every tracked RIS form x sampler x reuse, tracking on and off ------------------------------------------------------------
 # form: scene, size, rs_set_ris_table_pixels (None = the library's default), synchronous mode
 FORMS = {
-    "global": ("sponza:0.125", 160, 96, None),        # k_ris_tracked<false, *>: 15 360 pixels read the table from global memory
+    "global": ("sponza:0.125", 160, 96, None),        # k_ris<false, *, true>: 15 360 pixels read the table from global memory
     "lds": ("sponza:0.125", 160, 96, 0),              # k_ris_lds<*, true>: 128 lights in LDS
     "alias_lds": ("bistro:0.12", 160, 96, 0),         # k_ris_alias_lds<*, true>: 1 228 lights, the alias records in LDS
-    "env": ("cornell_textured", 128, 128, None),      # k_ris_tracked<true, *>: the environment map's entry (envId) is skipped
+    "env": ("cornell_textured", 128, 128, None),      # k_ris<true, *, true>: the environment map's entry (envId) is skipped
 }
 
 

@@ -1091,6 +1091,70 @@ def test_overlapped_frames_equal_synchronous_frames(hip, fused):
     assert not bits_equal(a["images"][0], a["images"][-1])
 
 
+def test_launch_forms_follow_the_plan_and_keep_the_images(hip):
+    """What a frame launched (rs_restir_last_launch) is what the plan of phase A (rs_debug_phase_a_plan, restir_amd/csrc/rs_frame_plan.h)
+    answers for the mode's inputs, in every mode a caller can put the library in -- and every mode's radiance and reservoirs equal the
+    synchronous run's bit for bit.  160 x 96 is 240 waves, a strip in the plan's terms; full-size decisions: tests/test_frame_plan.py."""
+    import torch
+    from restir_amd.scenes import orbit_position
+    sd = get_scene("sponza:0.03")
+    W, H, frames = 160, 96, 6
+    scene = hip_scene(hip, sd)
+    deferred = dict(deferredValid=1, deferredMatches=1, deferredY0=0, deferredY1=H)
+    # mode: (asynchronous, moving camera, stream plan, denoise stream, per-pass timing, the plan's inputs, expected (fused, chains))
+    modes = {
+        "synchronous": (False, True, None, 0, False, dict(async_=0), (0, 0)),
+        "synchronous, still": (False, False, None, 0, False, dict(async_=0), (0, 0)),
+        "default, moving": (True, True, None, 0, False, dict(async_=1, **deferred), (1, 3)),
+        "default, still": (True, False, None, 0, False, dict(async_=1, reusedFrame=1), (0, 3)),
+        "two chains, separate render": (True, True, (2, 0, 2), 0, False, dict(async_=1, smallChains=0, **deferred), (0, 2)),
+        "one chain": (True, True, (1, 0, 0), 0, False, dict(async_=1, chainStreams=1, smallChains=0, shadowOnMain=0, **deferred), (0, 1)),
+        "denoise stream": (True, True, None, 1, False, dict(async_=1, denoiseStream=1, chainsInFlight=2, **deferred), (1, 2)),
+        "per-pass timing": (True, True, None, 0, True, dict(async_=0, **deferred), (0, 0)),
+    }
+
+    def run(overlapped, moving, stream_plan, denoise, timing):
+        h = HipRenderer(hip, sd, W, H, scene=scene)
+        images = []
+        try:
+            hip.set_sync(not overlapped)
+            hip.set_stream_plan(*(stream_plan or (2, 1, 2)))
+            hip.set_denoise_stream(denoise)
+            h.restir.enable_timing(timing)
+            for frame in range(frames):
+                if moving:
+                    h.set_camera_position(orbit_position(sd.camera_args["position"], frame, radius=0.5))
+                h.gbuf.render(h.scene, h.cam)
+                h.restir.direct(h.scene, h.cam, h.gbuf, h.image.data_ptr(), 0, h.looper, 3)
+                h.looper += 1
+                images.append(h.image.clone())                           # enqueued on the library (= torch's current) stream
+                h.gbuf.update(h.cam)
+            hip.synchronize()
+            torch.cuda.synchronize()
+            form = h.restir.last_launch()
+        finally:
+            hip.set_sync(True)
+            hip.set_stream_plan(2, 1, 2)
+            hip.set_denoise_stream(0)
+        return dict(images=[t.cpu().numpy() for t in images], resv=h.restir.download(1), form=form)
+
+    out = {}
+    for name, (overlapped, moving, stream_plan, denoise, timing, inputs, expected) in modes.items():
+        out[name] = run(overlapped, moving, stream_plan, denoise, timing)
+        a = dict(chainStreams=2, smallChains=1, shadowOnMain=2, fuseMode=3, chainsInFlight=3, reusedThree=1, width=W, y0=0, y1=H,
+                 tuneChoice=-1, chain=(frames - 1) % 2, smallChain=(frames - 1) % 3, numLights=1, risGlobalBelow=RIS_TABLE_PIXELS_DEFAULT)
+        a.update(inputs)
+        p = hip.phase_a_plan(**a)
+        assert out[name]["form"] == (p.fuse, p.lastChains) == expected, (name, out[name]["form"], (p.fuse, p.lastChains))
+    for name, (_, moving, *_rest) in modes.items():
+        ref = out["synchronous" if moving else "synchronous, still"]
+        for frame in range(frames):
+            assert bits_equal(ref["images"][frame], out[name]["images"][frame]), (name, frame)
+        assert ref["resv"].tobytes() == out[name]["resv"].tobytes(), name
+    assert not bits_equal(out["synchronous"]["images"][0], out["synchronous"]["images"][-1])
+    assert out["synchronous"]["images"][-1].any() and out["synchronous, still"]["images"][-1].any()
+
+
 @pytest.mark.parametrize("join_every_frame", [False, True])
 def test_denoise_stream_equals_synchronous_frames(hip, join_every_frame):
     """rs_set_denoise_stream(1): LeveledEAWFilter of frame f and the tone map of its result run on a stream of the library next to the
