@@ -19,6 +19,9 @@
 //     without its range scaling and class test; every float of the range agrees.
 // The guards are wave-uniform (__all): one scalar branch, no exec-mask region; a wave with one operand outside the range takes the
 // compiler's operator for all its lanes.  Zero, negative numbers, infinity and NaN are outside the range by construction of the test.
+// Whole frames whose waves take the fallback, mix lanes inside and outside the range or carry `unused` lanes are compared with the oracle
+// bit for bit in tests/test_gpu_parameter_extremes.py (the cases of tests/extreme_cases.py: roughness 0 and 1e-6 on all or a part of the
+// scene, radiances from a denormal to 3e38, an emitter above 2^60 beside an ordinary one).
 #ifndef RS_MATH_H_BODY
 #include "rs_math.h"        // which includes this file once its vector type and operators are defined (normalize / length use the forms below)
 #elif !defined(RS_EXACT_H_BODY)
