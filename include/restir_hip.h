@@ -448,11 +448,18 @@ int  rs_restir_upload(rs_restir* r, int which, const rs_reservoir* host);
  * older reservoir.  With no edit the results are bit-identical to 0.  Switching on starts every reservoir's light as
  * unknown.
  * Costs 16 B/px of memory traffic per frame (RIS writes 4, the temporal merge reads 8 and writes 4).  A tracked rs_restir is refused by
- * rs_strips_frame / rs_strips_exchange_history with RS_ERR_UNSUPPORTED. */
+ * rs_strips_frame / rs_strips_exchange_history with RS_ERR_UNSUPPORTED unless the driver was told: rs_strips_set_light_tracking. */
 int  rs_restir_set_light_tracking(rs_restir* r, int enable);
 /* The light-sampler index of every reservoir's sample, width x height ints; which as rs_restir_download.  -1 = none
- * or unknown (all -1 while tracking is off).  Waits for the library stream. */
+ * or unknown (all -1 while tracking is off).  Waits for the library stream.  On a rank of the strip driver the rows of which = 2 (the
+ * published copy) outside the rank's strip mean nothing: the border rows of a frame travel without their ids (rs_strips_frame). */
 int  rs_restir_download_light_ids(const rs_restir* r, int which, int* host);
+/* Rows of the id plane that goes with reservoir buffer `which` (as rs_restir_download_light_ids), 4 B/px: what a history message
+ * carries next to rs_restir_rows_pack(r, 1, ...) when the lights are tracked.  Enqueue-only, like rs_restir_rows_pack.  Refused with
+ * RS_ERR_INVALID_ARGUMENT while tracking is off, for rows outside the frame and for a devBuffer that is not 4-byte aligned. */
+size_t rs_restir_light_rows_bytes(const rs_restir* r, int rows);
+int  rs_restir_light_rows_pack(const rs_restir* r, int which, int y0, int rows, void* devBuffer);
+int  rs_restir_light_rows_unpack(rs_restir* r, int which, int y0, int rows, const void* devBuffer);
 /* BVH walks (intersect + testOcclusion calls) performed by the last rs_restir_direct / phase_a,
  * for the Mrays/s metric. Synchronises. */
 int  rs_restir_ray_count(rs_restir* r, unsigned long long* rays);
@@ -541,6 +548,14 @@ int  rs_strips_set_comm_stream(rs_strips* strips, int ownStream);
  * denoiser follows (src/main.cpp:160-170), whose own exchange of those rows -- a packing launch, a group and an unpacking launch per frame -- is
  * then skipped.  The same value on every rank; strips of at least that many rows; between frames. */
 int  rs_strips_set_gbuffer_halo(rs_strips* strips, int rows);
+/* Light tracking (rs_restir_set_light_tracking) through the driver.  0 (default): a tracked rs_restir is refused with RS_ERR_UNSUPPORTED.
+ * 1: rs_strips_frame and rs_strips_exchange_history take a tracked rs_restir and refuse an untracked one with RS_ERR_INVALID_ARGUMENT.
+ * The border rows of a frame stay 68 B/px (no pass reads a neighbour's ids); every message of rs_strips_exchange_history becomes
+ * reservoir rows (40 B/px), G-buffer rows (20), then the reservoirs' light ids (4), so that after it the which = 1 reservoirs and ids of
+ * ALL rows equal the full frame's on every rank.  A setting of the driver, not read off the rs_restir, because it is the size of the
+ * messages: the same value on every rank; between frames, with no gather in flight.  With one rank the frames equal a tracked
+ * rs_restir_direct. */
+int  rs_strips_set_light_tracking(rs_strips* strips, int enable);
 /* GBuffer::render + ReSTIRDirect of this rank's rows; GBuffer::update stays with the caller, as in runCuda.  Afterwards rows
  * [y0, y1) of devDirectIllum hold the frame's radiance. */
 int  rs_strips_frame(rs_strips* strips, rs_restir* r, const rs_scene* scene, const rs_camera* cam, rs_gbuffer* g,
@@ -560,7 +575,8 @@ int  rs_strips_svgf_filter(rs_strips* strips, rs_svgf* f, rs_gbuffer* g, const r
 int  rs_strips_exchange_svgf_history(rs_strips* strips, rs_svgf* f);
 /* Moving camera (findTemporalNeighbor reads the reprojected pixel of the last frame, src/restir.cu:20-45, which may belong to
  * another strip): every rank's rows of the reservoirs the next temporal merge reads and of the "last" G-buffer planes travel to
- * every other rank.  Call after rs_gbuffer_update.  Not needed for a static camera (the reference's default). */
+ * every other rank (60 B/px; 64 with rs_strips_set_light_tracking).  Call after rs_gbuffer_update.  Not needed for a static camera
+ * (the reference's default). */
 int  rs_strips_exchange_history(rs_strips* strips, rs_restir* r, rs_gbuffer* g);
 /* Image assembly: rows [y0, y1) of every rank's devImage (full-frame sized, bytesPerPixel bytes per pixel: 12 for the radiance
  * image, 4 for the display image) arrive in the same rows on rank `root`, or on every rank for root = -1. */

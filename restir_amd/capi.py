@@ -132,12 +132,12 @@ EXPORTS = [
     "rs_gbuffer_create", "rs_gbuffer_destroy", "rs_gbuffer_render", "rs_gbuffer_render_rows", "rs_gbuffer_update",
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
-    "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
+    "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
     "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
     "rs_path_trace", "rs_path_trace_indirect", "rs_restir_indirect", "rs_restir_download_indirect",
     "rs_svgf_create", "rs_svgf_destroy", "rs_svgf_filter", "rs_svgf_next_frame", "rs_svgf_get_view",
     "rs_copy_image_to_pbo", "rs_copy_image2_to_pbo", "rs_copy_imagef_to_pbo", "rs_copy_imagei_to_pbo", "rs_eaw_create", "rs_eaw_destroy", "rs_eaw_set_params", "rs_eaw_get_params", "rs_eaw_set_tiled", "rs_eaw_set_fused", "rs_svgf_set_params", "rs_svgf_get_params", "rs_svgf_set_tiled", "rs_svgf_set_fused", "rs_eaw_filter", "rs_eaw_positions_rows", "rs_eaw_level_rows", "rs_modulate_albedo",
-    "rs_add_image", "rs_add_image3", "rs_comm_create_rccl", "rs_comm_create_rccl_lib", "rs_comm_create", "rs_comm_destroy", "rs_comm_self_exchange", "rs_strips_create", "rs_strips_destroy", "rs_strips_rows", "rs_strips_set_comm_stream", "rs_strips_set_gbuffer_halo", "rs_strips_frame", "rs_strips_eaw_filter", "rs_strips_svgf_filter", "rs_strips_exchange_svgf_history", "rs_strips_exchange_history", "rs_strips_gather", "rs_strips_gather_begin", "rs_strips_gather_end", "rs_strips_enable_timing", "rs_strips_halo_wait_ms",
+    "rs_add_image", "rs_add_image3", "rs_comm_create_rccl", "rs_comm_create_rccl_lib", "rs_comm_create", "rs_comm_destroy", "rs_comm_self_exchange", "rs_strips_create", "rs_strips_destroy", "rs_strips_rows", "rs_strips_set_comm_stream", "rs_strips_set_gbuffer_halo", "rs_strips_set_light_tracking", "rs_strips_frame", "rs_strips_eaw_filter", "rs_strips_svgf_filter", "rs_strips_exchange_svgf_history", "rs_strips_exchange_history", "rs_strips_gather", "rs_strips_gather_begin", "rs_strips_gather_end", "rs_strips_enable_timing", "rs_strips_halo_wait_ms",
     "rs_scene_file_load", "rs_scene_file_get", "rs_scene_file_free", "rs_build_transformation_matrix", "rs_bake_instance",
 ]
 
@@ -187,6 +187,10 @@ def lib():
     L.rs_scene_set_emission.argtypes = [vp, ci, vp, vp]
     L.rs_restir_set_light_tracking.argtypes = [vp, ci]
     L.rs_restir_download_light_ids.argtypes = [vp, ci, vp]
+    L.rs_restir_light_rows_bytes.argtypes = [vp, ci]
+    L.rs_restir_light_rows_bytes.restype = C.c_size_t
+    L.rs_restir_light_rows_pack.argtypes = [vp, ci, ci, ci, vp]
+    L.rs_restir_light_rows_unpack.argtypes = [vp, ci, ci, ci, vp]
     L.rs_camera_update.argtypes = [C.POINTER(Camera)]
     L.rs_trace_closest.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.rs_trace_occlusion.argtypes = [vp, ci, vp, vp]
@@ -271,6 +275,7 @@ def lib():
     L.rs_strips_rows.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
     L.rs_strips_set_comm_stream.argtypes = [vp, ci]
     L.rs_strips_set_gbuffer_halo.argtypes = [vp, ci]
+    L.rs_strips_set_light_tracking.argtypes = [vp, ci]
     L.rs_strips_frame.argtypes = [vp, vp, vp, C.POINTER(Camera), vp, vp, ci, ci, ci]
     L.rs_strips_eaw_filter.argtypes = [vp, vp, vp, C.POINTER(Camera), vp, C.POINTER(vp)]
     L.rs_strips_exchange_history.argtypes = [vp, vp, vp]
@@ -863,6 +868,16 @@ class ReSTIR:
         check(lib().rs_restir_download_light_ids(self.handle, which, _p(out)))
         return out
 
+    def light_rows_bytes(self, rows):
+        return int(lib().rs_restir_light_rows_bytes(self.handle, rows))
+
+    def light_rows_pack(self, which, y0, rows, dev_ptr):
+        """Rows of the id plane of reservoir buffer `which` (as download_light_ids), 4 B/px; refused while tracking is off."""
+        check(lib().rs_restir_light_rows_pack(self.handle, which, y0, rows, dev_ptr))
+
+    def light_rows_unpack(self, which, y0, rows, dev_ptr):
+        check(lib().rs_restir_light_rows_unpack(self.handle, which, y0, rows, dev_ptr))
+
     def ray_count(self):
         n = C.c_ulonglong(0)
         check(lib().rs_restir_ray_count(self.handle, C.byref(n)))
@@ -961,6 +976,10 @@ class Strips:
     def set_gbuffer_halo(self, rows):
         """G-buffer rows that travel with the reservoir rows of a frame: 5 (default), or 32 when a denoiser follows (rs_strips_set_gbuffer_halo)."""
         check(lib().rs_strips_set_gbuffer_halo(self.handle, int(rows)))
+
+    def set_light_tracking(self, on=True):
+        """The frames take a tracked ReSTIR and the history messages carry its light ids (rs_strips_set_light_tracking); the same on every rank."""
+        check(lib().rs_strips_set_light_tracking(self.handle, 1 if on else 0))
 
     def frame(self, restir, scene, cam, gbuf, dev_direct_illum_ptr, iter_, looper, reuse):
         check(lib().rs_strips_frame(self.handle, restir.handle, scene.handle, C.byref(cam), gbuf.handle, dev_direct_illum_ptr, iter_, looper, reuse))

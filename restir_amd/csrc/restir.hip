@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "rs_copy_segments.h"
 #include "rs_internal.h"
 
 #ifndef RS_WALK_WAVES
@@ -1284,6 +1285,33 @@ int rs_restir_rows_unpack(rs_restir* r, int which, int y0, int rows, const void*
 }
 int rs_restir_halo_pack(const rs_restir* r, int y0, int rows, void* devBuffer) { RS_SCOPE(r); return rs_restir_rows_pack(r, 2, y0, rows, devBuffer); }
 int rs_restir_halo_unpack(rs_restir* r, int y0, int rows, const void* devBuffer) { RS_SCOPE(r); return rs_restir_rows_unpack(r, 2, y0, rows, devBuffer); }
+
+// Light tracking: the rows of the id plane that goes with reservoir buffer `which` (as rs_restir_download_light_ids), 4 B/px.  The planes
+// exist only while tracking is on, so both directions are refused while it is off instead of packing rows nobody wrote.  One launch of the
+// copy kernel of rs_copy_segments.h each way (the buffer 4-byte aligned: the kernel moves ints where it cannot move 16 bytes).
+size_t rs_restir_light_rows_bytes(const rs_restir* r, int rows) {
+    RS_SCOPE(r);
+    return r ? (size_t)r->width * (size_t)(rows > 0 ? rows : 0) * sizeof(int) : 0;
+}
+namespace {
+int copy_light_rows(rs_restir* r, int which, int y0, int rows, char* buf, bool pack, const char* what) {
+    if (!r || !buf || ((size_t)buf & 3) || which < 0 || which > 2 || y0 < 0 || rows < 0 || y0 + rows > r->height || !r->track || !r->idCur) return rs_fail(RS_ERR_INVALID_ARGUMENT, what);
+    int* plane = (which == 0 ? r->idCur : which == 1 ? r->idLast : r->idTemp) + (size_t)y0 * r->width;
+    const size_t bytes = (size_t)r->width * rows * sizeof(int);
+    rs_copy::SegList l;
+    l.add(plane, buf, bytes);
+    RS_TRY(rs_copy::copy_segments(l, pack));
+    return rs_after_launch(what);
+}
+}  // namespace
+int rs_restir_light_rows_pack(const rs_restir* r, int which, int y0, int rows, void* devBuffer) {
+    RS_SCOPE(r);
+    return copy_light_rows(const_cast<rs_restir*>(r), which, y0, rows, (char*)devBuffer, true, "rs_restir_light_rows_pack: bad argument, or light tracking is off");
+}
+int rs_restir_light_rows_unpack(rs_restir* r, int which, int y0, int rows, const void* devBuffer) {
+    RS_SCOPE(r);
+    return copy_light_rows(r, which, y0, rows, (char*)const_cast<void*>(devBuffer), false, "rs_restir_light_rows_unpack: bad argument, or light tracking is off");
+}
 
 int rs_restir_download(const rs_restir* rc, int which, rs_reservoir* host) {
     RS_SCOPE(rc);

@@ -23,7 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "rs_internal.h"
+#include "rs_copy_segments.h"
 
 struct rs_comm {
     rs_transport t{};
@@ -52,6 +52,9 @@ struct rs_strips {
     // (one packing launch, one group and one unpacking launch less per frame than exchanging them again: gbufFresh)
     int gReach = RS_SPATIAL_HALO_ROWS;
     bool gbufFresh = false;                        // the current G-buffer set holds the neighbours' gReach rows (set by rs_strips_frame, consumed by the filters)
+    // rs_strips_set_light_tracking: the rs_restir of this driver's frames tracks lights (rs_restir_set_light_tracking), and the history
+    // messages carry the id rows of the reservoirs they carry.  A setting and not read off the rs_restir: it is the size of the messages.
+    bool track = false;
     char* sendUp = nullptr; char* recvUp = nullptr; char* sendDown = nullptr; char* recvDown = nullptr;
     // Where the transfers are enqueued.  commOnMain (default): on the library stream itself, in order with the packing copies before
     // and the unpacking copies after them -- no extra stream, no events.  The overlapped mode already keeps four streams busy (the
@@ -86,6 +89,8 @@ struct rs_strips {
 };
 
 namespace {
+using rs_copy::SegList;
+using rs_copy::copy_segments;
 
 constexpr int kHalo = RS_SPATIAL_HALO_ROWS;
 
@@ -106,43 +111,6 @@ int rccl_recv(void* ctx, void* buf, size_t bytes, int peer, void* stream) {
     return e ? rccl_fail(c, e, "ncclRecv") : 0;
 }
 
-// Packing and unpacking the border rows of a frame: 6 planes (published reservoirs li / wi / tap, G-buffer id / normal / depth) x 2
-// edges.  As 24 hipMemcpyAsync calls per frame they cost the HOST 0.12 ms -- more than half of what a 1/8 strip's kernels last
-// (tools/host_enqueue_strips.py: 0.210 ms of host time per frame against 0.18 ms of kernels) -- so all segments of a direction go
-// through ONE launch of a copy kernel that finds its segment from a table passed by value.
-constexpr int kMaxSegs = 12;
-struct CopyTable { const char* src[kMaxSegs]; char* dst[kMaxSegs]; unsigned start[kMaxSegs + 1]; int n; };      // start: in units of `unit` bytes
-template <typename T>
-__global__ void __launch_bounds__(256) k_copy_segments(CopyTable t) {
-    RS_SETPRIO(RS_PRIO_STREAM);
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= t.start[t.n]) return;
-    int k = 0;
-    while (i >= t.start[k + 1]) k++;
-    reinterpret_cast<T*>(t.dst[k])[i - t.start[k]] = reinterpret_cast<const T*>(t.src[k])[i - t.start[k]];
-}
-struct SegList {
-    const char* a[kMaxSegs]; char* b[kMaxSegs]; size_t bytes[kMaxSegs]; int n = 0;
-    void add(const void* plane, void* packed, size_t nbytes) { a[n] = (const char*)plane; b[n] = (char*)packed; bytes[n] = nbytes; n++; }
-};
-// pack: plane -> packed buffer; unpack: packed buffer -> plane
-int copy_segments(const SegList& l, bool pack) {
-    if (l.n == 0) return 0;
-    bool wide = true;
-    for (int k = 0; k < l.n; k++) wide = wide && l.bytes[k] % 16 == 0 && ((size_t)l.a[k] % 16 == 0) && ((size_t)l.b[k] % 16 == 0);
-    const unsigned unit = wide ? 16u : 4u;
-    CopyTable t; t.n = l.n; t.start[0] = 0;
-    for (int k = 0; k < l.n; k++) {
-        t.src[k] = pack ? l.a[k] : l.b[k];
-        t.dst[k] = pack ? l.b[k] : const_cast<char*>(l.a[k]);
-        t.start[k + 1] = t.start[k] + (unsigned)(l.bytes[k] / unit);
-    }
-    const unsigned total = t.start[t.n];
-    if (total == 0) return 0;
-    if (wide) hipLaunchKernelGGL(k_copy_segments<uint4>, dim3((total + 255) / 256), dim3(256), 0, rs_stream(), t);
-    else hipLaunchKernelGGL(k_copy_segments<unsigned>, dim3((total + 255) / 256), dim3(256), 0, rs_stream(), t);
-    return rs_check_hip(hipGetLastError(), "strip border rows");
-}
 // the border rows of one edge in the packed layout of rs_restir_halo_pack followed by rs_gbuffer_rows_pack: li, wi, tap, id, normal, depth
 // (yResv: first of the kHalo reservoir rows; yG: first of the gRows G-buffer rows -- the same edge of the strip, so the two ranges end or begin together)
 void halo_segments(SegList& l, rs_restir* r, rs_gbuffer* g, int yResv, int yG, int gRows, char* packed) {
@@ -152,6 +120,24 @@ void halo_segments(SegList& l, rs_restir* r, rs_gbuffer* g, int yResv, int yG, i
     char* gb = packed + n * 48;
     const size_t m = (size_t)r->width * gRows, offG = (size_t)yG * r->width;
     l.add(g->primId[c] + offG, gb, m * 4); l.add(g->normal[c] + offG * 3, gb + m * 4, m * 12); l.add(g->depth[c] + offG, gb + m * 16, m * 4);
+}
+
+// rows [y, y + rows) of what the next temporal merge reads, in the tracked layout of a history message: the reservoirs' li, wi, w, m
+// (rs_restir_rows_pack, which = 1), the "last" G-buffer id, normal, depth (rs_gbuffer_rows_pack, sel = 1), then the reservoirs' light ids
+// (rs_restir_light_rows_pack, which = 1) -- eight planes, so a message is packed by one launch and unpacked by one
+void history_segments(SegList& l, rs_restir* r, rs_gbuffer* g, int y, int rows, char* packed) {
+    const size_t n = (size_t)r->width * rows, off = (size_t)y * r->width;
+    const int f = g->prev();
+    l.add(r->last.li + off, packed, n * 16); l.add(r->last.wi + off, packed + n * 16, n * 16);
+    l.add(r->last.w + off, packed + n * 32, n * 4); l.add(r->last.m + off, packed + n * 36, n * 4);
+    l.add(g->primId[f] + off, packed + n * 40, n * 4); l.add(g->normal[f] + off * 3, packed + n * 44, n * 12); l.add(g->depth[f] + off, packed + n * 56, n * 4);
+    l.add(r->idLast + off, packed + n * 60, n * 4);
+}
+// the driver's setting and the rs_restir it is handed must agree: the setting is the size of the history messages
+int check_tracking(const rs_strips* s, const rs_restir* r, const char* unsupported, const char* mismatch) {
+    if (r->track && !s->track) return rs_fail(RS_ERR_UNSUPPORTED, unsupported);
+    if (!r->track && s->track) return rs_fail(RS_ERR_INVALID_ARGUMENT, mismatch);
+    return 0;
 }
 
 // One grouped exchange, ordered after everything enqueued on the library stream so far: on the driver's stream for a stream-ordered
@@ -442,6 +428,17 @@ int rs_strips_set_gbuffer_halo(rs_strips* s, int rows) {
     return 0;
 }
 
+// Light tracking through the driver: 0 (default) = a tracked rs_restir is refused, as before; 1 = rs_strips_frame and
+// rs_strips_exchange_history take a tracked rs_restir (and refuse an untracked one), and every history message grows by the 4 B/px of
+// the reservoirs' light ids.  Every rank must set the same value (it is the size of the messages); between frames, no gather in flight.
+int rs_strips_set_light_tracking(rs_strips* s, int enable) {
+    RS_SCOPE(s);
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_set_light_tracking: null");
+    for (bool pending : s->gatherPending) if (pending) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_set_light_tracking: a gather is in flight");
+    s->track = enable != 0;
+    return 0;
+}
+
 int rs_strips_rows(const rs_strips* s, int* y0, int* y1) {
     RS_SCOPE(s);
     if (!s || !y0 || !y1) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_rows: null argument");
@@ -455,7 +452,8 @@ int rs_strips_frame(rs_strips* s, rs_restir* r, const rs_scene* scene, const rs_
                     float* devDirectIllum, int iter, int looper, int reuse) {
     RS_SCOPE(s);
     if (!s || !r || !scene || !cam || !g || !devDirectIllum) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_frame: null argument");
-    if (r->track) return rs_fail(RS_ERR_UNSUPPORTED, "rs_strips_frame: light tracking (rs_restir_set_light_tracking) is not supported by the strip driver");
+    RS_TRY(check_tracking(s, r, "rs_strips_frame: light tracking (rs_restir_set_light_tracking) is not supported by the strip driver unless rs_strips_set_light_tracking(strips, 1)",
+                          "rs_strips_frame: rs_strips_set_light_tracking(strips, 1) needs an rs_restir with light tracking on"));
     if (g->width != s->width || g->height != s->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_frame: G-buffer size differs from the strips' frame");
     const int y0 = s->y0, y1 = s->y1;
     const rs_comm* c = s->comm;
@@ -467,7 +465,10 @@ int rs_strips_frame(rs_strips* s, rs_restir* r, const rs_scene* scene, const rs_
         RS_TRY(rs_restir_phase_b(r, scene, cam, g, devDirectIllum, iter, reuse, y0, y1));
         return rs_restir_end_frame(r);
     }
-    // pack the border rows (library stream): one launch for the six planes of both edges
+    // pack the border rows (library stream): one launch for the six planes of both edges.  With light tracking the rows are the same 68 B/px:
+    // the temporal pass reads the id of a published copy only at pixels of its own rows (where it re-evaluates the copy of a pixel that
+    // shades nothing), the neighbour has re-evaluated the rows it sends before it sends them, and the spatial pass reads no ids.  So rows
+    // of the published copy's id plane (which = 2) outside the strip stay whatever they were.
     RS_TRY(rs_gbuffer_join(g));
     {
         SegList l;
@@ -617,20 +618,35 @@ int rs_strips_exchange_svgf_history(rs_strips* s, rs_svgf* f) {
 int rs_strips_exchange_history(rs_strips* s, rs_restir* r, rs_gbuffer* g) {
     RS_SCOPE(s);
     if (!s || !r || !g) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_exchange_history: null argument");
-    if (r->track) return rs_fail(RS_ERR_UNSUPPORTED, "rs_strips_exchange_history: light tracking (rs_restir_set_light_tracking) is not supported by the strip driver");
+    RS_TRY(check_tracking(s, r, "rs_strips_exchange_history: light tracking (rs_restir_set_light_tracking) is not supported by the strip driver unless rs_strips_set_light_tracking(strips, 1)",
+                          "rs_strips_exchange_history: rs_strips_set_light_tracking(strips, 1) needs an rs_restir with light tracking on"));
     if (g->width != s->width || g->height != s->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_exchange_history: G-buffer size differs from the strips' frame");
+    if (r->width != s->width || r->height != s->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_exchange_history: reservoir size differs from the strips' frame");
     const rs_comm* c = s->comm;
     if (c->world == 1) return 0;
     RS_TRY(rs_denoise_join());                                   // a filter on the denoise stream writes rows of these planes just outside the strip
-    auto resvBytes = [&](int rank) { return rs_restir_rows_bytes(r, 1, s->bounds[(size_t)rank + 1] - s->bounds[(size_t)rank]); };
-    auto bytesOf = [&](int rank) { return resvBytes(rank) + rs_gbuffer_rows_bytes(g, s->bounds[(size_t)rank + 1] - s->bounds[(size_t)rank]); };
+    // a message: reservoir rows (40 B/px), G-buffer rows (20), with tracking the reservoirs' light ids (4) last -- the untracked layout is a prefix
+    const bool track = s->track;
+    auto rowsOf = [&](int rank) { return s->bounds[(size_t)rank + 1] - s->bounds[(size_t)rank]; };
+    auto resvBytes = [&](int rank) { return rs_restir_rows_bytes(r, 1, rowsOf(rank)); };
+    auto bytesOf = [&](int rank) { return resvBytes(rank) + rs_gbuffer_rows_bytes(g, rowsOf(rank)) + (track ? rs_restir_light_rows_bytes(r, rowsOf(rank)) : 0); };
     size_t others = 0;
     for (int k = 0; k < c->world; k++) if (k != c->rank) others += bytesOf(k);
     const size_t mine = bytesOf(c->rank);
     if (s->histSendBytes < mine) { rs_dev_free(s->histSend); s->histSend = nullptr; RS_TRY(rs_dev_alloc(&s->histSend, mine)); s->histSendBytes = mine; }
     if (s->histRecvBytes < others) { rs_dev_free(s->histRecv); s->histRecv = nullptr; RS_TRY(rs_dev_alloc(&s->histRecv, others)); s->histRecvBytes = others; }
-    RS_TRY(rs_restir_rows_pack(r, 1, s->y0, s->y1 - s->y0, s->histSend));
-    RS_TRY(rs_gbuffer_rows_pack(g, 1, s->y0, s->y1 - s->y0, s->histSend + resvBytes(c->rank)));
+    if (track) {
+        // eight planes a message: as hipMemcpyAsync calls they would be eight enqueues for the own rows and eight per peer, each dearer to the
+        // host than the copy is to the device (see k_copy_segments) -- one launch packs, one launch per peer unpacks
+        RS_TRY(rs_gbuffer_join(g));
+        SegList l;
+        history_segments(l, r, g, s->y0, s->y1 - s->y0, s->histSend);
+        RS_TRY(copy_segments(l, true));
+    }
+    else {
+        RS_TRY(rs_restir_rows_pack(r, 1, s->y0, s->y1 - s->y0, s->histSend));
+        RS_TRY(rs_gbuffer_rows_pack(g, 1, s->y0, s->y1 - s->y0, s->histSend + resvBytes(c->rank)));
+    }
     std::vector<Xfer> ops;
     size_t off = 0;
     for (int k = 0; k < c->world; k++) {
@@ -644,12 +660,20 @@ int rs_strips_exchange_history(rs_strips* s, rs_restir* r, rs_gbuffer* g) {
     off = 0;
     for (int k = 0; k < c->world; k++) {
         if (k == c->rank) continue;
-        const int a = s->bounds[(size_t)k], rows = s->bounds[(size_t)k + 1] - a;
-        RS_TRY(rs_restir_rows_unpack(r, 1, a, rows, s->histRecv + off));
-        RS_TRY(rs_gbuffer_rows_unpack(g, 1, a, rows, s->histRecv + off + resvBytes(k)));
+        const int a = s->bounds[(size_t)k], rows = rowsOf(k);
+        if (track) {
+            SegList l;
+            history_segments(l, r, g, a, rows, s->histRecv + off);
+            rs_gbuffer_note_write(g, g->prev(), a, rows);
+            RS_TRY(copy_segments(l, false));
+        }
+        else {
+            RS_TRY(rs_restir_rows_unpack(r, 1, a, rows, s->histRecv + off));
+            RS_TRY(rs_gbuffer_rows_unpack(g, 1, a, rows, s->histRecv + off + resvBytes(k)));
+        }
         off += bytesOf(k);
     }
-    return 0;
+    return track ? rs_after_launch("rs_strips_exchange_history") : 0;
 }
 
 // Image assembly: rows [y0, y1) of every rank's devImage (bytesPerPixel bytes per pixel, row-major, full-frame sized: the radiance

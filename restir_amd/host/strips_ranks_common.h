@@ -50,7 +50,9 @@ inline void start_watchdog(int seconds) {
     }).detach();
 }
 
-// a floor, a back wall of 24 x 12 slanted facets (so that strips see different geometry) and four small lights facing down
+// a floor, a back wall of 24 x 12 slanted facets (so that strips see different geometry) and four small lights.  The lights are
+// single-sided and as wound here they face UP: they light nothing below them, and the frames the rank programs compare are lit by no
+// lamp (what shows is the lamps themselves).  strips_tracking_ranks.cpp, which needs reservoirs that name a light, turns them over.
 inline void make_scene(std::vector<float>& v, std::vector<float>& n, std::vector<int>& matIds, std::vector<rs_material>& mats) {
     auto tri = [&](const float* a, const float* b, const float* c, int mat) {
         const float e1[3] = { b[0] - a[0], b[1] - a[1], b[2] - a[2] }, e2[3] = { c[0] - a[0], c[1] - a[1], c[2] - a[2] };
@@ -70,7 +72,7 @@ inline void make_scene(std::vector<float>& v, std::vector<float>& n, std::vector
     }
     for (int k = 0; k < 4; k++) {
         const float cx = -2.25f + 1.5f * k, a[3] = { cx - .2f, 3.2f, -3.2f }, b[3] = { cx, 3.2f, -2.8f }, c[3] = { cx + .2f, 3.2f, -3.2f };
-        tri(a, b, c, 3);                                           // counter-clockwise seen from below: the normal points down
+        tri(a, b, c, 3);                                           // (e1 x e2 has y = +0.16: the normal points up, see above)
     }
     mats.assign(4, rs_material{});
     const float col[3][3] = { { .7f, .7f, .7f }, { .8f, .3f, .3f }, { .3f, .5f, .8f } };

@@ -258,10 +258,12 @@ def calibrate_bounds(backend, world, rank, height, dist, synchronize, reuse=3, r
 class HipBackend:
     """librestir_hip objects of one rank."""
 
-    def __init__(self, capi, scene, cam, width, height):
+    def __init__(self, capi, scene, cam, width, height, track=False):
+        """track: light tracking on (rs_restir_set_light_tracking); the history messages then end with the reservoirs' light ids."""
         import torch
         self.torch = torch
         self.capi = capi
+        self.track = bool(track)
         self.scene, self.cam = scene, cam
         self.W, self.H = width, height
         # c10d orders a collective after the work on torch's CURRENT stream, and the buffers it sends are packed by copies the
@@ -269,6 +271,8 @@ class HipBackend:
         capi.set_stream(torch.cuda.current_stream().cuda_stream)
         self.gbuf = capi.GBuffer(width, height)
         self.restir = capi.ReSTIR(width, height)
+        if self.track:
+            self.restir.set_light_tracking(True)
         self.image = torch.zeros((width * height, 3), dtype=torch.float32, device="cuda")
 
     def empty(self, nbytes):
@@ -334,15 +338,18 @@ class HipBackend:
         self.restir.halo_unpack(y0, rows, buf.data_ptr())
         self.gbuf.rows_unpack(0, y0, rows, buf.data_ptr() + self.restir.halo_bytes(rows))
 
-    # history = reservoirs the next temporal merge reads (buffer 1 after end_frame) + "last" G-buffer planes
+    # history = reservoirs the next temporal merge reads (buffer 1 after end_frame) + "last" G-buffer planes; with light tracking the
+    # reservoirs' light ids last (the layout of rs_strips_exchange_history: the untracked message is a prefix)
     def history_bytes(self, rows):
-        return self.restir.rows_bytes(1, rows) + self.gbuf.rows_bytes(rows)
+        return self.restir.rows_bytes(1, rows) + self.gbuf.rows_bytes(rows) + (self.restir.light_rows_bytes(rows) if self.track else 0)
 
     def history_pack(self, y0, rows):
         nr = self.restir.rows_bytes(1, rows)
         buf = self.empty(self.history_bytes(rows))
         self.restir.rows_pack(1, y0, rows, buf.data_ptr())
         self.gbuf.rows_pack(1, y0, rows, buf.data_ptr() + nr)
+        if self.track:
+            self.restir.light_rows_pack(1, y0, rows, buf.data_ptr() + nr + self.gbuf.rows_bytes(rows))
         return buf
 
     def history_unpack(self, y0, rows, buf):
@@ -350,3 +357,5 @@ class HipBackend:
         buf = buf.contiguous()
         self.restir.rows_unpack(1, y0, rows, buf.data_ptr())
         self.gbuf.rows_unpack(1, y0, rows, buf.data_ptr() + nr)
+        if self.track:
+            self.restir.light_rows_unpack(1, y0, rows, buf.data_ptr() + nr + self.gbuf.rows_bytes(rows))
