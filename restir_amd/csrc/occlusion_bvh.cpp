@@ -8,7 +8,7 @@
 // for candidates T satisfying (b) in a compact, well-built tree with CONSERVATIVE (slightly inflated)
 // boxes and then check (a) for each candidate by walking T's ancestor chain in the reference's own
 // tree with the reference's exact box test.  A conservative tree finds every T with (b), therefore
-// OR over candidates of (a) is exactly the reference's answer (rs_scene.h trace_occluded_fast).
+// OR over candidates of (a) is exactly the reference's answer (rs_walk.h walk_occlusion_tree).
 //
 // "Conservative" needs no epsilon: the primitive bounds used here ARE the reference's leaf boxes and every
 // box of this tree is an exact (min/max) union of them, so it contains the leaf box L of each of its
@@ -244,7 +244,7 @@ int rs_reference_chain_tables(int bvhSize, const int* order0 /* 3 ints per node 
 // chosen by a surface-area sweep along the SEQUENCE (cumulative, where the reference's bucket sweep is not, src/bvh.cpp:92-100;
 // its tree costs 129 / 168 node visits per ray on the Sponza- / Bistro-class scene, this one 113 / 135 at half the bytes per
 // node, tools/models/ordered_tree_closest_hit.cpp), leaves of up to 4 consecutive triangles, boxes = exact unions of the
-// reference's leaf boxes (conservative for the relaxed slab test, see the top of this file).  The walk (rs_scene.h
+// reference's leaf boxes (conservative for the relaxed slab test, see the top of this file).  The walk (rs_walk.h
 // walk_ordered_tree) then applies the reference's rule literally: enter a node iff tBox' < closest -- a skipped node has
 // tBox' >= closest and tBox' <= tLeaf of all its triangles, so the reference would not enter those leaves either -- and accept a
 // triangle hit closer than closest iff the reference's own test passes on its leaf box with tLeaf < closest and on every ancestor.

@@ -27,9 +27,6 @@
 #include "rs_copy_segments.h"
 #include "rs_internal.h"
 
-#ifndef RS_WALK_WAVES
-#define RS_WALK_WAVES 8        // waves per SIMD the walk kernels are held to (launch bound; holding them to exactly that many was A/B'd in round 3: no gain)
-#endif
 using namespace rs;
 
 namespace {

@@ -8,6 +8,51 @@
 
 namespace rs {
 
+// ---- materials (src/material.h:34-124,171-186,218-228) -----------------------------------------
+// x / d, 1 / sqrt(x): on the device the short forms of rs_exact.h (the same IEEE results, fewer instructions for operands in [2^-60, 2^60))
+RS_HD float bsdf_div(float x, float d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return div_exact(x, d);
+#else
+    return x / d;
+#endif
+}
+RS_HD f3 bsdf_normalize(f3 v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return v * rcp_exact(sqrt_exact(dot(v, v)));
+#else
+    return normalize(v);
+#endif
+}
+RS_HD float schlick_g(float c, float alpha) { float a = alpha * .5f; return bsdf_div(c, c * (1.f - a) + a); }
+RS_HD float gtr2(float c, float alpha) {
+    if (c < 1e-6f) return 0.f;
+    float aa = alpha * alpha;
+    float den = c * c * (aa - 1.f) + 1.f;
+    den = den * den * kPi;
+    return bsdf_div(aa, den);
+}
+
+RS_HD f3 eval_bsdf(int type, f3 baseColor, float metallic, float roughness, f3 n, f3 wo, f3 wi) {
+    if (type == 0) {                                   // lambertianBSDF: baseColor * 1.f / Pi
+        return (baseColor * 1.f) / kPi;
+    }
+    if (type == 1) {                                   // metallicWorkflowBSDF
+        float alpha = roughness * roughness;
+        f3 h = bsdf_normalize(wo + wi);
+        float cosO = dot(n, wo);
+        float cosI = dot(n, wi);
+        if (cosI * cosO < 1e-7f) return splat(0.f);
+        f3 f0 = mix(splat(.08f), baseColor, metallic);
+        f3 f = mix(f0, splat(1.f), pow5(1.f - dot(h, wo)));
+        float g = schlick_g(gabs(cosO), alpha) * schlick_g(gabs(cosI), alpha);
+        float d = gtr2(dot(n, h), alpha);
+        f3 diffuse = ((baseColor * 1.f) / kPi) * (1.f - metallic);
+        return mix(diffuse, splat(bsdf_div(g * d, 4.f * cosI * cosO)), f);
+    }
+    return splat(0.f);                                 // Dielectric, Disney, Light
+}
+
 #if defined(__HIPCC__)
 enum : uint32_t { kBsDiffuse = 1u << 0, kBsGlossy = 1u << 1, kBsSpecular = 1u << 2, kBsReflection = 1u << 4, kBsTransmission = 1u << 5, kBsInvalid = 1u << 15 };
 struct BsdfSample { f3 dir, bsdf; float pdf; uint32_t type; };

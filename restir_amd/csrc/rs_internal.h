@@ -21,6 +21,8 @@
 #include <vector>
 
 #include "rs_scene.h"
+#include "rs_walk.h"
+#include "rs_bsdf.h"
 #include "rs_tilesplit.h"
 
 // ---- contexts ----------------------------------------------------------------------------------

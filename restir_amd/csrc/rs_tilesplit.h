@@ -1,6 +1,6 @@
 // rs_tilesplit.h -- heavy tiles of the closest-hit kernels as four waves instead of one.
 //
-// A packet walk (rs_scene.h trace_closest_packet) is a chain of dependent node fetches as long as the UNION of the nodes its 64
+// A packet walk (rs_walk.h trace_closest_packet) is a chain of dependent node fetches as long as the UNION of the nodes its 64
 // rays visit, and a launch lasts at least as long as its longest chain: on the Bistro-class scene the mean tile has 270 union
 // nodes and the worst 3 669, which alone is the 1.4 ms of its primary-ray kernel; a 1/8 strip of any scene is a single round of
 // waves and ends with its slowest tile.  tools/walk_stats.py: in tiles of >= 1024 union nodes the slowest RAY visits 598 nodes

@@ -35,7 +35,7 @@ int upload(T** dst, const std::vector<T>& src) {
     return 0;
 }
 
-// The shadow-ray tree and the reference chain records (rs_scene.h walk_occlusion_tree).  Needs every
+// The shadow-ray tree and the reference chain records (rs_walk.h walk_occlusion_tree).  Needs every
 // reference box finite with min <= max (always true for boxes from rs_build_bvh; a caller-supplied table
 // that is not leaves the fast path off and shadow rays walk the reference's tree).
 int build_occlusion_side(rs_scene* s) {
@@ -116,7 +116,7 @@ int build_occlusion_side(rs_scene* s) {
     return 0;
 }
 
-// The tree of the EMISSIVE triangles alone (rs_scene.h may_hit_emissive_wave).  The last bounce of a path (gi.hip) only asks whether its
+// The tree of the EMISSIVE triangles alone (rs_walk.h may_hit_emissive_wave).  The last bounce of a path (gi.hip) only asks whether its
 // closest hit is an emissive triangle; the reference accepts a triangle only if intersectTriangle hits it and its leaf box was entered, so a
 // ray that hits no emissive triangle whose reference leaf box it passes cannot have an emissive closest hit -- and that question is asked
 // of a tree over the reference leaf boxes of the few emissive triangles (the shadow tree's builder and grid: its relaxed box test cannot
@@ -154,7 +154,7 @@ int build_emissive_side(rs_scene* s) {
     return 0;
 }
 
-// The closest-hit trees of the incoherent rays (occlusion_bvh.cpp rs_build_ordered_bvh, rs_scene.h walk_ordered_tree): per axis
+// The closest-hit trees of the incoherent rays (occlusion_bvh.cpp rs_build_ordered_bvh, rs_walk.h walk_ordered_tree): per axis
 // one tree over the leaf sequence of the even threaded order, emitted in forward and mirrored pre-order -> six arrays of 16-byte
 // grid-box records like the shadow tree's, laid out at a common stride in ONE allocation so that a lane addresses its order by
 // k * stride; links are absolute byte offsets; the last slot of every stride is the self-linked empty record a finished walk
@@ -642,7 +642,7 @@ extern "C" int rs_scene_create(const rs_scene_desc* d, rs_scene** out) {
     }
     // Do the miss links of every threaded order nest (a node inside the span (a, link(a)) never links beyond link(a))?  They do
     // for a pre-order layout with link = end of the subtree, which is what BVHBuilder::buildMTBVH produces (src/bvh.cpp:160-202);
-    // the packet walk's next-node shortcut (rs_scene.h packet_walk_order) relies on it and is off for any other table.
+    // the packet walk's next-node shortcut (rs_walk.h packet_walk_order) relies on it and is off for any other table.
     {
         bool nested = true;
         std::vector<int> open;
@@ -678,7 +678,7 @@ extern "C" int rs_debug_walk_stats(rs_scene* s, unsigned long long* out64, int r
     if (reset) RS_HIP(hipMemset(s->dWalkStats, 0, 64 * sizeof(unsigned long long)));
     return 0;
 }
-// slots 64..95: the closest-hit walk of the bounce rays (rs_scene.h walk_ordered_tree; tools/bench_closest_wave.py)
+// slots 64..95: the closest-hit walk of the bounce rays (rs_walk.h walk_ordered_tree; tools/bench_closest_wave.py)
 extern "C" int rs_debug_walk_stats_ordered(rs_scene* s, unsigned long long* out32, int reset) {
     RS_SCOPE(s);
     RS_HIP(hipDeviceSynchronize());

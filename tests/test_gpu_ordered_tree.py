@@ -1,5 +1,5 @@
 """GPU parity tests of the closest-hit trees that keep the reference's visiting order (occlusion_bvh.cpp rs_build_ordered_bvh,
-rs_scene.h walk_ordered_tree): the wave-level service the multi-bounce kernels use for their bounce rays must return what
+rs_walk.h walk_ordered_tree): the wave-level service the multi-bounce kernels use for their bounce rays must return what
 DevScene::intersect (src/scene.h:245-284) returns -- primitive, material, position and normal bit for bit -- for every ray:
 against the library's literal per-lane walk of the reference's tree, against the same service with the trees switched off, and
 against the oracle."""
@@ -110,6 +110,31 @@ def test_ordered_tree_on_the_full_scenes(hip, name):
     sub = rays[::10]
     prim, mat, pos, nrm, _ = oracle_scene(sd).intersect(sub)
     gp, gm, gpos, gn = [t.cpu().numpy()[::10] for t in fast]
+    assert np.array_equal(prim, gp)
+    h = prim >= 0
+    assert np.array_equal(mat[h], gm[h]) and bits_equal(pos[h], gpos[h]) and bits_equal(nrm[h], gn[h])
+
+
+def test_ordered_tree_in_waves_that_mix_every_kind_of_ray(hip):
+    """closest_like_rays lays its kinds out in contiguous blocks, so almost every wave holds one kind.  Shuffled, every wave holds
+    general-case rays (the ordered trees) beside special-case and far-origin rays (the reference walk of the slow lanes), whose
+    results the service merges lane by lane.  4 133 rays: 64 full waves and one partial.  The oracle is asked about every ray."""
+    import torch
+    sd = get_scene("sponza:0.03")
+    hsc = hip_scene(hip, sd)
+    rays = closest_like_rays(sd, 4133, 34)
+    rays = np.ascontiguousarray(rays[np.random.default_rng(35).permutation(len(rays))])
+    dr = torch.from_numpy(rays).cuda()
+    ref = hip.trace_closest(hsc, dr)
+    assert hip.set_ordered_tree(hsc, True)
+    fast = hip.trace_closest_wave(hsc, dr)
+    hit = _same(ref, fast)
+    assert 0.3 < hit.mean() <= 1.0
+    assert hip.set_ordered_tree(hsc, False)
+    _same(ref, hip.trace_closest_wave(hsc, dr))
+    hip.set_ordered_tree(hsc, True)
+    prim, mat, pos, nrm, _ = oracle_scene(sd).intersect(rays)
+    gp, gm, gpos, gn = [t.cpu().numpy() for t in fast]
     assert np.array_equal(prim, gp)
     h = prim >= 0
     assert np.array_equal(mat[h], gm[h]) and bits_equal(pos[h], gpos[h]) and bits_equal(nrm[h], gn[h])

@@ -104,7 +104,7 @@ def _shadow_like_segments(sd, n, seed):
 
 
 def test_occlusion_tree_equals_reference_walk(hip, monkeypatch):
-    """Shadow rays go through a second tree + ancestor-chain verification (rs_scene.h walk_occlusion_tree); the
+    """Shadow rays go through a second tree + ancestor-chain verification (rs_walk.h walk_occlusion_tree); the
     result must equal DevScene::testOcclusion on the reference's tree for every segment: against the oracle, and at
     a larger count against the library's own reference walk (RS_NO_OCCLUSION_TREE)."""
     import torch
@@ -121,6 +121,26 @@ def test_occlusion_tree_equals_reference_walk(hip, monkeypatch):
     assert 0.05 < a.mean() < 0.95
     sub = seg[:: 10]
     assert np.array_equal(oracle_scene(sd).test_occlusion(sub), a[:: 10])
+
+
+def test_occlusion_tree_in_waves_that_mix_every_kind_of_segment(hip, monkeypatch):
+    """_shadow_like_segments lays its kinds out in contiguous blocks, so almost every wave holds one kind.  Shuffled, every wave
+    holds general-case segments (the shadow tree) beside special-case and far-origin ones (the reference walk of the slow lanes),
+    whose answers the service merges lane by lane.  4 133 segments: 64 full waves and one partial, all of them checked by the oracle."""
+    import torch
+    sd = get_scene("sponza:0.03")
+    seg = _shadow_like_segments(sd, 4133, 36)
+    seg = np.ascontiguousarray(seg[np.random.default_rng(37).permutation(len(seg))])
+    fast = hip.Scene(sd.vertices, sd.normals, sd.texcoords, sd.material_ids, sd.materials)
+    monkeypatch.setenv("RS_NO_OCCLUSION_TREE", "1")
+    slow = hip.Scene(sd.vertices, sd.normals, sd.texcoords, sd.material_ids, sd.materials)
+    monkeypatch.delenv("RS_NO_OCCLUSION_TREE")
+    dseg = torch.from_numpy(seg).cuda()
+    a = hip.trace_occlusion(fast, dseg).cpu().numpy()
+    b = hip.trace_occlusion(slow, dseg).cpu().numpy()
+    assert np.array_equal(a, b)
+    assert 0.05 < a.mean() < 0.95
+    assert np.array_equal(oracle_scene(sd).test_occlusion(seg), a)
 
 
 def test_occlusion_tree_with_caller_supplied_boxes(hip, monkeypatch):
@@ -447,7 +467,7 @@ def test_multi_bounce_kernels_bit_exact(hip, correctly_rounded_libm, name):
 @pytest.mark.parametrize("name", ["cornell", "cornell_textured", "sponza:0.03"])
 def test_restir_indirect_shallow_depths(hip, correctly_rounded_libm, name):
     """ReSTIRIndirect at trace depths 1 and 2.  The last bounce of a path only asks whether its closest hit is emissive and is answered
-    through the emissive triangles' own tree (rs_scene.h may_hit_emissive_wave) -- except at depth 1 of ReSTIRIndirect, whose sample records
+    through the emissive triangles' own tree (rs_walk.h may_hit_emissive_wave) -- except at depth 1 of ReSTIRIndirect, whose sample records
     the hit point whatever it is (src/restir.cu:345-360), and in scenes with an environment map, where a miss contributes: both exceptions
     and the rule itself against the oracle, images, ray counts and reservoirs bit for bit."""
     import torch

@@ -1,6 +1,6 @@
 // tools/micro/gather_rate.hip -- the rate at which a CU serves DEPENDENT per-lane 16-byte gathers: the roofline of an incoherent tree walk.
 //
-// A per-lane walk of a 16-byte-node tree (rs_scene.h walk_occlusion_tree / walk_ordered_tree) is, to the memory system, a pointer chase
+// A per-lane walk of a 16-byte-node tree (rs_walk.h walk_occlusion_tree / walk_ordered_tree) is, to the memory system, a pointer chase
 // per lane: load 16 bytes, a few dozen ALU instructions, the next address depends on what was loaded.  Neither the HBM roofline (the trees
 // sit in L2 / the Infinity Cache) nor the VALU issue rate describes it.  This measures what the hardware can do with that pattern:
 //

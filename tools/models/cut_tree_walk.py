@@ -1,5 +1,5 @@
 """tools/models/cut_tree_walk.py -- CPU model of the shadow tree cut below its top levels (restir_amd/csrc/scene.hip build_occlusion_side,
-rs_scene.h walk_occlusion_tree<true>): LDS slots in pre-order, link records below the inner nodes of the last level and after the
+rs_walk.h walk_occlusion_tree): LDS slots in pre-order, link records below the inner nodes of the last level and after the
 last slot; random trees and random box-test outcomes, the cut walk must visit the nodes of the plain walk in the same order."""
 import random, sys
 sys.setrecursionlimit(100000)

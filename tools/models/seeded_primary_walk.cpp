@@ -5,7 +5,7 @@
 // reference's rule (dist < closest, closest from +inf).  Every triangle at distance <= t0 lies in nodes the bound keeps, triangles the bound
 // removes are farther than T0 and can only have been temporary answers of the reference's walk, so the final (triangle, distance) is the
 // reference's -- the model checks that on every ray.  What it measures: nodes visited per ray, and the UNION of visited nodes per 8x8 tile,
-// which is what the wave-cooperative packet walk pays (rs_scene.h trace_closest_packet), for
+// which is what the wave-cooperative packet walk pays (rs_walk.h trace_closest_packet), for
 //   G        pixel-centre rays alone (k_render_gbuffer)
 //   P        jittered rays alone, unseeded (k_primary)
 //   G+P      both rays of an 8x4 tile in one wave (k_gbuffer_primary, the product's fused launch)
