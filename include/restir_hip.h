@@ -266,8 +266,40 @@ int  rs_scene_set_sample_sequence(rs_scene* scene, const uint32_t* data, int num
  * unchanged: count < 0, an id out of range or of a material that is not a Light, a negative, NaN or infinite
  * radiance, an edit that leaves the light sampler without a positive total power; with RS_ERR_UNSUPPORTED while the
  * library stream is being captured into a graph (captured frames keep the emission they were captured with).
- * Textured emission, the environment map and the emitters' geometry are not edited. */
+ * Textured emission and the emitters' geometry are not edited; the environment map is edited by
+ * rs_scene_set_texture. */
 int  rs_scene_set_emission(rs_scene* scene, int count, const int* materialIds, const float* radiance);
+/* Material records of materials that are not Lights.  Host arrays: count material ids and count full rs_material structs, copied as
+ * they are (no range checks on the values; a repeated id: the last record wins; count == 0 succeeds and changes nothing).  Ordered
+ * exactly as rs_scene_set_emission, in the same ring of versions, so that calls of both kinds stay in order: no device
+ * synchronisation, a render that has only been recorded is launched first with the old records, launches enqueued before the call read
+ * the old records and launches after it the new ones, and the host waits only when the ring runs out.  The type may change among
+ * Lambertian, MetallicWorkflow, Dielectric and Disney (0..3); map ids follow the rules of rs_scene_create against the scene's texture
+ * table.  A scene that had no map and no environment map takes its first map here (the procedural one, -2, included): the texture
+ * coordinates kept on the host are uploaded then.  Afterwards rs_scene_host_desc returns the new records and the scene renders, bit for
+ * bit, like one built afresh from the edited materials; any accepted edit invalidates retained G-buffer planes (base colour and its map
+ * feed the albedo plane, the normal map the normal plane).  Refused with RS_ERR_INVALID_ARGUMENT, the scene unchanged: count < 0 or
+ * null arrays with count > 0, an id out of range, a material that is a Light now or would become one (the light list, the emissive
+ * tree and the G-buffer's -2 ids depend on which materials are Lights; emission stays with rs_scene_set_emission), a bad map id, a
+ * first map on a scene created with texcoords == NULL; with RS_ERR_UNSUPPORTED while the library stream is being captured.
+ * ReSTIR's temporal reservoirs keep weights drawn under the old BSDF for up to the M clamp's 20 frames, as in the reference;
+ * rs_restir_reset drops them. */
+int  rs_scene_set_materials(rs_scene* scene, int count, const int* materialIds, const rs_material* records);
+/* The texels of texture texId of the scene's table: width x height must be the texture's own, data is host memory of 3 floats per
+ * texel and is copied.  Ordering and refusals as rs_scene_set_materials (texId out of range, other dimensions and null data are
+ * RS_ERR_INVALID_ARGUMENT).  Memory: a texture that is never edited keeps its one device array.  An edited texture holds at most three
+ * device arrays of its size (the original among them; the second and third are allocated by the first edits that find every existing
+ * one still referenced by a version in flight) and one pinned host array per device array it has filled; with all three referenced by
+ * frames in flight the host waits for the oldest.  A 1024 x 1024 map so costs at most 24 MiB of device and 36 MiB of pinned host
+ * memory beyond the unedited scene.  The environment sampler's alias table (8 bytes per texel) is kept the same way.
+ * If texId is the environment map the host rebuilds what rs_scene_build_textured builds from it -- rs_build_envmap_pdf, the map's
+ * alias table, its entry in the light sampler (the pdf's sum), then the light alias table and sumLightPower, which changes every light
+ * record -- and all of it reaches the device with the same version switch; rs_scene_host_desc then returns texels, envMapProb,
+ * envMapFailId, lightProb, lightFailId and sumLightPower equal, bit for bit, to those of a scene built afresh, and a later
+ * rs_scene_set_emission uses the new environment power.  An environment map whose pdf sum, or the resulting total light power, is not
+ * finite and positive is refused with RS_ERR_INVALID_ARGUMENT, the scene unchanged.  The environment entry stays outside light
+ * tracking (rs_restir_set_light_tracking), as before. */
+int  rs_scene_set_texture(rs_scene* scene, int texId, int width, int height, const float* data);
 /* Scene::clear / DevScene::destroy (src/scene.cpp:217-220,511-532). */
 int  rs_scene_destroy(rs_scene* scene);
 

@@ -128,7 +128,7 @@ RIS_GLOBAL, RIS_LDS, RIS_ALIAS_LDS = 0, 1, 2
 EXPORTS = [
     "rs_last_error", "rs_context_create", "rs_context_destroy", "rs_context_set_current", "rs_init", "rs_set_stream", "rs_set_sync", "rs_set_side_stream", "rs_set_ris_table_pixels", "rs_set_internal_stream_priority", "rs_internal_streams_info", "rs_choose_internal_streams_again", "rs_prepare_streams", "rs_set_stream_plan", "rs_set_denoise_stream", "rs_join_denoise_stream", "rs_set_tile_split", "rs_synchronize",
     "rs_build_bvh", "rs_build_light_table", "rs_build_alias_table", "rs_build_envmap_pdf", "rs_scene_build", "rs_scene_build_textured", "rs_scene_create",
-    "rs_scene_host_desc", "rs_scene_set_sample_sequence", "rs_scene_set_emission", "rs_scene_destroy", "rs_camera_update", "rs_trace_closest", "rs_trace_closest_wave", "rs_scene_set_ordered_tree", "rs_ordered_bvh_host_check", "rs_trace_occlusion",
+    "rs_scene_host_desc", "rs_scene_set_sample_sequence", "rs_scene_set_emission", "rs_scene_set_materials", "rs_scene_set_texture", "rs_scene_destroy", "rs_camera_update", "rs_trace_closest", "rs_trace_closest_wave", "rs_scene_set_ordered_tree", "rs_ordered_bvh_host_check", "rs_trace_occlusion",
     "rs_gbuffer_create", "rs_gbuffer_destroy", "rs_gbuffer_render", "rs_gbuffer_render_rows", "rs_gbuffer_update",
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
@@ -185,6 +185,8 @@ def lib():
     L.rs_scene_host_desc.argtypes = [vp, C.POINTER(SceneDesc)]
     L.rs_scene_destroy.argtypes = [vp]
     L.rs_scene_set_emission.argtypes = [vp, ci, vp, vp]
+    L.rs_scene_set_materials.argtypes = [vp, ci, vp, vp]
+    L.rs_scene_set_texture.argtypes = [vp, ci, ci, ci, vp]
     L.rs_restir_set_light_tracking.argtypes = [vp, ci]
     L.rs_restir_download_light_ids.argtypes = [vp, ci, vp]
     L.rs_restir_light_rows_bytes.argtypes = [vp, ci]
@@ -574,12 +576,13 @@ class Scene:
     @classmethod
     def from_tables(cls, vertices, normals, texcoords, material_ids, materials, tables, textures=(), env_map_tex=-1, env_sampler=None):
         """DevScene::create from caller-built tables (rs_scene_create): `tables` as returned by host_desc();
-        env_sampler = (prob, failId) of the environment map's alias table when env_map_tex >= 0."""
+        env_sampler = (prob, failId) of the environment map's alias table when env_map_tex >= 0; texcoords None = a scene created
+        without texture coordinates (rs_scene_desc::texcoords == NULL: it takes no texture map, at creation or by set_materials)."""
         self = cls.__new__(cls)
         t = tables
         self._tex, tex = _texture_table(textures)
         self._keep = (np.ascontiguousarray(vertices, np.float32), np.ascontiguousarray(normals, np.float32),
-                      np.ascontiguousarray(texcoords, np.float32), np.ascontiguousarray(material_ids, np.int32),
+                      None if texcoords is None else np.ascontiguousarray(texcoords, np.float32), np.ascontiguousarray(material_ids, np.int32),
                       np.ascontiguousarray(materials, MATERIAL_DTYPE),
                       np.ascontiguousarray(t["boxes"], np.float32), [np.ascontiguousarray(t["nodes"][k], np.int32) for k in range(6)],
                       np.ascontiguousarray(t["light_prim_ids"], np.int32), np.ascontiguousarray(t["light_radiance"], np.float32),
@@ -588,7 +591,7 @@ class Scene:
         self.num_prims = v.size // 9
         d = SceneDesc()
         d.numPrims = self.num_prims
-        d.vertices, d.normals, d.texcoords, d.materialIds = _p(v), _p(n), _p(tc), _p(m)
+        d.vertices, d.normals, d.texcoords, d.materialIds = _p(v), _p(n), (None if tc is None else _p(tc)), _p(m)
         d.numMaterials, d.materials = len(mats), _p(mats)
         d.bvhSize, d.boundingBoxes = len(boxes), _p(boxes)
         for k in range(6):
@@ -621,6 +624,23 @@ class Scene:
             raise ValueError("set_emission: one radiance row per material id")
         check(lib().rs_scene_set_emission(self.handle, int(ids.size), _p(ids), _p(rad)))
 
+    def set_materials(self, material_ids, records):
+        """rs_scene_set_materials: the records (MATERIAL_DTYPE) of the materials `material_ids`, none of them a Light before or after,
+        ordered on the library stream like set_emission (no synchronisation)."""
+        ids = np.ascontiguousarray(material_ids, np.int32).reshape(-1)
+        rec = np.ascontiguousarray(records, MATERIAL_DTYPE).reshape(-1)
+        if rec.size != ids.size:
+            raise ValueError("set_materials: one record per material id")
+        check(lib().rs_scene_set_materials(self.handle, int(ids.size), _p(ids), _p(rec)))
+
+    def set_texture(self, tex_id, image):
+        """rs_scene_set_texture: the texels of texture `tex_id` := `image` ((H, W, 3) float32 of the texture's own size), ordered like
+        set_emission; for the environment map its sampler and the light sampler are rebuilt as well."""
+        img = np.ascontiguousarray(image, np.float32)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("set_texture: textures are (H, W, 3) float32")
+        check(lib().rs_scene_set_texture(self.handle, int(tex_id), img.shape[1], img.shape[0], _p(img)))
+
     def host_desc(self):
         """numpy views of the arrays the scene was built from (for parity checks of the host build)."""
         d = SceneDesc()
@@ -647,6 +667,9 @@ class Scene:
             sum_power=np.float32(d.sumLightPower), num_lights=l, bvh_size=s, num_prims=n,
             env_map_tex=d.envMapTexId,
             env_prob=arr(d.envMapProb, np.float32, ne, (ne,)), env_fail=arr(d.envMapFailId, np.int32, ne, (ne,)),
+            materials=np.frombuffer(C.string_at(d.materials, d.numMaterials * MATERIAL_DTYPE.itemsize), MATERIAL_DTYPE).copy(),
+            textures=[arr(t.data, np.float32, t.width * t.height * 3, (t.height, t.width, 3))
+                      for t in C.cast(d.textures, C.POINTER(Texture))[:d.numTextures]],
         )
 
     def destroy(self):

@@ -194,6 +194,7 @@ struct rs_scene {
     std::vector<int> hEnvFail;
     int envMapTexId = -1;
     bool textured = false;                        // any material map or an environment map: kernels take the textured variant
+    bool hasTexcoords = false;                    // created with texcoords (rs_scene_set_materials: a first map needs them)
     uint32_t* dSampleSeq = nullptr;  // the Sobol table (rs_scene_set_sample_sequence); null: the default thrust engine
     uint4* dOccNodes = nullptr;      // shadow-ray tree (occlusion_bvh.cpp)
     rs::BvhNode* dOccChain = nullptr;   // reference boxes + parent links by original node id
@@ -212,7 +213,8 @@ struct rs_scene {
     int numPrims = 0, bvhSize = 0, numLights = 0;
     unsigned long long id = 0;       // unique per rs_scene_create (a freed scene's address can come back; its id cannot)
     unsigned long long edits = 0;    // counts the edits that change what GBuffer::render writes (rs_scene_set_emission: baseColor, hence the albedo plane); part of a G-buffer set's content key
-    // Emission edits (rs_scene_set_emission): a ring of versions of { materials, light records, alias table }.  Kernels capture
+    // Edits (rs_scene_set_emission, rs_scene_set_materials, rs_scene_set_texture): a ring of versions of { materials, light records,
+    // alias table, texture table }.  Kernels capture
     // `dev` by value at launch, so a version is never written while a launch that captured it may still run: an edit fills the
     // next slot (ordered before every later launch by an event) and points `dev` at it, and a slot is filled again only after the events recorded when the
     // scene moved off it -- on the library stream and on every auxiliary stream -- have completed.  Version 0 is the arrays above.
@@ -222,11 +224,25 @@ struct rs_scene {
         rs_material* materials = nullptr;
         rs::LightRec* lights = nullptr;
         rs::AliasRec* alias = nullptr;
+        rs::TexRec* textures = nullptr;          // the texture table: its records point at the texel arrays current when the slot was filled
         char* staging = nullptr;                 // pinned host copy the slot is filled from
         hipEvent_t retired[kVersionStreams] = {};
         bool retiredValid[kVersionStreams] = {};
     } ver[kVersions];
     int verCur = 0;
+    unsigned long long verSeq = 0;               // how many edits the scene has taken: version verSeq lives in slot verSeq % kVersions
+    // Texel arrays and the environment sampler's alias table are too large to ring eightfold, and most are never edited: each is one
+    // Edited, which holds only the original array until its first edit and at most kEditedCopies arrays after (rs_scene_set_texture
+    // takes a copy no version in flight points at, allocates one while it may, else waits for the oldest to retire).
+    static constexpr int kEditedCopies = 3;
+    struct Edited {
+        void* dev[kEditedCopies] = {};           // [0]: the array rs_scene_create uploaded (owned by dTexData / dEnvAlias)
+        char* staging[kEditedCopies] = {};       // pinned host copy each later array is filled from
+        unsigned long long lastSeq[kEditedCopies] = {};   // the last version whose tables point at the array (the current one: open)
+        int count = 1, cur = 0;
+    };
+    std::vector<Edited> texEdited;               // one per texture
+    Edited envEdited;
     bool verReady = false;                       // slots 1.. and the staging buffers allocated
     hipEvent_t verFilled = nullptr;              // the last fill: the library stream and the auxiliary streams wait for it
     hipStream_t verStream = nullptr;             // the fills' own stream (a free slot waits for no frame in flight)

@@ -16,13 +16,15 @@ namespace {
 
 // Map ids as getTexturedMaterialAndSurface reads them (src/scene.h:78-99): baseColor -1 none / -2 procedural / index;
 // metallic and roughness are used only when > -1; a normal map id other than -1 indexes `textures` directly.
-int check_materials(int n, const rs_material* m, int numTextures, bool* anyMap) {
+int check_materials(int n, const rs_material* m, int numTextures, bool* anyMap,
+                    const char* beyond = "rs_scene_create: material map id beyond the texture table",
+                    const char* invalid = "rs_scene_create: invalid material map id") {
     *anyMap = false;
     for (int i = 0; i < n; i++) {
         const int ids[4] = { m[i].baseColorMapId, m[i].metallicMapId, m[i].roughnessMapId, m[i].normalMapId };
         for (int k = 0; k < 4; k++)
-            if (ids[k] >= numTextures) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_create: material map id beyond the texture table");
-        if (ids[0] < -2 || ids[3] < -1) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_create: invalid material map id");
+            if (ids[k] >= numTextures) return rs_fail(RS_ERR_INVALID_ARGUMENT, beyond);
+        if (ids[0] < -2 || ids[3] < -1) return rs_fail(RS_ERR_INVALID_ARGUMENT, invalid);
         if (ids[0] != -1 || ids[1] > -1 || ids[2] > -1 || ids[3] != -1) *anyMap = true;
     }
     return 0;
@@ -259,15 +261,16 @@ void light_records(const rs_scene* s, float sumInv, LightRec* rec, AliasRec* al)
     }
 }
 
-// Byte offsets of one version's three tables in its staging buffer (each 64-byte aligned)
-struct VersionLayout { size_t mat, light, alias, total; };
+// Byte offsets of one version's tables in its staging buffer (each 64-byte aligned)
+struct VersionLayout { size_t mat, light, alias, tex, total; };
 VersionLayout version_layout(const rs_scene* s) {
     auto up = [](size_t b) { return (b + 63) & ~(size_t)63; };
     VersionLayout l;
     l.mat = 0;
     l.light = up(s->hMaterials.size() * sizeof(rs_material));
     l.alias = l.light + up((size_t)s->numLights * sizeof(LightRec));
-    l.total = l.alias + up((size_t)s->numLights * sizeof(AliasRec));
+    l.tex = l.alias + up((size_t)s->numLights * sizeof(AliasRec));
+    l.total = l.tex + up(s->hTextures.size() * sizeof(TexRec));
     return l;
 }
 
@@ -275,18 +278,23 @@ VersionLayout version_layout(const rs_scene* s) {
 int versions_prepare(rs_scene* s) {
     if (s->verReady) return 0;
     const VersionLayout l = version_layout(s);
-    const size_t nm = s->hMaterials.size(), nl = (size_t)s->numLights;
-    s->ver[0].materials = s->dMaterials; s->ver[0].lights = s->dLights; s->ver[0].alias = s->dAlias;
+    const size_t nm = s->hMaterials.size(), nl = (size_t)s->numLights, nt = s->hTextures.size();
+    s->ver[0].materials = s->dMaterials; s->ver[0].lights = s->dLights; s->ver[0].alias = s->dAlias; s->ver[0].textures = s->dTextures;
     for (int v = 0; v < rs_scene::kVersions; v++) {
         rs_scene::Version& x = s->ver[v];
         if (v > 0) {
             RS_TRY(rs_dev_alloc(&x.materials, nm));
             RS_TRY(rs_dev_alloc(&x.lights, nl));
             RS_TRY(rs_dev_alloc(&x.alias, nl));
+            if (nt) RS_TRY(rs_dev_alloc(&x.textures, nt));
         }
         RS_HIP(hipHostMalloc((void**)&x.staging, l.total, hipHostMallocDefault));
         for (hipEvent_t& e : x.retired) RS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
+    s->texEdited.assign(nt, rs_scene::Edited{});
+    for (size_t i = 0; i < nt; i++) s->texEdited[i].dev[0] = s->dTexData[i];
+    s->envEdited = rs_scene::Edited{};
+    s->envEdited.dev[0] = s->dEnvAlias;
     RS_HIP(hipEventCreateWithFlags(&s->verFilled, hipEventDisableTiming));
     RS_HIP(hipStreamCreateWithFlags(&s->verStream, hipStreamNonBlocking));
     // Math::triangleArea of every light primitive, as rs_build_light_table computes it (scene_build.cpp)
@@ -310,15 +318,145 @@ int versions_prepare(rs_scene* s) {
     return 0;
 }
 
+void edited_free(rs_scene::Edited& e) {
+    for (int k = 0; k < rs_scene::kEditedCopies; k++) {
+        if (k > 0 && e.dev[k]) (void)hipFree(e.dev[k]);           // ([0] is the scene's own array)
+        if (e.staging[k]) (void)hipHostFree(e.staging[k]);
+        e.dev[k] = nullptr; e.staging[k] = nullptr;
+    }
+}
+
 void versions_free(rs_scene* s) {
     for (int v = 0; v < rs_scene::kVersions; v++) {
         rs_scene::Version& x = s->ver[v];
-        if (v > 0) { rs_dev_free(x.materials); rs_dev_free(x.lights); rs_dev_free(x.alias); }
+        if (v > 0) { rs_dev_free(x.materials); rs_dev_free(x.lights); rs_dev_free(x.alias); rs_dev_free(x.textures); }
         if (x.staging) { (void)hipHostFree(x.staging); x.staging = nullptr; }
         for (hipEvent_t& e : x.retired) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     }
+    for (rs_scene::Edited& e : s->texEdited) edited_free(e);
+    edited_free(s->envEdited);
     if (s->verFilled) { (void)hipEventDestroy(s->verFilled); s->verFilled = nullptr; }
     if (s->verStream) { (void)hipStreamDestroy(s->verStream); s->verStream = nullptr; }
+}
+
+// Edits are not recorded into graphs: a captured frame keeps the tables it was captured with
+int refuse_while_capturing(const char* msg) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(rs_stream(), &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
+    if (capturing != hipStreamCaptureStatusNone) return rs_fail(RS_ERR_UNSUPPORTED, msg);
+    return 0;
+}
+
+// An edit, first half (the new host tables have been built and checked; nothing of the scene has changed yet): launches what has only
+// been recorded, with the old tables, and frees the slot the edit will fill.
+int version_begin(rs_scene* s) {
+    // frames in flight: a render that has only been recorded captures `dev` when it is launched -- launch it now, with the old tables
+    RS_TRY(rs_gbuffer_release_scene(s));
+    rs_scene::Version& nv = s->ver[(s->verCur + 1) % rs_scene::kVersions];
+    for (int k = 0; k < rs_scene::kVersionStreams; k++)          // the ring has run out only if a launch that captured the slot still runs
+        if (nv.retiredValid[k]) { RS_HIP(hipEventSynchronize(nv.retired[k])); nv.retiredValid[k] = false; }
+    return 0;
+}
+
+// Between version_begin and version_commit: the edit replaces the contents of `e` (`bytes`).  They go, on the fills' stream, to an array
+// that no version in flight points at -- edited_reserve finds it, edited_fill writes it, so that an edit that replaces two (the
+// environment map's texels and its alias table) has reserved both before it changes either.  version_begin has waited for version
+// verSeq + 1 - kVersions, and versions retire in order, so an array last used kVersions edits back is free; failing that a new one is
+// allocated while the Edited may grow; failing that the host waits for the versions that read the array left longest ago.
+int edited_reserve(rs_scene* s, rs_scene::Edited& e, size_t bytes, int* which) {
+    const unsigned long long newSeq = s->verSeq + 1;
+    int k = -1;
+    for (int i = 0; i < e.count && k < 0; i++)
+        if (i != e.cur && e.lastSeq[i] + rs_scene::kVersions <= newSeq) k = i;
+    if (k < 0 && e.count < rs_scene::kEditedCopies) {
+        RS_HIP(hipMalloc(&e.dev[e.count], bytes ? bytes : 1));
+        e.lastSeq[e.count] = 0;                                  // (never pointed at yet)
+        k = e.count++;
+    }
+    if (k < 0) {
+        for (int i = 0; i < e.count; i++)
+            if (i != e.cur && (k < 0 || e.lastSeq[i] < e.lastSeq[k])) k = i;
+        // the versions up to lastSeq[k] retire in order, and the events of lastSeq[k] are still in its slot (less than kVersions edits back)
+        rs_scene::Version& x = s->ver[e.lastSeq[k] % rs_scene::kVersions];
+        for (int j = 0; j < rs_scene::kVersionStreams; j++)
+            if (x.retiredValid[j]) { RS_HIP(hipEventSynchronize(x.retired[j])); x.retiredValid[j] = false; }
+    }
+    if (!e.staging[k]) RS_HIP(hipHostMalloc((void**)&e.staging[k], bytes ? bytes : 1, hipHostMallocDefault));
+    *which = k;
+    return 0;
+}
+int edited_fill(rs_scene* s, rs_scene::Edited& e, int k, const void* src, size_t bytes) {
+    std::memcpy(e.staging[k], src, bytes);
+    RS_HIP(hipMemcpyAsync(e.dev[k], e.staging[k], bytes, hipMemcpyHostToDevice, s->verStream));
+    e.lastSeq[e.cur] = s->verSeq;
+    e.cur = k;
+    return 0;
+}
+
+// An edit, second half (the scene's host tables are the new ones): fills the next slot from them and moves the scene there.
+int version_commit(rs_scene* s, const char* what) {
+    const int next = (s->verCur + 1) % rs_scene::kVersions;
+    rs_scene::Version& nv = s->ver[next];
+    const size_t nl = (size_t)s->numLights, nt = s->hTextures.size();
+    const float sumInv = 1.f / s->sumLightPower;                         // scene.cpp:489
+    const VersionLayout l = version_layout(s);
+    std::memcpy(nv.staging + l.mat, s->hMaterials.data(), s->hMaterials.size() * sizeof(rs_material));
+    light_records(s, sumInv, reinterpret_cast<LightRec*>(nv.staging + l.light), reinterpret_cast<AliasRec*>(nv.staging + l.alias));
+    TexRec* recs = reinterpret_cast<TexRec*>(nv.staging + l.tex);
+    for (size_t i = 0; i < nt; i++) {
+        const rs_scene::Edited& e = s->texEdited[i];
+        recs[i] = TexRec{ static_cast<float*>(e.dev[e.cur]), s->hTextures[i].width, s->hTextures[i].height };
+    }
+
+    // the current slot is retired by what has been enqueued so far on the library stream and on every auxiliary stream
+    rs_context* c = rs_ctx();
+    const hipStream_t st = rs_stream();
+    rs_scene::Version& ov = s->ver[s->verCur];
+    RS_HIP(hipEventRecord(ov.retired[0], st)); ov.retiredValid[0] = true;
+    for (int i = 0; i < rs_context::kAux; i++)
+        if (c->aux[i]) { RS_HIP(hipEventRecord(ov.retired[1 + i], c->aux[i])); ov.retiredValid[1 + i] = true; }
+    // The slot is free (no launch reads it), so its fill waits for nothing: it goes to a stream of the scene's own and the library and
+    // auxiliary streams wait for that copy alone.  (Filled on the library stream, the edit would order the auxiliary streams after the
+    // frames in flight there and end the overlap of consecutive frames: config 5 with an edit per frame 1.69 -> 3.12 ms.)
+    RS_HIP(hipMemcpyAsync(nv.materials, nv.staging + l.mat, s->hMaterials.size() * sizeof(rs_material), hipMemcpyHostToDevice, s->verStream));
+    if (nl) {
+        RS_HIP(hipMemcpyAsync(nv.lights, nv.staging + l.light, nl * sizeof(LightRec), hipMemcpyHostToDevice, s->verStream));
+        RS_HIP(hipMemcpyAsync(nv.alias, nv.staging + l.alias, nl * sizeof(AliasRec), hipMemcpyHostToDevice, s->verStream));
+    }
+    if (nt) RS_HIP(hipMemcpyAsync(nv.textures, nv.staging + l.tex, nt * sizeof(TexRec), hipMemcpyHostToDevice, s->verStream));
+    RS_HIP(hipEventRecord(s->verFilled, s->verStream));
+    RS_HIP(hipStreamWaitEvent(st, s->verFilled, 0));             // launches from now on see the new tables
+    for (int i = 0; i < rs_context::kAux; i++)
+        if (c->aux[i]) RS_HIP(hipStreamWaitEvent(c->aux[i], s->verFilled, 0));
+    s->dev.materials = nv.materials;
+    s->dev.lights = nv.lights;
+    s->dev.alias = nv.alias;
+    if (nt) s->dev.textures = nv.textures;
+    if (s->envMapTexId >= 0) s->dev.envAlias = static_cast<AliasRec*>(s->envEdited.dev[s->envEdited.cur]);
+    s->dev.sumLightPowerInv = sumInv;
+    s->verCur = next;
+    s->verSeq++;
+    s->edits++;                                                  // retained G-buffer planes are not this scene's any more
+    return rs_after_launch(what);
+}
+
+// The light sampler of the scene's light primitives with radiance `rad` (3 floats each) and the environment entry's power envPower, as
+// rs_scene_build_textured builds it (rs_build_light_table's powers, the environment map's entry last, rs_build_alias_table)
+int light_sampler(const rs_scene* s, const float* rad, float envPower, std::vector<float>& prob, std::vector<int>& fail, float* sumAll, const char* noPower) {
+    const size_t nl = (size_t)s->numLights, nlp = s->hLightPrimIds.size();
+    std::vector<float> power(nl);
+    prob.assign(nl, 0.f); fail.assign(nl, 0);
+    for (size_t i = 0; i < nlp; i++) {
+        const float perArea = luminance(ld3(rad + i * 3)) * 2.f * kGlmPi;       // rs_build_light_table (scene.cpp:164)
+        power[i] = perArea * s->hLightArea[i];
+    }
+    if (nlp < nl) power[nlp] = envPower;
+    *sumAll = 0.f;
+    if (nl) {
+        RS_TRY(rs_build_alias_table((int)nl, power.data(), prob.data(), fail.data(), sumAll));
+        if (!(*sumAll > 0.f) || std::isinf(*sumAll)) return rs_fail(RS_ERR_INVALID_ARGUMENT, noPower);
+    }
+    return 0;
 }
 
 }  // namespace
@@ -379,75 +517,108 @@ extern "C" int rs_scene_set_emission(rs_scene* s, int count, const int* material
             if (!(x >= 0.f) || std::isinf(x)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_emission: radiance must be finite and >= 0");
         }
     }
-    {
-        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(rs_stream(), &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
-        if (capturing != hipStreamCaptureStatusNone) return rs_fail(RS_ERR_UNSUPPORTED, "rs_scene_set_emission: the library stream is being captured into a graph");
-    }
+    RS_TRY(refuse_while_capturing("rs_scene_set_emission: the library stream is being captured into a graph"));
     RS_TRY(versions_prepare(s));
 
     // the new host tables (nothing of the scene changes before all of them have been built and checked)
     std::vector<rs_material> mats = s->hMaterials;
     for (int i = 0; i < count; i++) std::memcpy(mats[(size_t)materialIds[i]].baseColor, radiance + (size_t)i * 3, 3 * sizeof(float));
-    const size_t nl = (size_t)s->numLights, nlp = s->hLightPrimIds.size();
-    std::vector<float> rad(nlp * 3), power(nl), prob(nl);
-    std::vector<int> fail(nl);
-    for (size_t i = 0; i < nlp; i++) {
-        const f3 Le = ld3(mats[(size_t)s->hMaterialIds[(size_t)s->hLightPrimIds[i]]].baseColor);
-        st3(&rad[i * 3], Le);
-        const float perArea = luminance(Le) * 2.f * kGlmPi;            // rs_build_light_table (scene.cpp:164)
-        power[i] = perArea * s->hLightArea[i];
-    }
-    if (nlp < nl) power[nlp] = s->envPower;
+    const size_t nlp = s->hLightPrimIds.size();
+    std::vector<float> rad(nlp * 3), prob;
+    std::vector<int> fail;
+    for (size_t i = 0; i < nlp; i++) st3(&rad[i * 3], ld3(mats[(size_t)s->hMaterialIds[(size_t)s->hLightPrimIds[i]]].baseColor));
     float sumAll = 0.f;
-    if (nl) {
-        RS_TRY(rs_build_alias_table((int)nl, power.data(), prob.data(), fail.data(), &sumAll));
-        if (!(sumAll > 0.f) || std::isinf(sumAll))
-            return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_emission: the edit leaves the light sampler without a finite, positive total power");
-    }
+    RS_TRY(light_sampler(s, rad.data(), s->envPower, prob, fail, &sumAll,
+                         "rs_scene_set_emission: the edit leaves the light sampler without a finite, positive total power"));
 
-    // frames in flight: a render that has only been recorded captures `dev` when it is launched -- launch it now, with the old tables
-    RS_TRY(rs_gbuffer_release_scene(s));
-    const int next = (s->verCur + 1) % rs_scene::kVersions;
-    rs_scene::Version& nv = s->ver[next];
-    for (int k = 0; k < rs_scene::kVersionStreams; k++)          // the ring has run out only if a launch that captured the slot still runs
-        if (nv.retiredValid[k]) { RS_HIP(hipEventSynchronize(nv.retired[k])); nv.retiredValid[k] = false; }
-
+    RS_TRY(version_begin(s));
     s->hMaterials.swap(mats);
     s->hLightRadiance.swap(rad);
     s->hLightProb.swap(prob);
     s->hLightFailId.swap(fail);
     s->sumLightPower = sumAll;
-    const VersionLayout l = version_layout(s);
-    std::memcpy(nv.staging + l.mat, s->hMaterials.data(), s->hMaterials.size() * sizeof(rs_material));
-    light_records(s, 1.f / sumAll, reinterpret_cast<LightRec*>(nv.staging + l.light), reinterpret_cast<AliasRec*>(nv.staging + l.alias));
+    return version_commit(s, "rs_scene_set_emission");
+}
 
-    // the current slot is retired by what has been enqueued so far on the library stream and on every auxiliary stream
-    rs_context* c = rs_ctx();
-    const hipStream_t st = rs_stream();
-    rs_scene::Version& ov = s->ver[s->verCur];
-    RS_HIP(hipEventRecord(ov.retired[0], st)); ov.retiredValid[0] = true;
-    for (int i = 0; i < rs_context::kAux; i++)
-        if (c->aux[i]) { RS_HIP(hipEventRecord(ov.retired[1 + i], c->aux[i])); ov.retiredValid[1 + i] = true; }
-    // The slot is free (no launch reads it), so its fill waits for nothing: it goes to a stream of the scene's own and the library and
-    // auxiliary streams wait for that copy alone.  (Filled on the library stream, the edit would order the auxiliary streams after the
-    // frames in flight there and end the overlap of consecutive frames: config 5 with an edit per frame 1.69 -> 3.12 ms.)
-    RS_HIP(hipMemcpyAsync(nv.materials, nv.staging + l.mat, s->hMaterials.size() * sizeof(rs_material), hipMemcpyHostToDevice, s->verStream));
-    if (nl) {
-        RS_HIP(hipMemcpyAsync(nv.lights, nv.staging + l.light, nl * sizeof(LightRec), hipMemcpyHostToDevice, s->verStream));
-        RS_HIP(hipMemcpyAsync(nv.alias, nv.staging + l.alias, nl * sizeof(AliasRec), hipMemcpyHostToDevice, s->verStream));
+// Material records, stream-ordered like the emission (include/restir_hip.h).  Light materials stay with rs_scene_set_emission: the light
+// list, the emissive tree and the G-buffer's -2 ids are built from which materials are Lights.
+extern "C" int rs_scene_set_materials(rs_scene* s, int count, const int* materialIds, const rs_material* records) {
+    RS_SCOPE(s);
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_materials: null scene");
+    if (count < 0 || (count > 0 && (!materialIds || !records))) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_materials: count < 0 or null arrays");
+    const int nm = (int)s->hMaterials.size();
+    for (int i = 0; i < count; i++) {
+        const int m = materialIds[i];
+        if (m < 0 || m >= nm) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_materials: a material id out of range");
+        if (s->hMaterials[(size_t)m].type == 4 || records[i].type < 0 || records[i].type > 3)
+            return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_materials: a material that is a Light or would become one (or of an unknown type); emission is edited by rs_scene_set_emission");
     }
-    RS_HIP(hipEventRecord(s->verFilled, s->verStream));
-    RS_HIP(hipStreamWaitEvent(st, s->verFilled, 0));             // launches from now on see the new tables
-    for (int i = 0; i < rs_context::kAux; i++)
-        if (c->aux[i]) RS_HIP(hipStreamWaitEvent(c->aux[i], s->verFilled, 0));
-    s->dev.materials = nv.materials;
-    s->dev.lights = nv.lights;
-    s->dev.alias = nv.alias;
-    s->dev.sumLightPowerInv = 1.f / sumAll;                              // scene.cpp:489
-    s->verCur = next;
-    s->edits++;                                                          // baseColor feeds the albedo plane: retained G-buffer planes are not this scene's any more
-    return rs_after_launch("rs_scene_set_emission");
+    RS_TRY(refuse_while_capturing("rs_scene_set_materials: the library stream is being captured into a graph"));
+    if (count == 0) return 0;
+    std::vector<rs_material> mats = s->hMaterials;
+    for (int i = 0; i < count; i++) mats[(size_t)materialIds[i]] = records[i];           // a repeated id: the last record wins
+    bool anyMap = false;
+    RS_TRY(check_materials(nm, mats.data(), (int)s->hTextures.size(), &anyMap, "rs_scene_set_materials: material map id beyond the texture table",
+                           "rs_scene_set_materials: invalid material map id"));
+    if (anyMap && !s->hasTexcoords) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_materials: texture maps need texcoords, and the scene was created without");
+    RS_TRY(versions_prepare(s));
+
+    RS_TRY(version_begin(s));
+    if (anyMap && !s->textured) {
+        // the scene's first map: so far it ran the kernels that read no texture coordinates, and none are on the device
+        if (!s->dTexcoords) RS_TRY(rs_dev_alloc(&s->dTexcoords, s->hTexcoords.size()));
+        RS_HIP(hipMemcpyAsync(s->dTexcoords, s->hTexcoords.data(), s->hTexcoords.size() * sizeof(float), hipMemcpyHostToDevice, s->verStream));
+        s->dev.texcoords = s->dTexcoords;
+        s->textured = true;
+    }
+    s->hMaterials.swap(mats);
+    return version_commit(s, "rs_scene_set_materials");
+}
+
+// The texels of one texture, stream-ordered like the emission (include/restir_hip.h).  For the environment map the host rebuilds what
+// rs_scene_build_textured builds from it: the pdf, the map's alias table, its entry in the light sampler and with it the light sampler.
+extern "C" int rs_scene_set_texture(rs_scene* s, int texId, int width, int height, const float* data) {
+    RS_SCOPE(s);
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_texture: null scene");
+    if (texId < 0 || texId >= (int)s->hTextures.size()) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_texture: texture id out of range");
+    const rs_texture& t = s->hTextures[(size_t)texId];
+    if (width != t.width || height != t.height || !data) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_texture: null data, or dimensions other than the texture's");
+    RS_TRY(refuse_while_capturing("rs_scene_set_texture: the library stream is being captured into a graph"));
+    RS_TRY(versions_prepare(s));
+    const size_t n = (size_t)width * height;
+    const bool env = texId == s->envMapTexId;
+    std::vector<float> envProb, prob;
+    std::vector<int> envFail, fail;
+    float envSum = 0.f, sumAll = 0.f;
+    if (env) {
+        std::vector<float> pdf(n);
+        RS_TRY(rs_build_envmap_pdf(width, height, data, pdf.data()));
+        for (float p : pdf) envSum += p;                                 // rs_build_alias_table's sum, in its order
+        if (!(envSum > 0.f) || std::isinf(envSum)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_texture: the environment map's pdf has no finite, positive sum");
+        envProb.resize(n); envFail.resize(n);
+        RS_TRY(rs_build_alias_table((int)n, pdf.data(), envProb.data(), envFail.data(), &envSum));
+        RS_TRY(light_sampler(s, s->hLightRadiance.data(), envSum, prob, fail, &sumAll,
+                             "rs_scene_set_texture: the edit leaves the light sampler without a finite, positive total power"));
+    }
+
+    RS_TRY(version_begin(s));
+    int texels = 0, alias = 0;
+    RS_TRY(edited_reserve(s, s->texEdited[(size_t)texId], n * 3 * sizeof(float), &texels));
+    if (env) RS_TRY(edited_reserve(s, s->envEdited, n * sizeof(AliasRec), &alias));
+    RS_TRY(edited_fill(s, s->texEdited[(size_t)texId], texels, data, n * 3 * sizeof(float)));
+    std::memcpy(s->hTexData[(size_t)texId].data(), data, n * 3 * sizeof(float));
+    if (env) {
+        std::vector<AliasRec> al(n);
+        for (size_t i = 0; i < n; i++) { al[i].prob = envProb[i]; al[i].failId = envFail[i]; }
+        RS_TRY(edited_fill(s, s->envEdited, alias, al.data(), n * sizeof(AliasRec)));
+        s->hEnvProb.swap(envProb);
+        s->hEnvFail.swap(envFail);
+        s->hLightProb.swap(prob);
+        s->hLightFailId.swap(fail);
+        s->sumLightPower = sumAll;
+        s->envPower = envSum; s->envPowerKnown = true;
+    }
+    return version_commit(s, "rs_scene_set_texture");
 }
 
 int rs_check_looper(const rs_scene* scene, int looper, const char* what) {
@@ -490,6 +661,7 @@ extern "C" int rs_scene_create(const rs_scene_desc* d, rs_scene** out) {
     s->hVertices.assign(d->vertices, d->vertices + np * 9);
     s->hNormals.assign(d->normals, d->normals + np * 9);
     if (d->texcoords) s->hTexcoords.assign(d->texcoords, d->texcoords + np * 6); else s->hTexcoords.assign(np * 6, 0.f);
+    s->hasTexcoords = d->texcoords != nullptr;
     s->hMaterialIds.assign(d->materialIds, d->materialIds + np);
     s->hMaterials.assign(d->materials, d->materials + d->numMaterials);
     s->hBoxes.assign(d->boundingBoxes, d->boundingBoxes + nn * 6);
