@@ -198,6 +198,22 @@ __global__ void __launch_bounds__(256, RS_WALK_WAVES) k_gbuffer_primary_split(De
 constexpr int kRisThreads = RS_RIS_THREADS;
 // (kRisLdsLights, kRisAliasLdsLights: rs_frame_plan.h, with the rule that picks the form)
 
+// One candidate: the light sample for the draws r and its RIS weight, over the operations Ops (rs_exact.h).  LAMBERT: every lane of the
+// wave is Lambertian -- the BSDF is the constant 1 / Pi, without the per-lane dispatch, and wo / roughness are not read.
+struct RisMaterial { int type; float metallic, roughness; };
+template <bool ENV, bool LAMBERT, typename Ops, typename AliasPtr, typename LightPtr>
+__device__ __forceinline__ float ris_candidate(const DevScene& s, AliasPtr alias, LightPtr lights, f3 pos, f3 norm, f3 wo, const RisMaterial& m, f4 r,
+                                               Ops& ops, LightSample& c) {
+    const f3 baseColor = splat(1.f);                       // material.baseColor = 1 (restir.cu:141)
+    c = sample_light_with<ENV, Ops, AliasPtr, LightPtr>(s, alias, lights, s.numLights, pos, r, ops);
+    const f3 bsdf = LAMBERT ? eval_bsdf_with(0, baseColor, 0.f, 0.f, norm, wo, c.wi, ops)
+                            : eval_bsdf_with(m.type, baseColor, m.metallic, m.roughness, norm, wo, c.wi, ops);
+    const f3 g = c.Li * bsdf * sat_dot(norm, c.wi);
+    float weight = luminance(ops.div3(g, c.pdf, c.pdf <= 0.f));                  // pdf <= 0: the weight is replaced by 0 below
+    if (is_nan_or_inf(weight) || c.pdf <= 0.f) weight = 0.f;
+    return weight;
+}
+
 // TRACK (rs_restir_set_light_tracking): the winner's light-sampler index goes to candId as well (-1: no winner)
 template <bool ENV, bool SOBOL, bool TRACK, typename AliasPtr, typename LightPtr>
 __device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& sp, AliasPtr alias, LightPtr lights, int index, int looper, int* candId) {
@@ -207,8 +223,7 @@ __device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& s
     if (mk_kind(mk) != kKindShaded) return;
     const float4 nr = sp.norm[index];
     const f3 pos = mk3(pm.x, pm.y, pm.z), norm = mk3(nr.x, nr.y, nr.z);
-    struct { int type; float metallic, roughness; } m = { mk_type(mk), nr.w, 0.f };     // the material after its maps (k_primary)
-    const f3 baseColor = splat(1.f);                       // material.baseColor = 1 (restir.cu:141)
+    RisMaterial m = { mk_type(mk), nr.w, 0.f };            // the material after its maps (k_primary)
     f3 wo = splat(0.f);
     if (m.type == 1) { const float4 w4 = sp.wo[index]; wo = mk3(w4.x, w4.y, w4.z); m.roughness = w4.w; }
 
@@ -221,30 +236,55 @@ __device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& s
     // conditional moves per candidate instead of seven) and the sample is evaluated again after the loop (light_sample_again).
     int selId = -1;
     float selU = 0.f, selV = 0.f;
-    for (int i = 0; i < kReservoirSize; i++) {
-        f4 r = rng.uniform4();
-        LightSample c = sample_light_nv<ENV, AliasPtr, LightPtr>(s, alias, lights, s.numLights, pos, r);
-        f3 g = c.Li * eval_bsdf(m.type, baseColor, m.metallic, m.roughness, norm, wo, c.wi) * sat_dot(norm, c.wi);
-        float weight = luminance(div3_exact(g, c.pdf, c.pdf <= 0.f));             // pdf <= 0: the weight is replaced by 0 below
-        if (is_nan_or_inf(weight) || c.pdf <= 0.f) weight = 0.f;
+    // The candidate is evaluated with the short forms of rs_exact.h unguarded, and the wave is asked once whether every operand that a
+    // lane used was in their range (ExactSpeculative); if not, the candidate is evaluated again from the same draws with the compiler's
+    // operators.  Either way the bits are the IEEE results.
+    // Only the form with the light table in LDS speculates: it is the one bound by instruction issue.  k_ris and k_ris_alias_lds wait
+    // for their gathers of light records and keep one guard per operation: with the single guard their non-ENV instantiations need 66 - 67
+    // registers, and held to 64 they measured slower than before (k_ris_alias_lds 389 against 375 us, the config-5 frame 4 - 8 % slower:
+    // profiles/ris_single_guard_ab.log, EXPERIMENTS.md).  They still take the Lambertian-only loop below.
+    constexpr bool kSpeculateHere = !std::is_same<LightPtr, const LightRec*>::value;
+    auto loop = [&](auto LAMBERT) {
+        __builtin_assume(s.numLights > 0);                 // (an empty table: below)
+        for (int i = 0; i < kReservoirSize; i++) {
+            const f4 r = rng.uniform4();
+            LightSample c;
+            float weight;
+            if constexpr (kExactSpeculate && kSpeculateHere) {
+                ExactSpeculative ops;
+                weight = ris_candidate<ENV, LAMBERT(), ExactSpeculative, AliasPtr, LightPtr>(s, alias, lights, pos, norm, wo, m, r, ops, c);
+                if (__builtin_expect(!ops.in_range_or_unused(), 0)) {
+                    ExactPlain plain;
+                    weight = ris_candidate<ENV, LAMBERT(), ExactPlain, AliasPtr, LightPtr>(s, alias, lights, pos, norm, wo, m, r, plain, c);
+                }
+            }
+            else {
+                ExactGuarded ops;
+                weight = ris_candidate<ENV, LAMBERT(), ExactGuarded, AliasPtr, LightPtr>(s, alias, lights, pos, norm, wo, m, r, ops, c);
+            }
 #ifdef RS_WALK_STATS        // measurement builds (tools/ris_stats.py): how many candidates end without a valid pdf / with a zero weight
-        {
-            const unsigned long long all = __ballot(true), inv = __ballot(c.pdf <= 0.f), zero = __ballot(c.pdf > 0.f && weight == 0.f);
-            if (s.walkStats && __lane_id() == (unsigned)__ffsll((long long)all) - 1u) {
-                atomicAdd(&s.walkStats[88], (unsigned long long)__popcll(all)); atomicAdd(&s.walkStats[89], (unsigned long long)__popcll(inv));
-                atomicAdd(&s.walkStats[90], (unsigned long long)__popcll(zero)); atomicAdd(&s.walkStats[91], 1ull);
-                if (inv == all) atomicAdd(&s.walkStats[92], 1ull);
-                if ((inv | zero) == all) atomicAdd(&s.walkStats[93], 1ull);
+            {
+                const unsigned long long all = __ballot(true), inv = __ballot(c.pdf <= 0.f), zero = __ballot(c.pdf > 0.f && weight == 0.f);
+                if (s.walkStats && __lane_id() == (unsigned)__ffsll((long long)all) - 1u) {
+                    atomicAdd(&s.walkStats[88], (unsigned long long)__popcll(all)); atomicAdd(&s.walkStats[89], (unsigned long long)__popcll(inv));
+                    atomicAdd(&s.walkStats[90], (unsigned long long)__popcll(zero)); atomicAdd(&s.walkStats[91], 1ull);
+                    if (inv == all) atomicAdd(&s.walkStats[92], 1ull);
+                    if ((inv | zero) == all) atomicAdd(&s.walkStats[93], 1ull);
+                }
+            }
+#endif
+            float u = rng.uniform();
+            wsum += weight;                                    // Reservoir::update (restir.h:38-44)
+            if (u * wsum < weight) {
+                if (ENV) { selLi = c.Li; selWi = c.wi; selDist = c.dist; if (TRACK) selId = c.id; }
+                else { selId = c.id; selU = c.bu; selV = c.bv; }
             }
         }
-#endif
-        float u = rng.uniform();
-        wsum += weight;                                    // Reservoir::update (restir.h:38-44)
-        if (u * wsum < weight) {
-            if (ENV) { selLi = c.Li; selWi = c.wi; selDist = c.dist; if (TRACK) selId = c.id; }
-            else { selId = c.id; selU = c.bu; selV = c.bv; }
-        }
-    }
+    };
+    // wave-uniform: a wave of Lambertian pixels alone (almost every wave of an ordinary view) takes the loop without the material dispatch
+    if (s.numLights <= 0) { for (int i = 0; i < kReservoirSize; i++) { rng.uniform4(); rng.uniform(); } }     // no candidate has a weight: the draws alone
+    else if (__all(m.type == 0)) loop(std::true_type{});
+    else loop(std::false_type{});
     if (!ENV && selId >= 0) light_sample_again(lights, selId, selU, selV, pos, selLi, selWi, selDist);
     sp.candLi[index] = make_float4(selLi.x, selLi.y, selLi.z, selDist);
     sp.candWi[index] = make_float4(selWi.x, selWi.y, selWi.z, wsum);
@@ -265,17 +305,37 @@ __global__ void __launch_bounds__(256) k_ris(DevScene s, SurfPlanes sp, int widt
     ris_rows<ENV, SOBOL, TRACK>(s, sp, width, y0, y1, looper, candId);
 }
 
+// amdgpu_waves_per_eu(8): two 1 024-thread blocks per CU are 8 waves per SIMD, i.e. 64 registers at most, and nothing but this attribute
+// tells the register allocator so (the block size alone allows 128).  Left to itself the single-guard loop takes 67 and the kernel
+// loses half its waves.  The kernel now sits AT 64: a value added to the loop shows as scratch, not as a 65th register -- check the
+// scratch column of tools/kernel_resources.sh restir.hip after every change here (0 bytes today).
 template <bool SOBOL, bool TRACK>
-__global__ void __launch_bounds__(kRisThreads) k_ris_lds(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
+__global__ void __launch_bounds__(kRisThreads) __attribute__((amdgpu_waves_per_eu(8))) k_ris_lds(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
     // The copy is laid out by quarter: the lanes of a wave read the same quarter of 64 random records, and in record order those
     // 16 bytes lie in 2 of the 8 four-bank groups whatever the light (a 4-fold bank conflict; SQ_LDS_BANK_CONFLICT was 80 % of the
     // LDS cycles); by quarter, light i's lies in group i mod 8.
     __shared__ float4 sQuarters[4 * kRisLdsLights];
     __shared__ AliasRec sAlias[kRisLdsLights];
     {
+        // A thread's loads are issued together and waited for once: four quarters and an alias record with 1 024 lights and threads.
+        // (One load, one wait, one store at a time measured the same for the kernel alone, 263.9 against 263.2 us:
+        // profiles/ris_single_guard_ab.log.)
         const float4* src = reinterpret_cast<const float4*>(s.lights);
-        for (int i = threadIdx.x; i < s.numLights * 4; i += kRisThreads) sQuarters[(i & 3) * kRisLdsLights + (i >> 2)] = src[i];
-        for (int i = threadIdx.x; i < s.numLights; i += kRisThreads) sAlias[i] = s.alias[i];
+        const int n4 = s.numLights * 4;
+        for (int base = threadIdx.x; base < n4; base += 4 * kRisThreads) {
+            // (indices past the end read the last quarter again and store nothing: no branch between the loads; the launch plan takes
+            // this form for a table of at least one light)
+            const int i0 = base, i1 = base + kRisThreads, i2 = base + 2 * kRisThreads, i3 = base + 3 * kRisThreads;
+            const float4 q0 = src[i0], q1 = src[imin(i1, n4 - 1)], q2 = src[imin(i2, n4 - 1)], q3 = src[imin(i3, n4 - 1)];
+            const AliasRec al = s.alias[imin(base, s.numLights - 1)];
+            sQuarters[(i0 & 3) * kRisLdsLights + (i0 >> 2)] = q0;
+            if (i1 < n4) sQuarters[(i1 & 3) * kRisLdsLights + (i1 >> 2)] = q1;
+            if (i2 < n4) sQuarters[(i2 & 3) * kRisLdsLights + (i2 >> 2)] = q2;
+            if (i3 < n4) sQuarters[(i3 & 3) * kRisLdsLights + (i3 >> 2)] = q3;
+            if (base < kRisThreads && base < s.numLights) sAlias[base] = al;      // (the alias records go with the first batch)
+        }
+        if (kRisThreads < kRisLdsLights)               // (-DRS_RIS_THREADS builds: a block smaller than the table)
+            for (int i = threadIdx.x + kRisThreads; i < s.numLights; i += kRisThreads) sAlias[i] = s.alias[i];
     }
     __syncthreads();
     const int n0 = y0 * width, n1 = y1 * width;

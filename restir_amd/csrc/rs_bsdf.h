@@ -24,33 +24,48 @@ RS_HD f3 bsdf_normalize(f3 v) {
     return normalize(v);
 #endif
 }
-RS_HD float schlick_g(float c, float alpha) { float a = alpha * .5f; return bsdf_div(c, c * (1.f - a) + a); }
-RS_HD float gtr2(float c, float alpha) {
+// The BSDF over its divisions and its normalize: a set of operations of rs_exact.h, or BsdfGuarded -- ExactGuarded for a function that the
+// host compiles too (eval_bsdf is RS_HD; rs_exact.h is device code), there with the host's operators
+struct BsdfGuarded {
+    RS_HD float div(float x, float d) { return bsdf_div(x, d); }
+    RS_HD f3 normalize(f3 v) { return bsdf_normalize(v); }
+};
+template <typename Ops>
+RS_HD float schlick_g_with(float c, float alpha, Ops& ops) { float a = alpha * .5f; return ops.div(c, c * (1.f - a) + a); }
+template <typename Ops>
+RS_HD float gtr2_with(float c, float alpha, Ops& ops) {
     if (c < 1e-6f) return 0.f;
     float aa = alpha * alpha;
     float den = c * c * (aa - 1.f) + 1.f;
     den = den * den * kPi;
-    return bsdf_div(aa, den);
+    return ops.div(aa, den);
 }
+RS_HD float schlick_g(float c, float alpha) { BsdfGuarded ops; return schlick_g_with(c, alpha, ops); }
+RS_HD float gtr2(float c, float alpha) { BsdfGuarded ops; return gtr2_with(c, alpha, ops); }
 
-RS_HD f3 eval_bsdf(int type, f3 baseColor, float metallic, float roughness, f3 n, f3 wo, f3 wi) {
+template <typename Ops>
+RS_HD f3 eval_bsdf_with(int type, f3 baseColor, float metallic, float roughness, f3 n, f3 wo, f3 wi, Ops& ops) {
     if (type == 0) {                                   // lambertianBSDF: baseColor * 1.f / Pi
         return (baseColor * 1.f) / kPi;
     }
     if (type == 1) {                                   // metallicWorkflowBSDF
         float alpha = roughness * roughness;
-        f3 h = bsdf_normalize(wo + wi);
+        f3 h = ops.normalize(wo + wi);
         float cosO = dot(n, wo);
         float cosI = dot(n, wi);
         if (cosI * cosO < 1e-7f) return splat(0.f);
         f3 f0 = mix(splat(.08f), baseColor, metallic);
         f3 f = mix(f0, splat(1.f), pow5(1.f - dot(h, wo)));
-        float g = schlick_g(gabs(cosO), alpha) * schlick_g(gabs(cosI), alpha);
-        float d = gtr2(dot(n, h), alpha);
+        float g = schlick_g_with(gabs(cosO), alpha, ops) * schlick_g_with(gabs(cosI), alpha, ops);
+        float d = gtr2_with(dot(n, h), alpha, ops);
         f3 diffuse = ((baseColor * 1.f) / kPi) * (1.f - metallic);
-        return mix(diffuse, splat(bsdf_div(g * d, 4.f * cosI * cosO)), f);
+        return mix(diffuse, splat(ops.div(g * d, 4.f * cosI * cosO)), f);
     }
     return splat(0.f);                                 // Dielectric, Disney, Light
+}
+RS_HD f3 eval_bsdf(int type, f3 baseColor, float metallic, float roughness, f3 n, f3 wo, f3 wi) {
+    BsdfGuarded ops;
+    return eval_bsdf_with(type, baseColor, metallic, roughness, n, wo, wi, ops);
 }
 
 #if defined(__HIPCC__)

@@ -19,6 +19,10 @@
 //     without its range scaling and class test; every float of the range agrees.
 // The guards are wave-uniform (__all): one scalar branch, no exec-mask region; a wave with one operand outside the range takes the
 // compiler's operator for all its lanes.  Zero, negative numbers, infinity and NaN are outside the range by construction of the test.
+// The RIS loop over the light table in LDS (restir.hip ris_pixel in k_ris_lds, the form of the headline frame) no longer pays one such
+// branch per operation: it runs the short forms of a whole candidate unguarded, records the range of their operands and asks its wave
+// once per candidate (ExactSpeculative, at the end of this file).  The two forms that gather their light records from memory, k_ris and
+// k_ris_alias_lds, keep the per-operation guards (why: restir.hip ris_pixel), like every other caller.
 // Whole frames whose waves take the fallback, mix lanes inside and outside the range or carry `unused` lanes are compared with the oracle
 // bit for bit in tests/test_gpu_parameter_extremes.py (the cases of tests/extreme_cases.py: roughness 0 and 1e-6 on all or a part of the
 // scene, radiances from a denormal to 3e38, an emitter above 2^60 beside an ordinary one).
@@ -113,6 +117,64 @@ __device__ __forceinline__ float sqrt_exact(float x) {
     if (RS_EXACT_GUARD(exact_range(__float_as_uint(x)))) return sqrt_refined(x);
     return sqrtf(x);
 }
+
+// ---- one guard for a whole sequence of operations (restir.hip ris_pixel) ------------------------------------------------------------
+// A function written once over its arithmetic (sample_light_with, eval_bsdf_with) takes one of three sets of operations: ExactGuarded
+// (each operation behind its own guard, as above), ExactPlain (the compiler's operators) and ExactSpeculative, which runs the short
+// forms unguarded and only records the range of the operands it was given.  The caller asks the wave once, in_range_or_unused(), and
+// evaluates the sequence again with ExactPlain if the answer is no: for operands in range both give the same bits, so how many
+// operations one question covers does not matter, and out of range the speculative values are discarded unread.
+//   * A lane whose results the caller discards whatever they are says so with set_unused(), from a test that involves none of these
+//     operations (the facing test of a light sample; a pdf that came from the compiler's operators): its operands do not count.
+//   * A numerator may also be +0 (bit pattern 0): with d in range y is finite and positive, q0 = +0 * y = +0, rem = fma(-0, d, +0) = +0,
+//     q = fma(+0, y, +0) = +0, the IEEE quotient -- exact steps, nothing to round.  (-0 is refused: the form would return +0.)  A
+//     candidate below the surface's horizon has the numerator +0, one lane in nine of a Sponza-class view.
+//   * Implied and therefore not recorded: the argument of rcp_of_root is the root of a recorded x in [2^-60, 2^60), i.e. in [2^-30, 2^30].
+#if defined(RS_EXACT_PLAIN) || (defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__))
+constexpr bool kExactSpeculate = false;                 // callers run ExactGuarded alone, every operation of which is the compiler's
+#else
+constexpr bool kExactSpeculate = true;
+#endif
+
+struct ExactGuarded {
+    static constexpr bool kWholeWave = false;           // (kWholeWave: dead lanes run along instead of leaving through an exec-mask region)
+    __device__ __forceinline__ float sqrt(float x) { return sqrt_exact(x); }
+    __device__ __forceinline__ float rcp_of_root(float r) { return rcp_exact(r); }
+    __device__ __forceinline__ float div(float x, float d) { return div_exact(x, d); }
+    __device__ __forceinline__ f3 div3(f3 g, float d, bool unused) { return div3_exact(g, d, unused); }
+    __device__ __forceinline__ f3 normalize(f3 v) { return v * rcp_exact(sqrt_exact(dot(v, v))); }
+    __device__ __forceinline__ void set_unused(bool) {}
+};
+struct ExactPlain {
+    static constexpr bool kWholeWave = true;
+    __device__ __forceinline__ float sqrt(float x) { return sqrtf(x); }
+    __device__ __forceinline__ float rcp_of_root(float r) { return 1.f / r; }
+    __device__ __forceinline__ float div(float x, float d) { return x / d; }
+    __device__ __forceinline__ f3 div3(f3 g, float d, bool) { return g / d; }
+    __device__ __forceinline__ f3 normalize(f3 v) { return v * (1.f / sqrtf(dot(v, v))); }
+    __device__ __forceinline__ void set_unused(bool) {}
+};
+struct ExactSpeculative {
+    static constexpr bool kWholeWave = true;
+    unsigned lo = ~0u, loNum = ~0u, hi = 0u;            // min and max of the bit patterns; numerators' min apart, less one, so that 0 wraps past it
+    bool unused = false;
+    __device__ __forceinline__ void take(float x) { const unsigned b = __float_as_uint(x); lo = min(lo, b); hi = max(hi, b); }
+    __device__ __forceinline__ void take_num(float x) { const unsigned b = __float_as_uint(x); loNum = min(loNum, b - 1u); hi = max(hi, b); }
+    __device__ __forceinline__ float sqrt(float x) { take(x); return sqrt_refined(x); }
+    __device__ __forceinline__ float rcp_of_root(float r) { return rcp_refined(r); }
+    __device__ __forceinline__ float div(float x, float d) { take_num(x); take(d); return div_by_rcp(x, d, rcp_refined(d)); }
+    __device__ __forceinline__ f3 div3(f3 g, float d, bool) {
+        take_num(g.x); take_num(g.y); take_num(g.z); take(d);
+        const float y = rcp_refined(d);
+        return mk3(div_by_rcp(g.x, d, y), div_by_rcp(g.y, d, y), div_by_rcp(g.z, d, y));
+    }
+    __device__ __forceinline__ f3 normalize(f3 v) { const float r = sqrt(dot(v, v)); return v * rcp_of_root(r); }
+    __device__ __forceinline__ void set_unused(bool u) { unused = u; }
+    // wave-uniform: did every lane that uses its results give every operation operands in [2^-60, 2^60) (numerators: or +0)?
+    __device__ __forceinline__ bool in_range_or_unused() const {
+        return __all(unused | ((lo >= kExactLo) & (loNum >= kExactLo - 1u) & (hi < kExactHi)));      // (no exec-mask region for `unused`)
+    }
+};
 
 }  // namespace rs
 

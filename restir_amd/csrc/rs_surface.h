@@ -167,11 +167,14 @@ __device__ __forceinline__ void load_light(LightQuarters<N> lights, int id, floa
     a = lights.q[id]; b = lights.q[N + id]; c = lights.q[2 * N + id]; d = lights.q[3 * N + id];
 }
 
-template <bool ENV, typename AliasPtr, typename LightPtr>
-__device__ __forceinline__ LightSample sample_light_nv(const DevScene& s, AliasPtr alias, LightPtr lights, int numLights, f3 pos, f4 r) {
+// Ops: the divisions and the root (rs_exact.h).  With Ops::kWholeWave a sample that fails the facing test runs along and ends with
+// pdf = kInvalidPdf and nothing else defined (its Li / wi / dist are whatever the arithmetic gave: the caller multiplies them into a
+// weight that it replaces by 0); otherwise it leaves early with the zeroed sample.
+template <bool ENV, typename Ops, typename AliasPtr, typename LightPtr>
+__device__ __forceinline__ LightSample sample_light_with(const DevScene& s, AliasPtr alias, LightPtr lights, int numLights, f3 pos, f4 r, Ops& ops) {
     LightSample o;
     o.pdf = kInvalidPdf; o.Li = splat(0.f); o.wi = splat(0.f); o.dist = 0.f; o.point = splat(0.f); o.id = 0; o.bu = o.bv = 0.f;
-    if (numLights == 0) return o;
+    if (numLights == 0) { ops.set_unused(true); return o; }
     int pass = imin(f2i((float)numLights * r.x), numLights - 1);      // DevDiscreteSampler1D::sample
     AliasRec al = alias[pass];
     int id = r.y < al.prob ? pass : al.failId;
@@ -180,6 +183,7 @@ __device__ __forceinline__ LightSample sample_light_nv(const DevScene& s, AliasP
         o.dist = 1e10f;
         o.pdf = sample_env_nv(s, r.z, r.w, o.Li, o.wi);
         o.point = pos + o.wi * 1e6f;                                 // sampleEnvironmentMap's occlusion target (scene.h:387)
+        ops.set_unused(o.pdf <= 0.f);                                // (a pdf of the compiler's operators)
         return o;
     }
     float4 a, b, c, d;
@@ -192,14 +196,21 @@ __device__ __forceinline__ LightSample sample_light_nv(const DevScene& s, AliasP
     f3 sampled = v1 * u + v2 * v + v0 * (1.f - u - v);
     o.point = sampled; o.bu = u; o.bv = v;
     f3 toS = sampled - pos;
-    if (dot(nrm, toS) > -1e-6f) return o;          // SCENE_LIGHT_SINGLE_SIDED
+    const bool away = dot(nrm, toS) > -1e-6f;      // SCENE_LIGHT_SINGLE_SIDED
+    if (!Ops::kWholeWave && away) return o;
     float dd = dot(toS, toS);
-    float len = sqrt_exact(dd);                    // rs_exact.h: the IEEE results, fewer instructions for operands in [2^-60, 2^60)
+    float len = ops.sqrt(dd);                      // rs_exact.h: the IEEE results, fewer instructions for operands in [2^-60, 2^60)
     o.Li = mk3(d.x, d.y, d.z);
-    o.wi = toS * rcp_exact(len);
+    o.wi = toS * ops.rcp_of_root(len);
     o.dist = len;
-    o.pdf = div_exact(d.w * dd, gabs(-dot(nrm, o.wi)));
+    o.pdf = ops.div(d.w * dd, gabs(-dot(nrm, o.wi)));
+    if (Ops::kWholeWave) { ops.set_unused(away); if (away) o.pdf = kInvalidPdf; }
     return o;
+}
+template <bool ENV, typename AliasPtr, typename LightPtr>
+__device__ __forceinline__ LightSample sample_light_nv(const DevScene& s, AliasPtr alias, LightPtr lights, int numLights, f3 pos, f4 r) {
+    ExactGuarded ops;
+    return sample_light_with<ENV, ExactGuarded, AliasPtr, LightPtr>(s, alias, lights, numLights, pos, r, ops);
 }
 
 // The Li / wi / dist of an accepted triangle-light sample again, from its light and barycentric pair: the same expressions in the same
