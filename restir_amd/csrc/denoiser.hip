@@ -9,6 +9,7 @@
 // evaluated once per pixel into a position plane at the start of a filter call (same expression,
 // same bits) and the levels gather from it.
 #include <cmath>
+#include <type_traits>
 
 #include "rs_internal.h"
 
@@ -58,6 +59,8 @@ __device__ __forceinline__ float div_sigma(float x, float sigma, float rsigma) {
 // enters the result relative to the centre tap's .1621.  Stated tolerance of the filter against the oracle (glibc expf): rtol 1e-5.
 // 2 instructions for the 12 of the library expf (range reduction, v_exp_f32, ldexp, two range tests).
 __device__ __forceinline__ float exp_neg(float e) { return __builtin_amdgcn_exp2f(e * -1.44269504088896340736f); }
+// -log2(e) / sigma, rounded once from double: what the fused taps multiply a squared distance by, in place of the division and exp_neg
+RS_HD float neg_log2e_over(float sigma) { return (float)(-1.44269504088896340736 / (double)sigma); }
 
 // MUL == kFusedTaps: the fused form of the tap (rs_eaw_set_fused).  The three sigma arguments then hold -log2(e) / sigma (rounded once,
 // from double), the exponent is one chain of fused multiply-adds over the three squared distances, themselves fused dot products, and
@@ -356,7 +359,7 @@ __global__ void __launch_bounds__(256) k_svgf_wavelet(float* __restrict__ colorO
                                                       float sigDepth, float sigNormal, float sigLumin, int level, int y0, int y1) {
     const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = y0 + blockIdx.y * 8 + (threadIdx.x >> 5);
     if (x >= W || y >= y1) return;
-    const float rDepth = FUSED ? (float)(-1.44269504088896340736 / (double)sigDepth) : 1.f / sigDepth;
+    const float rDepth = FUSED ? neg_log2e_over(sigDepth) : 1.f / sigDepth;
     const int step = 1 << level;
     const int idxP = y * W + x;
     const int idP = primId[idxP];
@@ -435,7 +438,7 @@ __global__ void __launch_bounds__(kTileThreads) k_svgf_wavelet_tiled(float* __re
         sColId[e] = a; sNormPx[e] = b; sMisc[e] = c; sRden[e] = r;
     }
     __syncthreads();
-    const float rDepth = FUSED ? (float)(-1.44269504088896340736 / (double)sigDepth) : 1.f / sigDepth;
+    const float rDepth = FUSED ? neg_log2e_over(sigDepth) : 1.f / sigDepth;
     const int tx = threadIdx.x % kTileW, ty = threadIdx.x / kTileW;
     const int x = blockIdx.x * kTileW + tx, y = rowBase + ty * STEP;
     if (x >= W || y >= y1) return;
@@ -476,47 +479,58 @@ __global__ void __launch_bounds__(kTileThreads) k_svgf_wavelet_tiled(float* __re
     varOut[idxP] = sumW2 < 1.1920928955078125e-7f ? pc.z : sumVar / sumW2;
 }
 
+// ---- launching a level ------------------------------------------------------------------------------------------------------------------
+// fn(std::integral_constant<int, V>()) for the V of the list that equals v -- for the last of the list if none does
+template <int V, int... Vs, class Fn>
+void with_constant(int v, Fn&& fn) {
+    if constexpr (sizeof...(Vs) == 0) fn(std::integral_constant<int, V>());
+    else if (v == V) fn(std::integral_constant<int, V>());
+    else with_constant<Vs...>(v, fn);
+}
+dim3 rows_grid(int W, int y0, int y1) { return dim3((W + 31) / 32, (y1 - y0 + 7) / 8); }
+// the row-phase tiles of rows [y0, y1) at a step: `step` phases of every group of kTileH * step rows
+dim3 tiled_grid(int W, int y0, int y1, int step) { return dim3((W + kTileW - 1) / kTileW, ((y1 - y0 + kTileH * step - 1) / (kTileH * step)) * step); }
+// a sigma by which the taps divide exactly with one multiplication: a power of two whose reciprocal is a normal number
+bool is_pow2_sigma(float v) { int e; return v > 0.f && std::isfinite(v) && std::frexp(v, &e) == 0.5f && std::isnormal(1.f / v); }
+
+void launch_positions(float* devPos, const rs_gbuffer* g, const rs_camera* cam, int first, int last) {
+    hipLaunchKernelGGL(k_positions, dim3((last - first + 255) / 256), dim3(256), 0, rs_stream(), rs_make_cam_params(cam),
+                       g->depth[g->cur()], g->primId[g->cur()], devPos, first, last);
+}
+
 // pos0: level 0 computes the positions itself (and writes the plane): only for a full-frame call, whose level 0 visits every pixel
 int wavelet_level(const rs_eaw* f, float* out, const float* in, const rs_gbuffer* g, int level, int y0, int y1, const rs_camera* posCam = nullptr) {
-    const auto pow2 = [](float v) { int e; return v > 0.f && std::isfinite(v) && std::frexp(v, &e) == 0.5f && 1.f / v > 0.f && std::isfinite(1.f / v) && std::isnormal(1.f / v); };
     const bool fused = f->fused && f->sigLumin > 0.f && f->sigNormal > 0.f && f->sigDepth > 0.f;
-    const int mul = fused ? kFusedTaps : (pow2(f->sigLumin) ? 1 : 0) | (pow2(f->sigNormal) ? 2 : 0) | (pow2(f->sigDepth) ? 4 : 0);
-    const auto coef = [](float sigma) { return (float)(-1.44269504088896340736 / (double)sigma); };
-    const float aDepth = fused ? coef(f->sigDepth) : f->sigDepth, aNormal = fused ? coef(f->sigNormal) : f->sigNormal, aLumin = fused ? coef(f->sigLumin) : f->sigLumin;
-    const bool tiled = f->tiled && level <= 4;
-    const int c = g->cur();
-    if (tiled) {
-        const int step = 1 << level;
-        const dim3 grid((f->width + kTileW - 1) / kTileW, ((y1 - y0 + kTileH * step - 1) / (kTileH * step)) * step);
-        const bool pos0 = posCam != nullptr && level == 0;
-        const CamParams cp = pos0 ? rs_make_cam_params(posCam) : CamParams{};
-#define RS_TILED_ARGS out, in, g->primId[c], g->normal[c], f->devPos, g->depth[c], cp, f->width, f->height, aDepth, aNormal, aLumin, y0, y1
-#define RS_TILED(M) do { \
-        if (pos0) hipLaunchKernelGGL((k_wavelet_tiled<1, M, true>), grid, dim3(kTileThreads), 0, rs_stream(), RS_TILED_ARGS); \
-        else if (level == 0) hipLaunchKernelGGL((k_wavelet_tiled<1, M, false>), grid, dim3(kTileThreads), 0, rs_stream(), RS_TILED_ARGS); \
-        else if (level == 1) hipLaunchKernelGGL((k_wavelet_tiled<2, M, false>), grid, dim3(kTileThreads), 0, rs_stream(), RS_TILED_ARGS); \
-        else if (level == 2) hipLaunchKernelGGL((k_wavelet_tiled<4, M, false>), grid, dim3(kTileThreads), 0, rs_stream(), RS_TILED_ARGS); \
-        else if (level == 3) hipLaunchKernelGGL((k_wavelet_tiled<8, M, false>), grid, dim3(kTileThreads), 0, rs_stream(), RS_TILED_ARGS); \
-        else hipLaunchKernelGGL((k_wavelet_tiled<16, M, false>), grid, dim3(kTileThreads), 0, rs_stream(), RS_TILED_ARGS); } while (0)
-        switch (mul) {
-            case 0: RS_TILED(0); break; case 1: RS_TILED(1); break; case 2: RS_TILED(2); break; case 3: RS_TILED(3); break;
-            case 4: RS_TILED(4); break; case 5: RS_TILED(5); break; case 6: RS_TILED(6); break; case 7: RS_TILED(7); break;
-            default: RS_TILED(kFusedTaps); break;
+    const int mul = fused ? kFusedTaps : (is_pow2_sigma(f->sigLumin) ? 1 : 0) | (is_pow2_sigma(f->sigNormal) ? 2 : 0) | (is_pow2_sigma(f->sigDepth) ? 4 : 0);
+    const float aDepth = fused ? neg_log2e_over(f->sigDepth) : f->sigDepth, aNormal = fused ? neg_log2e_over(f->sigNormal) : f->sigNormal,
+                aLumin = fused ? neg_log2e_over(f->sigLumin) : f->sigLumin;
+    const bool tiled = f->tiled && level <= 4, pos0 = tiled && posCam != nullptr && level == 0;
+    const int c = g->cur(), step = 1 << level;
+    const CamParams cp = pos0 ? rs_make_cam_params(posCam) : CamParams{};
+    with_constant<0, 1, 2, 3, 4, 5, 6, 7, kFusedTaps>(mul, [&](auto M) {
+        if (!tiled) {
+            hipLaunchKernelGGL(k_wavelet<M()>, rows_grid(f->width, y0, y1), dim3(256), 0, rs_stream(), out, in, g->primId[c], g->normal[c], f->devPos,
+                               f->width, f->height, aDepth, aNormal, aLumin, level, y0, y1);
+            return;
         }
-#undef RS_TILED
-#undef RS_TILED_ARGS
-        return rs_after_launch("EAW Filter");
-    }
-    const dim3 grid((f->width + 31) / 32, (y1 - y0 + 7) / 8);
-#define RS_WAVELET(M) hipLaunchKernelGGL(k_wavelet<M>, grid, dim3(256), 0, rs_stream(), out, in, g->primId[c], g->normal[c], f->devPos, f->width, f->height, \
-                                         aDepth, aNormal, aLumin, level, y0, y1)
-    switch (mul) {
-        case 0: RS_WAVELET(0); break; case 1: RS_WAVELET(1); break; case 2: RS_WAVELET(2); break; case 3: RS_WAVELET(3); break;
-        case 4: RS_WAVELET(4); break; case 5: RS_WAVELET(5); break; case 6: RS_WAVELET(6); break; case 7: RS_WAVELET(7); break;
-        default: RS_WAVELET(kFusedTaps); break;
-    }
-#undef RS_WAVELET
+        const auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, tiled_grid(f->width, y0, y1, step), dim3(kTileThreads), 0, rs_stream(), out, in, g->primId[c], g->normal[c], f->devPos,
+                               g->depth[c], cp, f->width, f->height, aDepth, aNormal, aLumin, y0, y1);
+        };
+        if (pos0) launch(k_wavelet_tiled<1, M(), true>);
+        else with_constant<1, 2, 4, 8, 16>(step, [&](auto S) { launch(k_wavelet_tiled<S(), M(), false>); });
+    });
     return rs_after_launch("EAW Filter");
+}
+
+// The argument and size check of the filters' entry points.  argsOk: the entry point's own test of its pointers and ranges, which
+// covers f and g; cam: null where the entry point takes no camera.
+template <class Filter>
+int check_filter_args(bool argsOk, const char* badArgs, const char* mismatch, const Filter* f, const rs_gbuffer* g, const rs_camera* cam) {
+    if (!argsOk) return rs_fail(RS_ERR_INVALID_ARGUMENT, badArgs);
+    if (g->width != f->width || g->height != f->height || (cam && (cam->resolution[0] != f->width || cam->resolution[1] != f->height)))
+        return rs_fail(RS_ERR_INVALID_ARGUMENT, mismatch);
+    return 0;
 }
 
 }  // namespace
@@ -594,9 +608,7 @@ int rs_eaw_get_params(const rs_eaw* f, float* sigLumin, float* sigNormal, float*
 int rs_eaw_filter(rs_eaw* f, float** devColorOut, const float* devColorIn, const rs_gbuffer* g, const rs_camera* cam) {
     RS_SCOPE(f);
     RS_TRY(rs_gbuffer_join(g));                         // the render may still be on the auxiliary stream
-    if (!f || !devColorOut || !*devColorOut || !devColorIn || !g || !cam) return rs_fail(RS_ERR_INVALID_ARGUMENT, "EAW filter: null argument");
-    if (g->width != f->width || g->height != f->height || cam->resolution[0] != f->width || cam->resolution[1] != f->height)
-        return rs_fail(RS_ERR_INVALID_ARGUMENT, "EAW filter: size mismatch");
+    RS_TRY(check_filter_args(f && devColorOut && *devColorOut && devColorIn && g && cam, "EAW filter: null argument", "EAW filter: size mismatch", f, g, cam));
     const int n = f->width * f->height;
     const size_t imageBytes = (size_t)n * 3 * sizeof(float);
     // rs_set_denoise_stream(1), asynchronous launches: the levels go to the denoise stream, ordered after everything enqueued on the
@@ -609,8 +621,7 @@ int rs_eaw_filter(rs_eaw* f, float** devColorOut, const float* devColorIn, const
     RS_TRY(rs_denoise_order(devColorIn, false)); RS_TRY(rs_denoise_order(*devColorOut)); RS_TRY(rs_denoise_order(f->devTempImg));
     const bool fusedPositions = f->tiled;           // the tiled level 0 computes the positions while it stages its tile
     if (!fusedPositions) {
-        hipLaunchKernelGGL(k_positions, dim3((n + 255) / 256), dim3(256), 0, rs_stream(), rs_make_cam_params(cam),
-                           g->depth[g->cur()], g->primId[g->cur()], f->devPos, 0, n);
+        launch_positions(f->devPos, g, cam, 0, n);
         RS_TRY(rs_after_launch("EAW positions"));
     }
     // LeveledEAWFilter::filter (denoiser.cu:463-477): level 0 into out, then four ping-pongs with the
@@ -635,15 +646,11 @@ int rs_eaw_filter(rs_eaw* f, float** devColorOut, const float* devColorIn, const
 int rs_eaw_positions_rows(rs_eaw* f, const rs_gbuffer* g, const rs_camera* cam, int y0, int y1) {
     RS_SCOPE(f);
     RS_TRY(rs_gbuffer_join(g));
-    if (!f || !g || !cam) return rs_fail(RS_ERR_INVALID_ARGUMENT, "EAW positions: null argument");
-    if (g->width != f->width || g->height != f->height || cam->resolution[0] != f->width || cam->resolution[1] != f->height)
-        return rs_fail(RS_ERR_INVALID_ARGUMENT, "EAW filter: size mismatch");
+    RS_TRY(check_filter_args(f && g && cam, "EAW positions: null argument", "EAW filter: size mismatch", f, g, cam));
     if (y0 < 0) y0 = 0;
     if (y1 > f->height) y1 = f->height;
     if (y1 <= y0) return 0;
-    const int first = y0 * f->width, last = y1 * f->width;
-    hipLaunchKernelGGL(k_positions, dim3((last - first + 255) / 256), dim3(256), 0, rs_stream(), rs_make_cam_params(cam),
-                       g->depth[g->cur()], g->primId[g->cur()], f->devPos, first, last);
+    launch_positions(f->devPos, g, cam, y0 * f->width, y1 * f->width);
     return rs_after_launch("EAW positions");
 }
 
@@ -651,8 +658,7 @@ int rs_eaw_level_rows(rs_eaw* f, float* devColorOut, const float* devColorIn, co
     RS_SCOPE(f);
     RS_TRY(rs_gbuffer_join(g));
     // level <= 29: the taps lie +-2 << level pixels away, and x + 2 * (1 << 30) leaves the int range
-    if (!f || !devColorOut || !devColorIn || !g || level < 0 || level > 29) return rs_fail(RS_ERR_INVALID_ARGUMENT, "EAW level: bad argument");
-    if (g->width != f->width || g->height != f->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, "EAW filter: size mismatch");
+    RS_TRY(check_filter_args(f && devColorOut && devColorIn && g && level >= 0 && level <= 29, "EAW level: bad argument", "EAW filter: size mismatch", f, g, nullptr));
     if (y0 < 0) y0 = 0;
     if (y1 > f->height) y1 = f->height;
     if (y1 <= y0) return 0;
@@ -755,52 +761,46 @@ int rs_svgf_filter_rows(rs_svgf* f, float** devColorOut, const float* devColorIn
     const int W = f->width, H = f->height;
     const int fi = f->frameIdx;
     const GBufView gv = gbuf_view(g);
-    const auto grid_rows = [&](int a, int b) { return dim3((W + 31) / 32, (b - a + 7) / 8); };
     const auto clampRow = [&](int y) { return y < 0 ? 0 : (y > H ? H : y); };
     const bool strip = hooks != nullptr;
     const int reach = 2 << 4;
     {   // positions of every row a tap can look at
         const int a = clampRow(y0 - (strip ? reach : 0)), b = clampRow(y1 + (strip ? reach : 0));
-        hipLaunchKernelGGL(k_positions, dim3(((b - a) * W + 255) / 256), dim3(256), 0, rs_stream(), rs_make_cam_params(cam),
-                           g->depth[g->cur()], g->primId[g->cur()], f->devPos, a * W, b * W);
+        launch_positions(f->devPos, g, cam, a * W, b * W);
     }
     // temporalAccumulate (:506-519), estimateVariance (:521-527)
     hipLaunchKernelGGL(k_svgf_temporal, dim3(((y1 - y0) * W + 255) / 256), dim3(256), 0, rs_stream(), f->devAccumColor[fi], f->devAccumColor[fi ^ 1],
                        f->devAccumMoment[fi], f->devAccumMoment[fi ^ 1], devColorIn, gv, f->firstTime ? 1 : 0, y0 * W, y1 * W);
     f->firstTime = false;
     if (strip) RS_TRY(hooks->exchange(hooks->ctx, f->devAccumMoment[fi], 3, nullptr, 0, 1));
-    hipLaunchKernelGGL(k_svgf_variance, grid_rows(y0, y1), dim3(256), 0, rs_stream(), f->devVariance, f->devAccumMoment[fi], W, H, y0, y1);
+    hipLaunchKernelGGL(k_svgf_variance, rows_grid(W, y0, y1), dim3(256), 0, rs_stream(), f->devVariance, f->devAccumMoment[fi], W, H, y0, y1);
     RS_TRY(rs_after_launch("SpatioTemporalFilter::temporalAccumulate"));
 
-    int de = 0;
-    const bool depthPow2 = f->sigDepth > 0.f && std::isfinite(f->sigDepth) && std::frexp(f->sigDepth, &de) == 0.5f && std::isnormal(1.f / f->sigDepth);
+    // sigNormal 2^NSQ by squarings, any other by powf; sigNormal 128 (the reference's default) with a power-of-two sigDepth and any sigLumin
+    // from the LDS tile, and in fused arithmetic; other sigmas keep the plain gathers
+    const bool depthPow2 = is_pow2_sigma(f->sigDepth), defaults = f->sigNormal == 128.f && depthPow2;
+    const int nsq = f->sigNormal == 128.f ? 7 : f->sigNormal == 64.f ? 6 : f->sigNormal == 32.f ? 5 : -1;
     int err = 0;
     auto level = [&](float* out, float* in, int lv) {
         const int step = 1 << lv;
         if (strip && !err) err = hooks->exchange(hooks->ctx, in, 3, f->devVariance, 1, 2 * step + 1);
         const int va = clampRow(y0 - (strip ? 2 * step : 0)), vb = clampRow(y1 + (strip ? 2 * step : 0));
-        hipLaunchKernelGGL(k_svgf_filter_variance, grid_rows(va, vb), dim3(256), 0, rs_stream(), f->devFilteredVariance, f->devVariance, W, H, va, vb);
-#define RS_SVGF_WAVELET(N, D) hipLaunchKernelGGL((k_svgf_wavelet<N, D>), grid_rows(y0, y1), dim3(256), 0, rs_stream(), out, in, f->devTempVariance, f->devVariance, \
-                                                f->devFilteredVariance, gv.primId, gv.normal, f->devPos, W, H, f->sigDepth, f->sigNormal, f->sigLumin, lv, y0, y1)
-        // sigNormal 128 (the reference's default) with a power-of-two sigDepth and any sigLumin from the LDS tile; other sigmas keep the plain gathers
-        if (f->tiled && f->sigNormal == 128.f && depthPow2 && lv <= 4) {
-            const dim3 gridT((W + kTileW - 1) / kTileW, ((y1 - y0 + kTileH * step - 1) / (kTileH * step)) * step);
-#define RS_SVGF_TILED_ARGS gridT, dim3(kTileThreads), 0, rs_stream(), out, in, f->devTempVariance, f->devVariance, \
-                           f->devFilteredVariance, gv.primId, gv.normal, f->devPos, W, H, f->sigDepth, f->sigNormal, f->sigLumin, y0, y1
-#define RS_SVGF_TILED(S) do { if (f->fused) hipLaunchKernelGGL((k_svgf_wavelet_tiled<S, 7, true, true>), RS_SVGF_TILED_ARGS); \
-                              else hipLaunchKernelGGL((k_svgf_wavelet_tiled<S, 7, true>), RS_SVGF_TILED_ARGS); } while (0)
-            if (lv == 0) RS_SVGF_TILED(1); else if (lv == 1) RS_SVGF_TILED(2); else if (lv == 2) RS_SVGF_TILED(4); else if (lv == 3) RS_SVGF_TILED(8); else RS_SVGF_TILED(16);
-#undef RS_SVGF_TILED
-#undef RS_SVGF_TILED_ARGS
-        }
-        else if (f->sigNormal == 128.f && depthPow2 && f->fused)
-            hipLaunchKernelGGL((k_svgf_wavelet<7, true, true>), grid_rows(y0, y1), dim3(256), 0, rs_stream(), out, in, f->devTempVariance, f->devVariance,
-                               f->devFilteredVariance, gv.primId, gv.normal, f->devPos, W, H, f->sigDepth, f->sigNormal, f->sigLumin, lv, y0, y1);
-        else if (f->sigNormal == 128.f) { if (depthPow2) RS_SVGF_WAVELET(7, true); else RS_SVGF_WAVELET(7, false); }
-        else if (f->sigNormal == 64.f) { if (depthPow2) RS_SVGF_WAVELET(6, true); else RS_SVGF_WAVELET(6, false); }
-        else if (f->sigNormal == 32.f) { if (depthPow2) RS_SVGF_WAVELET(5, true); else RS_SVGF_WAVELET(5, false); }
-        else { if (depthPow2) RS_SVGF_WAVELET(-1, true); else RS_SVGF_WAVELET(-1, false); }
-#undef RS_SVGF_WAVELET
+        hipLaunchKernelGGL(k_svgf_filter_variance, rows_grid(W, va, vb), dim3(256), 0, rs_stream(), f->devFilteredVariance, f->devVariance, W, H, va, vb);
+        const auto launch = [&](auto kernel, dim3 grid, int threads, auto... rows) {
+            hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, rs_stream(), out, in, f->devTempVariance, f->devVariance, f->devFilteredVariance,
+                               gv.primId, gv.normal, f->devPos, W, H, f->sigDepth, f->sigNormal, f->sigLumin, rows...);
+        };
+        if (f->tiled && defaults && lv <= 4)
+            with_constant<1, 2, 4, 8, 16>(step, [&](auto S) {
+                if (f->fused) launch(k_svgf_wavelet_tiled<S(), 7, true, true>, tiled_grid(W, y0, y1, step), kTileThreads, y0, y1);
+                else launch(k_svgf_wavelet_tiled<S(), 7, true, false>, tiled_grid(W, y0, y1, step), kTileThreads, y0, y1);
+            });
+        else if (defaults && f->fused) launch(k_svgf_wavelet<7, true, true>, rows_grid(W, y0, y1), 256, lv, y0, y1);
+        else
+            with_constant<7, 6, 5, -1>(nsq, [&](auto N) {
+                if (depthPow2) launch(k_svgf_wavelet<N(), true, false>, rows_grid(W, y0, y1), 256, lv, y0, y1);
+                else launch(k_svgf_wavelet<N(), false, false>, rows_grid(W, y0, y1), 256, lv, y0, y1);
+            });
         float* t = f->devTempVariance; f->devTempVariance = f->devVariance; f->devVariance = t;      // std::swap(devTempVariance, devVariance)
     };
     level(*devColorOut, f->devAccumColor[fi], 0);
@@ -818,9 +818,7 @@ extern "C" {
 int rs_svgf_filter(rs_svgf* f, float** devColorOut, const float* devColorIn, const rs_gbuffer* g, const rs_camera* cam) {
     RS_SCOPE(f);
     RS_TRY(rs_gbuffer_join(g));                         // the render may still be on the auxiliary stream
-    if (!f || !devColorOut || !*devColorOut || !devColorIn || !g || !cam) return rs_fail(RS_ERR_INVALID_ARGUMENT, "SVGF filter: null argument");
-    if (g->width != f->width || g->height != f->height || cam->resolution[0] != f->width || cam->resolution[1] != f->height)
-        return rs_fail(RS_ERR_INVALID_ARGUMENT, "SVGF filter: size mismatch");
+    RS_TRY(check_filter_args(f && devColorOut && *devColorOut && devColorIn && g && cam, "SVGF filter: null argument", "SVGF filter: size mismatch", f, g, cam));
     RS_TRY(rs_denoise_order(devColorIn, false)); RS_TRY(rs_denoise_order(*devColorOut));
     return rs_svgf_filter_rows(f, devColorOut, devColorIn, g, cam, 0, f->height, nullptr);
 }
