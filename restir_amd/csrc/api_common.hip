@@ -497,6 +497,24 @@ int rs_tile_split_prepare(rs_tile_split* t, long long key, int numTiles, int reg
     return 0;
 }
 
+int rs_walk_counters(unsigned long long** counters) {
+    rs_context* c = rs_ctx();
+    if (!c->walkCount) RS_TRY(rs_dev_alloc(&c->walkCount, (size_t)kWalkSub * kWalkStride));
+    RS_HIP(hipMemsetAsync(c->walkCount, 0, sizeof(unsigned long long) * kWalkSub * kWalkStride, rs_stream()));
+    *counters = c->walkCount;
+    return 0;
+}
+int rs_walk_counters_sum(unsigned long long* rays) {
+    if (!rays) return 0;
+    if (!rs_ctx()->walkCount) return rs_fail(RS_ERR_INVALID_ARGUMENT, "walk counters: read before any launch counted into them");
+    unsigned long long h[kWalkSub * kWalkStride];
+    RS_HIP(hipStreamSynchronize(rs_stream()));
+    RS_HIP(hipMemcpy(h, rs_ctx()->walkCount, sizeof h, hipMemcpyDeviceToHost));
+    *rays = 0;
+    for (int i = 0; i < kWalkSub; i++) *rays += h[i * kWalkStride];
+    return 0;
+}
+
 extern "C" {
 
 int rs_set_tile_split(int threshold) {
@@ -541,7 +559,7 @@ int rs_context_destroy(rs_context* c) {
         for (hipStream_t& st : c->aux) if (st) { (void)hipStreamDestroy(st); st = nullptr; }
         for (auto& k : c->auxKept) for (hipStream_t st : k.aux) if (st) (void)hipStreamDestroy(st);
         c->auxKept.clear();
-        if (c->ptRayCount) { (void)hipFree(c->ptRayCount); c->ptRayCount = nullptr; }
+        rs_dev_free(c->walkCount);
         for (auto& b : c->denoiseBufs) if (b.ev) (void)hipEventDestroy(b.ev);
         c->denoiseBufs.clear();
         if (c->denoiseFork) { (void)hipEventDestroy(c->denoiseFork); c->denoiseFork = nullptr; }

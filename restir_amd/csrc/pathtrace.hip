@@ -17,10 +17,8 @@ namespace {
 template <bool TEX, bool SOBOL>
 __global__ void __launch_bounds__(256, RS_PT_BLOCKS) k_pt_direct(DevScene s, CamParams cam, float* __restrict__ directIllum,
                                                    int looper, int iter, int tilesX, unsigned long long* rayCount) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int bx = blockIdx.x % tilesX, by = blockIdx.x / tilesX;
-    const int x = bx * 32 + wave * 8 + (lane & 7);
-    const int y = by * 8 + (lane >> 3);
+    int x, y;
+    const int lane = pixel_of_lane(tilesX, 0, x, y);
     int walks = 0;
     const bool inside = x < cam.width && y < cam.height;
     const int index = y * cam.width + x;
@@ -32,9 +30,8 @@ __global__ void __launch_bounds__(256, RS_PT_BLOCKS) k_pt_direct(DevScene s, Cam
     // in gi.hip: the light sample first (sampleDirectLight tests occlusion towards the sampled point before it looks at the side or
     // the pdf, so every sampling lane has a segment), then one cooperative walk, then the shading.
     f3 direct = splat(0.f), norm = splat(0.f), wo = splat(0.f);
-    SurfMat m = SurfMat{ 0, splat(0.f), 0.f, 0.f, 0.f };
-    LightSample c;
-    c.pdf = kInvalidPdf; c.Li = splat(0.f); c.wi = splat(0.f); c.dist = 0.f; c.point = h.pos; c.id = 0; c.bu = c.bv = 0.f;
+    SurfMat m = empty_surf_mat();
+    LightSample c = invalid_light_sample(h.pos);
     bool nee = false;
     if (inside) {
         walks = 1;
@@ -54,8 +51,7 @@ __global__ void __launch_bounds__(256, RS_PT_BLOCKS) k_pt_direct(DevScene s, Cam
                 if (!delta) {
                     const f4 rl = rng.uniform4();
                     nee = s.numLights > 0;
-                    if (nee) c = (TEX && s.envTex >= 0) ? sample_light_nv<true, const AliasRec*, const LightRec*>(s, s.alias, s.lights, s.numLights, h.pos, rl)
-                                                        : sample_light_nv<false, const AliasRec*, const LightRec*>(s, s.alias, s.lights, s.numLights, h.pos, rl);
+                    if (nee) c = sample_scene_light<TEX>(s, h.pos, rl);
                 }
             }
         }
@@ -67,19 +63,14 @@ __global__ void __launch_bounds__(256, RS_PT_BLOCKS) k_pt_direct(DevScene s, Cam
     f3 value = splat(0.f);
     const bool valid = nee && c.pdf > 0.f;
     if (valid) value = ((c.Li * eval_bsdf(m.type, m.baseColor, m.metallic, m.roughness, norm, wo, c.wi)) * sat_dot(norm, c.wi)) / c.pdf;
-    const bool matters = valid && (__float_as_uint(value.x) | __float_as_uint(value.y) | __float_as_uint(value.z)) != 0u;
+    const bool matters = valid && any_bit(value);
     const bool occluded = trace_occluded_wave(s, h.pos, c.point, matters);
     if (nee) {
         walks++;
         if (matters && !occluded) direct = value;
     }
-    if (inside) {
-        float* o = directIllum + (size_t)index * 3;
-        st3(o, (ld3(o) * (float)iter + direct) / (float)(iter + 1));
-    }
-    // wave-level sum of walks, one atomic per wave
-    for (int off = 32; off > 0; off >>= 1) walks += __shfl_down(walks, off);
-    if (lane == 0 && walks) atomicAdd(rayCount, (unsigned long long)walks);
+    if (inside) accumulate(directIllum, index, direct, iter);
+    count_walks(rayCount, walks, lane);              // every wave to the same counter
 }
 
 __device__ __forceinline__ float filmic_curve(float c) {
@@ -155,32 +146,30 @@ int copy_debug(void* devPBO, const void* devImage, int width, int height, int ki
 
 extern "C" {
 
+// the current context's walk counters, which every path-tracing entry point also allocates by itself and rs_context_destroy frees
+// (rs_path_trace_init also clears them, in the order of the context's stream: every launch clears them again before it counts)
 int rs_path_trace_init(void) {
     rs_ctx_scope scope(nullptr);
-    if (!rs_ctx()->ptRayCount) RS_TRY(rs_dev_alloc(&rs_ctx()->ptRayCount, 1));
-    return 0;
+    unsigned long long* counters = nullptr;
+    return rs_walk_counters(&counters);
 }
-int rs_path_trace_free(void) { rs_ctx_scope scope(nullptr); rs_dev_free(rs_ctx()->ptRayCount); return 0; }
+int rs_path_trace_free(void) { rs_ctx_scope scope(nullptr); rs_dev_free(rs_ctx()->walkCount); return 0; }
 
 int rs_path_trace_direct(const rs_scene* scene, const rs_camera* cam, float* devDirectIllum, int iter, int looper, unsigned long long* rays) {
     RS_SCOPE(scene);
     if (!scene || !cam || !devDirectIllum) return rs_fail(RS_ERR_INVALID_ARGUMENT, "pathTraceDirect: null argument");
     RS_TRY(rs_check_looper(scene, looper, "pathTraceDirect"));
-    RS_TRY(rs_path_trace_init());
     RS_TRY(rs_denoise_order(devDirectIllum));           // an image a filter on the denoise stream may still be reading
-    RS_HIP(hipMemsetAsync(rs_ctx()->ptRayCount, 0, 8, rs_stream()));
+    unsigned long long* walkCount = nullptr;
+    RS_TRY(rs_walk_counters(&walkCount));
     const int W = cam->resolution[0], H = cam->resolution[1];
     const int tilesX = (W + 31) / 32, tilesY = (H + 7) / 8;
     rs_dispatch([&](auto TEX, auto SOBOL) {
         hipLaunchKernelGGL((k_pt_direct<TEX(), SOBOL()>), dim3(tilesX * tilesY), dim3(256), 0, rs_stream(), scene->dev,
-                           rs_make_cam_params(cam), devDirectIllum, looper, iter, tilesX, rs_ctx()->ptRayCount);
+                           rs_make_cam_params(cam), devDirectIllum, looper, iter, tilesX, walkCount);
     }, scene->textured, scene->dev.sampleSeq != nullptr);
     RS_TRY(rs_after_launch("pathTrace"));
-    if (rays) {
-        RS_HIP(hipStreamSynchronize(rs_stream()));
-        RS_HIP(hipMemcpy(rays, rs_ctx()->ptRayCount, 8, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    return rs_walk_counters_sum(rays);
 }
 
 int rs_copy_image_to_pbo(void* devPBO, const float* devImage, int width, int height, int toneMapping, float scale) {

@@ -56,13 +56,6 @@ struct SurfPlanes {
     float4* candWi;     // RIS winner wi.xyz, reservoir weight
 };
 
-__device__ __forceinline__ void pixel_of_lane(int tilesX, int y0, int& x, int& y) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int bx = blockIdx.x % tilesX, by = blockIdx.x / tilesX;
-    x = bx * 32 + wave * 8 + (lane & 7);
-    y = y0 + by * 8 + (lane >> 3);
-}
-
 // ---- phase A.1: primary hit ---------------------------------------------------------------------
 // what ReSTIRDirectKernel keeps of its primary hit (restir.cu:127-153) for the later passes; returns whether the pixel is shaded
 template <bool TEX>
@@ -469,7 +462,7 @@ __global__ void __launch_bounds__(256) k_temporal(SurfPlanes sp, GBufView g, Res
     r.M = kReservoirSize; r.W = cw.w;                             // 0 if the shadow ray was blocked (k_shadow)
     int id = TRACK ? ld_stream(ids.cand + index) : -1;
 
-    if (!first && (reuse & 1)) {                                  // findTemporalNeighbor, restir.cu:20-45
+    if (!first && (reuse & 1)) {                                  // findTemporalNeighbor, restir.cu:20-45 (gi.hip write_sample: the same test with plain loads)
         const int primId = gid;
         const int lastIdx = ld_stream(g.motion + index);
         bool diff = false;

@@ -65,7 +65,7 @@ struct rs_context {
     std::vector<DenoiseBuf> denoiseBufs;  // (an entry keeps its event for the buffer's next use)
     bool denoiseUsed = false;             // the denoise stream has carried work since the last rs_synchronize
     hipEvent_t denoiseFork = nullptr;     // library stream -> denoise stream
-    unsigned long long* ptRayCount = nullptr;   // pathTraceDirect's walk counter (pathtrace.hip)
+    unsigned long long* walkCount = nullptr;    // BVH-walk counters of the path kernels (gi.hip, pathtrace.hip): kWalkSub partial counters, rs_walk_counters
     int tileSplit = 0; bool tileSplitSet = false;   // union nodes from which a tile of a closest-hit kernel is traced by four waves (rs_tilesplit.h): rs_set_tile_split, default 768; 0 off; negative: |value|, also for launches that overlap others
 };
 rs_context* rs_ctx();                                   // the context this thread's library code runs under right now
@@ -139,6 +139,11 @@ inline void rs_dispatch(F&& f, bool b, Bools... rest) {
 // The Sobol branch indexes its table by the caller's looper (State::looper, kept below SobolSampleNum by the reference's
 // `(looper + 1) % SobolSampleNum`, restir.cu:441-445): a looper outside the table is refused instead of read.
 int rs_check_looper(const struct rs_scene* scene, int looper, const char* what);
+// The current context's walk counters (api_common.hip).  A path kernel adds its BVH walks to one of kWalkSub partial counters,
+// kWalkStride words apart; they belong to the context, so contexts on other streams or devices count for themselves.
+constexpr int kWalkSub = 64, kWalkStride = 8;
+int rs_walk_counters(unsigned long long** counters);    // allocated on first use, zeroed in the order of the context's stream
+int rs_walk_counters_sum(unsigned long long* rays);     // waits for the stream and adds the partial counters up (null: nothing to do)
 
 // ---- tile-split hints (rs_tilesplit.h) -------------------------------------------------------------
 // One per launch site and stream: the lists / flags the last launch of that geometry on that stream left for the next one.
@@ -380,6 +385,32 @@ static inline GBufView gbuf_view(const rs_gbuffer* g) {
 #define RS_PRIO_EAW 0
 #endif
 #define RS_SETPRIO(p) do { if ((p) > 0) __builtin_amdgcn_s_setprio(p); } while (0)
+
+// ---- what the per-pixel kernels share (restir.hip, gi.hip, pathtrace.hip) -----------------------------
+// One lane per pixel: a block of 256 threads takes 32x8 pixels, each of its four waves an 8x8 tile; rows count from y0.  Returns the
+// lane within the wave, for count_walks (kernels that count otherwise ignore it).
+__device__ __forceinline__ int pixel_of_lane(int tilesX, int y0, int& x, int& y) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bx = blockIdx.x % tilesX, by = blockIdx.x / tilesX;
+    x = bx * 32 + wave * 8 + (lane & 7);
+    y = y0 + by * 8 + (lane >> 3);
+    return lane;
+}
+// Does a shadow segment's visibility matter?  Not for a contribution whose three components are all +0 (x + (+0) = x for every x but
+// -0, and the sums start at +0); a NaN or -0 component has a bit set, and the segment is walked.
+__device__ __forceinline__ bool any_bit(rs::f3 v) { return (__float_as_uint(v.x) | __float_as_uint(v.y) | __float_as_uint(v.z)) != 0u; }
+// the running mean over iterations of the accumulating passes (pathtrace.cu:273-276,325)
+__device__ __forceinline__ void accumulate(float* image, int index, rs::f3 v, int iter) {
+    float* o = image + (size_t)index * 3;
+    rs::st3(o, (rs::ld3(o) * (float)iter + v) / (float)(iter + 1));
+}
+// BVH walks for the Mrays/s metric: wave-level sum, one atomic per wave (by `lane` 0), to the address the caller chose.
+// `lane` is the value pixel_of_lane returned, on purpose: a second `threadIdx.x & 63` here is not merged with the first and moved
+// k_path's register allocation (ReSTIR-GI, plain scene: 108 -> 116 B of scratch; EXPERIMENTS.md).
+__device__ __forceinline__ void count_walks(unsigned long long* counter, int walks, int lane) {
+    for (int off = 32; off > 0; off >>= 1) walks += __shfl_down(walks, off);
+    if (lane == 0 && walks) atomicAdd(counter, (unsigned long long)walks);
+}
 // what renderGBuffer writes for one pixel (src/gbuffer.cu:21-72); shared by k_render_gbuffer and the kernel that walks the
 // G-buffer ray together with the shading ray (restir.hip)
 struct GBufWrite {

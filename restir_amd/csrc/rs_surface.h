@@ -80,6 +80,7 @@ __device__ inline f3 local_to_world(f3 n, f3 v) {
 
 // what the kernels need of a Material after getTexturedMaterialAndSurface
 struct SurfMat { int type; f3 baseColor; float metallic, roughness, ior; };
+__device__ __forceinline__ SurfMat empty_surf_mat() { return SurfMat{ 0, splat(0.f), 0.f, 0.f, 0.f }; }     // of a lane without a shaded hit
 
 __device__ inline SurfMat plain_material(const DevScene& s, int matId) {
     const rs_material m = s.materials[matId];
@@ -167,13 +168,19 @@ __device__ __forceinline__ void load_light(LightQuarters<N> lights, int id, floa
     a = lights.q[id]; b = lights.q[N + id]; c = lights.q[2 * N + id]; d = lights.q[3 * N + id];
 }
 
+// a light sample nobody took: InvalidPdf, no radiance, `point` as the occlusion target of a segment that is counted and not walked
+__device__ __forceinline__ LightSample invalid_light_sample(f3 point) {
+    LightSample o;
+    o.pdf = kInvalidPdf; o.Li = splat(0.f); o.wi = splat(0.f); o.dist = 0.f; o.point = point; o.id = 0; o.bu = o.bv = 0.f;
+    return o;
+}
+
 // Ops: the divisions and the root (rs_exact.h).  With Ops::kWholeWave a sample that fails the facing test runs along and ends with
 // pdf = kInvalidPdf and nothing else defined (its Li / wi / dist are whatever the arithmetic gave: the caller multiplies them into a
 // weight that it replaces by 0); otherwise it leaves early with the zeroed sample.
 template <bool ENV, typename Ops, typename AliasPtr, typename LightPtr>
 __device__ __forceinline__ LightSample sample_light_with(const DevScene& s, AliasPtr alias, LightPtr lights, int numLights, f3 pos, f4 r, Ops& ops) {
-    LightSample o;
-    o.pdf = kInvalidPdf; o.Li = splat(0.f); o.wi = splat(0.f); o.dist = 0.f; o.point = splat(0.f); o.id = 0; o.bu = o.bv = 0.f;
+    LightSample o = invalid_light_sample(splat(0.f));
     if (numLights == 0) { ops.set_unused(true); return o; }
     int pass = imin(f2i((float)numLights * r.x), numLights - 1);      // DevDiscreteSampler1D::sample
     AliasRec al = alias[pass];
@@ -211,6 +218,12 @@ template <bool ENV, typename AliasPtr, typename LightPtr>
 __device__ __forceinline__ LightSample sample_light_nv(const DevScene& s, AliasPtr alias, LightPtr lights, int numLights, f3 pos, f4 r) {
     ExactGuarded ops;
     return sample_light_with<ENV, ExactGuarded, AliasPtr, LightPtr>(s, alias, lights, numLights, pos, r, ops);
+}
+// ... from the scene's own tables, with the environment map's sampler entry where the scene has one (TEX: it may have)
+template <bool TEX>
+__device__ __forceinline__ LightSample sample_scene_light(const DevScene& s, f3 pos, f4 r) {
+    return (TEX && s.envTex >= 0) ? sample_light_nv<true, const AliasRec*, const LightRec*>(s, s.alias, s.lights, s.numLights, pos, r)
+                                  : sample_light_nv<false, const AliasRec*, const LightRec*>(s, s.alias, s.lights, s.numLights, pos, r);
 }
 
 // The Li / wi / dist of an accepted triangle-light sample again, from its light and barycentric pair: the same expressions in the same

@@ -18,11 +18,13 @@ its cos / sin / atan2 correctly rounded (libm mode 1), as the device evaluates t
      extent through all three entry points.
   E. maxDepth 0, reuse 0, rs_restir_reset between indirect frames, the first-frame flag that rs_restir_direct and
      rs_restir_indirect share, the Sobol guard (depth 613 refused, 612 accepted) and the size checks of rs_restir_indirect.
+  F. The BVH-walk counters belong to the context: two host threads, each with its own context, stream and frame size, get the
+     counts and images of the same calls made single-threaded on the default context.
 
 The oracle's own figures asserted as non-vacuity (ray counts 3540 / 1164 / 1107 / 297, M = frame + 1 up to 20, at least half of the
 pixels at M = 20 from frame index 20 on) were checked on the CPU with the oracle alone.
 
-What the module found: nothing in gi.hip or the wave services; every comparison holds on an MI355X (32 tests, 3.6 s).
+What the module found: nothing in gi.hip or the wave services; every comparison holds on an MI355X (33 tests, 4.2 s).
 """
 import numpy as np
 import pytest
@@ -381,3 +383,69 @@ def test_restir_indirect_refuses_other_sizes(hip):
         assert (p.hi.bits() == BAND_BITS).all()
     p.hi.zero()
     p.indirect(0, 0, 1, 4)                                              # and the refused calls left the rs_restir as it was
+
+
+def _sixty_calls(hip, size):
+    """pathTrace, pathTraceIndirect and ReSTIRIndirect, 20 accumulating iterations each at depth 4, under the current context: every
+    call's ray count and the four final images."""
+    sd = _gi_scene("cornell_glass")
+    h = HipRenderer(hip, sd, *size)
+    n = size[0] * size[1]
+    direct, indirect, pti, gi = (_DevImage(n) for _ in range(4))
+    rays = []
+    for it in range(20):
+        rays.append(hip.path_trace(h.scene, h.cam, direct.ptr, indirect.ptr, it, it, 4))
+    for it in range(20):
+        rays.append(hip.path_trace_indirect(h.scene, h.cam, pti.ptr, it, it, 4))
+    for it in range(20):
+        h.gbuf.render(h.scene, h.cam)
+        rays.append(h.restir.indirect(h.scene, h.cam, h.gbuf, gi.ptr, it, it, 1, 4))
+        h.gbuf.update(h.cam)
+    hip.synchronize()
+    return rays, [img.get().copy() for img in (direct, indirect, pti, gi)]
+
+
+def test_ray_counts_belong_to_the_context(hip):
+    """F: two host threads, each with its own context, its own stream, asynchronous launches and its own frame size (97 x 61 and
+    41 x 27), run the three entry points at the same time.  Every call's ray count and every final image equal, count for count and
+    bit for bit, those of the same sixty calls made single-threaded on the default context beforehand.  The counters are a buffer
+    of the context (rs_context::walkCount), zeroed and read in the order of its stream; one buffer shared by the process would let
+    one thread's clearing fall into the other's kernel and both add into the same words.
+    (Two contexts on two devices -- each buffer allocated under its context's device by the entry point's scope -- cannot run on a
+    single GPU: that case is verified by reading)"""
+    import threading
+    import torch
+    sizes = {"one": (97, 61), "two": (41, 27)}
+    ref = {name: _sixty_calls(hip, size) for name, size in sizes.items()}
+    # non-vacuity: every call walked, and the two frame sizes do not count the same
+    assert all(r > 0 for name in sizes for r in ref[name][0])
+    assert all(a != b for a, b in zip(ref["one"][0], ref["two"][0]))
+    assert all(img.max() > 0 for name in sizes for img in ref[name][1])
+    results, errors = {}, []
+
+    def worker(name):
+        try:
+            torch.cuda.set_device(0)
+            ctx = hip.Context(0)
+            ctx.make_current()
+            stream = torch.cuda.Stream()
+            with torch.cuda.stream(stream):
+                hip.set_stream(stream.cuda_stream)
+                hip.set_sync(False)
+                results[name] = _sixty_calls(hip, sizes[name])
+                stream.synchronize()
+            hip.Context.use_default()
+            ctx.destroy()
+        except Exception as e:                          # pragma: no cover
+            errors.append((name, repr(e)))
+
+    threads = [threading.Thread(target=worker, args=(name,)) for name in sizes]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    for name in sizes:
+        assert results[name][0] == ref[name][0], (name, "rays", results[name][0], ref[name][0])
+        for k, (a, b) in enumerate(zip(ref[name][1], results[name][1])):
+            assert bits_equal(a, b), (name, "image", k, radiance_stats(a, b))
