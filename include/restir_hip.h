@@ -285,6 +285,34 @@ int  rs_scene_set_emission(rs_scene* scene, int count, const int* materialIds, c
  * ReSTIR's temporal reservoirs keep weights drawn under the old BSDF for up to the M clamp's 20 frames, as in the reference;
  * rs_restir_reset drops them. */
 int  rs_scene_set_materials(rs_scene* scene, int count, const int* materialIds, const rs_material* records);
+/* Triangles: the three vertices (9 floats) and, unless normals is NULL, the three vertex normals (9 floats) of count primitives.  Host
+ * arrays, copied before the call returns (through a small ring of pinned staging buffers: the host waits only when that ring is full
+ * of edits whose copies have not finished).  The topology of every tree is kept -- the six bvhNodes orders do not change -- and every
+ * box is refitted on the device: a leaf box is AABB(va, vb, vc) (src/bvh.h:20-21), an inner box the union of its two children, as
+ * rs_refit_boxes computes them.  Afterwards rs_scene_host_desc returns the edited vertices and normals and boundingBoxes equal to
+ * rs_refit_boxes of the edited vertices, everything else as before, and the scene renders, in every kernel, bit for bit like
+ * rs_scene_create of that description.  A scene created from caller-supplied boxes that were not exact unions has ALL of them replaced
+ * by exact unions by its first edit (scenes from rs_scene_build / rs_build_bvh already hold exact unions).
+ * Ordering as rs_scene_set_materials, except that geometry is edited in place behind device-side fences instead of in the ring of
+ * versions: no device synchronisation; a render that has only been recorded is launched first, with the old geometry; the library
+ * stream waits, by events, for what the library's internal streams have been handed so far, the refit runs on the library stream, and
+ * the next launch of every internal stream waits for it -- launches enqueued before the call read the old geometry, launches after
+ * it the new.  The first edit of a scene builds and uploads the refit's tables and waits for the device once.  Every edit refits the
+ * whole scene, O(numPrims) on the device and on the host, however few triangles it names (DESIGN.md section 3 has the cost).  An
+ * accepted edit invalidates retained G-buffer planes.  A repeated id takes its last record; count == 0 succeeds and changes nothing.
+ * Refused with RS_ERR_INVALID_ARGUMENT, the scene unchanged: count < 0 or null arrays with count > 0; an id out of range; a vertex or
+ * normal that is not finite; a triangle whose material is a Light (moving emitters is not supported yet: their area feeds the light
+ * sampler's power, their records sit in the light table and the emissive tree is built over them); and, while the scene has its
+ * shadow-ray tree, a vertex outside the root box the scene was created with (the trees' 16-bit grid lies over that box).  With
+ * RS_ERR_UNSUPPORTED while the library stream is being captured into a graph.  A large deformation makes the refitted trees slower,
+ * never wrong; the remedy is a new scene.  The G-buffer's motion plane stays camera-only. */
+int  rs_scene_set_triangles(rs_scene* scene, int count, const int* primIds, const float* vertices, const float* normals);
+/* The boxes of the reference tree refitted to `vertices` (9 floats per primitive), host only, no GPU call: order0 is bvhNodes[0] (3 ints
+ * per node: primitive or -1, boundingBoxId, miss link), from which the children are derived; boundingBoxes receives 6 floats per node
+ * by boundingBoxId.  Min and max are taken with -0 below +0, so the bits do not depend on the order of evaluation.  On the vertices a
+ * tree was built from this returns the boxes rs_build_bvh returned.  RS_ERR_INVALID_ARGUMENT: a null array, bvhSize other than
+ * 2 * numPrims - 1, a vertex that is not finite, a primitive id or link out of range, an order that is not a tree. */
+int  rs_refit_boxes(int numPrims, const float* vertices, int bvhSize, const int* order0, float* boundingBoxes);
 /* The texels of texture texId of the scene's table: width x height must be the texture's own, data is host memory of 3 floats per
  * texel and is copied.  Ordering and refusals as rs_scene_set_materials (texId out of range, other dimensions and null data are
  * RS_ERR_INVALID_ARGUMENT).  Memory: a texture that is never edited keeps its one device array.  An edited texture holds at most three

@@ -128,7 +128,7 @@ RIS_GLOBAL, RIS_LDS, RIS_ALIAS_LDS = 0, 1, 2
 EXPORTS = [
     "rs_last_error", "rs_context_create", "rs_context_destroy", "rs_context_set_current", "rs_init", "rs_set_stream", "rs_set_sync", "rs_set_side_stream", "rs_set_ris_table_pixels", "rs_set_internal_stream_priority", "rs_internal_streams_info", "rs_choose_internal_streams_again", "rs_prepare_streams", "rs_set_stream_plan", "rs_set_denoise_stream", "rs_join_denoise_stream", "rs_set_tile_split", "rs_synchronize",
     "rs_build_bvh", "rs_build_light_table", "rs_build_alias_table", "rs_build_envmap_pdf", "rs_scene_build", "rs_scene_build_textured", "rs_scene_create",
-    "rs_scene_host_desc", "rs_scene_set_sample_sequence", "rs_scene_set_emission", "rs_scene_set_materials", "rs_scene_set_texture", "rs_scene_destroy", "rs_camera_update", "rs_trace_closest", "rs_trace_closest_wave", "rs_scene_set_ordered_tree", "rs_ordered_bvh_host_check", "rs_trace_occlusion",
+    "rs_scene_host_desc", "rs_scene_set_sample_sequence", "rs_scene_set_emission", "rs_scene_set_materials", "rs_scene_set_texture", "rs_scene_set_triangles", "rs_refit_boxes", "rs_scene_destroy", "rs_camera_update", "rs_trace_closest", "rs_trace_closest_wave", "rs_scene_set_ordered_tree", "rs_ordered_bvh_host_check", "rs_trace_occlusion",
     "rs_gbuffer_create", "rs_gbuffer_destroy", "rs_gbuffer_render", "rs_gbuffer_render_rows", "rs_gbuffer_update",
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
@@ -187,6 +187,8 @@ def lib():
     L.rs_scene_set_emission.argtypes = [vp, ci, vp, vp]
     L.rs_scene_set_materials.argtypes = [vp, ci, vp, vp]
     L.rs_scene_set_texture.argtypes = [vp, ci, ci, ci, vp]
+    L.rs_scene_set_triangles.argtypes = [vp, ci, vp, vp, vp]
+    L.rs_refit_boxes.argtypes = [ci, vp, ci, vp, vp]
     L.rs_restir_set_light_tracking.argtypes = [vp, ci]
     L.rs_restir_download_light_ids.argtypes = [vp, ci, vp]
     L.rs_restir_light_rows_bytes.argtypes = [vp, ci]
@@ -455,6 +457,16 @@ def build_bvh(vertices):
     return boxes, nodes
 
 
+def refit_boxes(vertices, order0):
+    """rs_refit_boxes: the reference tree's boxes refitted to `vertices` ((n, 3, 3) float32); order0 = bvhNodes[0] ((2n - 1, 3) int32).
+    Host only.  Returns (2n - 1, 6) float32 by boundingBoxId."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1)
+    o = np.ascontiguousarray(order0, np.int32).reshape(-1, 3)
+    boxes = np.zeros((len(o), 6), np.float32)
+    check(lib().rs_refit_boxes(v.size // 9, _p(v), len(o), _p(o), _p(boxes)))
+    return boxes
+
+
 def ordered_bvh_host_check(boxes, nodes):
     """rs_ordered_bvh_host_check on rs_build_bvh's outputs; returns (error code, node counts per axis, depth per axis)."""
     boxes = np.ascontiguousarray(boxes, np.float32); nodes = [np.ascontiguousarray(nodes[k], np.int32) for k in range(6)]
@@ -640,6 +652,25 @@ class Scene:
         if img.ndim != 3 or img.shape[2] != 3:
             raise ValueError("set_texture: textures are (H, W, 3) float32")
         check(lib().rs_scene_set_texture(self.handle, int(tex_id), img.shape[1], img.shape[0], _p(img)))
+
+    def set_triangles(self, prim_ids, vertices, normals=None):
+        """rs_scene_set_triangles: the vertices ((n, 3, 3) float32) and, unless None, the vertex normals of the primitives `prim_ids`,
+        none of them emissive; every tree is refitted on the device, ordered on the library stream like set_emission (no synchronisation)."""
+        ids = np.ascontiguousarray(prim_ids, np.int32).reshape(-1)
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 9)
+        n = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 9)
+        if v.shape[0] != ids.size or (n is not None and n.shape[0] != ids.size):
+            raise ValueError("set_triangles: three vertices (and three normals) per primitive id")
+        check(lib().rs_scene_set_triangles(self.handle, int(ids.size), _p(ids), _p(v), None if n is None else _p(n)))
+
+    def geometry(self):
+        """The scene's vertices and vertex normals as rs_scene_host_desc returns them: two (n, 3, 3) float32 copies."""
+        d = SceneDesc()
+        check(lib().rs_scene_host_desc(self.handle, C.byref(d)))
+        n = d.numPrims
+        f = C.POINTER(C.c_float)
+        return (np.ctypeslib.as_array(C.cast(d.vertices, f), (n * 9,)).reshape(n, 3, 3).copy(),
+                np.ctypeslib.as_array(C.cast(d.normals, f), (n * 9,)).reshape(n, 3, 3).copy())
 
     def host_desc(self):
         """numpy views of the arrays the scene was built from (for parity checks of the host build)."""

@@ -213,6 +213,13 @@ struct rs_scene {
     std::vector<float> hVertices, hNormals, hTexcoords, hBoxes, hLightRadiance, hLightProb;
     std::vector<int> hMaterialIds, hNodes[6], hLightPrimIds, hLightFailId;
     std::vector<int> hParent, hLeafOf;   // reference tree: parent by original node id, leaf node of each primitive
+    // Geometry edits (rs_scene_set_triangles; rs_refit.h, scene_refit.hip).  Kept from creation, on the host only: the primitive in every
+    // slot of occTris, the box the shadow tree's grid was laid over (a moved vertex must stay inside it) and the grid's margin.
+    // Everything else -- device tables, scratch, staging -- belongs to `refit`, which the first edit allocates.
+    std::vector<int> hOccLeafPrims;
+    float gridLo[3] = {}, gridHi[3] = {};
+    double gridMargin = 0.0;
+    struct rs_refit* refit = nullptr;
     std::vector<rs_material> hMaterials;
     float sumLightPower = 0.f;
     int numPrims = 0, bvhSize = 0, numLights = 0;
@@ -590,6 +597,8 @@ rs::CamParams rs_make_cam_params(const rs_camera* cam);
 
 // occlusion_bvh.cpp
 int rs_build_occlusion_bvh(int numPrims, const float* primBoxes, std::vector<rs::BvhNode>& nodes, std::vector<int>& leafPrims);
-int rs_quantize_occlusion_bvh(const std::vector<rs::BvhNode>& nodes, float base[3], float scale[3], std::vector<unsigned>& out);
+int rs_quantize_occlusion_bvh(const std::vector<rs::BvhNode>& nodes, float base[3], float scale[3], std::vector<unsigned>& out, double* margin = nullptr);
 int rs_build_ordered_bvh(int numPrims, const float* primBoxes, const int* seq, std::vector<rs::BvhNode>& forward, std::vector<rs::BvhNode>& mirrored);
 int rs_reference_chain_tables(int bvhSize, const int* order0, std::vector<int>& parent, std::vector<int>& leafOfPrim, int numPrims);
+// scene_refit.hip
+void rs_refit_free(rs_scene* s);                        // rs_scene_destroy: what the first geometry edit allocated (nothing without one)

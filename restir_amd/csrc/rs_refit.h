@@ -1,0 +1,69 @@
+// rs_refit.h -- what rs_scene_set_triangles keeps per scene (scene.hip: the entry point; scene_refit.hip: tables, kernels, rs_refit_boxes).
+//
+// A refit keeps every tree's topology and recomputes every box from the vertices: the reference tree (nodesAll's six orders, occChain)
+// and the grid-box trees over the reference's leaf boxes (occNodes, the six orders of ordNodes).  A box is a min / max of floats, taken
+// on order-preserving integer keys (-0 below +0), so the result does not depend on the order in which threads arrive and the host
+// (rs_refit_boxes) and the device give the same bits.
+#pragma once
+
+#include "rs_internal.h"
+
+namespace rs {
+
+// float -> unsigned with the same order (negative values reversed, -0 < +0) and back
+RS_HD unsigned refit_key(float x) {
+    unsigned u;
+    __builtin_memcpy(&u, &x, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+RS_HD float refit_unkey(unsigned k) {
+    const unsigned u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
+    float x;
+    __builtin_memcpy(&x, &u, 4);
+    return x;
+}
+
+}  // namespace rs
+
+struct rs_refit {
+    // ---- tables, built on the host and uploaded by the first edit ----
+    int* dSlotOf = nullptr;          // [4][numPrims] primitive -> its slot in occTris, then in the three sequences of ordTris
+    int* dLeafOf = nullptr;          // [numPrims] reference leaf node of a primitive
+    int* dBoxId = nullptr;           // [6][bvhSize] boundingBoxId of every record of nodesAll
+    // One index space for every node a box is computed for: the reference's bvhSize nodes by original id, then the records of occNodes,
+    // then all 6 * ordStride / 16 records of ordNodes.  dParent: the parent in that space, -1 at a root, -2 for a record that is no
+    // node of a tree (the end records and the padding records: never written).
+    int* dParent = nullptr;
+    size_t numNodes = 0, gridFirst = 0, occRecords = 0, ordRecords = 0;      // ordRecords: per order (ordStride / 16)
+    // ---- scratch of one refit ----
+    unsigned* dKeys = nullptr;       // [numNodes][6] the boxes as keys
+    unsigned* dArrived = nullptr;    // [numNodes] children that have merged their box into the node
+    // ---- the edited triangles on their way to the device ----
+    static constexpr int kStaging = 4;
+    struct Stage { char* host = nullptr; size_t capacity = 0; hipEvent_t copied = nullptr; bool pending = false; } stage[kStaging];
+    int stageNext = 0;
+    char* dStage = nullptr;          // read by the scatter kernel, in the order of the library stream
+    size_t dStageCapacity = 0;
+    std::vector<unsigned> lastStamp; // [numPrims] the edit that named the primitive last (a repeated id takes its last record)
+    std::vector<int> lastIndex;      //            ... and its place in that edit's compacted list
+    unsigned stamp = 0;
+    // ---- fences ----
+    hipEvent_t before[rs_context::kAux] = {};      // what an internal stream has been handed so far
+    hipEvent_t after = nullptr;                    // the edit's kernels
+    // ---- the host's copy of the boxes ----
+    std::vector<int> hChild;         // [bvhSize][2] children by original node id (-1, -1 at a leaf)
+    size_t root = 0;
+};
+
+// scene_refit.hip
+// first edit: builds and uploads the tables, allocates the scratch (waits for the device once: it reads the grid-box trees back)
+int rs_refit_prepare(rs_scene* s);
+// one edit, on stream st: scatters the m staged triangles (ids, 9 floats of vertices each, 9 of normals or null: all device pointers) and refits
+int rs_refit_enqueue(rs_scene* s, int m, const int* dIds, const float* dVertices, const float* dNormals, hipStream_t st);
+// the host's side of rs_refit_boxes once the arguments have been checked: `parent` from rs_reference_chain_tables
+void rs_refit_boxes_host(int bvhSize, const float* vertices, const int* order0, const int* parent, float* boxes);
+// the same boxes when only the m primitives `ids` have moved (boxes: the exact unions of the vertices before the edit): the leaves'
+// boxes, then every ancestor's from its two children -- O(m * depth) instead of O(numPrims) for an edit of few triangles
+void rs_refit_boxes_host_some(int m, const int* ids, const float* vertices, const int* leafOf, const int* parent, const int* child, float* boxes);
+// parents of a pre-order array of 16-byte records (w: sign bit = leaf): parent[i] = base + index, -1 at the root; false: not one binary tree
+bool rs_refit_preorder_parents(const unsigned* records, size_t count, int base, int* parent);

@@ -9,6 +9,7 @@
 #include <thread>
 
 #include "rs_internal.h"
+#include "rs_refit.h"
 
 using namespace rs;
 
@@ -59,7 +60,11 @@ int build_occlusion_side(rs_scene* s) {
     if (no * 16 >= 0x7fffffffull || nn * sizeof(BvhNode) >= 0xffffffffull || np >= (1u << 27)) return 0;
     float base[3], scale[3];
     std::vector<unsigned> packed;
-    if (int e = rs_quantize_occlusion_bvh(nodes, base, scale, packed)) return e == RS_ERR_UNSUPPORTED ? 0 : e;
+    if (int e = rs_quantize_occlusion_bvh(nodes, base, scale, packed, &s->gridMargin)) return e == RS_ERR_UNSUPPORTED ? 0 : e;
+    // kept on the host for rs_scene_set_triangles: the box the grid lies over, and the tree's leaf order
+    s->gridLo[0] = nodes[0].bminx; s->gridLo[1] = nodes[0].bminy; s->gridLo[2] = nodes[0].bminz;
+    s->gridHi[0] = nodes[0].bmaxx; s->gridHi[1] = nodes[0].bmaxy; s->gridHi[2] = nodes[0].bmaxz;
+    s->hOccLeafPrims = leafPrims;
     std::vector<BvhNode> chain(nn);
     for (size_t i = 0; i < nn; i++) {
         const float* b = &s->hBoxes[i * 6];
@@ -472,6 +477,7 @@ extern "C" int rs_scene_destroy(rs_scene* s) {
     rs_dev_free(s->dTextures); rs_dev_free(s->dEnvAlias); rs_dev_free(s->dTexcoords); rs_dev_free(s->dSampleSeq);
     for (float*& p : s->dTexData) rs_dev_free(p);
     versions_free(s);
+    rs_refit_free(s);
     delete s;
     return 0;
 }
@@ -619,6 +625,113 @@ extern "C" int rs_scene_set_texture(rs_scene* s, int texId, int width, int heigh
         s->envPower = envSum; s->envPowerKnown = true;
     }
     return version_commit(s, "rs_scene_set_texture");
+}
+
+// Triangles, stream-ordered (include/restir_hip.h).  Geometry is too large for the ring of versions (nodesAll alone is 6 x 32 bytes per
+// node), so this edit works in place behind device-side fences: the library stream waits for what the internal streams have been handed
+// so far, the edit's kernels (scene_refit.hip) run on the library stream, and the next launch of every internal stream waits for them.
+// The host's tables follow at once: hVertices, hNormals, and hBoxes = rs_refit_boxes of the edited vertices.
+extern "C" int rs_scene_set_triangles(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals) {
+    RS_SCOPE(s);
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_triangles: null scene");
+    if (count < 0 || (count > 0 && (!primIds || !vertices))) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_triangles: count < 0 or null arrays");
+    const bool bounded = s->dOccNodes != nullptr;       // the 16-bit grid of the grid-box trees lies over the box the scene was created with
+    for (int i = 0; i < count; i++) {
+        const int p = primIds[i];
+        if (p < 0 || p >= s->numPrims) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_triangles: a primitive id out of range");
+        if (s->hMaterials[(size_t)s->hMaterialIds[(size_t)p]].type == 4)
+            return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_triangles: a triangle whose material is a Light (the light table, the sampler's powers and the emissive tree are built over the emitters' geometry; moving emitters is not supported)");
+        for (int k = 0; k < 9; k++) {
+            const float x = vertices[(size_t)i * 9 + k];
+            if (!std::isfinite(x) || (normals && !std::isfinite(normals[(size_t)i * 9 + k])))
+                return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_triangles: a vertex or normal that is not finite");
+            if (bounded && !(x >= s->gridLo[k % 3] && x <= s->gridHi[k % 3]))
+                return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_triangles: a vertex outside the root box the scene was created with (the grid of its shadow-ray tree lies over that box); build a new scene");
+        }
+    }
+    RS_TRY(refuse_while_capturing("rs_scene_set_triangles: the library stream is being captured into a graph"));
+    if (count == 0) return 0;
+    const bool first = s->refit == nullptr;
+    RS_TRY(rs_refit_prepare(s));
+    rs_refit* r = s->refit;
+    const size_t np = (size_t)s->numPrims, nn = (size_t)s->bvhSize;
+    if (first) {
+        // Boxes that were not the exact unions (a caller-supplied table): from now on they are.  The emissive tree was built over the boxes
+        // as given and is not refitted, so it no longer answers for the new ones: the last bounce asks the scene's trees again.
+        std::vector<float> exact(nn * 6);
+        rs_refit_boxes_host(s->bvhSize, s->hVertices.data(), s->hNodes[0].data(), s->hParent.data(), exact.data());
+        bool same = true;
+        for (size_t i = 0; i < nn * 6 && same; i++) same = exact[i] == s->hBoxes[i];
+        if (!same) s->dev.emiState = 0;
+        s->hBoxes.swap(exact);                           // (also when equal as values: rs_refit_boxes' signs of zero from here on)
+    }
+
+    // the edit's records, a repeated id keeping its last: ids | vertices | normals, each part 16-byte aligned
+    if (++r->stamp == 0u) { std::fill(r->lastStamp.begin(), r->lastStamp.end(), 0u); r->stamp = 1u; }
+    int m = 0;
+    for (int i = 0; i < count; i++) {
+        const size_t p = (size_t)primIds[i];
+        if (r->lastStamp[p] != r->stamp) { r->lastStamp[p] = r->stamp; r->lastIndex[p] = m++; }
+    }
+    auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t offV = up((size_t)m * sizeof(int)), offN = offV + up((size_t)m * 9 * sizeof(float));
+    const size_t bytes = offN + (normals ? up((size_t)m * 9 * sizeof(float)) : 0);
+    rs_refit::Stage& g = r->stage[r->stageNext];
+    if (g.pending) { RS_HIP(hipEventSynchronize(g.copied)); g.pending = false; }      // the ring is full of edits whose copies have not finished
+    if (g.capacity < bytes) {
+        if (g.host) { (void)hipHostFree(g.host); g.host = nullptr; g.capacity = 0; }
+        size_t cap = 4096;
+        while (cap < bytes) cap *= 2;
+        RS_HIP(hipHostMalloc((void**)&g.host, cap, hipHostMallocDefault));
+        g.capacity = cap;
+    }
+    if (r->dStageCapacity < bytes) {                     // (hipFree waits for the device: no earlier edit still reads the old buffer)
+        rs_dev_free(r->dStage);
+        r->dStageCapacity = 0;
+        RS_TRY(rs_dev_alloc(&r->dStage, g.capacity));
+        r->dStageCapacity = g.capacity;
+    }
+    int* ids = reinterpret_cast<int*>(g.host);
+    float* vs = reinterpret_cast<float*>(g.host + offV);
+    float* ns = reinterpret_cast<float*>(g.host + offN);
+    for (int i = 0; i < count; i++) {
+        const size_t p = (size_t)primIds[i], j = (size_t)r->lastIndex[p];
+        ids[j] = primIds[i];
+        std::memcpy(vs + j * 9, vertices + (size_t)i * 9, 9 * sizeof(float));
+        if (normals) std::memcpy(ns + j * 9, normals + (size_t)i * 9, 9 * sizeof(float));
+    }
+
+    // frames in flight: a render that has only been recorded is launched now, with the old geometry
+    RS_TRY(rs_gbuffer_release_scene(s));
+    rs_context* c = rs_ctx();
+    const hipStream_t st = rs_stream();
+    for (int i = 0; i < rs_context::kAux; i++)
+        if (c->aux[i]) { RS_HIP(hipEventRecord(r->before[i], c->aux[i])); RS_HIP(hipStreamWaitEvent(st, r->before[i], 0)); }
+    RS_HIP(hipMemcpyAsync(r->dStage, g.host, bytes, hipMemcpyHostToDevice, st));
+    RS_HIP(hipEventRecord(g.copied, st));
+    g.pending = true;
+    r->stageNext = (r->stageNext + 1) % rs_refit::kStaging;
+    RS_TRY(rs_refit_enqueue(s, m, reinterpret_cast<const int*>(r->dStage), reinterpret_cast<const float*>(r->dStage + offV),
+                            normals ? reinterpret_cast<const float*>(r->dStage + offN) : nullptr, st));
+    RS_HIP(hipEventRecord(r->after, st));
+    for (int i = 0; i < rs_context::kAux; i++)
+        if (c->aux[i]) RS_HIP(hipStreamWaitEvent(c->aux[i], r->after, 0));
+
+    // the host's tables
+    for (int j = 0; j < m; j++) {
+        std::memcpy(&s->hVertices[(size_t)ids[j] * 9], vs + (size_t)j * 9, 9 * sizeof(float));
+        if (normals) std::memcpy(&s->hNormals[(size_t)ids[j] * 9], ns + (size_t)j * 9, 9 * sizeof(float));
+    }
+    // ... hBoxes = rs_refit_boxes of the edited vertices.  They hold exact unions already (before the first edit: checked below), so an edit
+    // of few triangles recomputes only the moved leaves' ancestors: the same min / max, hence the same bits
+    if ((size_t)m * 16 < np) rs_refit_boxes_host_some(m, ids, s->hVertices.data(), s->hLeafOf.data(), s->hParent.data(), r->hChild.data(), s->hBoxes.data());
+    else rs_refit_boxes_host(s->bvhSize, s->hVertices.data(), s->hNodes[0].data(), s->hParent.data(), s->hBoxes.data());
+    if (bounded) {
+        s->dev.occRootLo = ld3(&s->hBoxes[r->root * 6]);
+        s->dev.occRootHi = ld3(&s->hBoxes[r->root * 6 + 3]);
+    }
+    s->edits++;                                                  // retained G-buffer planes are not this scene's any more
+    return rs_after_launch("rs_scene_set_triangles");
 }
 
 int rs_check_looper(const rs_scene* scene, int looper, const char* what) {

@@ -1,0 +1,375 @@
+// scene_refit.hip -- the device side of rs_scene_set_triangles (its entry point, checks, staging and fences: scene.hip) and
+// rs_refit_boxes, the same definition on the host.
+//
+// Every edit refits everything: O(numPrims), one code path, no ancestor can be left stale.  In the order of one stream:
+//   k_refit_clear   every box of the index space of rs_refit.h to the empty box (keys: min = all ones, max = 0), every counter to 0
+//   k_scatter       the edited vertices and normals, and the pre-differenced TriRec of every edited triangle wherever it is kept
+//                   (tris, occTris, the three sequences of ordTris; pad0 / pad1 stay; emiTris holds emissive triangles, which are refused)
+//   k_ref_leaves    leaf box = AABB(va, vb, vc) (src/bvh.h:20-21); then bottom-up: a node merges its box into its parent's and adds one
+//                   to the parent's counter, and the second arrival reads the finished union and climbs on.  The reference tree is up
+//                   to 52 deep and far from balanced (Sponza-class scene): nothing here depends on the depth but the length of a climb
+//   k_ref_write     the box half of nodesAll's 6 * bvhSize records (each fused with the box its boundingBoxId names) and of occChain
+//   k_grid_leaves   the same climb through occNodes and the six orders of ordNodes: a leaf's box is the union of the reference leaf
+//                   boxes of its triangles, so every record's box is the union of the reference LEAF boxes below it (the invariant of
+//                   occlusion_bvh.cpp; NOT of the reference's inner boxes, which this tree's spans do not match)
+//   k_grid_write    quantises outward on the scene's grid (rs_grid.h grid_box: the host builder's function) into the three box dwords
+//                   of each record; w -- leaf code or miss link -- the end records and the padding records are never written
+// The emissive tree (emiNodes) is left alone: it is built over the reference leaf boxes of the emissive triangles, and those cannot move
+// while emitters are refused.
+//
+// Hand-off inside a launch (the two climbs): a parent's box is only ever written by agent-scope atomic min / max and only ever read by
+// agent-scope atomic loads, both of which act on the one copy all eight XCDs agree on, never on a CU's L1; a child's merges are ordered
+// before its counter add (release, and the wave's outstanding memory operations drained), the second arrival's loads after its own add
+// (acquire).  Nobody waits for anybody: the first arrival simply ends.  min / max commute, so the bits do not depend on who arrives first.
+#include <cmath>
+#include <cstring>
+
+#include "rs_refit.h"
+#include "rs_grid.h"
+
+using namespace rs;
+
+namespace {
+
+#define RS_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+struct KeyBox { unsigned lo[3], hi[3]; };
+
+__device__ __forceinline__ KeyBox box_of_triangle(const float* __restrict__ v) {
+    KeyBox b;
+    for (int k = 0; k < 3; k++) {
+        const unsigned a = refit_key(v[k]), c = refit_key(v[3 + k]), d = refit_key(v[6 + k]);
+        b.lo[k] = min(a, min(c, d));
+        b.hi[k] = max(a, max(c, d));
+    }
+    return b;
+}
+
+// node `cur` holds the finished box b: merge it upwards until a parent still waits for its other child
+__device__ __forceinline__ void climb(unsigned* keys, unsigned* arrived, const int* __restrict__ parent, size_t cur, KeyBox b) {
+    for (;;) {
+        const int p = parent[cur];
+        if (p < 0) return;
+        unsigned* pk = keys + (size_t)p * 6;
+        for (int k = 0; k < 3; k++) {
+            (void)__hip_atomic_fetch_min(pk + k, b.lo[k], RS_RLX_AGENT);
+            (void)__hip_atomic_fetch_max(pk + 3 + k, b.hi[k], RS_RLX_AGENT);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned before = __hip_atomic_fetch_add(arrived + p, 1u, RS_RLX_AGENT);
+        if (before == 0u) return;                          // the other child will find both merges and go on
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        for (int k = 0; k < 3; k++) {
+            b.lo[k] = __hip_atomic_load(pk + k, RS_RLX_AGENT);
+            b.hi[k] = __hip_atomic_load(pk + 3 + k, RS_RLX_AGENT);
+        }
+        cur = (size_t)p;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_refit_clear(unsigned* __restrict__ keys, unsigned* __restrict__ arrived, size_t numNodes) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= numNodes) return;
+    unsigned* k = keys + i * 6;
+    k[0] = k[1] = k[2] = 0xffffffffu;
+    k[3] = k[4] = k[5] = 0u;
+    arrived[i] = 0u;
+}
+
+struct ScatterArgs {
+    float* vertices; float* normals;
+    TriRec* tris; TriRec* occTris; TriRec* ordTris;      // occTris / ordTris: null when the scene has no such tree
+    const int* slotOf;
+    int numPrims;
+};
+__device__ __forceinline__ void put_triangle(TriRec* r, f3 v0, f3 e1, f3 e2) {      // (pad0, pad1, pad2 stay)
+    r->v0x = v0.x; r->v0y = v0.y; r->v0z = v0.z;
+    r->e1x = e1.x; r->e1y = e1.y; r->e1z = e1.z;
+    r->e2x = e2.x; r->e2y = e2.y; r->e2z = e2.z;
+}
+// ids are distinct (the host keeps the last record of a repeated id) and in range (checked on the host)
+__global__ void __launch_bounds__(256) k_scatter(ScatterArgs a, int m, const int* __restrict__ ids, const float* __restrict__ vertices,
+                                                 const float* __restrict__ normals) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const size_t p = (size_t)ids[i], np = (size_t)a.numPrims;
+    const float* v = vertices + (size_t)i * 9;
+    for (int k = 0; k < 9; k++) a.vertices[p * 9 + k] = v[k];
+    if (normals) for (int k = 0; k < 9; k++) a.normals[p * 9 + k] = normals[(size_t)i * 9 + k];
+    const f3 v0 = ld3(v), v1 = ld3(v + 3), v2 = ld3(v + 6), e1 = v1 - v0, e2 = v2 - v0;      // as rs_scene_create differences them
+    put_triangle(a.tris + p, v0, e1, e2);
+    if (a.occTris) put_triangle(a.occTris + a.slotOf[p], v0, e1, e2);
+    if (a.ordTris) for (size_t s = 0; s < 3; s++) put_triangle(a.ordTris + s * np + (size_t)a.slotOf[(1 + s) * np + p], v0, e1, e2);
+}
+
+__global__ void __launch_bounds__(256) k_ref_leaves(int numPrims, const float* __restrict__ vertices, const int* __restrict__ leafOf,
+                                                    const int* __restrict__ parent, unsigned* keys, unsigned* arrived) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= numPrims) return;
+    const KeyBox b = box_of_triangle(vertices + (size_t)p * 9);
+    const size_t node = (size_t)leafOf[p];
+    for (int k = 0; k < 3; k++) { keys[node * 6 + k] = b.lo[k]; keys[node * 6 + 3 + k] = b.hi[k]; }
+    climb(keys, arrived, parent, node, b);
+}
+
+__device__ __forceinline__ void write_box_half(BvhNode* r, const unsigned* __restrict__ k) {
+    // BvhNode: { min.x, min.y, min.z, max.z | max.x, max.y, primId, next }
+    *reinterpret_cast<float4*>(r) = make_float4(refit_unkey(k[0]), refit_unkey(k[1]), refit_unkey(k[2]), refit_unkey(k[5]));
+    *reinterpret_cast<float2*>(&r->bmaxx) = make_float2(refit_unkey(k[3]), refit_unkey(k[4]));
+}
+// records [0, 6 * bvhSize): nodesAll; [6 * bvhSize, 7 * bvhSize): occChain (launched without them when the scene has no shadow tree)
+__global__ void __launch_bounds__(256) k_ref_write(size_t numRecords, size_t bvhSize, const int* __restrict__ boxId, const unsigned* __restrict__ keys,
+                                                   BvhNode* nodesAll, BvhNode* occChain) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= numRecords) return;
+    const bool chain = i >= 6 * bvhSize;
+    const size_t id = chain ? i - 6 * bvhSize : (size_t)boxId[i];
+    write_box_half(chain ? occChain + id : nodesAll + i, keys + id * 6);
+}
+
+struct GridArgs {
+    uint4* occNodes; uint4* ordNodes;                    // ordNodes: null when the scene has no ordered trees
+    const TriRec* occTris; const TriRec* ordTris;
+    size_t gridFirst, occRecords, ordRecords;
+    int numPrims;
+    float base[3], scale[3];
+    double margin;
+};
+// record g of the grid part of the index space: its address, and the triangles a leaf code counts through
+__device__ __forceinline__ uint4* grid_record(const GridArgs& a, size_t g, const TriRec** tris, int* step) {
+    if (g < a.occRecords) { *tris = a.occTris; *step = 1; return a.occNodes + g; }
+    const size_t r = g - a.occRecords, order = r / a.ordRecords;
+    *tris = a.ordTris + (order >> 1) * (size_t)a.numPrims;
+    *step = (order & 1) ? -1 : 1;                        // the mirrored order meets a leaf's triangles at start, start - 1, ...
+    return a.ordNodes + r;
+}
+__global__ void __launch_bounds__(256) k_grid_leaves(GridArgs a, size_t numRecords, const int* __restrict__ parent, unsigned* keys, unsigned* arrived) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= numRecords) return;
+    const size_t node = a.gridFirst + g;
+    if (parent[node] == -2) return;                      // an end record or a padding record
+    const TriRec* tris; int step;
+    const int meta = (int)grid_record(a, g, &tris, &step)->w;
+    if (meta >= 0) return;                               // an inner record: its children bring its box
+    const int code = ~meta;
+    int tri = code >> 3;
+    KeyBox b;
+    for (int k = 0; k < 3; k++) { b.lo[k] = 0xffffffffu; b.hi[k] = 0u; }
+    for (int n = code & 7; n > 0; n--, tri += step) {
+        const unsigned* leaf = keys + (size_t)__float_as_int(tris[tri].pad0) * 6;      // the triangle's reference leaf box (k_ref_leaves, an earlier launch)
+        for (int k = 0; k < 3; k++) { b.lo[k] = min(b.lo[k], leaf[k]); b.hi[k] = max(b.hi[k], leaf[3 + k]); }
+    }
+    for (int k = 0; k < 3; k++) { keys[node * 6 + k] = b.lo[k]; keys[node * 6 + 3 + k] = b.hi[k]; }
+    climb(keys, arrived, parent, node, b);
+}
+__global__ void __launch_bounds__(256) k_grid_write(GridArgs a, size_t numRecords, const int* __restrict__ parent, const unsigned* __restrict__ keys) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= numRecords) return;
+    const size_t node = a.gridFirst + g;
+    if (parent[node] == -2) return;
+    const TriRec* tris; int step;
+    uint4* rec = grid_record(a, g, &tris, &step);
+    const unsigned* k = keys + node * 6;
+    const float lo[3] = { refit_unkey(k[0]), refit_unkey(k[1]), refit_unkey(k[2]) }, hi[3] = { refit_unkey(k[3]), refit_unkey(k[4]), refit_unkey(k[5]) };
+    // (the host has checked every vertex against the grid's box, so every box fits; one that did not would become the whole grid: conservative)
+    unsigned q[3] = { 0u, 0xffff0000u, 0xffffffffu };
+    (void)grid_box(lo, hi, a.base, a.scale, a.margin, q);
+    rec->x = q[0]; rec->y = q[1]; rec->z = q[2];
+}
+
+template <typename T>
+int upload_table(T** dst, const std::vector<T>& src) {
+    RS_TRY(rs_dev_alloc(dst, src.size()));
+    if (!src.empty()) RS_HIP(hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+
+inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
+
+}  // namespace
+
+bool rs_refit_preorder_parents(const unsigned* records, size_t count, int base, int* parent) {
+    // pre-order, every inner record with exactly two subtrees behind it: the open inner records form a stack
+    struct Open { int node, left; };
+    std::vector<Open> open;
+    for (size_t i = 0; i < count; i++) {
+        if (i > 0 && open.empty()) return false;         // a second root
+        parent[i] = open.empty() ? -1 : base + open.back().node;
+        if (!open.empty() && --open.back().left == 0) open.pop_back();
+        if ((int)records[i * 4 + 3] >= 0) open.push_back(Open{ (int)i, 2 });
+    }
+    return count > 0 && open.empty();
+}
+
+void rs_refit_boxes_host(int bvhSize, const float* vertices, const int* order0, const int* parent, float* boxes) {
+    const size_t nn = (size_t)bvhSize;
+    std::vector<unsigned> keys(nn * 6);
+    for (size_t i = 0; i < nn; i++) { unsigned* k = &keys[i * 6]; k[0] = k[1] = k[2] = 0xffffffffu; k[3] = k[4] = k[5] = 0u; }
+    // order 0 is a pre-order (a child's index is larger than its parent's, rs_reference_chain_tables): backwards, a node's box is
+    // complete before it is merged into its parent's
+    for (size_t i = nn; i-- > 0;) {
+        const int prim = order0[i * 3], id = order0[i * 3 + 1];
+        unsigned* k = &keys[(size_t)id * 6];
+        if (prim >= 0) {
+            const float* v = vertices + (size_t)prim * 9;
+            for (int c = 0; c < 3; c++) {
+                const unsigned a = refit_key(v[c]), b = refit_key(v[3 + c]), d = refit_key(v[6 + c]);
+                k[c] = std::min(a, std::min(b, d));
+                k[3 + c] = std::max(a, std::max(b, d));
+            }
+        }
+        if (parent[id] >= 0) {
+            unsigned* q = &keys[(size_t)parent[id] * 6];
+            for (int c = 0; c < 3; c++) { q[c] = std::min(q[c], k[c]); q[3 + c] = std::max(q[3 + c], k[3 + c]); }
+        }
+    }
+    for (size_t i = 0; i < nn * 6; i++) boxes[i] = refit_unkey(keys[i]);
+}
+
+void rs_refit_boxes_host_some(int m, const int* ids, const float* vertices, const int* leafOf, const int* parent, const int* child, float* boxes) {
+    auto lower = [](float a, float b) { return refit_key(a) < refit_key(b) ? a : b; };
+    auto upper = [](float a, float b) { return refit_key(a) > refit_key(b) ? a : b; };
+    for (int j = 0; j < m; j++) {
+        const float* v = vertices + (size_t)ids[j] * 9;
+        float* b = boxes + (size_t)leafOf[ids[j]] * 6;
+        for (int c = 0; c < 3; c++) { b[c] = lower(v[c], lower(v[3 + c], v[6 + c])); b[3 + c] = upper(v[c], upper(v[3 + c], v[6 + c])); }
+    }
+    // One climb per moved leaf, every ancestor recomputed from its children as they are then.  An ancestor is final after the last climb
+    // through it: that climb comes through one child, just recomputed, and the other child saw its own last climb earlier.
+    for (int j = 0; j < m; j++)
+        for (int n = parent[leafOf[ids[j]]]; n >= 0; n = parent[n]) {
+            const float* a = boxes + (size_t)child[(size_t)n * 2] * 6;
+            const float* b = boxes + (size_t)child[(size_t)n * 2 + 1] * 6;
+            float* o = boxes + (size_t)n * 6;
+            for (int c = 0; c < 3; c++) { o[c] = lower(a[c], b[c]); o[3 + c] = upper(a[3 + c], b[3 + c]); }
+        }
+}
+
+extern "C" int rs_refit_boxes(int numPrims, const float* vertices, int bvhSize, const int* order0, float* boundingBoxes) {
+    if (numPrims <= 0 || bvhSize != 2 * numPrims - 1 || !vertices || !order0 || !boundingBoxes)
+        return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_refit_boxes: null array, or bvhSize is not 2 * numPrims - 1");
+    for (size_t i = 0; i < (size_t)numPrims * 9; i++)
+        if (!std::isfinite(vertices[i])) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_refit_boxes: a vertex that is not finite");
+    for (size_t i = 0; i < (size_t)bvhSize; i++) {
+        const int* n = order0 + i * 3;
+        if (n[0] < -1 || n[0] >= numPrims || n[2] <= (int)i || n[2] > bvhSize)
+            return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_refit_boxes: a primitive id out of range or a link that does not point forward");
+    }
+    std::vector<int> parent, leafOf;
+    RS_TRY(rs_reference_chain_tables(bvhSize, order0, parent, leafOf, numPrims));
+    rs_refit_boxes_host(bvhSize, vertices, order0, parent.data(), boundingBoxes);
+    return 0;
+}
+
+void rs_refit_free(rs_scene* s) {
+    rs_refit* r = s->refit;
+    if (!r) return;
+    rs_dev_free(r->dSlotOf); rs_dev_free(r->dLeafOf); rs_dev_free(r->dBoxId); rs_dev_free(r->dParent);
+    rs_dev_free(r->dKeys); rs_dev_free(r->dArrived); rs_dev_free(r->dStage);
+    for (rs_refit::Stage& g : r->stage) {
+        if (g.host) (void)hipHostFree(g.host);
+        if (g.copied) (void)hipEventDestroy(g.copied);
+    }
+    for (hipEvent_t e : r->before) if (e) (void)hipEventDestroy(e);
+    if (r->after) (void)hipEventDestroy(r->after);
+    delete r;
+    s->refit = nullptr;
+}
+
+int rs_refit_prepare(rs_scene* s) {
+    if (s->refit) return 0;
+    const size_t np = (size_t)s->numPrims, nn = (size_t)s->bvhSize;
+    rs_refit* r = new rs_refit();
+    s->refit = r;                                        // (whatever a failure below leaves allocated, rs_scene_destroy frees)
+    const bool occ = s->dOccNodes != nullptr, ord = s->dOrdNodes != nullptr;
+    r->occRecords = occ ? (size_t)s->dev.occCount : 0;
+    r->ordRecords = ord ? (size_t)s->dev.ordStride / 16 : 0;
+    r->gridFirst = nn;
+    r->numNodes = nn + r->occRecords + 6 * r->ordRecords;
+    if (r->numNodes >= 0x7fffffffull) { rs_refit_free(s); return rs_fail(RS_ERR_UNSUPPORTED, "rs_scene_set_triangles: the scene's trees have more than 2^31 nodes"); }
+
+    // primitive -> slot: occTris in the shadow tree's leaf order, ordTris in the sequences of the even threaded orders
+    std::vector<int> slotOf(4 * np, 0);
+    if (occ) {
+        if (s->hOccLeafPrims.size() != np) { rs_refit_free(s); return rs_fail(RS_ERR_INTERNAL, "rs_scene_set_triangles: the shadow tree's leaf order was not kept"); }
+        for (size_t i = 0; i < np; i++) slotOf[(size_t)s->hOccLeafPrims[i]] = (int)i;
+    }
+    if (ord)
+        for (size_t a = 0; a < 3; a++) {
+            size_t j = 0;
+            for (size_t i = 0; i < nn; i++) { const int p = s->hNodes[2 * a][i * 3]; if (p >= 0) slotOf[(1 + a) * np + (size_t)p] = (int)j++; }
+        }
+    std::vector<int> boxId(6 * nn);
+    for (size_t k = 0; k < 6; k++) for (size_t i = 0; i < nn; i++) boxId[k * nn + i] = s->hNodes[k][i * 3 + 1];
+
+    // parents: the reference's by original id (hParent); the grid-box trees' from their records, read back once
+    std::vector<int> parent(r->numNodes, -2);
+    std::memcpy(parent.data(), s->hParent.data(), nn * sizeof(int));
+    bool trees = true;
+    if (occ) {
+        std::vector<unsigned> rec(r->occRecords * 4);
+        RS_HIP(hipMemcpy(rec.data(), s->dOccNodes, rec.size() * 4, hipMemcpyDeviceToHost));
+        trees = rs_refit_preorder_parents(rec.data(), r->occRecords, (int)nn, &parent[nn]);
+    }
+    if (ord && trees) {
+        std::vector<unsigned> rec(6 * r->ordRecords * 4);
+        RS_HIP(hipMemcpy(rec.data(), s->dOrdNodes, rec.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < 6 && trees; k++) {
+            // the tree of order k: the records from the stride's start up to the first one that is linked to the end record without being
+            // a leaf and has an empty box (scene.hip build_ordered_side pads with those), i.e. as many as a binary tree over its leaves has
+            const unsigned* t = &rec[k * r->ordRecords * 4];
+            size_t leaves = 0, count = 0;
+            while (count < r->ordRecords - 1) {          // (the last slot is the end record)
+                if ((int)t[count * 4 + 3] < 0) leaves++;
+                count++;
+                if (count == 2 * leaves - 1) break;      // pre-order: the tree is complete exactly here
+            }
+            const size_t first = nn + r->occRecords + k * r->ordRecords;
+            trees = leaves > 0 && count == 2 * leaves - 1 && rs_refit_preorder_parents(t, count, (int)first, &parent[first]);
+        }
+    }
+    if (!trees) { rs_refit_free(s); return rs_fail(RS_ERR_INTERNAL, "rs_scene_set_triangles: a grid-box tree is not a binary tree in pre-order"); }
+
+    int e = upload_table(&r->dSlotOf, slotOf);
+    if (!e) e = upload_table(&r->dLeafOf, s->hLeafOf);
+    if (!e) e = upload_table(&r->dBoxId, boxId);
+    if (!e) e = upload_table(&r->dParent, parent);
+    if (!e) e = rs_dev_alloc(&r->dKeys, r->numNodes * 6);
+    if (!e) e = rs_dev_alloc(&r->dArrived, r->numNodes);
+    for (rs_refit::Stage& g : r->stage) if (!e) e = rs_check_hip(hipEventCreateWithFlags(&g.copied, hipEventDisableTiming), "hipEventCreate");
+    for (hipEvent_t& ev : r->before) if (!e) e = rs_check_hip(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
+    if (!e) e = rs_check_hip(hipEventCreateWithFlags(&r->after, hipEventDisableTiming), "hipEventCreate");
+    if (e) { rs_refit_free(s); return e; }
+    r->lastStamp.assign(np, 0u);
+    r->lastIndex.assign(np, 0);
+    r->hChild.assign(nn * 2, -1);
+    for (size_t i = 0; i < nn; i++) {
+        const int p = s->hParent[i];
+        if (p < 0) r->root = i;
+        else r->hChild[(size_t)p * 2 + (r->hChild[(size_t)p * 2] < 0 ? 0 : 1)] = (int)i;      // (a tree: rs_reference_chain_tables gave every inner node two children)
+    }
+    return 0;
+}
+
+int rs_refit_enqueue(rs_scene* s, int m, const int* dIds, const float* dVertices, const float* dNormals, hipStream_t st) {
+    rs_refit* r = s->refit;
+    const size_t np = (size_t)s->numPrims, nn = (size_t)s->bvhSize;
+    const bool occ = s->dOccNodes != nullptr, ord = s->dOrdNodes != nullptr;
+    hipLaunchKernelGGL(k_refit_clear, dim3(blocks_for(r->numNodes)), dim3(256), 0, st, r->dKeys, r->dArrived, r->numNodes);
+    ScatterArgs sa{ s->dVertices, s->dNormals, s->dTris, occ ? s->dOccTris : nullptr, ord ? s->dOrdTris : nullptr, r->dSlotOf, s->numPrims };
+    hipLaunchKernelGGL(k_scatter, dim3(blocks_for((size_t)m)), dim3(256), 0, st, sa, m, dIds, dVertices, dNormals);
+    hipLaunchKernelGGL(k_ref_leaves, dim3(blocks_for(np)), dim3(256), 0, st, s->numPrims, (const float*)s->dVertices, (const int*)r->dLeafOf,
+                       (const int*)r->dParent, r->dKeys, r->dArrived);
+    const size_t refRecords = (occ ? 7 : 6) * nn;
+    hipLaunchKernelGGL(k_ref_write, dim3(blocks_for(refRecords)), dim3(256), 0, st, refRecords, nn, (const int*)r->dBoxId, (const unsigned*)r->dKeys,
+                       s->dNodesAll, s->dOccChain);
+    const size_t gridRecords = r->occRecords + 6 * r->ordRecords;
+    if (gridRecords) {
+        GridArgs ga{ s->dOccNodes, s->dOrdNodes, s->dOccTris, s->dOrdTris, r->gridFirst, r->occRecords, r->ordRecords, s->numPrims,
+                     { s->dev.occBase.x, s->dev.occBase.y, s->dev.occBase.z }, { s->dev.occScale.x, s->dev.occScale.y, s->dev.occScale.z }, s->gridMargin };
+        hipLaunchKernelGGL(k_grid_leaves, dim3(blocks_for(gridRecords)), dim3(256), 0, st, ga, gridRecords, (const int*)r->dParent, r->dKeys, r->dArrived);
+        hipLaunchKernelGGL(k_grid_write, dim3(blocks_for(gridRecords)), dim3(256), 0, st, ga, gridRecords, (const int*)r->dParent, (const unsigned*)r->dKeys);
+    }
+    return rs_check_hip(hipGetLastError(), "rs_scene_set_triangles: refit kernels");
+}
