@@ -313,6 +313,30 @@ int  rs_scene_set_triangles(rs_scene* scene, int count, const int* primIds, cons
  * tree was built from this returns the boxes rs_build_bvh returned.  RS_ERR_INVALID_ARGUMENT: a null array, bvhSize other than
  * 2 * numPrims - 1, a vertex that is not finite, a primitive id or link out of range, an order that is not a tree. */
 int  rs_refit_boxes(int numPrims, const float* vertices, int bvhSize, const int* order0, float* boundingBoxes);
+/* Test hooks of rs_scene_set_triangles (tests/refit_tables.py holds every record of the refit's device tables to a host restatement).
+ * rs_debug_scene_table waits for the library stream and the library's internal streams, as rs_synchronize does, then copies one device
+ * array of the scene to `host`.  *bytes receives the array's size (0: the scene has no such array); host == NULL asks for the size
+ * only.  RS_ERR_INVALID_ARGUMENT, nothing written: a null scene or `bytes`, an unknown `which`, a capacity below the size.
+ * RS_ERR_UNSUPPORTED while the library stream is being captured. */
+#define RS_TABLE_VERTICES  0   /* float[9 * numPrims] */
+#define RS_TABLE_NORMALS   1   /* float[9 * numPrims] */
+#define RS_TABLE_TRIS      2   /* 48-byte triangle records { v0, pad0, e1, pad1, e2, pad2 } [numPrims] */
+#define RS_TABLE_NODES_ALL 3   /* 32-byte records { min.xyz, max.z, max.x, max.y, primId, next } [6 * bvhSize + 1] */
+#define RS_TABLE_OCC_NODES 4   /* 16-byte grid-box records [occCount + 1], the end record last */
+#define RS_TABLE_OCC_CHAIN 5   /* 32-byte records [bvhSize] by original node id */
+#define RS_TABLE_OCC_TRIS  6   /* triangle records [numPrims] in the shadow tree's leaf order */
+#define RS_TABLE_ORD_NODES 7   /* the whole allocation: 6 * ordStride bytes */
+#define RS_TABLE_ORD_TRIS  8   /* triangle records [3 * numPrims] */
+#define RS_TABLE_EMI_NODES 9   /* 16-byte grid-box records of the emissive tree and its end record */
+#define RS_TABLE_EMI_TRIS  10  /* triangle records, one per emissive triangle */
+int  rs_debug_scene_table(const rs_scene* scene, int which, void* host, size_t capacity, size_t* bytes);
+/* The 16-bit grid of the scene's grid-box trees: plane q of axis k lies at base[k] + q * scale[k]; the margin boxes are cleared by; the
+ * box the grid was laid over (a moved vertex must stay inside it); the shadow tree's record count and the byte stride of the ordered
+ * trees (0: the scene has no such tree; without the shadow tree everything is 0).  Any pointer may be NULL.  Host only. */
+int  rs_debug_scene_grid(const rs_scene* scene, float base[3], float scale[3], double* margin, float lo[3], float hi[3], int* occCount, int* ordStride);
+/* The function that turns one exact box into the three box dwords of a grid-box record (rs_grid.h grid_box), as it is.  Host only.
+ * *fits = 0, out untouched: the box does not fit the grid's 16 bits. */
+int  rs_debug_grid_box(const float lo[3], const float hi[3], const float base[3], const float scale[3], double margin, unsigned out[3], int* fits);
 /* The texels of texture texId of the scene's table: width x height must be the texture's own, data is host memory of 3 floats per
  * texel and is copied.  Ordering and refusals as rs_scene_set_materials (texId out of range, other dimensions and null data are
  * RS_ERR_INVALID_ARGUMENT).  Memory: a texture that is never edited keeps its one device array.  An edited texture holds at most three

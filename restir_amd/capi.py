@@ -128,7 +128,7 @@ RIS_GLOBAL, RIS_LDS, RIS_ALIAS_LDS = 0, 1, 2
 EXPORTS = [
     "rs_last_error", "rs_context_create", "rs_context_destroy", "rs_context_set_current", "rs_init", "rs_set_stream", "rs_set_sync", "rs_set_side_stream", "rs_set_ris_table_pixels", "rs_set_internal_stream_priority", "rs_internal_streams_info", "rs_choose_internal_streams_again", "rs_prepare_streams", "rs_set_stream_plan", "rs_set_denoise_stream", "rs_join_denoise_stream", "rs_set_tile_split", "rs_synchronize",
     "rs_build_bvh", "rs_build_light_table", "rs_build_alias_table", "rs_build_envmap_pdf", "rs_scene_build", "rs_scene_build_textured", "rs_scene_create",
-    "rs_scene_host_desc", "rs_scene_set_sample_sequence", "rs_scene_set_emission", "rs_scene_set_materials", "rs_scene_set_texture", "rs_scene_set_triangles", "rs_refit_boxes", "rs_scene_destroy", "rs_camera_update", "rs_trace_closest", "rs_trace_closest_wave", "rs_scene_set_ordered_tree", "rs_ordered_bvh_host_check", "rs_trace_occlusion",
+    "rs_scene_host_desc", "rs_scene_set_sample_sequence", "rs_scene_set_emission", "rs_scene_set_materials", "rs_scene_set_texture", "rs_scene_set_triangles", "rs_refit_boxes", "rs_debug_scene_table", "rs_debug_scene_grid", "rs_debug_grid_box", "rs_scene_destroy", "rs_camera_update", "rs_trace_closest", "rs_trace_closest_wave", "rs_scene_set_ordered_tree", "rs_ordered_bvh_host_check", "rs_trace_occlusion",
     "rs_gbuffer_create", "rs_gbuffer_destroy", "rs_gbuffer_render", "rs_gbuffer_render_rows", "rs_gbuffer_update",
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
@@ -189,6 +189,9 @@ def lib():
     L.rs_scene_set_texture.argtypes = [vp, ci, ci, ci, vp]
     L.rs_scene_set_triangles.argtypes = [vp, ci, vp, vp, vp]
     L.rs_refit_boxes.argtypes = [ci, vp, ci, vp, vp]
+    L.rs_debug_scene_table.argtypes = [vp, ci, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rs_debug_scene_grid.argtypes = [vp, vp, vp, C.POINTER(C.c_double), vp, vp, C.POINTER(ci), C.POINTER(ci)]
+    L.rs_debug_grid_box.argtypes = [vp, vp, vp, vp, C.c_double, vp, C.POINTER(ci)]
     L.rs_restir_set_light_tracking.argtypes = [vp, ci]
     L.rs_restir_download_light_ids.argtypes = [vp, ci, vp]
     L.rs_restir_light_rows_bytes.argtypes = [vp, ci]
@@ -467,6 +470,27 @@ def refit_boxes(vertices, order0):
     return boxes
 
 
+def grid_box(lo, hi, base, scale, margin):
+    """rs_debug_grid_box (test hook, host only): the three box dwords of the exact box [lo, hi] on the grid (base, scale, margin), or
+    None when the box does not fit the grid's 16 bits.  Also returns the output array, which a box that does not fit leaves untouched."""
+    a = [np.ascontiguousarray(x, np.float32).reshape(3) for x in (lo, hi, base, scale)]
+    out = np.full(3, 0xdeadbeef, np.uint32)
+    fits = C.c_int(-1)
+    check(lib().rs_debug_grid_box(_p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), float(margin), _p(out), C.byref(fits)))
+    return (out if fits.value else None), out
+
+
+# rs_debug_scene_table: name -> (RS_TABLE_*, record dtype)
+TRI_DTYPE = np.dtype([("v0", np.float32, 3), ("pad0", np.uint32), ("e1", np.float32, 3), ("pad1", np.uint32), ("e2", np.float32, 3), ("pad2", np.uint32)])
+NODE_DTYPE = np.dtype([("min", np.float32, 3), ("maxz", np.float32), ("maxx", np.float32), ("maxy", np.float32), ("primId", np.int32), ("next", np.int32)])
+GRID_DTYPE = np.dtype([("box", np.uint32, 3), ("w", np.int32)])
+SCENE_TABLES = {
+    "vertices": (0, np.dtype((np.float32, (3, 3)))), "normals": (1, np.dtype((np.float32, (3, 3)))), "tris": (2, TRI_DTYPE),
+    "nodesAll": (3, NODE_DTYPE), "occNodes": (4, GRID_DTYPE), "occChain": (5, NODE_DTYPE), "occTris": (6, TRI_DTYPE),
+    "ordNodes": (7, GRID_DTYPE), "ordTris": (8, TRI_DTYPE), "emiNodes": (9, GRID_DTYPE), "emiTris": (10, TRI_DTYPE),
+}
+
+
 def ordered_bvh_host_check(boxes, nodes):
     """rs_ordered_bvh_host_check on rs_build_bvh's outputs; returns (error code, node counts per axis, depth per axis)."""
     boxes = np.ascontiguousarray(boxes, np.float32); nodes = [np.ascontiguousarray(nodes[k], np.int32) for k in range(6)]
@@ -662,6 +686,27 @@ class Scene:
         if v.shape[0] != ids.size or (n is not None and n.shape[0] != ids.size):
             raise ValueError("set_triangles: three vertices (and three normals) per primitive id")
         check(lib().rs_scene_set_triangles(self.handle, int(ids.size), _p(ids), _p(v), None if n is None else _p(n)))
+
+    def debug_table(self, name):
+        """rs_debug_scene_table (test hook): a copy of one device array of the scene, after everything enqueued so far, as a NumPy array of
+        its records (SCENE_TABLES; pads and grid-box dwords as uint32 so that they compare bit for bit); length 0 when the scene has none."""
+        which, dtype = SCENE_TABLES[name]
+        size = C.c_size_t(0)
+        check(lib().rs_debug_scene_table(self.handle, which, None, 0, C.byref(size)))
+        raw = np.zeros(size.value, np.uint8)
+        if size.value:
+            check(lib().rs_debug_scene_table(self.handle, which, _p(raw), raw.size, C.byref(size)))
+        base = dtype.base if dtype.subdtype else dtype
+        out = raw.view(base)
+        return out.reshape((-1,) + dtype.shape) if dtype.subdtype else out
+
+    def debug_grid(self):
+        """rs_debug_scene_grid (test hook): dict(base, scale, margin, lo, hi, occ_count, ord_stride) of the grid of the grid-box trees;
+        the counts are 0 when the tree is absent."""
+        base, scale, lo, hi = (np.zeros(3, np.float32) for _ in range(4))
+        margin, occ, stride = C.c_double(0), C.c_int(0), C.c_int(0)
+        check(lib().rs_debug_scene_grid(self.handle, _p(base), _p(scale), C.byref(margin), _p(lo), _p(hi), C.byref(occ), C.byref(stride)))
+        return dict(base=base, scale=scale, margin=margin.value, lo=lo, hi=hi, occ_count=occ.value, ord_stride=stride.value)
 
     def geometry(self):
         """The scene's vertices and vertex normals as rs_scene_host_desc returns them: two (n, 3, 3) float32 copies."""

@@ -10,6 +10,7 @@
 
 #include "rs_internal.h"
 #include "rs_refit.h"
+#include "rs_grid.h"
 
 using namespace rs;
 
@@ -732,6 +733,62 @@ extern "C" int rs_scene_set_triangles(rs_scene* s, int count, const int* primIds
     }
     s->edits++;                                                  // retained G-buffer planes are not this scene's any more
     return rs_after_launch("rs_scene_set_triangles");
+}
+
+// Test hooks of the refit (include/restir_hip.h): the device tables as they are, the grid they are quantised on, and grid_box itself.
+extern "C" int rs_debug_scene_table(const rs_scene* s, int which, void* host, size_t capacity, size_t* bytes) {
+    RS_SCOPE(s);
+    if (!s || !bytes) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_scene_table: null argument");
+    const size_t np = (size_t)s->numPrims, nn = (size_t)s->bvhSize;
+    size_t emissive = 0;
+    for (size_t p = 0; p < np; p++) if (s->hMaterials[(size_t)s->hMaterialIds[p]].type == 4) emissive++;
+    const void* src = nullptr;
+    size_t size = 0;
+    switch (which) {
+    case RS_TABLE_VERTICES:  src = s->dVertices; size = np * 9 * sizeof(float); break;
+    case RS_TABLE_NORMALS:   src = s->dNormals; size = np * 9 * sizeof(float); break;
+    case RS_TABLE_TRIS:      src = s->dTris; size = np * sizeof(TriRec); break;
+    case RS_TABLE_NODES_ALL: src = s->dNodesAll; size = (nn * 6 + 1) * sizeof(BvhNode); break;
+    case RS_TABLE_OCC_NODES: src = s->dOccNodes; size = ((size_t)s->dev.occCount + 1) * 16; break;
+    case RS_TABLE_OCC_CHAIN: src = s->dOccChain; size = nn * sizeof(BvhNode); break;
+    case RS_TABLE_OCC_TRIS:  src = s->dOccTris; size = np * sizeof(TriRec); break;
+    case RS_TABLE_ORD_NODES: src = s->dOrdNodes; size = (size_t)s->dev.ordStride * 6; break;
+    case RS_TABLE_ORD_TRIS:  src = s->dOrdTris; size = np * 3 * sizeof(TriRec); break;
+    case RS_TABLE_EMI_NODES: src = s->dEmiNodes; size = ((size_t)s->dev.emiCount + 1) * 16; break;
+    case RS_TABLE_EMI_TRIS:  src = s->dEmiTris; size = emissive * sizeof(TriRec); break;
+    default: return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_scene_table: unknown table");
+    }
+    if (!src) size = 0;
+    if (host && capacity < size) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_scene_table: the host buffer is smaller than the table");
+    RS_TRY(refuse_while_capturing("rs_debug_scene_table: the library stream is being captured into a graph"));
+    if (host && size) {
+        RS_TRY(rs_synchronize());
+        RS_HIP(hipMemcpy(host, src, size, hipMemcpyDeviceToHost));
+    }
+    *bytes = size;
+    return 0;
+}
+
+extern "C" int rs_debug_scene_grid(const rs_scene* s, float base[3], float scale[3], double* margin, float lo[3], float hi[3], int* occCount, int* ordStride) {
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_scene_grid: null scene");
+    const bool occ = s->dOccNodes != nullptr;
+    const float b[3] = { s->dev.occBase.x, s->dev.occBase.y, s->dev.occBase.z }, c[3] = { s->dev.occScale.x, s->dev.occScale.y, s->dev.occScale.z };
+    for (int k = 0; k < 3; k++) {
+        if (base) base[k] = occ ? b[k] : 0.f;
+        if (scale) scale[k] = occ ? c[k] : 0.f;
+        if (lo) lo[k] = occ ? s->gridLo[k] : 0.f;
+        if (hi) hi[k] = occ ? s->gridHi[k] : 0.f;
+    }
+    if (margin) *margin = occ ? s->gridMargin : 0.0;
+    if (occCount) *occCount = occ ? s->dev.occCount : 0;
+    if (ordStride) *ordStride = s->dOrdNodes ? (int)s->dev.ordStride : 0;
+    return 0;
+}
+
+extern "C" int rs_debug_grid_box(const float lo[3], const float hi[3], const float base[3], const float scale[3], double margin, unsigned out[3], int* fits) {
+    if (!lo || !hi || !base || !scale || !out || !fits) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_grid_box: null argument");
+    *fits = grid_box(lo, hi, base, scale, margin, out) ? 1 : 0;
+    return 0;
 }
 
 int rs_check_looper(const rs_scene* scene, int looper, const char* what) {

@@ -1,4 +1,4 @@
-"""Helpers of tests/test_gpu_geometry_edits.py and tests/test_geometry_refit_host.py: triangle edits (rs_scene_set_triangles) driven
+"""Helpers of tests/test_gpu_geometry_edits.py, tests/test_gpu_refit_tables.py and tests/test_geometry_refit_host.py: triangle edits (rs_scene_set_triangles) driven
 through the oracle and the library alike.  The oracle has no edit of its own: its side of an edit is a fresh oracle.binding.Scene made
 from the edited vertices and normals, with the old threaded orders and the boxes refitted by capi.refit_boxes (rs_refit_boxes, host
 only) handed over as `prebuilt` -- never boxes read back from the scene under test."""
@@ -112,6 +112,83 @@ def geometry_edit(sd, vertices, kind, seed=0):
         p = corner_triangle(sd)
         return np.array([p], np.int32), orig[p][None].copy(), None
     raise KeyError(kind)
+
+
+# ---- the geometry at which box code goes wrong (tests/test_gpu_refit_tables.py) ----------------------------------------------------------
+EXTREME_KINDS = ("faces", "corners", "point_and_line", "signed_zeros", "tiny_edges", "thrice")
+
+
+def zero_axis(lo, hi):
+    """The first axis whose range holds 0 in its interior, or None."""
+    for k in range(3):
+        if lo[k] < 0 < hi[k]:
+            return k
+    return None
+
+
+def extreme_edit(sd, vertices, kind, lo, hi, seed=0):
+    """(ids, vertices, None) of an edit that puts triangles where box code goes wrong; lo, hi: the box of the scene's grid (every vertex
+    stays inside it).  Needs 8 movable triangles (6 for "faces", 2 for "point_and_line", 1 otherwise); "signed_zeros" and the subnormal
+    edge of "tiny_edges" need an axis with 0 inside (zero_axis)."""
+    rng = np.random.default_rng(seed)
+    cur = np.asarray(vertices, np.float32).reshape(-1, 3, 3)
+    lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
+    ids = movable(sd)
+    mid = ((lo.astype(np.float64) + hi) / 2).astype(np.float32)
+    if kind == "faces":                                      # one triangle flat on each of the six faces of the grid's box
+        pick = ids[np.linspace(0, len(ids) - 1, 6).astype(int)]
+        v = np.clip(cur[pick], lo, hi).astype(np.float32)
+        for j in range(6):
+            v[j, :, j >> 1] = (lo, hi)[j & 1][j >> 1]
+        return pick, v, None
+    if kind == "corners":                                    # a point triangle on each of the eight corners
+        pick = ids[np.linspace(0, len(ids) - 1, 8).astype(int)]
+        v = np.zeros((8, 3, 3), np.float32)
+        for j in range(8):
+            v[j, :] = [(lo, hi)[(j >> k) & 1][k] for k in range(3)]
+        return pick, v, None
+    if kind == "point_and_line":                             # zero-extent boxes in the interior: only the margin keeps them open
+        pick = ids[[0, len(ids) - 1]]
+        a = (lo + (hi - lo) * np.float32(0.3)).astype(np.float32)
+        b = (lo + (hi - lo) * np.float32(0.6)).astype(np.float32)
+        b[1:] = a[1:]                                        # the line runs along x
+        return pick, np.array([[a, a, a], [a, a, b]], np.float32), None
+    if kind == "signed_zeros":                               # -0 and +0 mixed on an axis whose range holds 0
+        k = zero_axis(lo, hi)
+        pick = ids[[0, len(ids) - 1]]
+        v = np.clip(cur[pick], lo, hi).astype(np.float32)
+        v[0, :, k] = (-0.0, 0.0, 0.0)
+        v[1, :, k] = (0.0, -0.0, -0.0)
+        return pick, v, None
+    if kind == "tiny_edges":
+        pick = ids[[len(ids) // 3]]
+        t = mid.copy()
+        v = [np.stack([t, np.nextafter(t, hi), t + (hi - lo) * np.float32(0.1)])]      # v1 = nextafter(v0)
+        k = zero_axis(lo, hi)
+        if k is not None and len(ids) > 1:                   # v1 - v0 is subnormal
+            pick = np.append(pick, ids[(len(ids) // 3 + 1) % len(ids)]).astype(np.int32)
+            a, b, c = mid.copy(), mid.copy(), (mid + (hi - lo) * np.float32(0.05)).astype(np.float32)
+            a[k], b[k] = 0.0, 1e-40
+            v.append(np.stack([a, b, c]))
+        return pick.astype(np.int32), np.stack(v).astype(np.float32), None
+    if kind == "thrice":                                     # every movable id three times in one call: the last record wins
+        ext = (hi - lo).astype(np.float32)
+        v = [np.clip(cur[ids] + rng.uniform(-0.05, 0.05, (len(ids), 3, 3)) * ext, lo, hi).astype(np.float32) for _ in range(3)]
+        return np.concatenate([ids, ids[::-1], ids]).astype(np.int32), np.concatenate([v[0], v[1][::-1], v[2]]), None
+    raise KeyError(kind)
+
+
+def soup_scene(count, seed=7):
+    """`count` random triangles in [-1, 1]^3 with one diffuse material and no light: the refit's tables at the smallest trees (2 and 3
+    triangles: the root's children are leaves) and around one block of 256 threads."""
+    from restir_amd import scenes
+    from restir_amd.ctypes_structs import LAMBERTIAN, make_materials
+    rng = np.random.default_rng(seed + count)
+    centre = rng.uniform(-0.8, 0.8, (count, 1, 3))
+    soup = scenes.TriangleSoup()
+    soup.add_flat((centre + rng.uniform(-0.2, 0.2, (count, 3, 3))).astype(np.float32), 0)
+    mats = make_materials([dict(type=LAMBERTIAN, baseColor=(0.6, 0.6, 0.6))])
+    return scenes.SceneData("soup%d" % count, soup, mats, dict(position=(0.0, 0.0, 3.5), rotation=(-90.0, 0.0, 0.0), fov_y=19.5, focal_dist=1.0))
 
 
 def rebuilt_oracle_scene(old, vertices, normals, boxes):
