@@ -213,6 +213,7 @@ struct rs_scene {
     std::vector<float> hVertices, hNormals, hTexcoords, hBoxes, hLightRadiance, hLightProb;
     std::vector<int> hMaterialIds, hNodes[6], hLightPrimIds, hLightFailId;
     std::vector<int> hParent, hLeafOf;   // reference tree: parent by original node id, leaf node of each primitive
+    bool properBoxes = false;            // the box table is a proper hierarchy (rs_scene_create); DevScene::axisCull also asks for small triangles
     // Geometry edits (rs_scene_set_triangles; rs_refit.h, scene_refit.hip).  Kept from creation, on the host only: the primitive in every
     // slot of occTris, the box the shadow tree's grid was laid over (a moved vertex must stay inside it) and the grid's margin.
     // Everything else -- device tables, scratch, staging -- belongs to `refit`, which the first edit allocates.

@@ -88,7 +88,10 @@ RS_HD bool box_hit(const RayBoxCtx& c, f3 bmin, f3 bmax, float& tMin) {
     // hit point lies inside its triangle's box up to rounding << tol), the visiting order of the
     // remaining nodes is unchanged, so closest hit, ties and occlusion results are identical.  That argument
     // needs boxes that contain their triangles and their children, which rs_scene_create checks
-    // (DevScene::axisCull); for any other caller-supplied table the cull is off.
+    // (DevScene::axisCull); for any other caller-supplied table the cull is off.  It also needs the hit point to be where the
+    // ray is, which fails for a ray inside a triangle's plane: every quantity of the test is rounding then, and only the
+    // reference's absolute threshold on the determinant rejects it.  In a scene with triangles large enough for such a
+    // determinant to pass that threshold the cull is off as well (scene.hip far_skip_allowed clears DevScene::axisCull).
     if (c.zx && oyz) return slab_max_min(tn.y, tn.z, tf.y, tf.z, tMin) && !(c.cull && skip_far_on_axis(c.o.x, c.d.x, bmin.x, bmax.x, tMin, fminf(tf.y, tf.z)));
     if (c.zy && ozx) return slab_max_min(tn.z, tn.x, tf.z, tf.x, tMin) && !(c.cull && skip_far_on_axis(c.o.y, c.d.y, bmin.y, bmax.y, tMin, fminf(tf.z, tf.x)));
     if (c.zz && oxy) return slab_max_min(tn.x, tn.y, tf.x, tf.y, tMin) && !(c.cull && skip_far_on_axis(c.o.z, c.d.z, bmin.z, bmax.z, tMin, fminf(tf.x, tf.y)));

@@ -71,7 +71,8 @@ struct DevScene {
     f3 occBase, occScale;         // grid plane q on axis c = occBase.c + q * occScale.c
     f3 occRootLo, occRootHi;      // the reference's root box
     bool occNested;               // every reference box lies inside its parent's (enables the leaf shortcut)
-    bool axisCull;                // boxes contain their children and triangles (enables skip_far_on_axis)
+    bool axisCull;                // boxes contain their children and triangles, and no triangle is too large for skip_far_on_axis (scene.hip far_skip_allowed):
+                                  // enables that cull and, with linksNested, the packet walk's fast form (which needs the hierarchy alone and shares the flag)
     bool linksNested;             // in every threaded order the miss links nest: c in (a, link(a)) => link(c) <= link(a)
     int occCount;
     // the emissive triangles alone, as a tree of the shadow tree's kind (scene.hip build_emissive_side; may_hit_emissive_wave):

@@ -39,6 +39,32 @@ int upload(T** dst, const std::vector<T>& src) {
     return 0;
 }
 
+// May skip_far_on_axis (rs_intersect.h) run on a scene with these triangles?  The cull skips a box that a ray with a near-zero
+// direction component stays away from on that axis, on the ground that a triangle the reference hits lies where the ray passes.  A ray
+// inside a triangle's plane breaks that: determinant and barycentrics of intersectTriangle are pure rounding, and the reference
+// accepts such a "hit" on a triangle the ray passes at any distance within the plane -- unless the determinant stays below its
+// ABSOLUTE threshold FLT_EPSILON = 2^-23 (src/intersections.h:17-54).  The determinant of an in-plane ray is about 2^-27 * a * b, at
+// most about 2^-24 * a * b, a and b the largest components of the triangle's two edge vectors, so the threshold rejects every one
+// in a scene of small triangles and none of them in the same scene scaled up.
+// The bound below is MEASURED, NOT PROVEN.  A worst-case rounding bound on dot(e01, cross(d, e02)) for a unit d is about 10 * 2^-24 * a * b,
+// which passes FLT_EPSILON from a * b = 0.2 on; a cull that is provably exact would therefore be off on the full Sponza-class scene
+// (a * b = 0.39; Bistro-class 0.17), where it is worth a factor of four of the frame time (EXPERIMENTS.md).  Measured on the oracle
+// with 100 000 rays of every kind: no such hit up to a * b = 13.2, the first ones at 16 (the Cornell box scaled by 2) and 18.7,
+// hundreds from 64 on, and with 32 000 in-plane rays alone one at a * b = 4.  The bound is 1, a factor of 4 below the smallest product
+// seen to fail: a missed in-plane hit below it is unlikely, not impossible.  A scene with ONE larger triangle -- most scenes modelled in
+// metres with a floor or a wall in two triangles -- walks all its rays with a near-zero direction component without the cull, as the
+// reference does (and its packets without their fast form: DevScene::axisCull is one flag, so that no kernel's code changes); what that costs such a scene is in EXPERIMENTS.md ("Near-zero direction components").
+constexpr float kFarSkipEdgeProduct = 1.f;
+bool far_skip_allowed(const float* vertices, size_t count) {
+    for (size_t p = 0; p < count; p++) {
+        const float* t = vertices + p * 9;
+        float a = 0.f, b = 0.f;
+        for (int k = 0; k < 3; k++) { a = std::max(a, std::fabs(t[3 + k] - t[k])); b = std::max(b, std::fabs(t[6 + k] - t[k])); }
+        if (!(a * b <= kFarSkipEdgeProduct)) return false;
+    }
+    return true;
+}
+
 // The shadow-ray tree and the reference chain records (rs_walk.h walk_occlusion_tree).  Needs every
 // reference box finite with min <= max (always true for boxes from rs_build_bvh; a caller-supplied table
 // that is not leaves the fast path off and shadow rays walk the reference's tree).
@@ -85,7 +111,7 @@ int build_occlusion_side(rs_scene* s) {
     }
     int root = 0;
     for (size_t i = 0; i < nn; i++) if (parent[i] < 0) root = (int)i;
-    s->dev.occNested = s->dev.axisCull;          // a proper hierarchy is in particular nested
+    s->dev.occNested = s->properBoxes;           // a proper hierarchy is in particular nested
     s->dev.occRootLo = ld3(&s->hBoxes[(size_t)root * 6]);
     s->dev.occRootHi = ld3(&s->hBoxes[(size_t)root * 6 + 3]);
     // one record past the end: an empty box (lo = 65535 > hi = 0 on every axis fails the slab test for either sign of the direction)
@@ -727,6 +753,7 @@ extern "C" int rs_scene_set_triangles(rs_scene* s, int count, const int* primIds
     // of few triangles recomputes only the moved leaves' ancestors: the same min / max, hence the same bits
     if ((size_t)m * 16 < np) rs_refit_boxes_host_some(m, ids, s->hVertices.data(), s->hLeafOf.data(), s->hParent.data(), r->hChild.data(), s->hBoxes.data());
     else rs_refit_boxes_host(s->bvhSize, s->hVertices.data(), s->hNodes[0].data(), s->hParent.data(), s->hBoxes.data());
+    if (s->dev.axisCull && !far_skip_allowed(vs, (size_t)m)) s->dev.axisCull = false;      // (never back on: that would need every triangle again)
     if (bounded) {
         s->dev.occRootLo = ld3(&s->hBoxes[r->root * 6]);
         s->dev.occRootHi = ld3(&s->hBoxes[r->root * 6 + 3]);
@@ -980,7 +1007,8 @@ extern "C" int rs_scene_create(const rs_scene_desc* d, rs_scene** out) {
             for (int v = 0; v < 3; v++)
                 for (int k = 0; k < 3; k++) { const float x = s->hVertices[p * 9 + v * 3 + k]; proper = proper && c[k] <= x && x <= c[3 + k]; }
         }
-        s->dev.axisCull = proper;
+        s->properBoxes = proper;
+        s->dev.axisCull = proper && far_skip_allowed(s->hVertices.data(), np);
     }
     // Do the miss links of every threaded order nest (a node inside the span (a, link(a)) never links beyond link(a))?  They do
     // for a pre-order layout with link = end of the subtree, which is what BVHBuilder::buildMTBVH produces (src/bvh.cpp:160-202);

@@ -14,7 +14,8 @@ import pytest
 
 from oracle import binding as ob
 from tests.common import HipRenderer, OracleRenderer, bits_equal, get_scene, hip_scene, oracle_scene, radiance_stats
-from tests.test_gpu_parity import _compare_reservoirs, _random_rays, _shadow_like_segments
+from tests.ray_cases import _shadow_like_segments
+from tests.test_gpu_parity import _compare_reservoirs, _random_rays
 
 pytestmark = pytest.mark.gpu
 

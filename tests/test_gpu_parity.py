@@ -20,6 +20,7 @@ from oracle import binding as ob
 from restir_amd.ctypes_structs import RESERVOIR_DTYPE
 from tests.common import (RIS_TABLE_PIXELS_DEFAULT, HipRenderer, OracleRenderer, bits_equal, get_scene, hip_scene, mismatch_fraction, oracle_scene,
                           radiance_stats)
+from tests.ray_cases import _shadow_like_segments
 
 pytestmark = pytest.mark.gpu
 
@@ -67,40 +68,6 @@ def test_trace_closest_and_occlusion(hip, name):
     gocc = hip.trace_occlusion(hsc, torch.from_numpy(seg).cuda()).cpu().numpy()
     assert np.array_equal(occ, gocc)
     assert 0 < occ.sum() < len(occ)
-
-
-def _shadow_like_segments(sd, n, seed):
-    """Segments of the kinds the shadow pass produces and the corner cases of the occlusion tree: surface point ->
-    light point, random pairs, short, grazing along a triangle's plane, axis-aligned / near-zero directions
-    (reference walk), and origins far outside the scene (beyond the grid test's reach)."""
-    rng = np.random.default_rng(seed)
-    v = sd.vertices.reshape(-1, 3, 3).astype(np.float64)
-    lights = np.nonzero(sd.materials["type"][sd.material_ids] == 4)[0]
-
-    def points_on(tris, k):
-        t = v[rng.choice(tris, k)]
-        u = rng.uniform(size=(k, 2)); flip = u.sum(1) > 1; u[flip] = 1 - u[flip]
-        p = t[:, 0] * (1 - u.sum(1))[:, None] + t[:, 1] * u[:, :1] + t[:, 2] * u[:, 1:]
-        nrm = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0]); nrm /= np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-20)
-        return p, nrm, t
-
-    a, na, _ = points_on(np.arange(len(v)), n)
-    b, _, _ = points_on(lights if len(lights) else np.arange(len(v)), n)
-    na *= np.sign(np.einsum("ij,ij->i", na, b - a))[:, None]
-    a = a + 1e-4 * na
-    k = n // 8
-    b[k:2 * k] = points_on(np.arange(len(v)), k)[0]                                   # random surface pairs
-    b[2 * k:3 * k] = a[2 * k:3 * k] + rng.normal(size=(k, 3)) * 0.05                      # short
-    g, ng, tg = points_on(np.arange(len(v)), k)                                           # grazing: inside a triangle's plane
-    a[3 * k:4 * k] = g + (tg[:, 0] - g) * 3.0; b[3 * k:4 * k] = g + (tg[:, 1] - g) * 3.0
-    ax = rng.integers(0, 3, k)                                                            # axis-aligned / near-zero components
-    b[4 * k:5 * k] = a[4 * k:5 * k]; b[np.arange(4 * k, 5 * k), ax] += rng.choice([-3.0, 3.0], k)
-    b[4 * k:4 * k + k // 2, (ax[:k // 2] + 1) % 3] += rng.uniform(-2e-6, 2e-6, k // 2)
-    lo, hi = v.reshape(-1, 3).min(0), v.reshape(-1, 3).max(0)
-    a[5 * k:5 * k + 64] = hi + (hi - lo) * rng.uniform(6, 40, (64, 1))                    # far origins
-    seg = np.ascontiguousarray(np.concatenate([a, b], 1), np.float32)
-    seg[-16:, 3:] = seg[-16:, :3]                                                         # x == y: NaN direction
-    return seg
 
 
 def test_occlusion_tree_equals_reference_walk(hip, monkeypatch):
