@@ -10,7 +10,7 @@
 #include <cstring>
 #include <mutex>
 
-#include "rs_internal.h"
+#include "rs_row_layouts.h"
 
 using namespace rs;
 
@@ -326,35 +326,25 @@ int rs_gbuffer_update(rs_gbuffer* g, const rs_camera* cam) {
     return 0;
 }
 
-// rows of the id / normal / depth planes, packed [id rows][normal rows][depth rows] (20 B / px);
-// sel 0 = the planes of the current frameIdx, 1 = the "last" planes (what findTemporalNeighbor reads)
-size_t rs_gbuffer_rows_bytes(const rs_gbuffer* g, int rows) { RS_SCOPE(g); return g ? (size_t)g->width * (size_t)(rows > 0 ? rows : 0) * 20u : 0; }
+// rows of the id / normal / depth planes, packed [id rows][normal rows][depth rows] (20 B / px: rs_row_layouts.h gbuffer_planes);
+// sel 0 = the planes of the current frameIdx, 1 = the "last" planes (what findTemporalNeighbor reads).  One hipMemcpyAsync per plane.
+size_t rs_gbuffer_rows_bytes(const rs_gbuffer* g, int rows) { RS_SCOPE(g); return g ? rs_rows::gbuffer_planes(nullptr, 0).bytes(g->width, rows) : 0; }
 
+static int copy_gbuffer_rows(rs_gbuffer* g, int sel, int y0, int rows, char* buf, bool pack, const char* name) {
+    if (!g || !buf || (sel != 0 && sel != 1) || y0 < 0 || rows < 0 || y0 + rows > g->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, (std::string(name) + ": bad argument").c_str());
+    RS_TRY(rs_gbuffer_join(g));
+    rs_rows::SegList l(pack);
+    rs_rows::add_rows(l, rs_rows::gbuffer_planes(g, sel ? g->prev() : g->cur()), y0, rows, buf);      // (unpacking: the set's content key hears of it there)
+    RS_TRY(rs_copy::memcpy_segments(l));
+    return rs_after_launch(name);
+}
 int rs_gbuffer_rows_pack(const rs_gbuffer* g, int sel, int y0, int rows, void* devBuffer) {
     RS_SCOPE(g);
-    if (!g || !devBuffer || (sel != 0 && sel != 1) || y0 < 0 || rows < 0 || y0 + rows > g->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_gbuffer_rows_pack: bad argument");
-    RS_TRY(rs_gbuffer_join(g));
-    const int f = sel ? g->prev() : g->cur();
-    const size_t n = (size_t)g->width * rows, off = (size_t)y0 * g->width;
-    char* b = (char*)devBuffer;
-    RS_HIP(hipMemcpyAsync(b, g->primId[f] + off, n * 4, hipMemcpyDeviceToDevice, rs_stream()));
-    RS_HIP(hipMemcpyAsync(b + n * 4, g->normal[f] + off * 3, n * 12, hipMemcpyDeviceToDevice, rs_stream()));
-    RS_HIP(hipMemcpyAsync(b + n * 16, g->depth[f] + off, n * 4, hipMemcpyDeviceToDevice, rs_stream()));
-    return rs_after_launch("rs_gbuffer_rows_pack");
+    return copy_gbuffer_rows(const_cast<rs_gbuffer*>(g), sel, y0, rows, (char*)devBuffer, true, "rs_gbuffer_rows_pack");
 }
-
 int rs_gbuffer_rows_unpack(rs_gbuffer* g, int sel, int y0, int rows, const void* devBuffer) {
     RS_SCOPE(g);
-    if (!g || !devBuffer || (sel != 0 && sel != 1) || y0 < 0 || rows < 0 || y0 + rows > g->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_gbuffer_rows_unpack: bad argument");
-    RS_TRY(rs_gbuffer_join(g));
-    const int f = sel ? g->prev() : g->cur();
-    rs_gbuffer_note_write(g, f, y0, rows);
-    const size_t n = (size_t)g->width * rows, off = (size_t)y0 * g->width;
-    const char* b = (const char*)devBuffer;
-    RS_HIP(hipMemcpyAsync(g->primId[f] + off, b, n * 4, hipMemcpyDeviceToDevice, rs_stream()));
-    RS_HIP(hipMemcpyAsync(g->normal[f] + off * 3, b + n * 4, n * 12, hipMemcpyDeviceToDevice, rs_stream()));
-    RS_HIP(hipMemcpyAsync(g->depth[f] + off, b + n * 16, n * 4, hipMemcpyDeviceToDevice, rs_stream()));
-    return rs_after_launch("rs_gbuffer_rows_unpack");
+    return copy_gbuffer_rows(g, sel, y0, rows, (char*)const_cast<void*>(devBuffer), false, "rs_gbuffer_rows_unpack");
 }
 
 int rs_gbuffer_get_view(const rs_gbuffer* g, rs_gbuffer_view* v) {

@@ -24,7 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "rs_copy_segments.h"
+#include "rs_row_layouts.h"
 #include "rs_internal.h"
 
 using namespace rs;
@@ -1284,47 +1284,29 @@ int rs_restir_direct(rs_restir* r, const rs_scene* scene, const rs_camera* cam, 
     return rs_after_launch("ReSTIR Direct");
 }
 
-size_t rs_restir_halo_bytes(const rs_restir* r, int rows) {
-    RS_SCOPE(r);
-    return r ? (size_t)r->width * (size_t)(rows > 0 ? rows : 0) * 48u : 0;      // li 16 + wi 16 + tap 16
-}
-size_t rs_restir_rows_bytes(const rs_restir* r, int which, int rows) {
-    RS_SCOPE(r);
-    if (!r || rows < 0) return 0;
-    return (size_t)r->width * (size_t)rows * (which == 2 ? 48u : 40u);         // cur/last: li 16 + wi 16 + w 4 + m 4
-}
-
+// Row packing.  Packed layout of `rows` rows: the planes of the buffer one after the other (cur/last: li, wi, w, m; the published copy,
+// which = 2: li, wi, tap) -- rs_row_layouts.h says which planes those are; sizes and copies here are read off it.
 namespace {
-struct Span { void* ptr; size_t bytesPerPixel; };
-int spans_of(rs_restir* r, int which, Span out[4]) {
-    if (which == 2) {
-        out[0] = { r->temp.li, 16 }; out[1] = { r->temp.wi, 16 }; out[2] = { r->temp.tap, 16 };
-        return 3;
-    }
-    ResvPlanes* p = pick(r, which);
-    if (!p) return 0;
-    out[0] = { p->li, 16 }; out[1] = { p->wi, 16 }; out[2] = { p->w, 4 }; out[3] = { p->m, 4 };
-    return 4;
-}
+// one hipMemcpyAsync per plane
 int copy_rows(rs_restir* r, int which, int y0, int rows, char* buf, bool pack, const char* what) {
-    Span sp[4];
-    const int k = r ? spans_of(r, which, sp) : 0;
-    if (!k || !buf || y0 < 0 || rows < 0 || y0 + rows > r->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, what);
-    const size_t n = (size_t)r->width * rows, off = (size_t)y0 * r->width;
-    size_t pos = 0;
-    for (int i = 0; i < k; i++) {
-        char* plane = (char*)sp[i].ptr + off * sp[i].bytesPerPixel;
-        const size_t bytes = n * sp[i].bytesPerPixel;
-        if (bytes) RS_HIP(hipMemcpyAsync(pack ? (void*)(buf + pos) : (void*)plane, pack ? (const void*)plane : (const void*)(buf + pos), bytes,
-                                         hipMemcpyDeviceToDevice, rs_stream()));
-        pos += bytes;
-    }
+    if (!r || which < 0 || which > 2 || !buf || y0 < 0 || rows < 0 || y0 + rows > r->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, what);
+    rs_rows::SegList l(pack);
+    rs_rows::add_rows(l, rs_rows::restir_planes(r, which), y0, rows, buf);
+    RS_TRY(rs_copy::memcpy_segments(l));
+    return rs_after_launch(what);
+}
+// the light-id plane of buffer `which`: one launch of the copy kernel (refusals: see rs_restir_light_rows_bytes below)
+int copy_light_rows(rs_restir* r, int which, int y0, int rows, char* buf, bool pack, const char* what) {
+    if (!r || !buf || ((size_t)buf & 3) || which < 0 || which > 2 || y0 < 0 || rows < 0 || y0 + rows > r->height || !r->track || !r->idCur) return rs_fail(RS_ERR_INVALID_ARGUMENT, what);
+    rs_rows::SegList l(pack);
+    rs_rows::add_rows(l, rs_rows::light_id_plane(r, which), y0, rows, buf);
+    RS_TRY(rs_copy::copy_segments(l));
     return rs_after_launch(what);
 }
 }  // namespace
 
-// packed layout of `rows` rows: the planes of the buffer one after the other (cur/last: li, wi, w, m;
-// temp: li, wi, tap)
+size_t rs_restir_halo_bytes(const rs_restir* r, int rows) { RS_SCOPE(r); return r ? rs_rows::restir_planes(r, 2).bytes(r->width, rows) : 0; }
+size_t rs_restir_rows_bytes(const rs_restir* r, int which, int rows) { RS_SCOPE(r); return r && rows >= 0 ? rs_rows::restir_planes(r, which).bytes(r->width, rows) : 0; }
 int rs_restir_rows_pack(const rs_restir* r, int which, int y0, int rows, void* devBuffer) {
     RS_SCOPE(r);
     return copy_rows(const_cast<rs_restir*>(r), which, y0, rows, (char*)devBuffer, true, "rs_restir_rows_pack: bad argument");
@@ -1339,21 +1321,7 @@ int rs_restir_halo_unpack(rs_restir* r, int y0, int rows, const void* devBuffer)
 // Light tracking: the rows of the id plane that goes with reservoir buffer `which` (as rs_restir_download_light_ids), 4 B/px.  The planes
 // exist only while tracking is on, so both directions are refused while it is off instead of packing rows nobody wrote.  One launch of the
 // copy kernel of rs_copy_segments.h each way (the buffer 4-byte aligned: the kernel moves ints where it cannot move 16 bytes).
-size_t rs_restir_light_rows_bytes(const rs_restir* r, int rows) {
-    RS_SCOPE(r);
-    return r ? (size_t)r->width * (size_t)(rows > 0 ? rows : 0) * sizeof(int) : 0;
-}
-namespace {
-int copy_light_rows(rs_restir* r, int which, int y0, int rows, char* buf, bool pack, const char* what) {
-    if (!r || !buf || ((size_t)buf & 3) || which < 0 || which > 2 || y0 < 0 || rows < 0 || y0 + rows > r->height || !r->track || !r->idCur) return rs_fail(RS_ERR_INVALID_ARGUMENT, what);
-    int* plane = (which == 0 ? r->idCur : which == 1 ? r->idLast : r->idTemp) + (size_t)y0 * r->width;
-    const size_t bytes = (size_t)r->width * rows * sizeof(int);
-    rs_copy::SegList l;
-    l.add(plane, buf, bytes);
-    RS_TRY(rs_copy::copy_segments(l, pack));
-    return rs_after_launch(what);
-}
-}  // namespace
+size_t rs_restir_light_rows_bytes(const rs_restir* r, int rows) { RS_SCOPE(r); return r ? rs_rows::light_id_plane(nullptr, 0).bytes(r->width, rows) : 0; }
 int rs_restir_light_rows_pack(const rs_restir* r, int which, int y0, int rows, void* devBuffer) {
     RS_SCOPE(r);
     return copy_light_rows(const_cast<rs_restir*>(r), which, y0, rows, (char*)devBuffer, true, "rs_restir_light_rows_pack: bad argument, or light tracking is off");

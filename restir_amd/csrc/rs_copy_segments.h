@@ -1,5 +1,5 @@
 // rs_copy_segments.h -- several rows-of-a-plane copies as ONE launch: the strip driver's messages (strips.hip) and the row packing of the
-// light-id planes (restir.hip).
+// light-id planes (restir.hip); or, where it always was, one hipMemcpyAsync per plane.  Which planes a packed layout has: rs_row_layouts.h.
 #pragma once
 #include "rs_internal.h"
 
@@ -22,20 +22,25 @@ __global__ void __launch_bounds__(256) k_copy_segments(CopyTable t) {
     while (i >= t.start[k + 1]) k++;
     reinterpret_cast<T*>(t.dst[k])[i - t.start[k]] = reinterpret_cast<const T*>(t.src[k])[i - t.start[k]];
 }
+// pack: plane -> packed buffer; unpack: packed buffer -> plane.  Said once, when the list is made: whoever adds segments knows which side is written.
 struct SegList {
+    const bool pack;
     const char* a[kMaxSegs]; char* b[kMaxSegs]; size_t bytes[kMaxSegs]; int n = 0;
+    explicit SegList(bool packing) : pack(packing) {}
     void add(const void* plane, void* packed, size_t nbytes) { a[n] = (const char*)plane; b[n] = (char*)packed; bytes[n] = nbytes; n++; }
+    const char* src(int k) const { return pack ? a[k] : b[k]; }
+    char* dst(int k) const { return pack ? b[k] : const_cast<char*>(a[k]); }
 };
-// pack: plane -> packed buffer; unpack: packed buffer -> plane
-inline int copy_segments(const SegList& l, bool pack) {
+// the two ways to carry a list out, both on the library stream: one launch of the copy kernel ...
+inline int copy_segments(const SegList& l) {
     if (l.n == 0) return 0;
     bool wide = true;
     for (int k = 0; k < l.n; k++) wide = wide && l.bytes[k] % 16 == 0 && ((size_t)l.a[k] % 16 == 0) && ((size_t)l.b[k] % 16 == 0);
     const unsigned unit = wide ? 16u : 4u;
     CopyTable t; t.n = l.n; t.start[0] = 0;
     for (int k = 0; k < l.n; k++) {
-        t.src[k] = pack ? l.a[k] : l.b[k];
-        t.dst[k] = pack ? l.b[k] : const_cast<char*>(l.a[k]);
+        t.src[k] = l.src(k);
+        t.dst[k] = l.dst(k);
         t.start[k + 1] = t.start[k] + (unsigned)(l.bytes[k] / unit);
     }
     const unsigned total = t.start[t.n];
@@ -43,6 +48,12 @@ inline int copy_segments(const SegList& l, bool pack) {
     if (wide) hipLaunchKernelGGL(k_copy_segments<uint4>, dim3((total + 255) / 256), dim3(256), 0, rs_stream(), t);
     else hipLaunchKernelGGL(k_copy_segments<unsigned>, dim3((total + 255) / 256), dim3(256), 0, rs_stream(), t);
     return rs_check_hip(hipGetLastError(), "copy of plane rows (k_copy_segments)");
+}
+// ... or one hipMemcpyAsync per segment (the public reservoir and G-buffer row packing, the untracked history message)
+inline int memcpy_segments(const SegList& l) {
+    for (int k = 0; k < l.n; k++)
+        if (l.bytes[k]) RS_HIP(hipMemcpyAsync(l.dst(k), l.src(k), l.bytes[k], hipMemcpyDeviceToDevice, rs_stream()));
+    return 0;
 }
 
 }  // namespace rs_copy

@@ -23,7 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "rs_copy_segments.h"
+#include "rs_row_layouts.h"
 
 struct rs_comm {
     rs_transport t{};
@@ -91,6 +91,7 @@ struct rs_strips {
 namespace {
 using rs_copy::SegList;
 using rs_copy::copy_segments;
+using rs_rows::add_rows;
 
 constexpr int kHalo = RS_SPATIAL_HALO_ROWS;
 
@@ -111,33 +112,72 @@ int rccl_recv(void* ctx, void* buf, size_t bytes, int peer, void* stream) {
     return e ? rccl_fail(c, e, "ncclRecv") : 0;
 }
 
-// the border rows of one edge in the packed layout of rs_restir_halo_pack followed by rs_gbuffer_rows_pack: li, wi, tap, id, normal, depth
+// The messages, as concatenations of the layouts of rs_row_layouts.h: the public packs of include/restir_hip.h (tests/test_gpu_strip_wire_layout.py).
+// The border rows of one edge: rs_restir_halo_pack followed by rs_gbuffer_rows_pack of the current planes
 // (yResv: first of the kHalo reservoir rows; yG: first of the gRows G-buffer rows -- the same edge of the strip, so the two ranges end or begin together)
 void halo_segments(SegList& l, rs_restir* r, rs_gbuffer* g, int yResv, int yG, int gRows, char* packed) {
-    const size_t n = (size_t)r->width * kHalo, off = (size_t)yResv * r->width;
-    const int c = g->cur();
-    l.add(r->temp.li + off, packed, n * 16); l.add(r->temp.wi + off, packed + n * 16, n * 16); l.add(r->temp.tap + off, packed + n * 32, n * 16);
-    char* gb = packed + n * 48;
-    const size_t m = (size_t)r->width * gRows, offG = (size_t)yG * r->width;
-    l.add(g->primId[c] + offG, gb, m * 4); l.add(g->normal[c] + offG * 3, gb + m * 4, m * 12); l.add(g->depth[c] + offG, gb + m * 16, m * 4);
+    packed = add_rows(l, rs_rows::published_planes(r), yResv, kHalo, packed);
+    add_rows(l, rs_rows::gbuffer_planes(g, g->cur()), yG, gRows, packed);
 }
+size_t halo_bytes(int width, int gRows) { return rs_rows::published_planes(nullptr).bytes(width, kHalo) + rs_rows::gbuffer_planes(nullptr, 0).bytes(width, gRows); }
 
-// rows [y, y + rows) of what the next temporal merge reads, in the tracked layout of a history message: the reservoirs' li, wi, w, m
-// (rs_restir_rows_pack, which = 1), the "last" G-buffer id, normal, depth (rs_gbuffer_rows_pack, sel = 1), then the reservoirs' light ids
-// (rs_restir_light_rows_pack, which = 1) -- eight planes, so a message is packed by one launch and unpacked by one
-void history_segments(SegList& l, rs_restir* r, rs_gbuffer* g, int y, int rows, char* packed) {
-    const size_t n = (size_t)r->width * rows, off = (size_t)y * r->width;
-    const int f = g->prev();
-    l.add(r->last.li + off, packed, n * 16); l.add(r->last.wi + off, packed + n * 16, n * 16);
-    l.add(r->last.w + off, packed + n * 32, n * 4); l.add(r->last.m + off, packed + n * 36, n * 4);
-    l.add(g->primId[f] + off, packed + n * 40, n * 4); l.add(g->normal[f] + off * 3, packed + n * 44, n * 12); l.add(g->depth[f] + off, packed + n * 56, n * 4);
-    l.add(r->idLast + off, packed + n * 60, n * 4);
+// Rows [y, y + rows) of what the next temporal merge reads, a history message: rs_restir_rows_pack (which = 1), rs_gbuffer_rows_pack of the
+// "last" planes (sel = 1), then with light tracking rs_restir_light_rows_pack (which = 1) -- the untracked layout is a prefix of the tracked one
+void history_segments(SegList& l, rs_restir* r, rs_gbuffer* g, bool track, int y, int rows, char* packed) {
+    packed = add_rows(l, rs_rows::reservoir_planes(r, 1), y, rows, packed);
+    packed = add_rows(l, rs_rows::gbuffer_planes(g, g->prev()), y, rows, packed);
+    if (track) add_rows(l, rs_rows::light_id_plane(r, 1), y, rows, packed);
 }
 // the driver's setting and the rs_restir it is handed must agree: the setting is the size of the history messages
 int check_tracking(const rs_strips* s, const rs_restir* r, const char* unsupported, const char* mismatch) {
     if (r->track && !s->track) return rs_fail(RS_ERR_UNSUPPORTED, unsupported);
     if (!r->track && s->track) return rs_fail(RS_ERR_INVALID_ARGUMENT, mismatch);
     return 0;
+}
+
+// The four staging buffers of a frame's border rows as one unit, sized for gRows G-buffer rows (rs_strips_create, rs_strips_set_gbuffer_halo):
+// the new buffers first; gReach, haloBytes and the pointers change, and the old buffers go, only when every allocation has succeeded -- a
+// resize that fails leaves a driver that still works.  The caller has made sure nothing is in flight.
+int resize_halo(rs_strips* s, int gRows) {
+    const rs_comm* c = s->comm;
+    const size_t bytes = halo_bytes(s->width, gRows);
+    char** held[4] = { &s->sendUp, &s->recvUp, &s->sendDown, &s->recvDown };
+    char* fresh[4] = { nullptr, nullptr, nullptr, nullptr };
+    int e = 0;
+    for (int i = 0; i < 4 && !e; i++) if (i < 2 ? c->rank > 0 : c->rank + 1 < c->world) e = rs_dev_alloc(&fresh[i], bytes);
+    for (int i = 0; i < 4; i++) { if (!e) std::swap(*held[i], fresh[i]); rs_dev_free(fresh[i]); }      // (the old buffers; after a failure the new ones)
+    if (!e) { s->gReach = gRows; s->haloBytes = bytes; }
+    return e;
+}
+
+// The two exchange patterns.
+// "Swap with the neighbours": `bytes` at sendUp / sendDown to the strip above / below, theirs into recvUp / recvDown; up to four transfers
+size_t neighbour_xfers(const rs_comm* c, Xfer* ops, void* sendUp, void* recvUp, void* sendDown, void* recvDown, size_t bytes) {
+    size_t n = 0;
+    if (c->rank > 0) { ops[n++] = { true, sendUp, bytes, c->rank - 1 }; ops[n++] = { false, recvUp, bytes, c->rank - 1 }; }
+    if (c->rank + 1 < c->world) { ops[n++] = { true, sendDown, bytes, c->rank + 1 }; ops[n++] = { false, recvDown, bytes, c->rank + 1 }; }
+    return n;
+}
+// "Every other rank": where(k, part) is where rank k's part lives -- for this rank what it sends (the same to everybody), for another
+// rank where its bytes land.  root >= 0: only towards root / only on root.
+struct Span { void* buf; size_t bytes; };
+template <class Where>
+std::vector<Xfer> all_rank_xfers(const rs_strips* s, int parts, int root, Where where) {
+    const rs_comm* c = s->comm;
+    std::vector<Xfer> ops;
+    for (int k = 0; k < c->world; k++)
+        for (int part = 0; part < parts && k != c->rank; part++) {
+            if (root < 0 || root == k) { const Span mine = where(c->rank, part); ops.push_back({ true, mine.buf, mine.bytes, k }); }
+            if (root < 0 || root == c->rank) { const Span theirs = where(k, part); ops.push_back({ false, theirs.buf, theirs.bytes, k }); }
+        }
+    return ops;
+}
+// the rows of rank k's strip in a row-major image, which travel from and into place; image assembly (rs_strips_gather, rs_strips_gather_begin)
+Span strip_rows(const rs_strips* s, void* image, size_t rowBytes, int k) {
+    return { (char*)image + (size_t)s->bounds[(size_t)k] * rowBytes, (size_t)(s->bounds[(size_t)k + 1] - s->bounds[(size_t)k]) * rowBytes };
+}
+std::vector<Xfer> gather_xfers(const rs_strips* s, void* devImage, size_t rowBytes, int root) {
+    return all_rank_xfers(s, 1, root, [&](int k, int) { return strip_rows(s, devImage, rowBytes, k); });
 }
 
 // One grouped exchange, ordered after everything enqueued on the library stream so far: on the driver's stream for a stream-ordered
@@ -191,48 +231,48 @@ int exchange_gbuffer_rows(rs_strips* s, rs_gbuffer* g, int reach) {
     const size_t gBytes = rs_gbuffer_rows_bytes(g, reach);
     for (int i = 0; i < 2; i++)
         if ((i == 0 ? up : down) && !s->eawSend[i]) { RS_TRY(rs_dev_alloc(&s->eawSend[i], gBytes)); RS_TRY(rs_dev_alloc(&s->eawRecv[i], gBytes)); }
-    // the packed layout of rs_gbuffer_rows_pack: id rows, normal rows, depth rows -- all six segments of a direction in ONE copy launch
+    // the packed layout of rs_gbuffer_rows_pack -- all six segments of a direction in ONE copy launch
     // (as 12 hipMemcpyAsync calls they were a dozen launches of ~8 us on the library stream of every filtered frame)
     RS_TRY(rs_gbuffer_join(g));
-    const int cur = g->cur();
-    const auto segments = [&](SegList& l, int y, char* packed) {
-        const size_t n = (size_t)s->width * reach, off = (size_t)y * s->width;
-        l.add(g->primId[cur] + off, packed, n * 4); l.add(g->normal[cur] + off * 3, packed + n * 4, n * 12); l.add(g->depth[cur] + off, packed + n * 16, n * 4);
-    };
-    Xfer ops[4]; size_t n = 0;
+    const rs_rows::Planes planes = rs_rows::gbuffer_planes(g, g->cur());
     {
-        SegList l;
-        if (up) { segments(l, y0, s->eawSend[0]); ops[n++] = { true, s->eawSend[0], gBytes, c->rank - 1 }; ops[n++] = { false, s->eawRecv[0], gBytes, c->rank - 1 }; }
-        if (down) { segments(l, y1 - reach, s->eawSend[1]); ops[n++] = { true, s->eawSend[1], gBytes, c->rank + 1 }; ops[n++] = { false, s->eawRecv[1], gBytes, c->rank + 1 }; }
-        RS_TRY(copy_segments(l, true));
+        SegList l(true);
+        if (up) add_rows(l, planes, y0, reach, s->eawSend[0]);
+        if (down) add_rows(l, planes, y1 - reach, reach, s->eawSend[1]);
+        RS_TRY(copy_segments(l));
     }
-    RS_TRY(post(s, ops, n));
+    Xfer ops[4];
+    RS_TRY(post(s, ops, neighbour_xfers(c, ops, s->eawSend[0], s->eawRecv[0], s->eawSend[1], s->eawRecv[1], gBytes)));
     RS_TRY(join(s, false));
-    {
-        SegList l;
-        if (up) { segments(l, y0 - reach, s->eawRecv[0]); rs_gbuffer_note_write(g, cur, y0 - reach, reach); }
-        if (down) { segments(l, y1, s->eawRecv[1]); rs_gbuffer_note_write(g, cur, y1, reach); }
-        RS_TRY(copy_segments(l, false));
-    }
-    return 0;
+    SegList l(false);
+    if (up) add_rows(l, planes, y0 - reach, reach, s->eawRecv[0]);
+    if (down) add_rows(l, planes, y1, reach, s->eawRecv[1]);
+    return copy_segments(l);
 }
 // the first / last `rows` rows of the strip's part of a row-major image (and of a second one) to the strips above / below, theirs
 // into the rows just outside the strip: sent from and received into place
 int exchange_image_rows(rs_strips* s, float* a, int ca, float* b, int cb, int rows) {
     const rs_comm* c = s->comm;
-    const int W = s->width, y0 = s->y0, y1 = s->y1;
-    const bool up = c->rank > 0, down = c->rank + 1 < c->world;
-    if (!up && !down) return 0;
+    if (c->world == 1) return 0;
     Xfer ops[8]; size_t n = 0;
     float* img[2] = { a, b }; const int comp[2] = { ca, cb };
     for (int k = 0; k < 2; k++) {
         if (!img[k]) continue;
-        const size_t row = (size_t)W * comp[k], bytes = row * rows * sizeof(float);
-        if (up) { ops[n++] = { true, img[k] + (size_t)y0 * row, bytes, c->rank - 1 }; ops[n++] = { false, img[k] + (size_t)(y0 - rows) * row, bytes, c->rank - 1 }; }
-        if (down) { ops[n++] = { true, img[k] + (size_t)(y1 - rows) * row, bytes, c->rank + 1 }; ops[n++] = { false, img[k] + (size_t)y1 * row, bytes, c->rank + 1 }; }
+        const size_t row = (size_t)s->width * comp[k];
+        float* top = img[k] + (size_t)s->y0 * row; float* bottom = img[k] + (size_t)s->y1 * row;
+        n += neighbour_xfers(c, ops + n, top, c->rank > 0 ? top - rows * row : nullptr, bottom - rows * row, bottom, row * rows * sizeof(float));
     }
     RS_TRY(post(s, ops, n));
     return join(s, false);
+}
+// the neighbours' border rows of a frame out of recvUp / recvDown into the rows just outside the strip, one launch; the current G-buffer set
+// then holds their gReach rows (gbufFresh)
+int unpack_halo(rs_strips* s, rs_restir* r, rs_gbuffer* g) {
+    SegList l(false);
+    if (s->comm->rank > 0) halo_segments(l, r, g, s->y0 - kHalo, s->y0 - s->gReach, s->gReach, s->recvUp);
+    if (s->comm->rank + 1 < s->comm->world) halo_segments(l, r, g, s->y1, s->y1, s->gReach, s->recvDown);
+    s->gbufFresh = true;
+    return copy_segments(l);
 }
 int svgf_exchange_hook(void* ctx, float* a, int ca, float* b, int cb, int rows) { return exchange_image_rows((rs_strips*)ctx, a, ca, b, cb, rows); }
 
@@ -363,10 +403,7 @@ int rs_strips_create(rs_comm* comm, int width, int height, const int* bounds, rs
     for (int r = 0; r < comm->world && ok; r++) ok = s->bounds[(size_t)r + 1] - s->bounds[(size_t)r] >= (comm->world > 1 ? kHalo : 1);
     if (!ok) { delete s; return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_create: the bounds must tile [0, height) in rank order with strips of at least 5 rows"); }
     s->y0 = s->bounds[(size_t)comm->rank]; s->y1 = s->bounds[(size_t)comm->rank + 1];
-    s->haloBytes = (size_t)width * kHalo * (48u + 20u);          // rs_restir_halo_bytes + rs_gbuffer_rows_bytes
-    int e = 0;
-    if (comm->rank > 0) { e = rs_dev_alloc(&s->sendUp, s->haloBytes); if (!e) e = rs_dev_alloc(&s->recvUp, s->haloBytes); }
-    if (!e && comm->rank + 1 < comm->world) { e = rs_dev_alloc(&s->sendDown, s->haloBytes); if (!e) e = rs_dev_alloc(&s->recvDown, s->haloBytes); }
+    int e = resize_halo(s, s->gReach);
     if (!e && comm->world > 1) {
         if (!e) e = rs_check_hip(hipEventCreateWithFlags(&s->packed, hipEventDisableTiming), "hipEventCreate");
         if (!e) e = rs_check_hip(hipEventCreateWithFlags(&s->arrived, hipEventDisableTiming), "hipEventCreate");
@@ -420,11 +457,8 @@ int rs_strips_set_gbuffer_halo(rs_strips* s, int rows) {
             if (s->bounds[(size_t)r + 1] - s->bounds[(size_t)r] < rows) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_set_gbuffer_halo: a strip is shorter than the rows asked for");
     if (rows == s->gReach) return 0;
     RS_TRY(rs_synchronize());
-    s->gReach = rows; s->gbufFresh = false;
-    s->haloBytes = (size_t)s->width * ((size_t)kHalo * 48u + (size_t)rows * 20u);
-    rs_dev_free(s->sendUp); rs_dev_free(s->recvUp); rs_dev_free(s->sendDown); rs_dev_free(s->recvDown);
-    if (c->rank > 0) { RS_TRY(rs_dev_alloc(&s->sendUp, s->haloBytes)); RS_TRY(rs_dev_alloc(&s->recvUp, s->haloBytes)); }
-    if (c->rank + 1 < c->world) { RS_TRY(rs_dev_alloc(&s->sendDown, s->haloBytes)); RS_TRY(rs_dev_alloc(&s->recvDown, s->haloBytes)); }
+    RS_TRY(resize_halo(s, rows));
+    s->gbufFresh = false;
     return 0;
 }
 
@@ -471,28 +505,22 @@ int rs_strips_frame(rs_strips* s, rs_restir* r, const rs_scene* scene, const rs_
     // of the published copy's id plane (which = 2) outside the strip stay whatever they were.
     RS_TRY(rs_gbuffer_join(g));
     {
-        SegList l;
+        SegList l(true);
         if (up) halo_segments(l, r, g, y0, y0, s->gReach, s->sendUp);
         if (down) halo_segments(l, r, g, y1 - kHalo, y1 - s->gReach, s->gReach, s->sendDown);
-        RS_TRY(copy_segments(l, true));
+        RS_TRY(copy_segments(l));
     }
     // the transfers: after the packing copies
-    Xfer ops[4]; size_t n = 0;
-    if (up) { ops[n++] = { true, s->sendUp, s->haloBytes, c->rank - 1 }; ops[n++] = { false, s->recvUp, s->haloBytes, c->rank - 1 }; }
-    if (down) { ops[n++] = { true, s->sendDown, s->haloBytes, c->rank + 1 }; ops[n++] = { false, s->recvDown, s->haloBytes, c->rank + 1 }; }
+    Xfer ops[4];
     const bool timeMain = s->commOnMain && c->t.stream_ordered && s->timing;
     if (timeMain) RS_HIP(hipEventRecord(s->waitFrom, rs_stream()));
-    RS_TRY(post(s, ops, n));
+    RS_TRY(post(s, ops, neighbour_xfers(c, ops, s->sendUp, s->recvUp, s->sendDown, s->recvDown, s->haloBytes)));
     if (timeMain) { RS_HIP(hipEventRecord(s->waitTo, rs_stream())); s->waitValid = true; }
     if (s->commOnMain && c->t.stream_ordered) {
         // The transfers are in the library stream's own order: nothing runs next to them there, so splitting phase B into interior rows
         // and two 5-row bands would only buy two more launches -- and the bands are 5 rows in 16-row tiles.  Unpack, then ONE launch over
         // the strip (a 1/8 strip of 1080p: three launches of 14.6 + 8.5 + 8.8 us -> one of 15; results do not depend on the partition).
-        SegList l;
-        if (up) { halo_segments(l, r, g, y0 - kHalo, y0 - s->gReach, s->gReach, s->recvUp); rs_gbuffer_note_write(g, g->cur(), y0 - s->gReach, s->gReach); }
-        if (down) { halo_segments(l, r, g, y1, y1, s->gReach, s->recvDown); rs_gbuffer_note_write(g, g->cur(), y1, s->gReach); }
-        s->gbufFresh = true;
-        RS_TRY(copy_segments(l, false));
+        RS_TRY(unpack_halo(s, r, g));
         RS_TRY(rs_restir_phase_b(r, scene, cam, g, devDirectIllum, iter, reuse, y0, y1));
         return rs_restir_end_frame(r);
     }
@@ -501,13 +529,7 @@ int rs_strips_frame(rs_strips* s, rs_restir* r, const rs_scene* scene, const rs_
     const int botStart = down ? (y1 - kHalo > topEnd ? y1 - kHalo : topEnd) : y1;
     if (botStart > topEnd) RS_TRY(rs_restir_phase_b(r, scene, cam, g, devDirectIllum, iter, reuse, topEnd, botStart));
     RS_TRY(join(s, true));
-    {
-        SegList l;
-        if (up) { halo_segments(l, r, g, y0 - kHalo, y0 - s->gReach, s->gReach, s->recvUp); rs_gbuffer_note_write(g, g->cur(), y0 - s->gReach, s->gReach); }
-        if (down) { halo_segments(l, r, g, y1, y1, s->gReach, s->recvDown); rs_gbuffer_note_write(g, g->cur(), y1, s->gReach); }
-        s->gbufFresh = true;
-        RS_TRY(copy_segments(l, false));
-    }
+    RS_TRY(unpack_halo(s, r, g));
     if (topEnd > y0) RS_TRY(rs_restir_phase_b(r, scene, cam, g, devDirectIllum, iter, reuse, y0, topEnd));
     if (y1 > botStart) RS_TRY(rs_restir_phase_b(r, scene, cam, g, devDirectIllum, iter, reuse, botStart, y1));
     return rs_restir_end_frame(r);
@@ -524,7 +546,6 @@ int rs_strips_eaw_filter(rs_strips* s, rs_eaw* f, rs_gbuffer* g, const rs_camera
     if (g->width != s->width || g->height != s->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_eaw_filter: G-buffer size differs from the strips' frame");
     const rs_comm* c = s->comm;
     const int W = s->width, y0 = s->y0, y1 = s->y1, kLevels = 5, reach = 2 << (kLevels - 1);
-    const bool up = c->rank > 0, down = c->rank + 1 < c->world;
     if (c->world > 1)
         for (int r = 0; r < c->world; r++)
             if (s->bounds[(size_t)r + 1] - s->bounds[(size_t)r] < reach) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_eaw_filter: strips must be at least 32 rows tall");
@@ -544,15 +565,7 @@ int rs_strips_eaw_filter(rs_strips* s, rs_eaw* f, rs_gbuffer* g, const rs_camera
     for (int level = 0; level < kLevels; level++) {
         float* in = level == 0 ? devColor : s->eawBuf[(level - 1) % 2];
         float* out = s->eawBuf[level % 2];
-        if (up || down) {
-            const int rows = 2 << level;
-            const size_t bytes = (size_t)rows * W * 3 * sizeof(float);
-            Xfer ops[4]; size_t n = 0;
-            if (up) { ops[n++] = { true, in + (size_t)y0 * W * 3, bytes, c->rank - 1 }; ops[n++] = { false, in + (size_t)(y0 - rows) * W * 3, bytes, c->rank - 1 }; }
-            if (down) { ops[n++] = { true, in + (size_t)(y1 - rows) * W * 3, bytes, c->rank + 1 }; ops[n++] = { false, in + (size_t)y1 * W * 3, bytes, c->rank + 1 }; }
-            RS_TRY(post(s, ops, n));
-            RS_TRY(join(s, false));
-        }
+        RS_TRY(exchange_image_rows(s, in, 3, nullptr, 0, 2 << level));
         RS_TRY(rs_eaw_level_rows(f, out, in, g, level, y0, y1));
         // (the image: read by level 0, its rows just outside the strip written by that level's exchange; the next frame's phase B writes it)
         if (level == 0 && onDenoiseStream.active) RS_TRY(rs_denoise_mark(devColor, image, false));
@@ -597,16 +610,9 @@ int rs_strips_exchange_svgf_history(rs_strips* s, rs_svgf* f) {
     if (f->width != s->width || f->height != s->height) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_exchange_svgf_history: size mismatch");
     const rs_comm* c = s->comm;
     if (c->world == 1) return 0;
-    const size_t row = (size_t)s->width * 3;
+    const size_t row = (size_t)s->width * 3 * sizeof(float);
     float* planes[2] = { f->devAccumColor[f->frameIdx], f->devAccumMoment[f->frameIdx] };
-    std::vector<Xfer> ops;
-    for (int k = 0; k < c->world; k++) {
-        if (k == c->rank) continue;
-        for (float* p : planes) {
-            ops.push_back({ true, p + (size_t)s->y0 * row, (size_t)(s->y1 - s->y0) * row * sizeof(float), k });
-            ops.push_back({ false, p + (size_t)s->bounds[(size_t)k] * row, (size_t)(s->bounds[(size_t)k + 1] - s->bounds[(size_t)k]) * row * sizeof(float), k });
-        }
-    }
+    const std::vector<Xfer> ops = all_rank_xfers(s, 2, -1, [&](int k, int part) { return strip_rows(s, planes[part], row, k); });
     RS_TRY(post(s, ops.data(), ops.size()));
     return join(s, false);
 }
@@ -625,55 +631,32 @@ int rs_strips_exchange_history(rs_strips* s, rs_restir* r, rs_gbuffer* g) {
     const rs_comm* c = s->comm;
     if (c->world == 1) return 0;
     RS_TRY(rs_denoise_join());                                   // a filter on the denoise stream writes rows of these planes just outside the strip
-    // a message: reservoir rows (40 B/px), G-buffer rows (20), with tracking the reservoirs' light ids (4) last -- the untracked layout is a prefix
+    // a message (history_segments): reservoir rows, G-buffer rows, with tracking the reservoirs' light ids last -- the untracked layout is a prefix
     const bool track = s->track;
     auto rowsOf = [&](int rank) { return s->bounds[(size_t)rank + 1] - s->bounds[(size_t)rank]; };
-    auto resvBytes = [&](int rank) { return rs_restir_rows_bytes(r, 1, rowsOf(rank)); };
-    auto bytesOf = [&](int rank) { return resvBytes(rank) + rs_gbuffer_rows_bytes(g, rowsOf(rank)) + (track ? rs_restir_light_rows_bytes(r, rowsOf(rank)) : 0); };
+    const size_t perPixel = rs_rows::reservoir_planes(r, 1).bytes_per_pixel() + rs_rows::gbuffer_planes(g, 0).bytes_per_pixel() + (track ? rs_rows::light_id_plane(r, 1).bytes_per_pixel() : 0);
+    auto bytesOf = [&](int rank) { return (size_t)s->width * rowsOf(rank) * perPixel; };
+    std::vector<size_t> at((size_t)c->world, 0);                 // where rank k's message lands in histRecv: rank order
     size_t others = 0;
-    for (int k = 0; k < c->world; k++) if (k != c->rank) others += bytesOf(k);
+    for (int k = 0; k < c->world; k++) if (k != c->rank) { at[(size_t)k] = others; others += bytesOf(k); }
     const size_t mine = bytesOf(c->rank);
     if (s->histSendBytes < mine) { rs_dev_free(s->histSend); s->histSend = nullptr; RS_TRY(rs_dev_alloc(&s->histSend, mine)); s->histSendBytes = mine; }
     if (s->histRecvBytes < others) { rs_dev_free(s->histRecv); s->histRecv = nullptr; RS_TRY(rs_dev_alloc(&s->histRecv, others)); s->histRecvBytes = others; }
-    if (track) {
-        // eight planes a message: as hipMemcpyAsync calls they would be eight enqueues for the own rows and eight per peer, each dearer to the
-        // host than the copy is to the device (see k_copy_segments) -- one launch packs, one launch per peer unpacks
-        RS_TRY(rs_gbuffer_join(g));
-        SegList l;
-        history_segments(l, r, g, s->y0, s->y1 - s->y0, s->histSend);
-        RS_TRY(copy_segments(l, true));
-    }
-    else {
-        RS_TRY(rs_restir_rows_pack(r, 1, s->y0, s->y1 - s->y0, s->histSend));
-        RS_TRY(rs_gbuffer_rows_pack(g, 1, s->y0, s->y1 - s->y0, s->histSend + resvBytes(c->rank)));
-    }
-    std::vector<Xfer> ops;
-    size_t off = 0;
-    for (int k = 0; k < c->world; k++) {
-        if (k == c->rank) continue;
-        ops.push_back({ true, s->histSend, mine, k });
-        ops.push_back({ false, s->histRecv + off, bytesOf(k), k });
-        off += bytesOf(k);
-    }
+    // The copies.  Tracked, eight planes a message: as hipMemcpyAsync calls eight enqueues for the own rows and eight per peer, each dearer to the host than
+    // the copy is to the device (see k_copy_segments) -- one launch packs, one per peer unpacks.  Untracked: still one hipMemcpyAsync per plane (seven).
+    const auto copy = [&](int y, int rows, char* packed, bool pack) {
+        SegList l(pack);
+        history_segments(l, r, g, track, y, rows, packed);
+        return track ? copy_segments(l) : rs_copy::memcpy_segments(l);
+    };
+    RS_TRY(rs_gbuffer_join(g));
+    RS_TRY(copy(s->y0, s->y1 - s->y0, s->histSend, true));
+    const std::vector<Xfer> ops = all_rank_xfers(s, 1, -1, [&](int k, int) { return k == c->rank ? Span{ s->histSend, mine } : Span{ s->histRecv + at[(size_t)k], bytesOf(k) }; });
     RS_TRY(post(s, ops.data(), ops.size()));
     RS_TRY(join(s, false));
-    off = 0;
-    for (int k = 0; k < c->world; k++) {
-        if (k == c->rank) continue;
-        const int a = s->bounds[(size_t)k], rows = rowsOf(k);
-        if (track) {
-            SegList l;
-            history_segments(l, r, g, a, rows, s->histRecv + off);
-            rs_gbuffer_note_write(g, g->prev(), a, rows);
-            RS_TRY(copy_segments(l, false));
-        }
-        else {
-            RS_TRY(rs_restir_rows_unpack(r, 1, a, rows, s->histRecv + off));
-            RS_TRY(rs_gbuffer_rows_unpack(g, 1, a, rows, s->histRecv + off + resvBytes(k)));
-        }
-        off += bytesOf(k);
-    }
-    return track ? rs_after_launch("rs_strips_exchange_history") : 0;
+    for (int k = 0; k < c->world; k++)
+        if (k != c->rank) RS_TRY(copy(s->bounds[(size_t)k], rowsOf(k), s->histRecv + at[(size_t)k], false));
+    return rs_after_launch("rs_strips_exchange_history");
 }
 
 // Image assembly: rows [y0, y1) of every rank's devImage (bytesPerPixel bytes per pixel, row-major, full-frame sized: the radiance
@@ -686,12 +669,7 @@ int rs_strips_gather(rs_strips* s, void* devImage, size_t bytesPerPixel, int roo
     const size_t row = (size_t)s->width * bytesPerPixel;
     char* base = (char*)devImage;
     RS_TRY(rs_denoise_order(base + (size_t)s->y0 * row));        // rows the denoise stream wrote: the library stream after it
-    std::vector<Xfer> ops;
-    for (int k = 0; k < c->world; k++) {
-        if (k == c->rank) continue;
-        if (root < 0 || root == k) ops.push_back({ true, base + (size_t)s->y0 * row, (size_t)(s->y1 - s->y0) * row, k });
-        if (root < 0 || root == c->rank) ops.push_back({ false, base + (size_t)s->bounds[(size_t)k] * row, (size_t)(s->bounds[(size_t)k + 1] - s->bounds[(size_t)k]) * row, k });
-    }
+    const std::vector<Xfer> ops = gather_xfers(s, devImage, row, root);
     RS_TRY(post(s, ops.data(), ops.size()));
     return join(s, false);
 }
@@ -709,12 +687,7 @@ int rs_strips_gather_begin(rs_strips* s, void* devImage, size_t bytesPerPixel, i
     if (s->gatherPending[slot]) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_strips_gather_begin: the slot's previous gather has not been ended");
     const size_t row = (size_t)s->width * bytesPerPixel;
     char* base = (char*)devImage;
-    std::vector<Xfer> ops;
-    for (int k = 0; k < c->world; k++) {
-        if (k == c->rank) continue;
-        if (root < 0 || root == k) ops.push_back({ true, base + (size_t)s->y0 * row, (size_t)(s->y1 - s->y0) * row, k });
-        if (root < 0 || root == c->rank) ops.push_back({ false, base + (size_t)s->bounds[(size_t)k] * row, (size_t)(s->bounds[(size_t)k + 1] - s->bounds[(size_t)k]) * row, k });
-    }
+    const std::vector<Xfer> ops = gather_xfers(s, devImage, row, root);
     // rows that the denoise stream wrote (the tone map of a filtered image, rs_set_denoise_stream): the gather is ordered on that stream
     const bool there = rs_denoise_owns(base + (size_t)s->y0 * row) && rs_denoise_stream() != nullptr;
     s->gatherOnDenoise[slot] = there;
