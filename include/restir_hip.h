@@ -582,6 +582,16 @@ int  rs_debug_sqrt_of_unit_floats_mismatches(unsigned long long* mismatches);
  * both.  out3[0] = results that differ (must be 0), out3[1] = operands
  * (pairs) compared, out3[2] reserved.  tools/verify_exact_division.py walks op 2 over all 2^23 denominators: every pair of significands. */
 int  rs_debug_exact_ops_mismatches(int op, unsigned firstSig, unsigned countSig, int expX, int expD, unsigned long long* out3);
+/* Test hook: the default sampler's generator keeps its state minus one and steps that (restir_amd/csrc/rs_math.h Rng), and the RIS
+ * loop compares two of a candidate's draws before their division by 2^31, against a scaled light count and a scaled alias threshold.
+ * For EVERY state x in [1, 2^31 - 2] this compares, with the step x' = 48271 x mod (2^31 - 1) and the draw float(x' - 1) / 2^31
+ * written out as they were: the next state and the bits of the draw (also of the form that steps x itself, which k_path takes: Rng and
+ * RngOnX), the sampler entry the draw picks of 1, 3, 1 024, 1 500, 10 240 and
+ * 2^24 + 1 lights, and `draw < prob` for prob = 0, the smallest subnormal, 2^-31, 0.5, the float below 1, 1, 2 and a NaN.
+ * out2[0] = results that differ (must be 0), out2[1] = results compared (19 per state). */
+int  rs_debug_rng_step_mismatches(unsigned long long* out2);
+/* The same comparison of the same shared code on the host, for the `count` states from `first` on (all in [1, 2^31 - 2]): needs no device. */
+int  rs_debug_rng_step_host_mismatches(unsigned first, unsigned count, unsigned long long* out2);
 
 /* ---- framebuffer tiling across the GPUs of one node: the row-strip frame of one rank ------------------------------------------
  * One process per GPU, the scene replicated, the framebuffer of runCuda (src/main.cpp:146-185) cut into `world` row strips.  A rank

@@ -1,5 +1,6 @@
 // exact_checks.hip -- test hooks for rs_exact.h: the short forms of reciprocal, quotient and square root against the compiler's
-// correctly rounded operators (-fhip-fp32-correctly-rounded-divide-sqrt), on every operand the guards of rs_exact.h admit.
+// correctly rounded operators (-fhip-fp32-correctly-rounded-divide-sqrt), on every operand the guards of rs_exact.h admit; and for
+// the generator's step (rs_math.h Rng) against the form it replaced, on every state.
 #include "rs_internal.h"
 #include "rs_exact.h"
 
@@ -53,9 +54,86 @@ __global__ void __launch_bounds__(256) k_check_division(unsigned firstSig, int e
     tally(out, bad, n, 0);
 }
 
+// ---- the generator's step on y = x - 1 (rs_math.h Rng) against the fold on x it replaced, and the two comparisons of the RIS loop that
+// take a draw before its division (rs_surface.h sample_light_with, restir.hip ris_pixel) against the comparisons of the divided draw.
+// The step as it was, written out: x' = 48271 x mod (2^31 - 1) and the draw float(x' - 1) / 2^31.
+RS_HD uint32_t reference_step(uint32_t x) {
+    const uint64_t p = (uint64_t)x * 48271u;
+    uint32_t s = (uint32_t)(p & 0x7fffffffu) + (uint32_t)(p >> 31);
+    if (s >= 2147483647u) s -= 2147483647u;
+    return s;
+}
+RS_HD float reference_draw(uint32_t next) { return (float)(next - 1u) / 2147483648.f; }
+RS_HD uint32_t float_bits(float f) { union { float f; uint32_t u; } v; v.f = f; return v.u; }
+RS_HD float bits_float(uint32_t u) { union { float f; uint32_t u; } v; v.u = u; return v.f; }
+
+constexpr unsigned kRngCheckPerState = 3 + 2 + 6 + 8;
+
+// the results that differ for the state x in [1, 2^31 - 2]: of kRngCheckPerState compared
+RS_HD unsigned rng_forms_differ(uint32_t x) {
+    const int lights[6] = { 1, 3, 1024, 1500, 10240, (1 << 24) + 1 };
+    // 0, the smallest subnormal, 2^-31, 0.5, the float below 1, 1, 2, a NaN
+    const uint32_t probBits[8] = { 0u, 1u, 0x30000000u, 0x3f000000u, 0x3f7fffffu, 0x3f800000u, 0x40000000u, 0x7fc00000u };
+    const uint32_t next = reference_step(x);
+    const float draw = reference_draw(next);
+    Rng a = Rng::from_state(x), b = a;
+    const float u = a.uniform(), raw = b.raw();
+    unsigned bad = 0;
+    bad += a.state() != next;
+    bad += float_bits(u) != float_bits(draw);
+    bad += b.state() != next;
+    RngOnX c = RngOnX::from_state(x);                    // the form on x (k_path, procedural_texture)
+    const float ux = c.uniform();
+    bad += c.state() != next;
+    bad += float_bits(ux) != float_bits(draw);
+    for (int i = 0; i < 6; i++) {
+        const int n = lights[i];
+        bad += sampler_entry((float)n * (1.f / kRngRawScale), raw, n) != imin(f2i((float)n * draw), n - 1);
+    }
+    for (int i = 0; i < 8; i++) {
+        const float prob = bits_float(probBits[i]);
+        bad += (raw < prob * kRngRawScale) != (draw < prob);
+    }
+    return bad;
+}
+
+// every state of the period; out[0] results that differ, out[1] results compared
+__global__ void __launch_bounds__(256) k_check_rng_step(unsigned long long* out) {
+    unsigned long long bad = 0, n = 0;
+    for (unsigned long long k = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x + 1ull; k <= 0x7ffffffeull; k += (unsigned long long)gridDim.x * blockDim.x) {
+        bad += rng_forms_differ((uint32_t)k);
+        n += kRngCheckPerState;
+    }
+    tally(out, bad, n, 0);
+}
+
 }  // namespace
 
 extern "C" {
+
+int rs_debug_rng_step_mismatches(unsigned long long* out2) {
+    rs_ctx_scope scope(nullptr);
+    if (!out2) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_rng_step_mismatches: null");
+    unsigned long long* d = nullptr;
+    RS_TRY(rs_dev_alloc(&d, 3));
+    RS_HIP(hipMemsetAsync(d, 0, 24, rs_stream()));
+    hipLaunchKernelGGL(k_check_rng_step, dim3(4096), dim3(256), 0, rs_stream(), d);
+    int err = rs_after_launch("rs_debug_rng_step_mismatches");
+    if (!err) err = rs_check_hip(hipStreamSynchronize(rs_stream()), "rs_debug_rng_step_mismatches: synchronize");
+    if (!err) err = rs_check_hip(hipMemcpy(out2, d, 16, hipMemcpyDeviceToHost), "rs_debug_rng_step_mismatches: copy");
+    rs_dev_free(d);
+    return err;
+}
+
+int rs_debug_rng_step_host_mismatches(unsigned first, unsigned count, unsigned long long* out2) {
+    if (!out2 || first < 1u || count == 0u || first > 0x7ffffffeu || count - 1u > 0x7ffffffeu - first)
+        return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_rng_step_host_mismatches: null, no state, or states outside [1, 2^31 - 2]");
+    unsigned long long bad = 0;
+    for (unsigned k = 0; k < count; k++) bad += rng_forms_differ(first + k);
+    out2[0] = bad;
+    out2[1] = (unsigned long long)count * kRngCheckPerState;
+    return 0;
+}
 
 int rs_debug_exact_ops_mismatches(int op, unsigned firstSig, unsigned countSig, int expX, int expD, unsigned long long* out3) {
     rs_ctx_scope scope(nullptr);

@@ -307,7 +307,8 @@ __global__ void __launch_bounds__(kPathLanes, RS_PATH_BLOCKS) k_path(DevScene s,
     const int lane = pixel_of_lane(tilesX, 0, x, y);
     const bool inside = x < cam.width && y < cam.height;
     const int index = y * cam.width + x;
-    SamplerT<SOBOL> rng = SamplerT<SOBOL>::seeded(s.sampleSeq, looper, index, 0);     // pathtrace.cu:170,339, restir.cu:256
+    using Sampler = typename PathSamplerOf<SOBOL>::type;                // the default engine on x: no register for an addend here (rs_math.h RngOnX)
+    Sampler rng = Sampler::seeded(s.sampleSeq, looper, index, 0);     // pathtrace.cu:170,339, restir.cu:256
     const f4 r = rng.uniform4();
     const Ray ray = camera_sample(cam, x, y, r.x, r.y);
     const Hit h = trace_closest_packet(s, ray, inside);                // all 64 lanes take part in the wave's walk
@@ -350,7 +351,7 @@ __global__ void __launch_bounds__(kPathLanes, RS_PATH_BLOCKS) k_path(DevScene s,
         }
     }
     st.surf.set_mat(material);
-    path_loop<MODE, TEX, SamplerT<SOBOL>>(s, hh, ray, rng, maxDepth, alive, st, rec);                 // every lane of the wave takes part
+    path_loop<MODE, TEX, Sampler>(s, hh, ray, rng, maxDepth, alive, st, rec);                 // every lane of the wave takes part
     if (inside) {
         f3 indirect = st.indirect.get();
         if constexpr (MODE == kModePT) {

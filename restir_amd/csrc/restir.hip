@@ -195,10 +195,10 @@ constexpr int kRisThreads = RS_RIS_THREADS;
 // wave is Lambertian -- the BSDF is the constant 1 / Pi, without the per-lane dispatch, and wo / roughness are not read.
 struct RisMaterial { int type; float metallic, roughness; };
 template <bool ENV, bool LAMBERT, typename Ops, typename AliasPtr, typename LightPtr>
-__device__ __forceinline__ float ris_candidate(const DevScene& s, AliasPtr alias, LightPtr lights, f3 pos, f3 norm, f3 wo, const RisMaterial& m, f4 r,
-                                               Ops& ops, LightSample& c) {
+__device__ __forceinline__ float ris_candidate(const DevScene& s, AliasPtr alias, LightPtr lights, float lightsOverScale, f3 pos, f3 norm, f3 wo,
+                                               const RisMaterial& m, f4 r, Ops& ops, LightSample& c) {
     const f3 baseColor = splat(1.f);                       // material.baseColor = 1 (restir.cu:141)
-    c = sample_light_with<ENV, Ops, AliasPtr, LightPtr>(s, alias, lights, s.numLights, pos, r, ops);
+    c = sample_light_with<ENV, Ops, AliasPtr, LightPtr>(s, alias, lights, s.numLights, lightsOverScale, pos, r, ops);
     const f3 bsdf = LAMBERT ? eval_bsdf_with(0, baseColor, 0.f, 0.f, norm, wo, c.wi, ops)
                             : eval_bsdf_with(m.type, baseColor, m.metallic, m.roughness, norm, wo, c.wi, ops);
     const f3 g = c.Li * bsdf * sat_dot(norm, c.wi);
@@ -208,7 +208,14 @@ __device__ __forceinline__ float ris_candidate(const DevScene& s, AliasPtr alias
 }
 
 // TRACK (rs_restir_set_light_tracking): the winner's light-sampler index goes to candId as well (-1: no winner)
-template <bool ENV, bool SOBOL, bool TRACK, typename AliasPtr, typename LightPtr>
+// Two of a candidate's five draws are only compared -- the one that picks the sampler entry and the one that is held against the entry's
+// prob -- and a power-of-two scale commutes with both comparisons (sample_light_with): they are taken before the generator's multiply by
+// 2^-31 (Rng::raw).  The first meets numLights * 2^-31, a constant of the launch; the second needs prob * 2^31, which a kernel that
+// copies the alias records into LDS writes there for nothing (SCALED_ALIAS: `alias` holds prob * kRisRawScale<SOBOL>) and which
+// k_ris, reading the scene's table, would pay for per candidate what it saves: it scales its second draw as before.  The Sobol sampler's
+// draws come as they are (scale 1).
+template <bool SOBOL> constexpr float kRisRawScale = SOBOL ? 1.f : kRngRawScale;
+template <bool ENV, bool SOBOL, bool TRACK, bool SCALED_ALIAS, typename AliasPtr, typename LightPtr>
 __device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& sp, AliasPtr alias, LightPtr lights, int index, int looper, int* candId) {
     RS_SETPRIO(RS_PRIO_RIS);
     const float4 pm = sp.posMat[index];
@@ -237,23 +244,28 @@ __device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& s
     // registers, and held to 64 they measured slower than before (k_ris_alias_lds 389 against 375 us, the config-5 frame 4 - 8 % slower:
     // profiles/ris_single_guard_ab.log, EXPERIMENTS.md).  They still take the Lambertian-only loop below.
     constexpr bool kSpeculateHere = !std::is_same<LightPtr, const LightRec*>::value;
+    const float lightsOverScale = (float)s.numLights * (1.f / kRisRawScale<SOBOL>);
+    const uint32_t mul = kSpeculateHere ? rng_multiplier_in_vector_register() : kRngMultiplier;      // k_ris_lds is at its 64 registers
+    auto raw = [&]() { if constexpr (SOBOL) return rng.uniform(); else return rng.raw(mul); };
+    auto uniform = [&]() { if constexpr (SOBOL) return rng.uniform(); else return rng.uniform(mul); };
     auto loop = [&](auto LAMBERT) {
         __builtin_assume(s.numLights > 0);                 // (an empty table: below)
         for (int i = 0; i < kReservoirSize; i++) {
-            const f4 r = rng.uniform4();
+            f4 r;                                              // sample4D, in its order
+            r.x = raw(); r.y = SCALED_ALIAS ? raw() : uniform(); r.z = uniform(); r.w = uniform();
             LightSample c;
             float weight;
             if constexpr (kExactSpeculate && kSpeculateHere) {
                 ExactSpeculative ops;
-                weight = ris_candidate<ENV, LAMBERT(), ExactSpeculative, AliasPtr, LightPtr>(s, alias, lights, pos, norm, wo, m, r, ops, c);
+                weight = ris_candidate<ENV, LAMBERT(), ExactSpeculative, AliasPtr, LightPtr>(s, alias, lights, lightsOverScale, pos, norm, wo, m, r, ops, c);
                 if (__builtin_expect(!ops.in_range_or_unused(), 0)) {
                     ExactPlain plain;
-                    weight = ris_candidate<ENV, LAMBERT(), ExactPlain, AliasPtr, LightPtr>(s, alias, lights, pos, norm, wo, m, r, plain, c);
+                    weight = ris_candidate<ENV, LAMBERT(), ExactPlain, AliasPtr, LightPtr>(s, alias, lights, lightsOverScale, pos, norm, wo, m, r, plain, c);
                 }
             }
             else {
                 ExactGuarded ops;
-                weight = ris_candidate<ENV, LAMBERT(), ExactGuarded, AliasPtr, LightPtr>(s, alias, lights, pos, norm, wo, m, r, ops, c);
+                weight = ris_candidate<ENV, LAMBERT(), ExactGuarded, AliasPtr, LightPtr>(s, alias, lights, lightsOverScale, pos, norm, wo, m, r, ops, c);
             }
 #ifdef RS_WALK_STATS        // measurement builds (tools/ris_stats.py): how many candidates end without a valid pdf / with a zero weight
             {
@@ -266,7 +278,7 @@ __device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& s
                 }
             }
 #endif
-            float u = rng.uniform();
+            float u = uniform();
             wsum += weight;                                    // Reservoir::update (restir.h:38-44)
             if (u * wsum < weight) {
                 if (ENV) { selLi = c.Li; selWi = c.wi; selDist = c.dist; if (TRACK) selId = c.id; }
@@ -290,7 +302,7 @@ __device__ __forceinline__ void ris_rows(const DevScene& s, const SurfPlanes& sp
     const int n0 = y0 * width, n1 = y1 * width;
     const int index = n0 + blockIdx.x * blockDim.x + threadIdx.x;
     if (index >= n1) return;
-    ris_pixel<ENV, SOBOL, TRACK, const AliasRec*, const LightRec*>(s, sp, s.alias, s.lights, index, looper, candId);
+    ris_pixel<ENV, SOBOL, TRACK, false, const AliasRec*, const LightRec*>(s, sp, s.alias, s.lights, index, looper, candId);
 }
 
 template <bool ENV, bool SOBOL, bool TRACK>
@@ -320,7 +332,8 @@ __global__ void __launch_bounds__(kRisThreads) __attribute__((amdgpu_waves_per_e
             // this form for a table of at least one light)
             const int i0 = base, i1 = base + kRisThreads, i2 = base + 2 * kRisThreads, i3 = base + 3 * kRisThreads;
             const float4 q0 = src[i0], q1 = src[imin(i1, n4 - 1)], q2 = src[imin(i2, n4 - 1)], q3 = src[imin(i3, n4 - 1)];
-            const AliasRec al = s.alias[imin(base, s.numLights - 1)];
+            AliasRec al = s.alias[imin(base, s.numLights - 1)];
+            al.prob *= kRisRawScale<SOBOL>;             // ris_pixel<SCALED_ALIAS>: exact, a power of two times a finite prob
             sQuarters[(i0 & 3) * kRisLdsLights + (i0 >> 2)] = q0;
             if (i1 < n4) sQuarters[(i1 & 3) * kRisLdsLights + (i1 >> 2)] = q1;
             if (i2 < n4) sQuarters[(i2 & 3) * kRisLdsLights + (i2 >> 2)] = q2;
@@ -328,13 +341,13 @@ __global__ void __launch_bounds__(kRisThreads) __attribute__((amdgpu_waves_per_e
             if (base < kRisThreads && base < s.numLights) sAlias[base] = al;      // (the alias records go with the first batch)
         }
         if (kRisThreads < kRisLdsLights)               // (-DRS_RIS_THREADS builds: a block smaller than the table)
-            for (int i = threadIdx.x + kRisThreads; i < s.numLights; i += kRisThreads) sAlias[i] = s.alias[i];
+            for (int i = threadIdx.x + kRisThreads; i < s.numLights; i += kRisThreads) { AliasRec al = s.alias[i]; al.prob *= kRisRawScale<SOBOL>; sAlias[i] = al; }
     }
     __syncthreads();
     const int n0 = y0 * width, n1 = y1 * width;
     const int index = n0 + blockIdx.x * kRisThreads + threadIdx.x;
     if (index >= n1) return;
-    ris_pixel<false, SOBOL, TRACK, const AliasRec*, LightQuarters<kRisLdsLights>>(s, sp, sAlias, LightQuarters<kRisLdsLights>{ sQuarters }, index, looper, candId);
+    ris_pixel<false, SOBOL, TRACK, true, const AliasRec*, LightQuarters<kRisLdsLights>>(s, sp, sAlias, LightQuarters<kRisLdsLights>{ sQuarters }, index, looper, candId);
 }
 
 // More lights than the LDS copy of the whole table holds (config 5: 10 240): the alias records alone (8 B per light) still fit -- one
@@ -343,12 +356,12 @@ __global__ void __launch_bounds__(kRisThreads) __attribute__((amdgpu_waves_per_e
 template <bool SOBOL, bool TRACK>
 __global__ void __launch_bounds__(kRisThreads) k_ris_alias_lds(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
     extern __shared__ AliasRec sAliasDyn[];
-    for (int i = threadIdx.x; i < s.numLights; i += kRisThreads) sAliasDyn[i] = s.alias[i];
+    for (int i = threadIdx.x; i < s.numLights; i += kRisThreads) { AliasRec al = s.alias[i]; al.prob *= kRisRawScale<SOBOL>; sAliasDyn[i] = al; }     // ris_pixel<SCALED_ALIAS>
     __syncthreads();
     const int n0 = y0 * width, n1 = y1 * width;
     const int index = n0 + blockIdx.x * kRisThreads + threadIdx.x;
     if (index >= n1) return;
-    ris_pixel<false, SOBOL, TRACK, const AliasRec*, const LightRec*>(s, sp, sAliasDyn, s.lights, index, looper, candId);
+    ris_pixel<false, SOBOL, TRACK, true, const AliasRec*, const LightRec*>(s, sp, sAliasDyn, s.lights, index, looper, candId);
 }
 
 // ---- phase A.3: shadow ray, temporal merge, publish -------------------------------------------------

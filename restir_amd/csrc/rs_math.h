@@ -49,8 +49,7 @@ RS_HD f3    vmax(f3 a, f3 b) { return mk3(gmax(a.x, b.x), gmax(a.y, b.y), gmax(a
 RS_HD float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 RS_HD f3 cross(f3 a, f3 b) {
     return mk3(a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y);
-}
-}  // namespace rs
+}}  // namespace rs
 #define RS_MATH_H_BODY
 #include "rs_exact.h"          // device: sqrt_exact / rcp_exact -- the IEEE results, fewer instructions for operands in [2^-60, 2^60)
 namespace rs {
@@ -107,19 +106,60 @@ RS_HD uint32_t utilhash(uint32_t a) {
 }
 
 // ---- RNG: thrust::minstd_rand + uniform_real_distribution<float>(0,1) as used by sampler.h:38-61.
-// x <- 48271*x mod (2^31-1); the 64-bit product is folded with 2^31 == 1 (mod m), which yields
-// the same residue as thrust's Schrage form.
+// x <- 48271*x mod m, m = 2^31-1, x in [1, m-1]; the 64-bit product is folded with 2^31 == 1 (mod m), which yields the same residue as
+// thrust's Schrage form.  A draw is float(x - 1) / 2^31 and nothing else reads the state, so the register holds y = x - 1 in [0, m-2]:
+//     q  = 96542 * y + 96540              = 2 * (p - 1) with p = 48271 * x; below 2^48
+//     s  = (lo32(q) >> 1) + hi32(q)       = ((p - 1) mod 2^31) + ((p - 1) >> 31), so s == x' - 1 (mod m) and s < 2^31 + 2^17
+//     y' = min(s, s - m)                  the difference wraps when s < m; s == m - 1 would be x' == 0, which the generator never reaches
+// The addend rides in the multiply-add and one shift takes the place of the mask and the funnel shift of the fold on x: three vector
+// instructions fewer per draw.  state() / from_state() speak the canonical x: what seeds the generator and what a pass hands to the next
+// (rs_debug_rng_step_mismatches holds the step to the fold on x over the whole period).
+constexpr float kRngRawScale = 2147483648.f;            // raw() = uniform() * 2^31, exactly
+constexpr uint32_t kRngMultiplier = 96542u;             // 2 * 48271
+// The multiply-add takes one scalar operand.  Of its two constants the compiler gives it the multiplier and keeps the 64-bit addend in a
+// vector register PAIR for the length of a loop, which k_ris_lds at its 64 registers pays with scratch.  This is kRngMultiplier as a
+// value the compiler cannot see through: it stays in ONE vector register and the addend goes to a scalar pair.  For a loop that is short
+// of registers: taken once before the loop and handed to every draw (inside the loop the move would be issued by every iteration).
+RS_HD uint32_t rng_multiplier_in_vector_register() {
+    uint32_t a = kRngMultiplier;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_mov_b32 %0, 0x1791e" : "=v"(a));
+#endif
+    return a;
+}
 struct Rng {
-    uint32_t x;
-    RS_HD uint32_t next() {
-        uint64_t p = (uint64_t)x * 48271u;
-        uint32_t s = (uint32_t)(p & 0x7fffffffu) + (uint32_t)(p >> 31);
-        if (s >= 2147483647u) s -= 2147483647u;
-        x = s;
-        return s;
+    uint32_t y;
+    static RS_HD Rng from_state(uint32_t x) { Rng r; r.y = x - 1u; return r; }
+    RS_HD uint32_t state() const { return y + 1u; }
+    RS_HD uint32_t next(uint32_t a = kRngMultiplier) {  // the new y; a: kRngMultiplier or rng_multiplier_in_vector_register()
+        const uint64_t q = (uint64_t)y * a + 96540u;
+        const uint32_t s = ((uint32_t)q >> 1) + (uint32_t)(q >> 32);
+        const uint32_t t = s - 2147483647u;
+        y = s < t ? s : t;
+        return y;
     }
+    // The draw before its division: for a caller that only compares it, with a threshold it can scale instead (restir.hip ris_pixel).
+    RS_HD float raw(uint32_t a = kRngMultiplier) { return (float)next(a); }
     // float(x - min) / (1.f + float(max - min)) with min=1, max=2^31-2: the divisor is 2^31 exactly
-    RS_HD float uniform() { return (float)(next() - 1u) / 2147483648.f; }
+    RS_HD float uniform(uint32_t a = kRngMultiplier) { return raw(a) / kRngRawScale; }
+    RS_HD f2 uniform2() { f2 r; r.x = uniform(); r.y = uniform(); return r; }
+    RS_HD f4 uniform4() { f4 r; r.x = uniform(); r.y = uniform(); r.z = uniform(); r.w = uniform(); return r; }
+};
+// The same generator on x itself, for code that has no register to spare for the addend (k_path, which spills already, and
+// procedural_texture inside it): q = 96542 x = 2 p, s = (lo32(q) >> 1) + hi32(q) == x' (mod m), never m itself, below 2^31 + 2^17;
+// x' = min(s, s - m).  One vector instruction fewer per draw than the fold with mask and funnel shift, and no new live value.
+struct RngOnX {
+    uint32_t x;
+    static RS_HD RngOnX from_state(uint32_t x) { RngOnX r; r.x = x; return r; }
+    RS_HD uint32_t state() const { return x; }
+    RS_HD uint32_t next() {
+        const uint64_t q = (uint64_t)x * kRngMultiplier;
+        const uint32_t s = ((uint32_t)q >> 1) + (uint32_t)(q >> 32);
+        const uint32_t t = s - 2147483647u;
+        x = s < t ? s : t;
+        return x;
+    }
+    RS_HD float uniform() { return (float)(next() - 1u) / kRngRawScale; }
     RS_HD f2 uniform2() { f2 r; r.x = uniform(); r.y = uniform(); return r; }
     RS_HD f4 uniform4() { f4 r; r.x = uniform(); r.y = uniform(); r.z = uniform(); r.w = uniform(); return r; }
 };
@@ -128,9 +168,13 @@ struct Rng {
 RS_HD Rng seeded_rng(int iter, int index, int dim) {
     uint32_t h = utilhash(0x80000000u | ((uint32_t)dim << 22) | (uint32_t)iter) ^ utilhash((uint32_t)index);
     uint32_t v = h % 2147483647u;
-    Rng r; r.x = v == 0u ? 1u : v;
-    return r;
+    return Rng::from_state(v == 0u ? 1u : v);
 }
+
+// DevDiscreteSampler1D::sample's first step (sampler.h:203-207): the entry a draw r picks of `len`, imin(f2i((float)len * r), len - 1).
+// lenOverScale = (float)len / 2^k for a draw that arrives multiplied by 2^k (Rng::raw: k = 31): the product is the same real number,
+// never subnormal (the draw is 0 or at least 2^-31 before its scale), so it rounds to the same float and the entry is the same.
+RS_HD int sampler_entry(float lenOverScale, float r, int len) { return imin(f2i(lenOverScale * r), len - 1); }
 
 // ---- the Sobol branch of src/sampler.h:9-36 (SAMPLER_USE_SOBOL): Sampler{ptr, scramble, data} over the table
 // DevScene::sampleSequence, SobolSampleNum x SobolSampleDim uint32 (scene.cpp:500-506).
@@ -153,9 +197,9 @@ struct SobolSampler {
 // scramble -- the table position is then iter * SobolSampleDim + dim + (draws made so far), which the passes of ReSTIRDirect know.
 template <bool SOBOL> struct SamplerT;
 template <> struct SamplerT<false> : Rng {
-    static RS_HD SamplerT seeded(const uint32_t*, int iter, int index, int dim) { SamplerT s; s.x = seeded_rng(iter, index, dim).x; return s; }
-    static RS_HD SamplerT resume(const uint32_t*, uint32_t word, int, int) { SamplerT s; s.x = word; return s; }
-    RS_HD uint32_t word() const { return x; }
+    static RS_HD SamplerT seeded(const uint32_t*, int iter, int index, int dim) { SamplerT s; s.y = seeded_rng(iter, index, dim).y; return s; }
+    static RS_HD SamplerT resume(const uint32_t*, uint32_t word, int, int) { SamplerT s; s.y = from_state(word).y; return s; }
+    RS_HD uint32_t word() const { return state(); }
 };
 template <> struct SamplerT<true> : SobolSampler {
     static RS_HD SamplerT seeded(const uint32_t* table, int iter, int index, int dim) {           // sampler.h:30-32
@@ -166,5 +210,11 @@ template <> struct SamplerT<true> : SobolSampler {
     }
     RS_HD uint32_t word() const { return scramble; }
 };
+// k_path's sampler: the Sobol sampler, or the default engine stepped on x (RngOnX)
+struct EngineOnX : RngOnX {
+    static RS_HD EngineOnX seeded(const uint32_t*, int iter, int index, int dim) { EngineOnX s; s.x = seeded_rng(iter, index, dim).state(); return s; }
+};
+template <bool SOBOL> struct PathSamplerOf { typedef SamplerT<true> type; };
+template <> struct PathSamplerOf<false> { typedef EngineOnX type; };
 
 }  // namespace rs

@@ -52,7 +52,7 @@ __device__ inline f3 linear_sample(const TexRec t, float u, float v) {
 __device__ inline f3 procedural_texture(float u, float v) {
     const uint32_t seed = (uint32_t)(f2i(u * 1024.f) * 1024 + f2i(v * 1024.f));
     const uint32_t m = seed % 2147483647u;
-    Rng rng; rng.x = m == 0u ? 1u : m;                                    // linear_congruential_engine::seed
+    RngOnX rng = RngOnX::from_state(m == 0u ? 1u : m);                    // linear_congruential_engine::seed
     const float rx = rng.uniform();
     const float ry = rng.uniform();
     const float f = (cr_sin(u * 10.f * kPiTwo + rx * kPiTwo) + 1.f) * .5f;
@@ -178,11 +178,14 @@ __device__ __forceinline__ LightSample invalid_light_sample(f3 point) {
 // Ops: the divisions and the root (rs_exact.h).  With Ops::kWholeWave a sample that fails the facing test runs along and ends with
 // pdf = kInvalidPdf and nothing else defined (its Li / wi / dist are whatever the arithmetic gave: the caller multiplies them into a
 // weight that it replaces by 0); otherwise it leaves early with the zeroed sample.
+// r.x and r.y are only compared, so a caller may hand them over before the generator's division by 2^31 (Rng::raw) and scale the other
+// side once instead: r.x * 2^k with lightsOverScale = (float)numLights / 2^k (sampler_entry, rs_math.h), r.y * 2^j with alias[].prob * 2^j
+// -- scaling a finite prob up is exact, so `<` answers the same.  r.z and r.w are always the variates themselves.
 template <bool ENV, typename Ops, typename AliasPtr, typename LightPtr>
-__device__ __forceinline__ LightSample sample_light_with(const DevScene& s, AliasPtr alias, LightPtr lights, int numLights, f3 pos, f4 r, Ops& ops) {
+__device__ __forceinline__ LightSample sample_light_with(const DevScene& s, AliasPtr alias, LightPtr lights, int numLights, float lightsOverScale, f3 pos, f4 r, Ops& ops) {
     LightSample o = invalid_light_sample(splat(0.f));
     if (numLights == 0) { ops.set_unused(true); return o; }
-    int pass = imin(f2i((float)numLights * r.x), numLights - 1);      // DevDiscreteSampler1D::sample
+    int pass = sampler_entry(lightsOverScale, r.x, numLights);        // DevDiscreteSampler1D::sample
     AliasRec al = alias[pass];
     int id = r.y < al.prob ? pass : al.failId;
     o.id = id;
@@ -217,7 +220,7 @@ __device__ __forceinline__ LightSample sample_light_with(const DevScene& s, Alia
 template <bool ENV, typename AliasPtr, typename LightPtr>
 __device__ __forceinline__ LightSample sample_light_nv(const DevScene& s, AliasPtr alias, LightPtr lights, int numLights, f3 pos, f4 r) {
     ExactGuarded ops;
-    return sample_light_with<ENV, ExactGuarded, AliasPtr, LightPtr>(s, alias, lights, numLights, pos, r, ops);
+    return sample_light_with<ENV, ExactGuarded, AliasPtr, LightPtr>(s, alias, lights, numLights, (float)numLights, pos, r, ops);
 }
 // ... from the scene's own tables, with the environment map's sampler entry where the scene has one (TEX: it may have)
 template <bool TEX>
