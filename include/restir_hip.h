@@ -301,12 +301,34 @@ int  rs_scene_set_materials(rs_scene* scene, int count, const int* materialIds, 
  * whole scene, O(numPrims) on the device and on the host, however few triangles it names (DESIGN.md section 3 has the cost).  An
  * accepted edit invalidates retained G-buffer planes.  A repeated id takes its last record; count == 0 succeeds and changes nothing.
  * Refused with RS_ERR_INVALID_ARGUMENT, the scene unchanged: count < 0 or null arrays with count > 0; an id out of range; a vertex or
- * normal that is not finite; a triangle whose material is a Light (moving emitters is not supported yet: their area feeds the light
- * sampler's power, their records sit in the light table and the emissive tree is built over them); and, while the scene has its
- * shadow-ray tree, a vertex outside the root box the scene was created with (the trees' 16-bit grid lies over that box).  With
+ * normal that is not finite; a triangle whose material is a Light (this is the call that guarantees that the light sampler, the light
+ * records and the emissive tree are untouched; rs_scene_set_geometry moves emitters); and, while the scene has its shadow-ray tree, a vertex outside the root box the scene was created with (the trees' 16-bit grid lies over that box).  With
  * RS_ERR_UNSUPPORTED while the library stream is being captured into a graph.  A large deformation makes the refitted trees slower,
  * never wrong; the remedy is a new scene.  The G-buffer's motion plane stays camera-only. */
 int  rs_scene_set_triangles(rs_scene* scene, int count, const int* primIds, const float* vertices, const float* normals);
+/* rs_scene_set_triangles that also takes triangles whose material is a Light, alone or mixed with others in one call: arguments,
+ * staging, fences, refit and "a repeated id takes its last record" are the same, and a call that names no emitter does exactly what
+ * rs_scene_set_triangles does (no version of the ring is consumed, no byte of the emissive tree is written).  A call that names an
+ * emitter in addition
+ *   - rebuilds the light sampler as rs_scene_build_textured builds it: rs_build_light_table's powers (the new areas) over the same
+ *     light primitives in the same order, the environment map's entry last with its power kept, then rs_build_alias_table;
+ *   - fills the next slot of the ring of versions (rs_scene_set_emission) with light records of the new vertices, normal and pdfArea;
+ *   - refits the tree of the emissive triangles that answers the last bounce of a path, on a grid laid anew over the new emissive root
+ *     box by the function a fresh build uses, so that the grid equals that of rs_scene_create of the edited description.
+ * Afterwards rs_scene_host_desc returns the edited vertices and normals, boundingBoxes equal to rs_refit_boxes of them, and lightProb,
+ * lightFailId and sumLightPower as just described (lightPrimIds and lightUnitRadiance do not change: the set of emitters is the same),
+ * and the scene renders, in every kernel, bit for bit like rs_scene_create of that description.
+ * Both transitions are made at one point of the library stream: launches enqueued before the call read the old geometry and the old
+ * lights, launches after it the new of both.  The host waits only where rs_scene_set_triangles and rs_scene_set_emission wait (a full
+ * staging ring, a version ring that has run out).
+ * An emitter may flip, may become degenerate (a point or three collinear vertices: power 0) and may move anywhere inside the root box
+ * the scene was created with.  When all emitters collapse into a box without extent the emissive tree is switched off, as a fresh build
+ * leaves it off, until an edit brings an extent back.  (A scene CREATED with such emitters has no emissive tree and gets none.)
+ * Refused with RS_ERR_INVALID_ARGUMENT, the scene unchanged: everything rs_scene_set_triangles refuses except emitters, and an edit that
+ * leaves the light sampler without a finite, positive total power.  RS_ERR_UNSUPPORTED while the library stream is being captured.
+ * Temporal reservoirs keep the direction, distance and radiance they were drawn with for up to the M clamp's 20 frames, as in the
+ * reference; rs_restir_reset drops them.  Adding or removing emitters still takes a new scene. */
+int  rs_scene_set_geometry(rs_scene* scene, int count, const int* primIds, const float* vertices, const float* normals);
 /* The boxes of the reference tree refitted to `vertices` (9 floats per primitive), host only, no GPU call: order0 is bvhNodes[0] (3 ints
  * per node: primitive or -1, boundingBoxId, miss link), from which the children are derived; boundingBoxes receives 6 floats per node
  * by boundingBoxId.  Min and max are taken with -0 below +0, so the bits do not depend on the order of evaluation.  On the vertices a
@@ -334,6 +356,10 @@ int  rs_debug_scene_table(const rs_scene* scene, int which, void* host, size_t c
  * box the grid was laid over (a moved vertex must stay inside it); the shadow tree's record count and the byte stride of the ordered
  * trees (0: the scene has no such tree; without the shadow tree everything is 0).  Any pointer may be NULL.  Host only. */
 int  rs_debug_scene_grid(const rs_scene* scene, float base[3], float scale[3], double* margin, float lo[3], float hi[3], int* occCount, int* ordStride);
+/* The grid of the emissive tree (RS_TABLE_EMI_NODES), which rs_scene_set_geometry lays anew when emitters move: base, scale and margin
+ * as above; *state = 1 while the tree answers the last bounce, 0 while it is off; *count = its records without the end record (0, with
+ * base, scale and margin 0: the scene has no such tree).  Any pointer may be NULL.  Host only. */
+int  rs_debug_scene_emissive_grid(const rs_scene* scene, float base[3], float scale[3], double* margin, int* state, int* count);
 /* The function that turns one exact box into the three box dwords of a grid-box record (rs_grid.h grid_box), as it is.  Host only.
  * *fits = 0, out untouched: the box does not fit the grid's 16 bits. */
 int  rs_debug_grid_box(const float lo[3], const float hi[3], const float base[3], const float scale[3], double margin, unsigned out[3], int* fits);

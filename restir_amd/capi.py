@@ -128,7 +128,7 @@ RIS_GLOBAL, RIS_LDS, RIS_ALIAS_LDS = 0, 1, 2
 EXPORTS = [
     "rs_last_error", "rs_context_create", "rs_context_destroy", "rs_context_set_current", "rs_init", "rs_set_stream", "rs_set_sync", "rs_set_side_stream", "rs_set_ris_table_pixels", "rs_set_internal_stream_priority", "rs_internal_streams_info", "rs_choose_internal_streams_again", "rs_prepare_streams", "rs_set_stream_plan", "rs_set_denoise_stream", "rs_join_denoise_stream", "rs_set_tile_split", "rs_synchronize",
     "rs_build_bvh", "rs_build_light_table", "rs_build_alias_table", "rs_build_envmap_pdf", "rs_scene_build", "rs_scene_build_textured", "rs_scene_create",
-    "rs_scene_host_desc", "rs_scene_set_sample_sequence", "rs_scene_set_emission", "rs_scene_set_materials", "rs_scene_set_texture", "rs_scene_set_triangles", "rs_refit_boxes", "rs_debug_scene_table", "rs_debug_scene_grid", "rs_debug_grid_box", "rs_scene_destroy", "rs_camera_update", "rs_trace_closest", "rs_trace_closest_wave", "rs_scene_set_ordered_tree", "rs_ordered_bvh_host_check", "rs_trace_occlusion",
+    "rs_scene_host_desc", "rs_scene_set_sample_sequence", "rs_scene_set_emission", "rs_scene_set_materials", "rs_scene_set_texture", "rs_scene_set_triangles", "rs_scene_set_geometry", "rs_refit_boxes", "rs_debug_scene_table", "rs_debug_scene_grid", "rs_debug_scene_emissive_grid", "rs_debug_grid_box", "rs_scene_destroy", "rs_camera_update", "rs_trace_closest", "rs_trace_closest_wave", "rs_scene_set_ordered_tree", "rs_ordered_bvh_host_check", "rs_trace_occlusion",
     "rs_gbuffer_create", "rs_gbuffer_destroy", "rs_gbuffer_render", "rs_gbuffer_render_rows", "rs_gbuffer_update",
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
@@ -188,6 +188,8 @@ def lib():
     L.rs_scene_set_materials.argtypes = [vp, ci, vp, vp]
     L.rs_scene_set_texture.argtypes = [vp, ci, ci, ci, vp]
     L.rs_scene_set_triangles.argtypes = [vp, ci, vp, vp, vp]
+    L.rs_scene_set_geometry.argtypes = [vp, ci, vp, vp, vp]
+    L.rs_debug_scene_emissive_grid.argtypes = [vp, vp, vp, C.POINTER(C.c_double), C.POINTER(ci), C.POINTER(ci)]
     L.rs_refit_boxes.argtypes = [ci, vp, ci, vp, vp]
     L.rs_debug_scene_table.argtypes = [vp, ci, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rs_debug_scene_grid.argtypes = [vp, vp, vp, C.POINTER(C.c_double), vp, vp, C.POINTER(ci), C.POINTER(ci)]
@@ -679,15 +681,30 @@ class Scene:
             raise ValueError("set_texture: textures are (H, W, 3) float32")
         check(lib().rs_scene_set_texture(self.handle, int(tex_id), img.shape[1], img.shape[0], _p(img)))
 
-    def set_triangles(self, prim_ids, vertices, normals=None):
-        """rs_scene_set_triangles: the vertices ((n, 3, 3) float32) and, unless None, the vertex normals of the primitives `prim_ids`,
-        none of them emissive; every tree is refitted on the device, ordered on the library stream like set_emission (no synchronisation)."""
+    def _set_vertices(self, call, what, prim_ids, vertices, normals):
         ids = np.ascontiguousarray(prim_ids, np.int32).reshape(-1)
         v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 9)
         n = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 9)
         if v.shape[0] != ids.size or (n is not None and n.shape[0] != ids.size):
-            raise ValueError("set_triangles: three vertices (and three normals) per primitive id")
-        check(lib().rs_scene_set_triangles(self.handle, int(ids.size), _p(ids), _p(v), None if n is None else _p(n)))
+            raise ValueError(what + ": three vertices (and three normals) per primitive id")
+        check(call(self.handle, int(ids.size), _p(ids), _p(v), None if n is None else _p(n)))
+
+    def set_triangles(self, prim_ids, vertices, normals=None):
+        """rs_scene_set_triangles: the vertices ((n, 3, 3) float32) and, unless None, the vertex normals of the primitives `prim_ids`,
+        none of them emissive; every tree is refitted on the device, ordered on the library stream like set_emission (no synchronisation)."""
+        self._set_vertices(lib().rs_scene_set_triangles, "set_triangles", prim_ids, vertices, normals)
+
+    def set_geometry(self, prim_ids, vertices, normals=None):
+        """rs_scene_set_geometry: set_triangles that also takes emissive triangles; an edit that names one rebuilds the light sampler and the
+        light records and refits the emissive tree at the same point of the library stream."""
+        self._set_vertices(lib().rs_scene_set_geometry, "set_geometry", prim_ids, vertices, normals)
+
+    def emissive_grid(self):
+        """rs_debug_scene_emissive_grid (test hook): dict(base, scale, margin, state, count) of the emissive tree's grid."""
+        base, scale = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        margin, state, count = C.c_double(0), C.c_int(0), C.c_int(0)
+        check(lib().rs_debug_scene_emissive_grid(self.handle, _p(base), _p(scale), C.byref(margin), C.byref(state), C.byref(count)))
+        return dict(base=base, scale=scale, margin=margin.value, state=state.value, count=count.value)
 
     def debug_table(self, name):
         """rs_debug_scene_table (test hook): a copy of one device array of the scene, after everything enqueued so far, as a NumPy array of

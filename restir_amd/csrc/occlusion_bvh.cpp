@@ -168,19 +168,25 @@ int rs_build_occlusion_bvh(int numPrims, const float* primBoxes, std::vector<Bvh
 // plane, i.e. within 2^-21 * D in space; the grid planes are moved outward until they clear the exact
 // box by 2^-17 * extent >= 4 * 2^-21 * D * 2 on every axis (checked here in double), a fraction of one
 // grid step (2^-16 * extent).
-int rs_quantize_occlusion_bvh(const std::vector<BvhNode>& nodes, float base[3], float scale[3], std::vector<unsigned>& out, double* marginOut) {
-    if (nodes.empty()) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_quantize_occlusion_bvh: empty tree");
-    const BvhNode& root = nodes[0];
-    const float lo[3] = { root.bminx, root.bminy, root.bminz }, hi[3] = { root.bmaxx, root.bmaxy, root.bmaxz };
+bool rs_grid_over_box(const float lo[3], const float hi[3], float base[3], float scale[3], double* margin) {
     float ext = 0.f;
     for (int k = 0; k < 3; k++) ext = std::max(ext, hi[k] - lo[k]);
-    if (!(ext > 0.f) || !std::isfinite(ext)) return rs_fail(RS_ERR_UNSUPPORTED, "rs_quantize_occlusion_bvh: degenerate scene bounds");
-    const double margin = std::ldexp((double)ext, -17);
-    if (marginOut) *marginOut = margin;
+    if (!(ext > 0.f) || !std::isfinite(ext)) return false;
+    *margin = std::ldexp((double)ext, -17);
     for (int k = 0; k < 3; k++) {
         scale[k] = ext / 65000.f;                       // one cubic grid: same resolution on every axis
         base[k] = lo[k] - 200.f * scale[k];
     }
+    return true;
+}
+
+int rs_quantize_occlusion_bvh(const std::vector<BvhNode>& nodes, float base[3], float scale[3], std::vector<unsigned>& out, double* marginOut) {
+    if (nodes.empty()) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_quantize_occlusion_bvh: empty tree");
+    const BvhNode& root = nodes[0];
+    const float lo[3] = { root.bminx, root.bminy, root.bminz }, hi[3] = { root.bmaxx, root.bmaxy, root.bmaxz };
+    double margin = 0.0;
+    if (!rs_grid_over_box(lo, hi, base, scale, &margin)) return rs_fail(RS_ERR_UNSUPPORTED, "rs_quantize_occlusion_bvh: degenerate scene bounds");
+    if (marginOut) *marginOut = margin;
     out.resize(nodes.size() * 4);
     for (size_t i = 0; i < nodes.size(); i++) {
         const BvhNode& n = nodes[i];

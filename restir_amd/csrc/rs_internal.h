@@ -214,12 +214,15 @@ struct rs_scene {
     std::vector<int> hMaterialIds, hNodes[6], hLightPrimIds, hLightFailId;
     std::vector<int> hParent, hLeafOf;   // reference tree: parent by original node id, leaf node of each primitive
     bool properBoxes = false;            // the box table is a proper hierarchy (rs_scene_create); DevScene::axisCull also asks for small triangles
-    // Geometry edits (rs_scene_set_triangles; rs_refit.h, scene_refit.hip).  Kept from creation, on the host only: the primitive in every
+    // Geometry edits (rs_scene_set_triangles, rs_scene_set_geometry; rs_refit.h, scene_refit.hip).  Kept from creation, on the host only: the primitive in every
     // slot of occTris, the box the shadow tree's grid was laid over (a moved vertex must stay inside it) and the grid's margin.
     // Everything else -- device tables, scratch, staging -- belongs to `refit`, which the first edit allocates.
     std::vector<int> hOccLeafPrims;
     float gridLo[3] = {}, gridHi[3] = {};
     double gridMargin = 0.0;
+    // ... and of the emissive tree: the primitive in every slot of emiTris, and the margin of its own grid (dev.emiBase / emiScale)
+    std::vector<int> hEmiLeafPrims;
+    double emiMargin = 0.0;
     struct rs_refit* refit = nullptr;
     std::vector<rs_material> hMaterials;
     float sumLightPower = 0.f;
@@ -599,6 +602,9 @@ rs::CamParams rs_make_cam_params(const rs_camera* cam);
 // occlusion_bvh.cpp
 int rs_build_occlusion_bvh(int numPrims, const float* primBoxes, std::vector<rs::BvhNode>& nodes, std::vector<int>& leafPrims);
 int rs_quantize_occlusion_bvh(const std::vector<rs::BvhNode>& nodes, float base[3], float scale[3], std::vector<unsigned>& out, double* margin = nullptr);
+// the 16-bit grid a grid-box tree with root box [lo, hi] is quantised on (rs_quantize_occlusion_bvh lays it; an edit that moves emitters
+// lays the emissive tree's anew); false: the box has no finite, positive extent
+bool rs_grid_over_box(const float lo[3], const float hi[3], float base[3], float scale[3], double* margin);
 int rs_build_ordered_bvh(int numPrims, const float* primBoxes, const int* seq, std::vector<rs::BvhNode>& forward, std::vector<rs::BvhNode>& mirrored);
 int rs_reference_chain_tables(int bvhSize, const int* order0, std::vector<int>& parent, std::vector<int>& leafOfPrim, int numPrims);
 // scene_refit.hip

@@ -1,7 +1,9 @@
-// rs_refit.h -- what rs_scene_set_triangles keeps per scene (scene.hip: the entry point; scene_refit.hip: tables, kernels, rs_refit_boxes).
+// rs_refit.h -- what rs_scene_set_triangles / rs_scene_set_geometry keep per scene (scene.hip: the entry points; scene_refit.hip: tables,
+// kernels, rs_refit_boxes).
 //
 // A refit keeps every tree's topology and recomputes every box from the vertices: the reference tree (nodesAll's six orders, occChain)
-// and the grid-box trees over the reference's leaf boxes (occNodes, the six orders of ordNodes).  A box is a min / max of floats, taken
+// and the grid-box trees over the reference's leaf boxes (occNodes, the six orders of ordNodes and, when the edit names an emitter,
+// emiNodes on the emissive tree's own grid).  A box is a min / max of floats, taken
 // on order-preserving integer keys (-0 below +0), so the result does not depend on the order in which threads arrive and the host
 // (rs_refit_boxes) and the device give the same bits.
 #pragma once
@@ -27,14 +29,17 @@ RS_HD float refit_unkey(unsigned k) {
 
 struct rs_refit {
     // ---- tables, built on the host and uploaded by the first edit ----
-    int* dSlotOf = nullptr;          // [4][numPrims] primitive -> its slot in occTris, then in the three sequences of ordTris
+    int* dSlotOf = nullptr;          // [5][numPrims] primitive -> its slot in occTris, then in the three sequences of ordTris, then in emiTris (-1: not emissive)
+    int* dEmiLeaf = nullptr;         // [emissive triangles] slot of emiTris -> reference leaf node of its primitive
     int* dLeafOf = nullptr;          // [numPrims] reference leaf node of a primitive
     int* dBoxId = nullptr;           // [6][bvhSize] boundingBoxId of every record of nodesAll
     // One index space for every node a box is computed for: the reference's bvhSize nodes by original id, then the records of occNodes,
-    // then all 6 * ordStride / 16 records of ordNodes.  dParent: the parent in that space, -1 at a root, -2 for a record that is no
-    // node of a tree (the end records and the padding records: never written).
+    // then all 6 * ordStride / 16 records of ordNodes, then the emiCount + 1 records of emiNodes.  dParent: the parent in that space,
+    // -1 at a root, -2 for a record that is no node of a tree (the end records and the padding records: never written).
     int* dParent = nullptr;
     size_t numNodes = 0, gridFirst = 0, occRecords = 0, ordRecords = 0;      // ordRecords: per order (ordStride / 16)
+    size_t emiRecords = 0;           // last in the index space, so that an edit that names no emitter simply stops short of them
+    bool emiSticky = false;          // the emissive tree was switched off for good (caller-supplied boxes that were not exact unions)
     // ---- scratch of one refit ----
     unsigned* dKeys = nullptr;       // [numNodes][6] the boxes as keys
     unsigned* dArrived = nullptr;    // [numNodes] children that have merged their box into the node
@@ -52,14 +57,17 @@ struct rs_refit {
     hipEvent_t after = nullptr;                    // the edit's kernels
     // ---- the host's copy of the boxes ----
     std::vector<int> hChild;         // [bvhSize][2] children by original node id (-1, -1 at a leaf)
+    bool boxesExact = false;         // hBoxes hold rs_refit_boxes of the vertices (from the first accepted edit on)
     size_t root = 0;
 };
 
 // scene_refit.hip
 // first edit: builds and uploads the tables, allocates the scratch (waits for the device once: it reads the grid-box trees back)
 int rs_refit_prepare(rs_scene* s);
-// one edit, on stream st: scatters the m staged triangles (ids, 9 floats of vertices each, 9 of normals or null: all device pointers) and refits
-int rs_refit_enqueue(rs_scene* s, int m, const int* dIds, const float* dVertices, const float* dNormals, hipStream_t st);
+// one edit, on stream st: scatters the m staged triangles (ids, 9 floats of vertices each, 9 of normals or null: all device pointers) and refits.
+// emiTris: the edit names emitters, whose records in emiTris are written too; emiNodes: the emissive tree's boxes are refitted as well, on
+// the grid dev.emiBase / emiScale / emiMargin hold at the call
+int rs_refit_enqueue(rs_scene* s, int m, const int* dIds, const float* dVertices, const float* dNormals, bool emiTris, bool emiNodes, hipStream_t st);
 // the host's side of rs_refit_boxes once the arguments have been checked: `parent` from rs_reference_chain_tables
 void rs_refit_boxes_host(int bvhSize, const float* vertices, const int* order0, const int* parent, float* boxes);
 // the same boxes when only the m primitives `ids` have moved (boxes: the exact unions of the vertices before the edit): the leaves'

@@ -76,7 +76,8 @@ struct DevScene {
     bool linksNested;             // in every threaded order the miss links nest: c in (a, link(a)) => link(c) <= link(a)
     int occCount;
     // the emissive triangles alone, as a tree of the shadow tree's kind (scene.hip build_emissive_side; may_hit_emissive_wave):
-    // emiState 0 = not built (every ray may hit one), 1 = built, emiCount nodes (0: the scene has no emissive triangle)
+    // emiState 0 = not built, or switched off by an edit (every ray may hit one), 1 = built, emiCount nodes (0: the scene has no emissive
+    // triangle); emiBase / emiScale: its own grid, which rs_scene_set_geometry lays anew when emitters move
     const uint4*   emiNodes;
     const TriRec*  emiTris;
     f3 emiBase, emiScale;

@@ -170,9 +170,12 @@ int build_emissive_side(rs_scene* s) {
     if (int e = rs_build_occlusion_bvh((int)prims.size(), boxes.data(), nodes, leafPrims)) return e == RS_ERR_UNSUPPORTED ? 0 : e;
     float base[3], scale[3];
     std::vector<unsigned> packed;
-    if (int e = rs_quantize_occlusion_bvh(nodes, base, scale, packed)) return e == RS_ERR_UNSUPPORTED ? 0 : e;
+    if (int e = rs_quantize_occlusion_bvh(nodes, base, scale, packed, &s->emiMargin)) return e == RS_ERR_UNSUPPORTED ? 0 : e;
     const size_t no = nodes.size();
     packed.push_back(0xffffffffu); packed.push_back(0x0000ffffu); packed.push_back(0u); packed.push_back((unsigned)(no * 16));      // the end record
+    // kept on the host for rs_scene_set_geometry: the primitive in every slot of emiTris
+    s->hEmiLeafPrims.resize(prims.size());
+    for (size_t i = 0; i < prims.size(); i++) s->hEmiLeafPrims[i] = prims[(size_t)leafPrims[i]];
     std::vector<TriRec> rec(prims.size());
     for (size_t i = 0; i < prims.size(); i++) {
         const float* t = &s->hVertices[(size_t)prims[(size_t)leafPrims[i]] * 9];
@@ -306,6 +309,11 @@ VersionLayout version_layout(const rs_scene* s) {
     return l;
 }
 
+float triangle_area(const float* t) {
+    const f3 v0 = ld3(t), v1 = ld3(t + 3), v2 = ld3(t + 6);
+    return length(cross(v1 - v0, v2 - v0)) * .5f;
+}
+
 // First edit: slots 1.. of the version ring, every slot's staging buffer and events, the per-light areas and the environment map's power
 int versions_prepare(rs_scene* s) {
     if (s->verReady) return 0;
@@ -331,11 +339,7 @@ int versions_prepare(rs_scene* s) {
     RS_HIP(hipStreamCreateWithFlags(&s->verStream, hipStreamNonBlocking));
     // Math::triangleArea of every light primitive, as rs_build_light_table computes it (scene_build.cpp)
     s->hLightArea.resize(s->hLightPrimIds.size());
-    for (size_t i = 0; i < s->hLightArea.size(); i++) {
-        const float* t = &s->hVertices[(size_t)s->hLightPrimIds[i] * 9];
-        f3 v0 = ld3(t), v1 = ld3(t + 3), v2 = ld3(t + 6);
-        s->hLightArea[i] = length(cross(v1 - v0, v2 - v0)) * .5f;
-    }
+    for (size_t i = 0; i < s->hLightArea.size(); i++) s->hLightArea[i] = triangle_area(&s->hVertices[(size_t)s->hLightPrimIds[i] * 9]);
     // the environment map's sampler entry keeps its power: the sum of its pdf, as rs_scene_build_textured passes it on (a scene made by
     // rs_scene_create from a description does not carry it)
     if (s->envMapTexId >= 0 && !s->envPowerKnown) {
@@ -472,15 +476,15 @@ int version_commit(rs_scene* s, const char* what) {
     return rs_after_launch(what);
 }
 
-// The light sampler of the scene's light primitives with radiance `rad` (3 floats each) and the environment entry's power envPower, as
+// The light sampler of the scene's light primitives with radiance `rad` (3 floats each), areas `area` and the environment entry's power envPower, as
 // rs_scene_build_textured builds it (rs_build_light_table's powers, the environment map's entry last, rs_build_alias_table)
-int light_sampler(const rs_scene* s, const float* rad, float envPower, std::vector<float>& prob, std::vector<int>& fail, float* sumAll, const char* noPower) {
+int light_sampler(const rs_scene* s, const float* rad, const float* area, float envPower, std::vector<float>& prob, std::vector<int>& fail, float* sumAll, const char* noPower) {
     const size_t nl = (size_t)s->numLights, nlp = s->hLightPrimIds.size();
     std::vector<float> power(nl);
     prob.assign(nl, 0.f); fail.assign(nl, 0);
     for (size_t i = 0; i < nlp; i++) {
         const float perArea = luminance(ld3(rad + i * 3)) * 2.f * kGlmPi;       // rs_build_light_table (scene.cpp:164)
-        power[i] = perArea * s->hLightArea[i];
+        power[i] = perArea * area[i];
     }
     if (nlp < nl) power[nlp] = envPower;
     *sumAll = 0.f;
@@ -561,7 +565,7 @@ extern "C" int rs_scene_set_emission(rs_scene* s, int count, const int* material
     std::vector<int> fail;
     for (size_t i = 0; i < nlp; i++) st3(&rad[i * 3], ld3(mats[(size_t)s->hMaterialIds[(size_t)s->hLightPrimIds[i]]].baseColor));
     float sumAll = 0.f;
-    RS_TRY(light_sampler(s, rad.data(), s->envPower, prob, fail, &sumAll,
+    RS_TRY(light_sampler(s, rad.data(), s->hLightArea.data(), s->envPower, prob, fail, &sumAll,
                          "rs_scene_set_emission: the edit leaves the light sampler without a finite, positive total power"));
 
     RS_TRY(version_begin(s));
@@ -630,7 +634,7 @@ extern "C" int rs_scene_set_texture(rs_scene* s, int texId, int width, int heigh
         if (!(envSum > 0.f) || std::isinf(envSum)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_texture: the environment map's pdf has no finite, positive sum");
         envProb.resize(n); envFail.resize(n);
         RS_TRY(rs_build_alias_table((int)n, pdf.data(), envProb.data(), envFail.data(), &envSum));
-        RS_TRY(light_sampler(s, s->hLightRadiance.data(), envSum, prob, fail, &sumAll,
+        RS_TRY(light_sampler(s, s->hLightRadiance.data(), s->hLightArea.data(), envSum, prob, fail, &sumAll,
                              "rs_scene_set_texture: the edit leaves the light sampler without a finite, positive total power"));
     }
 
@@ -658,40 +662,52 @@ extern "C" int rs_scene_set_texture(rs_scene* s, int texId, int width, int heigh
 // node), so this edit works in place behind device-side fences: the library stream waits for what the internal streams have been handed
 // so far, the edit's kernels (scene_refit.hip) run on the library stream, and the next launch of every internal stream waits for them.
 // The host's tables follow at once: hVertices, hNormals, and hBoxes = rs_refit_boxes of the edited vertices.
-extern "C" int rs_scene_set_triangles(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals) {
-    RS_SCOPE(s);
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_triangles: null scene");
-    if (count < 0 || (count > 0 && (!primIds || !vertices))) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_triangles: count < 0 or null arrays");
+//
+// One implementation behind two entry points.  rs_scene_set_triangles refuses emitters and thereby guarantees that the light sampler, the
+// light records and the emissive tree are untouched.  rs_scene_set_geometry takes them: an edit that names one also rebuilds the light
+// sampler from the new areas (as rs_scene_set_emission does from new radiance), fills the next slot of the version ring -- light_records
+// derives LightRec from hVertices -- and refits the emissive tree on a grid laid anew over the new emissive root box.  Both transitions
+// are made at the same point of the library stream: the in-place edit behind before[] / after, the version switch behind verFilled, with
+// no launch between them.  An edit through rs_scene_set_geometry that names no emitter does exactly what rs_scene_set_triangles does.
+namespace {
+
+int fail_named(int code, const char* name, const char* text) {
+    static thread_local std::string msg;
+    msg = std::string(name) + ": " + text;
+    return rs_fail(code, msg.c_str());
+}
+
+int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals, bool emitters, const char* name) {
+    if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
+    if (count < 0 || (count > 0 && (!primIds || !vertices))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "count < 0 or null arrays");
     const bool bounded = s->dOccNodes != nullptr;       // the 16-bit grid of the grid-box trees lies over the box the scene was created with
+    bool lamps = false;
     for (int i = 0; i < count; i++) {
         const int p = primIds[i];
-        if (p < 0 || p >= s->numPrims) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_triangles: a primitive id out of range");
-        if (s->hMaterials[(size_t)s->hMaterialIds[(size_t)p]].type == 4)
-            return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_triangles: a triangle whose material is a Light (the light table, the sampler's powers and the emissive tree are built over the emitters' geometry; moving emitters is not supported)");
+        if (p < 0 || p >= s->numPrims) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a primitive id out of range");
+        if (s->hMaterials[(size_t)s->hMaterialIds[(size_t)p]].type == 4) {
+            if (!emitters)
+                return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a triangle whose material is a Light (the light table, the sampler's powers and the emissive tree are built over the emitters' geometry; rs_scene_set_geometry moves emitters)");
+            lamps = true;
+        }
         for (int k = 0; k < 9; k++) {
             const float x = vertices[(size_t)i * 9 + k];
             if (!std::isfinite(x) || (normals && !std::isfinite(normals[(size_t)i * 9 + k])))
-                return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_triangles: a vertex or normal that is not finite");
+                return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a vertex or normal that is not finite");
             if (bounded && !(x >= s->gridLo[k % 3] && x <= s->gridHi[k % 3]))
-                return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_triangles: a vertex outside the root box the scene was created with (the grid of its shadow-ray tree lies over that box); build a new scene");
+                return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a vertex outside the root box the scene was created with (the grid of its shadow-ray tree lies over that box); build a new scene");
         }
     }
-    RS_TRY(refuse_while_capturing("rs_scene_set_triangles: the library stream is being captured into a graph"));
+    {
+        static thread_local std::string msg;
+        msg = std::string(name) + ": the library stream is being captured into a graph";
+        RS_TRY(refuse_while_capturing(msg.c_str()));
+    }
     if (count == 0) return 0;
-    const bool first = s->refit == nullptr;
     RS_TRY(rs_refit_prepare(s));
+    if (lamps) RS_TRY(versions_prepare(s));             // (the ring's slots, hLightArea, the environment entry's power)
     rs_refit* r = s->refit;
     const size_t np = (size_t)s->numPrims, nn = (size_t)s->bvhSize;
-    if (first) {
-        // Boxes that were not the exact unions (a caller-supplied table): from now on they are.  The emissive tree was built over the boxes
-        // as given and is not refitted, so it no longer answers for the new ones: the last bounce asks the scene's trees again.
-        std::vector<float> exact(nn * 6);
-        rs_refit_boxes_host(s->bvhSize, s->hVertices.data(), s->hNodes[0].data(), s->hParent.data(), exact.data());
-        bool same = true;
-        for (size_t i = 0; i < nn * 6 && same; i++) same = exact[i] == s->hBoxes[i];
-        if (!same) s->dev.emiState = 0;
-        s->hBoxes.swap(exact);                           // (also when equal as values: rs_refit_boxes' signs of zero from here on)
-    }
 
     // the edit's records, a repeated id keeping its last: ids | vertices | normals, each part 16-byte aligned
     if (++r->stamp == 0u) { std::fill(r->lastStamp.begin(), r->lastStamp.end(), 0u); r->stamp = 1u; }
@@ -727,9 +743,60 @@ extern "C" int rs_scene_set_triangles(rs_scene* s, int count, const int* primIds
         std::memcpy(vs + j * 9, vertices + (size_t)i * 9, 9 * sizeof(float));
         if (normals) std::memcpy(ns + j * 9, normals + (size_t)i * 9, 9 * sizeof(float));
     }
+    // where a primitive's vertices are once the edit has been applied (so far only the staging buffer has been written)
+    auto edited = [&](size_t p) { return r->lastStamp[p] == r->stamp ? vs + (size_t)r->lastIndex[p] * 9 : &s->hVertices[p * 9]; };
 
-    // frames in flight: a render that has only been recorded is launched now, with the old geometry
-    RS_TRY(rs_gbuffer_release_scene(s));
+    // An emitter moves: the new light sampler and the emissive tree's new grid, built and checked before anything of the scene changes
+    std::vector<float> area, prob;
+    std::vector<int> fail;
+    float sumAll = 0.f, emiBase[3] = {}, emiScale[3] = {};
+    double emiMargin = 0.0;
+    bool emiGrid = false;
+    if (lamps) {
+        area = s->hLightArea;
+        for (size_t i = 0; i < area.size(); i++) {
+            const size_t p = (size_t)s->hLightPrimIds[i];
+            if (r->lastStamp[p] == r->stamp) area[i] = triangle_area(edited(p));
+        }
+        static thread_local std::string msg;
+        msg = std::string(name) + ": the edit leaves the light sampler without a finite, positive total power";
+        RS_TRY(light_sampler(s, s->hLightRadiance.data(), area.data(), s->envPower, prob, fail, &sumAll, msg.c_str()));
+        if (r->emiRecords) {
+            // the emissive root box: the union of the emissive triangles' boxes, which is what a fresh build_emissive_side starts from
+            float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+            for (int p : s->hEmiLeafPrims) {
+                const float* t = edited((size_t)p);
+                for (int k = 0; k < 9; k++) { lo[k % 3] = std::min(lo[k % 3], t[k]); hi[k % 3] = std::max(hi[k % 3], t[k]); }
+            }
+            emiGrid = rs_grid_over_box(lo, hi, emiBase, emiScale, &emiMargin);
+        }
+    }
+
+    // frames in flight: a render that has only been recorded is launched now, with the old geometry (and the old lights)
+    if (lamps) RS_TRY(version_begin(s));
+    else RS_TRY(rs_gbuffer_release_scene(s));
+    if (!r->boxesExact) {
+        // Boxes that were not the exact unions (a caller-supplied table): from now on they are.  The emissive tree was built over the boxes
+        // as given, so it no longer answers for the new ones: the last bounce asks the scene's trees again, for good.
+        std::vector<float> exact(nn * 6);
+        rs_refit_boxes_host(s->bvhSize, s->hVertices.data(), s->hNodes[0].data(), s->hParent.data(), exact.data());
+        bool same = true;
+        for (size_t i = 0; i < nn * 6 && same; i++) same = exact[i] == s->hBoxes[i];
+        if (!same) { s->dev.emiState = 0; r->emiSticky = true; }
+        s->hBoxes.swap(exact);                           // (also when equal as values: rs_refit_boxes' signs of zero from here on)
+        r->boxesExact = true;
+    }
+    // The emissive tree's grid moves with the lamps (DevScene travels by value; the fences keep earlier launches on the old tree).  Emitters
+    // collapsed to a box without extent: a fresh build has no emissive tree either (the quantiser refuses), so the last bounce asks the
+    // scene's trees until an edit brings an extent back -- that edit refits every emissive record, whichever emitters it names.
+    const bool emiNodes = lamps && r->emiRecords && emiGrid && !r->emiSticky;
+    if (lamps && r->emiRecords && !r->emiSticky) {
+        s->dev.emiState = emiGrid ? 1 : 0;
+        if (emiGrid) {
+            s->dev.emiBase = mk3(emiBase[0], emiBase[1], emiBase[2]); s->dev.emiScale = mk3(emiScale[0], emiScale[1], emiScale[2]);
+            s->emiMargin = emiMargin;
+        }
+    }
     rs_context* c = rs_ctx();
     const hipStream_t st = rs_stream();
     for (int i = 0; i < rs_context::kAux; i++)
@@ -739,7 +806,7 @@ extern "C" int rs_scene_set_triangles(rs_scene* s, int count, const int* primIds
     g.pending = true;
     r->stageNext = (r->stageNext + 1) % rs_refit::kStaging;
     RS_TRY(rs_refit_enqueue(s, m, reinterpret_cast<const int*>(r->dStage), reinterpret_cast<const float*>(r->dStage + offV),
-                            normals ? reinterpret_cast<const float*>(r->dStage + offN) : nullptr, st));
+                            normals ? reinterpret_cast<const float*>(r->dStage + offN) : nullptr, lamps, emiNodes, st));
     RS_HIP(hipEventRecord(r->after, st));
     for (int i = 0; i < rs_context::kAux; i++)
         if (c->aux[i]) RS_HIP(hipStreamWaitEvent(c->aux[i], r->after, 0));
@@ -749,7 +816,7 @@ extern "C" int rs_scene_set_triangles(rs_scene* s, int count, const int* primIds
         std::memcpy(&s->hVertices[(size_t)ids[j] * 9], vs + (size_t)j * 9, 9 * sizeof(float));
         if (normals) std::memcpy(&s->hNormals[(size_t)ids[j] * 9], ns + (size_t)j * 9, 9 * sizeof(float));
     }
-    // ... hBoxes = rs_refit_boxes of the edited vertices.  They hold exact unions already (before the first edit: checked below), so an edit
+    // ... hBoxes = rs_refit_boxes of the edited vertices.  They hold exact unions already (before the first edit: checked above), so an edit
     // of few triangles recomputes only the moved leaves' ancestors: the same min / max, hence the same bits
     if ((size_t)m * 16 < np) rs_refit_boxes_host_some(m, ids, s->hVertices.data(), s->hLeafOf.data(), s->hParent.data(), r->hChild.data(), s->hBoxes.data());
     else rs_refit_boxes_host(s->bvhSize, s->hVertices.data(), s->hNodes[0].data(), s->hParent.data(), s->hBoxes.data());
@@ -759,7 +826,25 @@ extern "C" int rs_scene_set_triangles(rs_scene* s, int count, const int* primIds
         s->dev.occRootHi = ld3(&s->hBoxes[r->root * 6 + 3]);
     }
     s->edits++;                                                  // retained G-buffer planes are not this scene's any more
-    return rs_after_launch("rs_scene_set_triangles");
+    if (!lamps) return rs_after_launch(name);
+    // the lights' version: light_records reads the vertices just written; launches from here on see new geometry and new lights alike
+    s->hLightArea.swap(area);
+    s->hLightProb.swap(prob);
+    s->hLightFailId.swap(fail);
+    s->sumLightPower = sumAll;
+    return version_commit(s, name);
+}
+
+}  // namespace
+
+extern "C" int rs_scene_set_triangles(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals) {
+    RS_SCOPE(s);
+    return set_geometry(s, count, primIds, vertices, normals, false, "rs_scene_set_triangles");
+}
+
+extern "C" int rs_scene_set_geometry(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals) {
+    RS_SCOPE(s);
+    return set_geometry(s, count, primIds, vertices, normals, true, "rs_scene_set_geometry");
 }
 
 // Test hooks of the refit (include/restir_hip.h): the device tables as they are, the grid they are quantised on, and grid_box itself.
@@ -809,6 +894,20 @@ extern "C" int rs_debug_scene_grid(const rs_scene* s, float base[3], float scale
     if (margin) *margin = occ ? s->gridMargin : 0.0;
     if (occCount) *occCount = occ ? s->dev.occCount : 0;
     if (ordStride) *ordStride = s->dOrdNodes ? (int)s->dev.ordStride : 0;
+    return 0;
+}
+
+extern "C" int rs_debug_scene_emissive_grid(const rs_scene* s, float base[3], float scale[3], double* margin, int* state, int* count) {
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_scene_emissive_grid: null scene");
+    const bool emi = s->dEmiNodes != nullptr;
+    const float b[3] = { s->dev.emiBase.x, s->dev.emiBase.y, s->dev.emiBase.z }, c[3] = { s->dev.emiScale.x, s->dev.emiScale.y, s->dev.emiScale.z };
+    for (int k = 0; k < 3; k++) {
+        if (base) base[k] = emi ? b[k] : 0.f;
+        if (scale) scale[k] = emi ? c[k] : 0.f;
+    }
+    if (margin) *margin = emi ? s->emiMargin : 0.0;
+    if (state) *state = s->dev.emiState;
+    if (count) *count = emi ? s->dev.emiCount : 0;
     return 0;
 }
 

@@ -1,10 +1,10 @@
-// scene_refit.hip -- the device side of rs_scene_set_triangles (its entry point, checks, staging and fences: scene.hip) and
-// rs_refit_boxes, the same definition on the host.
+// scene_refit.hip -- the device side of rs_scene_set_triangles and rs_scene_set_geometry (their entry points, checks, staging and fences:
+// scene.hip) and rs_refit_boxes, the same definition on the host.
 //
 // Every edit refits everything: O(numPrims), one code path, no ancestor can be left stale.  In the order of one stream:
 //   k_refit_clear   every box of the index space of rs_refit.h to the empty box (keys: min = all ones, max = 0), every counter to 0
 //   k_scatter       the edited vertices and normals, and the pre-differenced TriRec of every edited triangle wherever it is kept
-//                   (tris, occTris, the three sequences of ordTris; pad0 / pad1 stay; emiTris holds emissive triangles, which are refused)
+//                   (tris, occTris, the three sequences of ordTris, and emiTris for an emitter; pad0 / pad1 / pad2 stay)
 //   k_ref_leaves    leaf box = AABB(va, vb, vc) (src/bvh.h:20-21); then bottom-up: a node merges its box into its parent's and adds one
 //                   to the parent's counter, and the second arrival reads the finished union and climbs on.  The reference tree is up
 //                   to 52 deep and far from balanced (Sponza-class scene): nothing here depends on the depth but the length of a climb
@@ -14,8 +14,10 @@
 //                   occlusion_bvh.cpp; NOT of the reference's inner boxes, which this tree's spans do not match)
 //   k_grid_write    quantises outward on the scene's grid (rs_grid.h grid_box: the host builder's function) into the three box dwords
 //                   of each record; w -- leaf code or miss link -- the end records and the padding records are never written
-// The emissive tree (emiNodes) is left alone: it is built over the reference leaf boxes of the emissive triangles, and those cannot move
-// while emitters are refused.
+// The emissive tree (emiNodes: the shadow tree's kind over the reference leaf boxes of the emissive triangles alone) takes part in the last
+// two launches when, and only when, the edit names an emitter (rs_scene_set_geometry): its records come last in the index space, so an edit
+// of other triangles stops short of them and writes no byte of emiNodes / emiTris.  Its grid is its own and moves with the lamps: the host
+// lays it over the new emissive root box before the launches (scene.hip), so base, scale and margin are per record range (GridArgs).
 //
 // Hand-off inside a launch (the two climbs): a parent's box is only ever written by agent-scope atomic min / max and only ever read by
 // agent-scope atomic loads, both of which act on the one copy all eight XCDs agree on, never on a CU's L1; a child's merges are ordered
@@ -80,6 +82,7 @@ __global__ void __launch_bounds__(256) k_refit_clear(unsigned* __restrict__ keys
 struct ScatterArgs {
     float* vertices; float* normals;
     TriRec* tris; TriRec* occTris; TriRec* ordTris;      // occTris / ordTris: null when the scene has no such tree
+    TriRec* emiTris;                                     // null unless the edit names an emitter
     const int* slotOf;
     int numPrims;
 };
@@ -101,6 +104,7 @@ __global__ void __launch_bounds__(256) k_scatter(ScatterArgs a, int m, const int
     put_triangle(a.tris + p, v0, e1, e2);
     if (a.occTris) put_triangle(a.occTris + a.slotOf[p], v0, e1, e2);
     if (a.ordTris) for (size_t s = 0; s < 3; s++) put_triangle(a.ordTris + s * np + (size_t)a.slotOf[(1 + s) * np + p], v0, e1, e2);
+    if (a.emiTris) { const int slot = a.slotOf[4 * np + p]; if (slot >= 0) put_triangle(a.emiTris + slot, v0, e1, e2); }
 }
 
 __global__ void __launch_bounds__(256) k_ref_leaves(int numPrims, const float* __restrict__ vertices, const int* __restrict__ leafOf,
@@ -129,16 +133,18 @@ __global__ void __launch_bounds__(256) k_ref_write(size_t numRecords, size_t bvh
 }
 
 struct GridArgs {
-    uint4* occNodes; uint4* ordNodes;                    // ordNodes: null when the scene has no ordered trees
+    uint4* occNodes; uint4* ordNodes; uint4* emiNodes;   // ordNodes: null when the scene has no ordered trees
     const TriRec* occTris; const TriRec* ordTris;
-    size_t gridFirst, occRecords, ordRecords;
+    const int* emiLeaf;                                  // emiTris carries no reference leaf in pad0: the slot's leaf is kept here
+    size_t gridFirst, occRecords, ordRecords, emiFirst;  // emiFirst: the first record (counted from gridFirst) of the emissive tree
     int numPrims;
-    float base[3], scale[3];
-    double margin;
+    float base[3], scale[3], emiBase[3], emiScale[3];
+    double margin, emiMargin;
 };
-// record g of the grid part of the index space: its address, and the triangles a leaf code counts through
+// record g of the grid part of the index space: its address, and the triangles a leaf code counts through (null: the emissive tree's)
 __device__ __forceinline__ uint4* grid_record(const GridArgs& a, size_t g, const TriRec** tris, int* step) {
     if (g < a.occRecords) { *tris = a.occTris; *step = 1; return a.occNodes + g; }
+    if (g >= a.emiFirst) { *tris = nullptr; *step = 1; return a.emiNodes + (g - a.emiFirst); }
     const size_t r = g - a.occRecords, order = r / a.ordRecords;
     *tris = a.ordTris + (order >> 1) * (size_t)a.numPrims;
     *step = (order & 1) ? -1 : 1;                        // the mirrored order meets a leaf's triangles at start, start - 1, ...
@@ -157,7 +163,7 @@ __global__ void __launch_bounds__(256) k_grid_leaves(GridArgs a, size_t numRecor
     KeyBox b;
     for (int k = 0; k < 3; k++) { b.lo[k] = 0xffffffffu; b.hi[k] = 0u; }
     for (int n = code & 7; n > 0; n--, tri += step) {
-        const unsigned* leaf = keys + (size_t)__float_as_int(tris[tri].pad0) * 6;      // the triangle's reference leaf box (k_ref_leaves, an earlier launch)
+        const unsigned* leaf = keys + (size_t)(tris ? __float_as_int(tris[tri].pad0) : a.emiLeaf[tri]) * 6;      // the triangle's reference leaf box (k_ref_leaves, an earlier launch)
         for (int k = 0; k < 3; k++) { b.lo[k] = min(b.lo[k], leaf[k]); b.hi[k] = max(b.hi[k], leaf[3 + k]); }
     }
     for (int k = 0; k < 3; k++) { keys[node * 6 + k] = b.lo[k]; keys[node * 6 + 3 + k] = b.hi[k]; }
@@ -174,7 +180,8 @@ __global__ void __launch_bounds__(256) k_grid_write(GridArgs a, size_t numRecord
     const float lo[3] = { refit_unkey(k[0]), refit_unkey(k[1]), refit_unkey(k[2]) }, hi[3] = { refit_unkey(k[3]), refit_unkey(k[4]), refit_unkey(k[5]) };
     // (the host has checked every vertex against the grid's box, so every box fits; one that did not would become the whole grid: conservative)
     unsigned q[3] = { 0u, 0xffff0000u, 0xffffffffu };
-    (void)grid_box(lo, hi, a.base, a.scale, a.margin, q);
+    if (g >= a.emiFirst) (void)grid_box(lo, hi, a.emiBase, a.emiScale, a.emiMargin, q);
+    else (void)grid_box(lo, hi, a.base, a.scale, a.margin, q);
     rec->x = q[0]; rec->y = q[1]; rec->z = q[2];
 }
 
@@ -265,7 +272,7 @@ extern "C" int rs_refit_boxes(int numPrims, const float* vertices, int bvhSize, 
 void rs_refit_free(rs_scene* s) {
     rs_refit* r = s->refit;
     if (!r) return;
-    rs_dev_free(r->dSlotOf); rs_dev_free(r->dLeafOf); rs_dev_free(r->dBoxId); rs_dev_free(r->dParent);
+    rs_dev_free(r->dSlotOf); rs_dev_free(r->dEmiLeaf); rs_dev_free(r->dLeafOf); rs_dev_free(r->dBoxId); rs_dev_free(r->dParent);
     rs_dev_free(r->dKeys); rs_dev_free(r->dArrived); rs_dev_free(r->dStage);
     for (rs_refit::Stage& g : r->stage) {
         if (g.host) (void)hipHostFree(g.host);
@@ -285,12 +292,19 @@ int rs_refit_prepare(rs_scene* s) {
     const bool occ = s->dOccNodes != nullptr, ord = s->dOrdNodes != nullptr;
     r->occRecords = occ ? (size_t)s->dev.occCount : 0;
     r->ordRecords = ord ? (size_t)s->dev.ordStride / 16 : 0;
+    const bool emi = s->dEmiNodes != nullptr && s->dev.emiCount > 0;
+    r->emiRecords = emi ? (size_t)s->dev.emiCount + 1 : 0;
     r->gridFirst = nn;
-    r->numNodes = nn + r->occRecords + 6 * r->ordRecords;
+    r->numNodes = nn + r->occRecords + 6 * r->ordRecords + r->emiRecords;
     if (r->numNodes >= 0x7fffffffull) { rs_refit_free(s); return rs_fail(RS_ERR_UNSUPPORTED, "rs_scene_set_triangles: the scene's trees have more than 2^31 nodes"); }
 
     // primitive -> slot: occTris in the shadow tree's leaf order, ordTris in the sequences of the even threaded orders
-    std::vector<int> slotOf(4 * np, 0);
+    std::vector<int> slotOf(5 * np, 0), emiLeaf(s->hEmiLeafPrims.size());
+    std::fill(slotOf.begin() + 4 * np, slotOf.end(), -1);
+    for (size_t i = 0; i < emiLeaf.size(); i++) {
+        slotOf[4 * np + (size_t)s->hEmiLeafPrims[i]] = (int)i;
+        emiLeaf[i] = s->hLeafOf[(size_t)s->hEmiLeafPrims[i]];
+    }
     if (occ) {
         if (s->hOccLeafPrims.size() != np) { rs_refit_free(s); return rs_fail(RS_ERR_INTERNAL, "rs_scene_set_triangles: the shadow tree's leaf order was not kept"); }
         for (size_t i = 0; i < np; i++) slotOf[(size_t)s->hOccLeafPrims[i]] = (int)i;
@@ -329,9 +343,21 @@ int rs_refit_prepare(rs_scene* s) {
             trees = leaves > 0 && count == 2 * leaves - 1 && rs_refit_preorder_parents(t, count, (int)first, &parent[first]);
         }
     }
+    if (emi && trees) {
+        std::vector<unsigned> rec((size_t)s->dev.emiCount * 4);
+        RS_HIP(hipMemcpy(rec.data(), s->dEmiNodes, rec.size() * 4, hipMemcpyDeviceToHost));
+        const size_t first = nn + r->occRecords + 6 * r->ordRecords;
+        trees = rs_refit_preorder_parents(rec.data(), (size_t)s->dev.emiCount, (int)first, &parent[first]);
+        // a leaf code must stay inside emiTris: the refit reads emiLeaf through it
+        for (size_t i = 0; i < (size_t)s->dev.emiCount && trees; i++) {
+            const int w = (int)rec[i * 4 + 3];
+            if (w < 0) trees = (size_t)(~w >> 3) + (size_t)(~w & 7) <= emiLeaf.size();
+        }
+    }
     if (!trees) { rs_refit_free(s); return rs_fail(RS_ERR_INTERNAL, "rs_scene_set_triangles: a grid-box tree is not a binary tree in pre-order"); }
 
     int e = upload_table(&r->dSlotOf, slotOf);
+    if (!e) e = upload_table(&r->dEmiLeaf, emiLeaf);
     if (!e) e = upload_table(&r->dLeafOf, s->hLeafOf);
     if (!e) e = upload_table(&r->dBoxId, boxId);
     if (!e) e = upload_table(&r->dParent, parent);
@@ -352,22 +378,26 @@ int rs_refit_prepare(rs_scene* s) {
     return 0;
 }
 
-int rs_refit_enqueue(rs_scene* s, int m, const int* dIds, const float* dVertices, const float* dNormals, hipStream_t st) {
+int rs_refit_enqueue(rs_scene* s, int m, const int* dIds, const float* dVertices, const float* dNormals, bool emiTris, bool emiNodes, hipStream_t st) {
     rs_refit* r = s->refit;
     const size_t np = (size_t)s->numPrims, nn = (size_t)s->bvhSize;
     const bool occ = s->dOccNodes != nullptr, ord = s->dOrdNodes != nullptr;
-    hipLaunchKernelGGL(k_refit_clear, dim3(blocks_for(r->numNodes)), dim3(256), 0, st, r->dKeys, r->dArrived, r->numNodes);
-    ScatterArgs sa{ s->dVertices, s->dNormals, s->dTris, occ ? s->dOccTris : nullptr, ord ? s->dOrdTris : nullptr, r->dSlotOf, s->numPrims };
+    const size_t emiRecords = emiNodes ? r->emiRecords : 0, numNodes = r->numNodes - r->emiRecords + emiRecords;
+    hipLaunchKernelGGL(k_refit_clear, dim3(blocks_for(numNodes)), dim3(256), 0, st, r->dKeys, r->dArrived, numNodes);
+    ScatterArgs sa{ s->dVertices, s->dNormals, s->dTris, occ ? s->dOccTris : nullptr, ord ? s->dOrdTris : nullptr,
+                    emiTris && r->emiRecords ? s->dEmiTris : nullptr, r->dSlotOf, s->numPrims };
     hipLaunchKernelGGL(k_scatter, dim3(blocks_for((size_t)m)), dim3(256), 0, st, sa, m, dIds, dVertices, dNormals);
     hipLaunchKernelGGL(k_ref_leaves, dim3(blocks_for(np)), dim3(256), 0, st, s->numPrims, (const float*)s->dVertices, (const int*)r->dLeafOf,
                        (const int*)r->dParent, r->dKeys, r->dArrived);
     const size_t refRecords = (occ ? 7 : 6) * nn;
     hipLaunchKernelGGL(k_ref_write, dim3(blocks_for(refRecords)), dim3(256), 0, st, refRecords, nn, (const int*)r->dBoxId, (const unsigned*)r->dKeys,
                        s->dNodesAll, s->dOccChain);
-    const size_t gridRecords = r->occRecords + 6 * r->ordRecords;
+    const size_t emiFirst = r->occRecords + 6 * r->ordRecords, gridRecords = emiFirst + emiRecords;
     if (gridRecords) {
-        GridArgs ga{ s->dOccNodes, s->dOrdNodes, s->dOccTris, s->dOrdTris, r->gridFirst, r->occRecords, r->ordRecords, s->numPrims,
-                     { s->dev.occBase.x, s->dev.occBase.y, s->dev.occBase.z }, { s->dev.occScale.x, s->dev.occScale.y, s->dev.occScale.z }, s->gridMargin };
+        GridArgs ga{ s->dOccNodes, s->dOrdNodes, s->dEmiNodes, s->dOccTris, s->dOrdTris, r->dEmiLeaf, r->gridFirst, r->occRecords, r->ordRecords, emiFirst, s->numPrims,
+                     { s->dev.occBase.x, s->dev.occBase.y, s->dev.occBase.z }, { s->dev.occScale.x, s->dev.occScale.y, s->dev.occScale.z },
+                     { s->dev.emiBase.x, s->dev.emiBase.y, s->dev.emiBase.z }, { s->dev.emiScale.x, s->dev.emiScale.y, s->dev.emiScale.z },
+                     s->gridMargin, s->emiMargin };
         hipLaunchKernelGGL(k_grid_leaves, dim3(blocks_for(gridRecords)), dim3(256), 0, st, ga, gridRecords, (const int*)r->dParent, r->dKeys, r->dArrived);
         hipLaunchKernelGGL(k_grid_write, dim3(blocks_for(gridRecords)), dim3(256), 0, st, ga, gridRecords, (const int*)r->dParent, (const unsigned*)r->dKeys);
     }
