@@ -219,6 +219,12 @@ int  rs_join_denoise_stream(void);
  * other (synchronous mode, per-pass timing); 0 = off; negative = |threshold| for every launch, also with the frames overlapped
  * (measured slower there); default 768. */
 int  rs_set_tile_split(int threshold);
+/* Test hook: waits as rs_synchronize does, then reports how many tiles the helper blocks of the most recent split launch took over (the
+ * tiles the launch before it listed as heavy), the largest figure over the launch sites of the G-buffer (GBuffer::render as its own
+ * launch) and of the ReSTIR object (primary rays, alone or in one launch with the render).  0: no split launch has run there, or none that
+ * found a tile listed.  Either object and either output may be NULL.  It tells a test that set a low threshold whether the four-wave
+ * form really ran. */
+int  rs_debug_split_tiles(const rs_gbuffer* gbuffer, const rs_restir* restir, unsigned* renderTiles, unsigned* primaryTiles);
 int  rs_synchronize(void);
 
 /* ---- host scene build: replaces Scene::buildDevData (src/scene.cpp:159-215) ----------- */
@@ -304,7 +310,8 @@ int  rs_scene_set_materials(rs_scene* scene, int count, const int* materialIds, 
  * normal that is not finite; a triangle whose material is a Light (this is the call that guarantees that the light sampler, the light
  * records and the emissive tree are untouched; rs_scene_set_geometry moves emitters); and, while the scene has its shadow-ray tree, a vertex outside the root box the scene was created with (the trees' 16-bit grid lies over that box).  With
  * RS_ERR_UNSUPPORTED while the library stream is being captured into a graph.  A large deformation makes the refitted trees slower,
- * never wrong; the remedy is a new scene.  The G-buffer's motion plane stays camera-only. */
+ * never wrong; the remedy is a new scene.  The G-buffer's motion plane follows moved triangles on a scene that tracks motion
+ * (rs_scene_set_motion_tracking below) and is camera-only otherwise. */
 int  rs_scene_set_triangles(rs_scene* scene, int count, const int* primIds, const float* vertices, const float* normals);
 /* rs_scene_set_triangles that also takes triangles whose material is a Light, alone or mixed with others in one call: arguments,
  * staging, fences, refit and "a repeated id takes its last record" are the same, and a call that names no emitter does exactly what
@@ -329,6 +336,32 @@ int  rs_scene_set_triangles(rs_scene* scene, int count, const int* primIds, cons
  * Temporal reservoirs keep the direction, distance and radiance they were drawn with for up to the M clamp's 20 frames, as in the
  * reference; rs_restir_reset drops them.  Adding or removing emitters still takes a new scene. */
 int  rs_scene_set_geometry(rs_scene* scene, int count, const int* primIds, const float* vertices, const float* normals);
+/* Motion tracking: the previous pose of the scene, for the G-buffer's motion plane.  (The reference has no moving geometry: there is no
+ * reference line to cite.  Its renderGBuffer, src/gbuffer.cu:49-54, asks where the hit's world point was on last frame's screen.)
+ * A tracked scene keeps a second vertex array on the device, 36 bytes per triangle: the vertices as they stood at the last
+ * rs_scene_advance_motion.  GBuffer::render then writes, for a hit with barycentrics (bx, by) on primitive p,
+ *     prevPos = pv1 * bx + pv2 * by + pv0 * (1 - bx - by)          (pv*: p's previous vertices; the expression that gives the hit position)
+ *     motion  = lastCamera.getRasterCoord(prevPos), -1 when outside the image
+ * instead of lastCamera.getRasterCoord(hit position); a miss writes 0 as before, and every other plane is unchanged.  A triangle that has
+ * not moved since the last advance gets the untracked value, bit for bit.  Consumers (ReSTIR's temporal pass, ReSTIR-GI, SVGF) read the
+ * plane as before.
+ * rs_scene_set_motion_tracking(scene, 1) allocates the array and fills it with the current vertices; (scene, 0) makes later launches
+ * camera-only again (the memory stays until rs_scene_destroy).  A scene that never switches it on allocates nothing and launches the
+ * kernels it always launched.  A failed allocation leaves the scene untracked and unchanged.
+ * rs_scene_advance_motion: the geometry as it stands at this point of the library stream becomes the previous pose for every launch
+ * enqueued after the call.  Call it once per frame, next to rs_gbuffer_update.  rs_scene_set_triangles / rs_scene_set_geometry never
+ * write the previous pose: after any number of edits it is still the pose at the last advance.  On an untracked scene the call succeeds
+ * and does nothing; with no accepted geometry edit since the last advance it enqueues nothing and retained G-buffer planes stay valid;
+ * otherwise it copies the vertex array on the device (DESIGN.md section 3 has the cost) and invalidates retained planes.
+ * Ordering of both calls as rs_scene_set_triangles: no device synchronisation; a render that has only been recorded is launched first,
+ * with the old previous pose; the copy runs on the library stream behind what the internal streams have been handed so far, and their
+ * next launches wait for it.  RS_ERR_INVALID_ARGUMENT: a null scene.  RS_ERR_UNSUPPORTED while the library stream is being captured into
+ * a graph (a captured frame keeps the pose it was captured with).  INTEGRATION.md section 3e has the frame loop and what stays as it is. */
+int  rs_scene_set_motion_tracking(rs_scene* scene, int on);
+int  rs_scene_advance_motion(rs_scene* scene);
+/* Test hook: waits as rs_synchronize does, then copies the previous pose (9 floats per primitive) to `out`.  RS_ERR_INVALID_ARGUMENT: a
+ * null argument, or a scene that does not track motion.  RS_ERR_UNSUPPORTED while the library stream is being captured. */
+int  rs_scene_download_prev_vertices(const rs_scene* scene, float* out);
 /* The boxes of the reference tree refitted to `vertices` (9 floats per primitive), host only, no GPU call: order0 is bvhNodes[0] (3 ints
  * per node: primitive or -1, boundingBoxId, miss link), from which the children are derived; boundingBoxes receives 6 floats per node
  * by boundingBoxId.  Min and max are taken with -0 below +0, so the bits do not depend on the order of evaluation.  On the vertices a

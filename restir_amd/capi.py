@@ -126,9 +126,9 @@ RIS_GLOBAL, RIS_LDS, RIS_ALIAS_LDS = 0, 1, 2
 
 # every symbol include/restir_hip.h declares; tests check that the library exports all of them
 EXPORTS = [
-    "rs_last_error", "rs_context_create", "rs_context_destroy", "rs_context_set_current", "rs_init", "rs_set_stream", "rs_set_sync", "rs_set_side_stream", "rs_set_ris_table_pixels", "rs_set_internal_stream_priority", "rs_internal_streams_info", "rs_choose_internal_streams_again", "rs_prepare_streams", "rs_set_stream_plan", "rs_set_denoise_stream", "rs_join_denoise_stream", "rs_set_tile_split", "rs_synchronize",
+    "rs_last_error", "rs_context_create", "rs_context_destroy", "rs_context_set_current", "rs_init", "rs_set_stream", "rs_set_sync", "rs_set_side_stream", "rs_set_ris_table_pixels", "rs_set_internal_stream_priority", "rs_internal_streams_info", "rs_choose_internal_streams_again", "rs_prepare_streams", "rs_set_stream_plan", "rs_set_denoise_stream", "rs_join_denoise_stream", "rs_set_tile_split", "rs_debug_split_tiles", "rs_synchronize",
     "rs_build_bvh", "rs_build_light_table", "rs_build_alias_table", "rs_build_envmap_pdf", "rs_scene_build", "rs_scene_build_textured", "rs_scene_create",
-    "rs_scene_host_desc", "rs_scene_set_sample_sequence", "rs_scene_set_emission", "rs_scene_set_materials", "rs_scene_set_texture", "rs_scene_set_triangles", "rs_scene_set_geometry", "rs_refit_boxes", "rs_debug_scene_table", "rs_debug_scene_grid", "rs_debug_scene_emissive_grid", "rs_debug_grid_box", "rs_scene_destroy", "rs_camera_update", "rs_trace_closest", "rs_trace_closest_wave", "rs_scene_set_ordered_tree", "rs_ordered_bvh_host_check", "rs_trace_occlusion",
+    "rs_scene_host_desc", "rs_scene_set_sample_sequence", "rs_scene_set_emission", "rs_scene_set_materials", "rs_scene_set_texture", "rs_scene_set_triangles", "rs_scene_set_geometry", "rs_scene_set_motion_tracking", "rs_scene_advance_motion", "rs_scene_download_prev_vertices", "rs_refit_boxes", "rs_debug_scene_table", "rs_debug_scene_grid", "rs_debug_scene_emissive_grid", "rs_debug_grid_box", "rs_scene_destroy", "rs_camera_update", "rs_trace_closest", "rs_trace_closest_wave", "rs_scene_set_ordered_tree", "rs_ordered_bvh_host_check", "rs_trace_occlusion",
     "rs_gbuffer_create", "rs_gbuffer_destroy", "rs_gbuffer_render", "rs_gbuffer_render_rows", "rs_gbuffer_update",
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
@@ -168,6 +168,7 @@ def lib():
     L.rs_context_set_current.argtypes = [vp]
     L.rs_set_stream.argtypes = [vp]
     L.rs_set_sync.argtypes = [ci]
+    L.rs_debug_split_tiles.argtypes = [vp, vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     L.rs_set_side_stream.argtypes = [ci]
     L.rs_set_ris_table_pixels.argtypes = [ci]
     L.rs_build_bvh.argtypes = [ci, vp, vp, C.POINTER(vp * 6), C.POINTER(ci)]
@@ -189,6 +190,9 @@ def lib():
     L.rs_scene_set_texture.argtypes = [vp, ci, ci, ci, vp]
     L.rs_scene_set_triangles.argtypes = [vp, ci, vp, vp, vp]
     L.rs_scene_set_geometry.argtypes = [vp, ci, vp, vp, vp]
+    L.rs_scene_set_motion_tracking.argtypes = [vp, ci]
+    L.rs_scene_advance_motion.argtypes = [vp]
+    L.rs_scene_download_prev_vertices.argtypes = [vp, vp]
     L.rs_debug_scene_emissive_grid.argtypes = [vp, vp, vp, C.POINTER(C.c_double), C.POINTER(ci), C.POINTER(ci)]
     L.rs_refit_boxes.argtypes = [ci, vp, ci, vp, vp]
     L.rs_debug_scene_table.argtypes = [vp, ci, vp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -416,6 +420,14 @@ def join_denoise_stream():
 def set_tile_split(threshold):
     """Closest-hit kernels: tiles whose last walk visited at least `threshold` nodes are traced by four waves (rs_set_tile_split); 0 = off."""
     check(lib().rs_set_tile_split(int(threshold)))
+
+
+def split_tiles(gbuf=None, restir=None):
+    """rs_debug_split_tiles (test hook): (render, primary) -- tiles that helper blocks took over in the most recent split launch of the
+    G-buffer's own render and of the ReSTIR object's primary-ray launches; 0 = the four-wave form did not run there."""
+    a, b = C.c_uint(0), C.c_uint(0)
+    check(lib().rs_debug_split_tiles(gbuf.handle if gbuf else None, restir.handle if restir else None, C.byref(a), C.byref(b)))
+    return a.value, b.value
 
 
 def write_jpg(path, rgb):
@@ -698,6 +710,24 @@ class Scene:
         """rs_scene_set_geometry: set_triangles that also takes emissive triangles; an edit that names one rebuilds the light sampler and the
         light records and refits the emissive tree at the same point of the library stream."""
         self._set_vertices(lib().rs_scene_set_geometry, "set_geometry", prim_ids, vertices, normals)
+
+    def set_motion_tracking(self, on=True):
+        """rs_scene_set_motion_tracking: the scene keeps its pose at the last advance_motion() on the device, and the G-buffer's motion
+        plane follows moved triangles to where they were; off: camera-only again."""
+        check(lib().rs_scene_set_motion_tracking(self.handle, 1 if on else 0))
+
+    def advance_motion(self):
+        """rs_scene_advance_motion: the geometry as it stands becomes the previous pose for every launch enqueued from here on; once per
+        frame, next to GBuffer.update.  Nothing on an untracked scene or when no geometry edit was accepted since the last call."""
+        check(lib().rs_scene_advance_motion(self.handle))
+
+    def prev_vertices(self):
+        """rs_scene_download_prev_vertices (test hook): the previous pose, (n, 3, 3) float32, after everything enqueued so far."""
+        d = SceneDesc()
+        check(lib().rs_scene_host_desc(self.handle, C.byref(d)))
+        out = np.zeros((d.numPrims, 3, 3), np.float32)
+        check(lib().rs_scene_download_prev_vertices(self.handle, _p(out)))
+        return out
 
     def emissive_grid(self):
         """rs_debug_scene_emissive_grid (test hook): dict(base, scale, margin, state, count) of the emissive tree's grid."""

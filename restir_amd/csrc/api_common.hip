@@ -522,6 +522,23 @@ int rs_set_tile_split(int threshold) {
     return 0;
 }
 
+// Test hook (include/restir_hip.h): what the report words of the objects' launch sites say (rs_tilesplit.h: written by every split
+// launch, the number of listed tiles its helper blocks found in the hint they read)
+int rs_debug_split_tiles(const rs_gbuffer* g, const rs_restir* r, unsigned* renderTiles, unsigned* primaryTiles) {
+    rs_ctx_scope scope(g ? g->ctx : r ? r->ctx : nullptr);
+    RS_TRY(rs_synchronize());
+    auto listed = [](const rs_tile_split& t) {
+        const unsigned long long rep = t.report ? *reinterpret_cast<volatile unsigned long long*>(t.report) : ~0ull;
+        return rep == ~0ull ? 0u : (unsigned)rep;
+    };
+    unsigned a = 0, b = 0;
+    if (g) for (const rs_tile_split& t : g->split) a = std::max(a, listed(t));
+    if (r) for (const auto& perStream : r->split) for (const rs_tile_split& t : perStream) b = std::max(b, listed(t));
+    if (renderTiles) *renderTiles = a;
+    if (primaryTiles) *primaryTiles = b;
+    return 0;
+}
+
 
 const char* rs_last_error(void) {
     std::lock_guard<std::mutex> lock(g_errMutex);

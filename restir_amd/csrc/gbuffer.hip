@@ -16,7 +16,8 @@ using namespace rs;
 
 // TEX: the scene has texture maps or an environment map (getTexturedMaterialAndSurface, gbuffer.cu:38,59-62)
 // 8 blocks per CU: without the bound the kernel takes 100+ SGPRs and runs at 7 waves per SIMD (0.392 -> 0.370 ms at 1080p)
-template <bool TEX, bool SPLIT>
+// MOTION: the scene tracks motion (gbuffer_store, rs_internal.h); launch_render picks the instantiation, the untracked ones are unchanged
+template <bool TEX, bool SPLIT, bool MOTION>
 __device__ __forceinline__ void render_gbuffer_body(const DevScene& s, const CamParams& cam, const CamParams& lastCam, const GBufWrite& g,
                                                     int y0, int y1, int tilesX, const TileSplit& ts) {
     // block = 4 waves, each an 8x8 tile; the block covers 32x8 pixels (a tile that was heavy last time: four waves of 4x4, rs_tilesplit.h)
@@ -31,17 +32,17 @@ __device__ __forceinline__ void render_gbuffer_body(const DevScene& s, const Cam
     Ray ray = camera_center_ray(cam, x, y);
     unsigned unionNodes = 0;
     Hit h = trace_closest_packet<SPLIT>(s, ray, inside, &unionNodes);       // all 64 lanes take part in the wave's walk
-    if (inside) gbuffer_store<TEX>(s, cam, lastCam, g, idx, ray, h);
+    if (inside) gbuffer_store<TEX, MOTION>(s, cam, lastCam, g, idx, ray, h);
     if (SPLIT) tile_split_report(ts.base, ts.rot, tile, helper, !helper && !mine, unionNodes);
 }
 
-template <bool TEX>
+template <bool TEX, bool MOTION>
 __global__ void __launch_bounds__(256, RS_WALK_WAVES) k_render_gbuffer(DevScene s, CamParams cam, CamParams lastCam, GBufWrite g, int y0, int y1, int tilesX) {
-    render_gbuffer_body<TEX, false>(s, cam, lastCam, g, y0, y1, tilesX, TileSplit{ nullptr, 0, 0 });
+    render_gbuffer_body<TEX, false, MOTION>(s, cam, lastCam, g, y0, y1, tilesX, TileSplit{ nullptr, 0, 0 });
 }
-template <bool TEX>
+template <bool TEX, bool MOTION>
 __global__ void __launch_bounds__(256, RS_WALK_WAVES) k_render_gbuffer_split(DevScene s, CamParams cam, CamParams lastCam, GBufWrite g, int y0, int y1, int tilesX, TileSplit ts) {
-    render_gbuffer_body<TEX, true>(s, cam, lastCam, g, y0, y1, tilesX, ts);
+    render_gbuffer_body<TEX, true, MOTION>(s, cam, lastCam, g, y0, y1, tilesX, ts);
 }
 
 namespace {
@@ -68,10 +69,10 @@ int launch_render(const rs_gbuffer* g, const rs_scene* scene, const rs_camera* c
     RS_TRY(rs_tile_split_prepare(&g->split[st == rs_stream() ? 0 : 1], (((long long)y0 << 20 | y1) << 12 | tilesX), tilesX * 4 * tilesY, tilesX * tilesY,
                                  rs_split_mode(alone, rs_launch_waves(tilesX, tilesY)), st, &ts, &helpers));
     const CamParams cp = rs_make_cam_params(cam), lp = rs_make_cam_params(lastCam);
-    rs_dispatch([&](auto TEX) {
-        if (ts.base) hipLaunchKernelGGL(k_render_gbuffer_split<TEX()>, dim3(helpers + tilesX * tilesY), dim3(256), 0, st, scene->dev, cp, lp, w, y0, y1, tilesX, ts);
-        else hipLaunchKernelGGL(k_render_gbuffer<TEX()>, dim3(tilesX * tilesY), dim3(256), 0, st, scene->dev, cp, lp, w, y0, y1, tilesX);
-    }, scene->textured);
+    rs_dispatch([&](auto TEX, auto MOTION) {
+        if (ts.base) hipLaunchKernelGGL((k_render_gbuffer_split<TEX(), MOTION()>), dim3(helpers + tilesX * tilesY), dim3(256), 0, st, scene->dev, cp, lp, w, y0, y1, tilesX, ts);
+        else hipLaunchKernelGGL((k_render_gbuffer<TEX(), MOTION()>), dim3(tilesX * tilesY), dim3(256), 0, st, scene->dev, cp, lp, w, y0, y1, tilesX);
+    }, scene->textured, scene->dev.prevVertices != nullptr);
     return 0;
 }
 

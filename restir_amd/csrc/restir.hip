@@ -139,7 +139,8 @@ __global__ void __launch_bounds__(256, RS_WALK_WAVES) k_primary_split(DevScene s
 // the single walk's cost per visit.  (Round 1's form walked both rays in one lane, one after the other at every node of an 8x8 tile's
 // union: it paid both slab tests per visit and, after the round-2 walk, measured 1.29 ms per frame against 1.20 for two launches and
 // 1.193 for this form.)  Tiles are 8x4 from the G-buffer rows [gy0, gy1), blocks 32x4 pixels; the shading ray is active on rows [y0, y1).
-template <bool TEX, bool SOBOL, bool SPLIT>
+// MOTION: the scene tracks motion (gbuffer_store, rs_internal.h)
+template <bool TEX, bool SOBOL, bool SPLIT, bool MOTION>
 __device__ __forceinline__ void gbuffer_primary_body(const DevScene& s, const CamParams& cam, const CamParams& lastCam, const GBufWrite& g, const SurfPlanes& sp, int looper,
                                                      int gy0, int gy1, int y0, int y1, int tilesX, unsigned long long* rayCount, const TileSplit& ts) {
     RS_SETPRIO(RS_PRIO_WALK);
@@ -159,7 +160,7 @@ __device__ __forceinline__ void gbuffer_primary_body(const DevScene& s, const Ca
     int shaded = 0;
     if (inside) {
         if (shading) shaded = primary_store<TEX>(s, sp, index, ray, h, rng.word());
-        else gbuffer_store<TEX>(s, cam, lastCam, g, index, ray, h);
+        else gbuffer_store<TEX, MOTION>(s, cam, lastCam, g, index, ray, h);
     }
     const unsigned long long ballotIn = __ballot(inside && shading), ballotSh = __ballot(shaded);
     if (lane == 0) {
@@ -169,15 +170,15 @@ __device__ __forceinline__ void gbuffer_primary_body(const DevScene& s, const Ca
     if (SPLIT) tile_split_report(ts.base, ts.rot, tile, helper, !helper && !mine, unionNodes);
 }
 
-template <bool TEX, bool SOBOL>
+template <bool TEX, bool SOBOL, bool MOTION>
 __global__ void __launch_bounds__(256, RS_WALK_WAVES) k_gbuffer_primary(DevScene s, CamParams cam, CamParams lastCam, GBufWrite g, SurfPlanes sp, int looper,
                                                                   int gy0, int gy1, int y0, int y1, int tilesX, unsigned long long* rayCount) {
-    gbuffer_primary_body<TEX, SOBOL, false>(s, cam, lastCam, g, sp, looper, gy0, gy1, y0, y1, tilesX, rayCount, TileSplit{ nullptr, 0, 0 });
+    gbuffer_primary_body<TEX, SOBOL, false, MOTION>(s, cam, lastCam, g, sp, looper, gy0, gy1, y0, y1, tilesX, rayCount, TileSplit{ nullptr, 0, 0 });
 }
-template <bool TEX, bool SOBOL>
+template <bool TEX, bool SOBOL, bool MOTION>
 __global__ void __launch_bounds__(256, RS_WALK_WAVES) k_gbuffer_primary_split(DevScene s, CamParams cam, CamParams lastCam, GBufWrite g, SurfPlanes sp, int looper,
                                                                   int gy0, int gy1, int y0, int y1, int tilesX, unsigned long long* rayCount, TileSplit ts) {
-    gbuffer_primary_body<TEX, SOBOL, true>(s, cam, lastCam, g, sp, looper, gy0, gy1, y0, y1, tilesX, rayCount, ts);
+    gbuffer_primary_body<TEX, SOBOL, true, MOTION>(s, cam, lastCam, g, sp, looper, gy0, gy1, y0, y1, tilesX, rayCount, ts);
 }
 
 // ---- phase A.2: RIS over the light table ----------------------------------------------------------
@@ -1131,10 +1132,10 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
         const CamParams lp = rs_make_cam_params(&d.lastCam);
         TileSplit ts; int helpers = 0;
         RS_TRY(rs_tile_split_prepare(hints, ((((long long)1 << 20 | d.y0) << 20 | d.y1) << 12 | tilesX) ^ ((long long)(y0 * 4099 + y1) << 44), tilesX * 4 * gTilesY, tilesX * gTilesY, p.splitMode, st, &ts, &helpers));
-        rs_dispatch([&](auto TEX, auto SOBOL) {
-            if (ts.base) hipLaunchKernelGGL((k_gbuffer_primary_split<TEX(), SOBOL()>), dim3(helpers + tilesX * gTilesY), dim3(256), 0, st, scene->dev, cp, lp, gw, sp, looper, d.y0, d.y1, y0, y1, tilesX, rayCounter, ts);
-            else hipLaunchKernelGGL((k_gbuffer_primary<TEX(), SOBOL()>), dim3(tilesX * gTilesY), dim3(256), 0, st, scene->dev, cp, lp, gw, sp, looper, d.y0, d.y1, y0, y1, tilesX, rayCounter);
-        }, tex, sobol);
+        rs_dispatch([&](auto TEX, auto SOBOL, auto MOTION) {
+            if (ts.base) hipLaunchKernelGGL((k_gbuffer_primary_split<TEX(), SOBOL(), MOTION()>), dim3(helpers + tilesX * gTilesY), dim3(256), 0, st, scene->dev, cp, lp, gw, sp, looper, d.y0, d.y1, y0, y1, tilesX, rayCounter, ts);
+            else hipLaunchKernelGGL((k_gbuffer_primary<TEX(), SOBOL(), MOTION()>), dim3(tilesX * gTilesY), dim3(256), 0, st, scene->dev, cp, lp, gw, sp, looper, d.y0, d.y1, y0, y1, tilesX, rayCounter);
+        }, tex, sobol, scene->dev.prevVertices != nullptr);
         RS_HIP(hipEventRecord(g->doneEv, aux));              // the planes are ready when this kernel is
         g->pending = true;
     }

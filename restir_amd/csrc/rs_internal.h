@@ -224,6 +224,14 @@ struct rs_scene {
     std::vector<int> hEmiLeafPrims;
     double emiMargin = 0.0;
     struct rs_refit* refit = nullptr;
+    // Motion tracking (rs_scene_set_motion_tracking, rs_scene_advance_motion): dev.prevVertices is dPrevVertices while tracking is on, null
+    // otherwise; the array stays allocated until rs_scene_destroy.  motionDirty: a geometry edit has been accepted since prevVertices was
+    // last made equal to the vertices, i.e. the two may differ.  The fences are the geometry edits' (rs_refit::before / after), the scene's own
+    // because a scene can be tracked before its first edit.
+    float* dPrevVertices = nullptr;
+    bool motionDirty = false;
+    hipEvent_t motionBefore[rs_context::kAux] = {};
+    hipEvent_t motionAfter = nullptr;
     std::vector<rs_material> hMaterials;
     float sumLightPower = 0.f;
     int numPrims = 0, bvhSize = 0, numLights = 0;
@@ -428,7 +436,10 @@ struct GBufWrite {
     float* albedo; int* motion; float* normal; int* primId; float* depth;
 };
 
-template <bool TEX>
+// MOTION (the scene tracks motion, DevScene::prevVertices): the motion plane asks where the hit point of the TRIANGLE was on last frame's
+// screen -- the hit's barycentrics on the triangle's previous pose, in hit_of_walk's expression and order, so that a triangle that has not
+// moved gives h.pos bit for bit -- instead of where the world point h.pos was.  A compile-time form: the untracked kernels keep their code.
+template <bool TEX, bool MOTION = false>
 __device__ __forceinline__ void gbuffer_store(const rs::DevScene& s, const rs::CamParams& cam, const rs::CamParams& lastCam, const GBufWrite& g,
                                               int idx, const rs::Ray& ray, const rs::Hit& h) {
     using namespace rs;
@@ -442,7 +453,12 @@ __device__ __forceinline__ void gbuffer_store(const rs::DevScene& s, const rs::C
         g.primId[idx] = matId;
         g.depth[idx] = length(ray.o - h.pos);            // glm::distance(pos, origin) = length(origin - pos)
         int lx, ly;
-        camera_raster_coord(lastCam, h.pos, lx, ly);
+        f3 prevPos = h.pos;
+        if (MOTION) {
+            const float* pv = s.prevVertices + (size_t)h.primId * 9;
+            prevPos = ld3(pv + 3) * h.bx + ld3(pv + 6) * h.by + ld3(pv) * (1.f - h.bx - h.by);
+        }
+        camera_raster_coord(lastCam, prevPos, lx, ly);
         g.motion[idx] = (lx >= 0 && lx < cam.width && ly >= 0 && ly < cam.height) ? ly * cam.width + lx : -1;
     }
     else {

@@ -68,6 +68,8 @@ int rs_refit_prepare(rs_scene* s);
 // emiTris: the edit names emitters, whose records in emiTris are written too; emiNodes: the emissive tree's boxes are refitted as well, on
 // the grid dev.emiBase / emiScale / emiMargin hold at the call
 int rs_refit_enqueue(rs_scene* s, int m, const int* dIds, const float* dVertices, const float* dNormals, bool emiTris, bool emiNodes, hipStream_t st);
+// rs_scene_set_motion_tracking / rs_scene_advance_motion: prevVertices = vertices (9 floats per triangle, both device arrays), on stream st
+int rs_motion_copy_enqueue(const float* vertices, float* prevVertices, size_t numPrims, hipStream_t st);
 // the host's side of rs_refit_boxes once the arguments have been checked: `parent` from rs_reference_chain_tables
 void rs_refit_boxes_host(int bvhSize, const float* vertices, const int* order0, const int* parent, float* boxes);
 // the same boxes when only the m primitives `ids` have moved (boxes: the exact unions of the vertices before the edit): the leaves'

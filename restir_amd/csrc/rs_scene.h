@@ -10,6 +10,8 @@
 //                                 intersectTriangle, src/intersections.h:20-21, hoisted to scene build;
 //                                 IEEE subtraction, so bit-identical) -> three dwordx4 per leaf test.
 //   vertices / normals            float[9] per triangle, as given (attribute fetch of the final hit only)
+//   prevVertices                  float[9] per triangle: the vertices at the last rs_scene_advance_motion (allocated when motion tracking is
+//                                 switched on, written by that call alone; null otherwise)
 //   materialIds, materials        as given (44-B Material records)
 //   lights     LightRec[numLights] 64 B: v0,v1,v2, geometric normal, unit radiance and the
 //                                 per-light constant pdfArea = lum(Le)/(area*2*pi) * sumLightPowerInv
@@ -98,6 +100,9 @@ struct DevScene {
     // by a guard of kSobolGuard zeros; null = the default thrust engine (SAMPLER_USE_SOBOL false).  rs_scene_set_sample_sequence.
     const uint32_t* sampleSeq;
     int sampleCount;
+    // The scene's pose at the last rs_scene_advance_motion: 9 floats per triangle, laid out like `vertices`; null = motion tracking off
+    // (rs_scene_set_motion_tracking).  Read by the MOTION form of gbuffer_store alone.  Last, so that every other field keeps its offset.
+    const float* prevVertices;
 };
 constexpr int kSobolGuard = 4096;
 

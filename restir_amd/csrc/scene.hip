@@ -375,6 +375,13 @@ void versions_free(rs_scene* s) {
     if (s->verStream) { (void)hipStreamDestroy(s->verStream); s->verStream = nullptr; }
 }
 
+// what rs_scene_set_motion_tracking allocated
+void motion_free(rs_scene* s) {
+    rs_dev_free(s->dPrevVertices);
+    for (hipEvent_t& e : s->motionBefore) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    if (s->motionAfter) { (void)hipEventDestroy(s->motionAfter); s->motionAfter = nullptr; }
+}
+
 // Edits are not recorded into graphs: a captured frame keeps the tables it was captured with
 int refuse_while_capturing(const char* msg) {
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
@@ -509,6 +516,7 @@ extern "C" int rs_scene_destroy(rs_scene* s) {
     for (float*& p : s->dTexData) rs_dev_free(p);
     versions_free(s);
     rs_refit_free(s);
+    motion_free(s);
     delete s;
     return 0;
 }
@@ -677,6 +685,23 @@ int fail_named(int code, const char* name, const char* text) {
     return rs_fail(code, msg.c_str());
 }
 
+// An edit in place of arrays that launches on the library's internal streams read (the geometry; the previous pose): the library stream waits,
+// by events, for what those streams have been handed so far (fence_before), the edit's kernels run on the library stream, and the next
+// launch of every internal stream waits for them (fence_after).  Launches enqueued before the edit read the old arrays, launches after it the new.
+int fence_before(hipEvent_t* before) {
+    rs_context* c = rs_ctx();
+    for (int i = 0; i < rs_context::kAux; i++)
+        if (c->aux[i]) { RS_HIP(hipEventRecord(before[i], c->aux[i])); RS_HIP(hipStreamWaitEvent(rs_stream(), before[i], 0)); }
+    return 0;
+}
+int fence_after(hipEvent_t after) {
+    rs_context* c = rs_ctx();
+    RS_HIP(hipEventRecord(after, rs_stream()));
+    for (int i = 0; i < rs_context::kAux; i++)
+        if (c->aux[i]) RS_HIP(hipStreamWaitEvent(c->aux[i], after, 0));
+    return 0;
+}
+
 int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals, bool emitters, const char* name) {
     if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
     if (count < 0 || (count > 0 && (!primIds || !vertices))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "count < 0 or null arrays");
@@ -797,19 +822,15 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
             s->emiMargin = emiMargin;
         }
     }
-    rs_context* c = rs_ctx();
     const hipStream_t st = rs_stream();
-    for (int i = 0; i < rs_context::kAux; i++)
-        if (c->aux[i]) { RS_HIP(hipEventRecord(r->before[i], c->aux[i])); RS_HIP(hipStreamWaitEvent(st, r->before[i], 0)); }
+    RS_TRY(fence_before(r->before));
     RS_HIP(hipMemcpyAsync(r->dStage, g.host, bytes, hipMemcpyHostToDevice, st));
     RS_HIP(hipEventRecord(g.copied, st));
     g.pending = true;
     r->stageNext = (r->stageNext + 1) % rs_refit::kStaging;
     RS_TRY(rs_refit_enqueue(s, m, reinterpret_cast<const int*>(r->dStage), reinterpret_cast<const float*>(r->dStage + offV),
                             normals ? reinterpret_cast<const float*>(r->dStage + offN) : nullptr, lamps, emiNodes, st));
-    RS_HIP(hipEventRecord(r->after, st));
-    for (int i = 0; i < rs_context::kAux; i++)
-        if (c->aux[i]) RS_HIP(hipStreamWaitEvent(c->aux[i], r->after, 0));
+    RS_TRY(fence_after(r->after));
 
     // the host's tables
     for (int j = 0; j < m; j++) {
@@ -826,6 +847,7 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
         s->dev.occRootHi = ld3(&s->hBoxes[r->root * 6 + 3]);
     }
     s->edits++;                                                  // retained G-buffer planes are not this scene's any more
+    if (s->dev.prevVertices) s->motionDirty = true;              // rs_scene_advance_motion has something to copy
     if (!lamps) return rs_after_launch(name);
     // the lights' version: light_records reads the vertices just written; launches from here on see new geometry and new lights alike
     s->hLightArea.swap(area);
@@ -845,6 +867,70 @@ extern "C" int rs_scene_set_triangles(rs_scene* s, int count, const int* primIds
 extern "C" int rs_scene_set_geometry(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals) {
     RS_SCOPE(s);
     return set_geometry(s, count, primIds, vertices, normals, true, "rs_scene_set_geometry");
+}
+
+// ---- motion tracking: the previous pose of the scene (include/restir_hip.h) ----
+namespace {
+
+// prevVertices = vertices, for every launch enqueued after this call.  Launches already handed to an auxiliary stream may read prevVertices
+// (a render that was deferred to it), so the copy sits behind the fences of a geometry edit (fence_before / fence_after).  A render that has only been recorded was launched before (rs_gbuffer_release_scene).
+int motion_copy(rs_scene* s, const char* name) {
+    RS_TRY(fence_before(s->motionBefore));
+    RS_TRY(rs_motion_copy_enqueue(s->dVertices, s->dPrevVertices, (size_t)s->numPrims, rs_stream()));
+    RS_TRY(fence_after(s->motionAfter));
+    s->motionDirty = false;
+    return rs_after_launch(name);
+}
+
+}  // namespace
+
+extern "C" int rs_scene_set_motion_tracking(rs_scene* s, int on) {
+    RS_SCOPE(s);
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_motion_tracking: null scene");
+    RS_TRY(refuse_while_capturing("rs_scene_set_motion_tracking: the library stream is being captured into a graph"));
+    const bool tracked = s->dev.prevVertices != nullptr;
+    if ((on != 0) == tracked) return 0;
+    if (on && !s->dPrevVertices) {
+        // everything that can fail comes first: a failure leaves the scene untracked and unchanged
+        int e = rs_dev_alloc(&s->dPrevVertices, (size_t)s->numPrims * 9);
+        for (hipEvent_t& ev : s->motionBefore) if (!e) e = rs_check_hip(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
+        if (!e) e = rs_check_hip(hipEventCreateWithFlags(&s->motionAfter, hipEventDisableTiming), "hipEventCreate");
+        if (e) { motion_free(s); return e; }
+    }
+    // a render that has only been recorded captures `dev` when it is launched: launch it now, in the form it was requested in
+    RS_TRY(rs_gbuffer_release_scene(s));
+    if (on) {
+        RS_TRY(motion_copy(s, "rs_scene_set_motion_tracking"));      // previous pose = current pose: the motion plane of an untracked scene
+        s->dev.prevVertices = s->dPrevVertices;
+        return 0;
+    }
+    s->dev.prevVertices = nullptr;
+    if (s->motionDirty) s->edits++;                     // the previous pose differed: the camera-only plane is not the retained one
+    s->motionDirty = false;
+    return 0;
+}
+
+extern "C" int rs_scene_advance_motion(rs_scene* s) {
+    RS_SCOPE(s);
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_advance_motion: null scene");
+    RS_TRY(refuse_while_capturing("rs_scene_advance_motion: the library stream is being captured into a graph"));
+    // untracked: nothing to do.  No accepted geometry edit since the last advance: prevVertices equals the vertices already, nothing is
+    // enqueued and retained G-buffer planes stay this scene's
+    if (!s->dev.prevVertices || !s->motionDirty) return 0;
+    RS_TRY(rs_gbuffer_release_scene(s));                // with the old previous pose
+    RS_TRY(motion_copy(s, "rs_scene_advance_motion"));
+    s->edits++;                                         // the motion plane of the frame after a move is not the one of the frame of the move
+    return 0;
+}
+
+extern "C" int rs_scene_download_prev_vertices(const rs_scene* s, float* out) {
+    RS_SCOPE(s);
+    if (!s || !out) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_prev_vertices: null argument");
+    if (!s->dev.prevVertices) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_prev_vertices: the scene does not track motion (rs_scene_set_motion_tracking)");
+    RS_TRY(refuse_while_capturing("rs_scene_download_prev_vertices: the library stream is being captured into a graph"));
+    RS_TRY(rs_synchronize());
+    RS_HIP(hipMemcpy(out, s->dPrevVertices, (size_t)s->numPrims * 9 * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // Test hooks of the refit (include/restir_hip.h): the device tables as they are, the grid they are quantised on, and grid_box itself.

@@ -19,6 +19,8 @@
 // of other triangles stops short of them and writes no byte of emiNodes / emiTris.  Its grid is its own and moves with the lamps: the host
 // lays it over the new emissive root box before the launches (scene.hip), so base, scale and margin are per record range (GridArgs).
 //
+// Next to the refit: k_copy_pose, the copy rs_scene_advance_motion makes of the vertices into the scene's previous pose (scene.hip).
+//
 // Hand-off inside a launch (the two climbs): a parent's box is only ever written by agent-scope atomic min / max and only ever read by
 // agent-scope atomic loads, both of which act on the one copy all eight XCDs agree on, never on a CU's L1; a child's merges are ordered
 // before its counter add (release, and the wave's outstanding memory operations drained), the second arrival's loads after its own add
@@ -185,6 +187,13 @@ __global__ void __launch_bounds__(256) k_grid_write(GridArgs a, size_t numRecord
     rec->x = q[0]; rec->y = q[1]; rec->z = q[2];
 }
 
+// rs_scene_advance_motion: the pose as it stands becomes the previous pose.  The whole array, one float per lane (DESIGN.md section 3:
+// 36 B per triangle read and written once costs less than a dirty list's staging copy and fence)
+__global__ void __launch_bounds__(256) k_copy_pose(const float* __restrict__ vertices, float* __restrict__ prevVertices, size_t count) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) prevVertices[i] = vertices[i];
+}
+
 template <typename T>
 int upload_table(T** dst, const std::vector<T>& src) {
     RS_TRY(rs_dev_alloc(dst, src.size()));
@@ -267,6 +276,13 @@ extern "C" int rs_refit_boxes(int numPrims, const float* vertices, int bvhSize, 
     RS_TRY(rs_reference_chain_tables(bvhSize, order0, parent, leafOf, numPrims));
     rs_refit_boxes_host(bvhSize, vertices, order0, parent.data(), boundingBoxes);
     return 0;
+}
+
+int rs_motion_copy_enqueue(const float* vertices, float* prevVertices, size_t numPrims, hipStream_t st) {
+    const size_t count = numPrims * 9;
+    if (count == 0) return 0;
+    hipLaunchKernelGGL(k_copy_pose, dim3(blocks_for(count)), dim3(256), 0, st, vertices, prevVertices, count);
+    return rs_check_hip(hipGetLastError(), "rs_scene_advance_motion: copy kernel");
 }
 
 void rs_refit_free(rs_scene* s) {
