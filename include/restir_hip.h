@@ -336,6 +336,44 @@ int  rs_scene_set_triangles(rs_scene* scene, int count, const int* primIds, cons
  * Temporal reservoirs keep the direction, distance and radiance they were drawn with for up to the M clamp's 20 frames, as in the
  * reference; rs_restir_reset drops them.  Adding or removing emitters still takes a new scene. */
 int  rs_scene_set_geometry(rs_scene* scene, int count, const int* primIds, const float* vertices, const float* normals);
+/* Rigid parts: sets of triangles that each move by one matrix (a door, a prop, a swinging lamp), with a rest pose the scene keeps on the
+ * host and on the device.  (The reference has no moving geometry: there is no reference line to cite.)
+ * rs_scene_define_parts: partFirst holds numParts + 1 offsets into primIds (0 first, non-decreasing; an empty part is allowed), primIds
+ * the parts' primitives, emitters among them if wanted, no primitive twice; restVertices / restNormals hold 9 floats per listed primitive
+ * in the order of primIds, or are both NULL: the rest pose is then the scene's pose as rs_scene_host_desc returns it at the call.  All arrays
+ * are copied: ids and rest pose to the host and to the device (72 bytes per listed triangle), the offsets to the host (a transform carries
+ * each named part's range to the device itself).  The call renders nothing and changes no geometry.  Calling it again replaces the definition;
+ * numParts == 0 drops it and frees the arrays.  Ordering: a definition that replaces or drops an earlier one waits for the device, as the
+ * first edit of a scene does, so a transform enqueued earlier keeps the old tables and a later one finds the new.
+ * Refused with RS_ERR_INVALID_ARGUMENT, the definition unchanged: a null scene, numParts < 0, null or bad offsets, an id out of range, a
+ * primitive listed twice (in one part or in two), exactly one of the two rest arrays NULL, a rest value that is not finite; with
+ * RS_ERR_UNSUPPORTED while the library stream is being captured into a graph.
+ * rs_scene_set_part_transforms: matrices16 holds one column-major 4x4 per entry of partIds.  The call does what
+ * rs_scene_set_geometry(scene, m, ids, v, n) does, where ids are the primitives of the named parts in the order of the call (a part named
+ * twice keeps its place and takes its last matrix) and v, n are rs_bake_matrix of each part's matrix over its rest arrays: the same
+ * refusals with the scene unchanged (a baked vertex or normal that is not finite, e.g. from a singular matrix; a vertex outside the
+ * creation-time root box; a light sampler left without finite positive power; RS_ERR_UNSUPPORTED while captured), the same
+ * rs_scene_host_desc and the same device tables afterwards, lights moved the same way, retained G-buffer planes invalidated, the
+ * previous pose of a tracked scene left alone, the same fences at the same point of the library stream.  Only the source of the records
+ * differs: the host stages one 112-byte record per named part (the matrix, the normal matrix computed once on the host with GLM's inverse,
+ * the part's range in the rest arrays, its offset in the output) through the ring of pinned buffers, and a kernel writes the
+ * ids | vertices | normals the refit reads from the device's rest pose, with the arithmetic of rs_bake_matrix, bit for bit.  The host
+ * still bakes the named triangles once itself: for the checks above, the light areas, and the tables rs_scene_host_desc returns.
+ * The rest pose is never written and transforms do not accumulate: a matrix always acts on the rest pose, so rounding does not drift over
+ * any number of frames.  rs_scene_set_triangles / rs_scene_set_geometry on a part's triangle is allowed and moves it until the next
+ * transform of that part puts it back on the baked rest pose.  count == 0, or only empty parts, succeeds and changes nothing.
+ * Additionally refused with RS_ERR_INVALID_ARGUMENT: no parts defined, a part id out of range, null arrays with count > 0.
+ * INTEGRATION.md section 3f has the frame loop; DESIGN.md section 3 the cost (every edit still refits the whole scene). */
+int  rs_scene_define_parts(rs_scene* scene, int numParts, const int* partFirst, const int* primIds, const float* restVertices, const float* restNormals);
+int  rs_scene_set_part_transforms(rs_scene* scene, int count, const int* partIds, const float* matrices16);
+/* Host only: the number of parts and of primitives listed in them (0, 0: none defined).  Either pointer may be NULL. */
+int  rs_scene_parts_info(const rs_scene* scene, int* numParts, int* numListedPrims);
+/* Test hooks.  rs_scene_download_part_rest waits as rs_synchronize does, then copies the DEVICE copies of the parts' primitive ids and
+ * rest pose out (sizes: rs_scene_parts_info; any array may be NULL).  RS_ERR_INVALID_ARGUMENT: a null scene, or no parts defined;
+ * RS_ERR_UNSUPPORTED while the library stream is being captured.  rs_debug_scene_staged_bytes: the bytes the most recent accepted
+ * geometry edit of either kind copied from the host to the device (0 before the first); host only. */
+int  rs_scene_download_part_rest(const rs_scene* scene, int* primIds, float* restVertices, float* restNormals);
+int  rs_debug_scene_staged_bytes(const rs_scene* scene, size_t* bytes);
 /* Motion tracking: the previous pose of the scene, for the G-buffer's motion plane.  (The reference has no moving geometry: there is no
  * reference line to cite.  Its renderGBuffer, src/gbuffer.cu:49-54, asks where the hit's world point was on last frame's screen.)
  * A tracked scene keeps a second vertex array on the device, 36 bytes per triangle: the vertices as they stood at the last
@@ -445,11 +483,23 @@ typedef struct rs_scene_file_view {
 int  rs_scene_file_load(const char* path, rs_scene_file** file);
 int  rs_scene_file_get(const rs_scene_file* file, rs_scene_file_view* view);
 int  rs_scene_file_free(rs_scene_file* file);
+/* The "Object" blocks of the loaded file, in file order (skipped objects are not among them): firstPrim has *numObjects + 1 entries and
+ * tiles [0, numPrims) of the view; transforms16 holds each object's load-time matrix (16 floats, column-major); meshVertices[i] /
+ * meshNormals[i] point to object i's object-space, de-indexed mesh, 9 floats per triangle (objects that name one mesh file share it).
+ * This is what turns objects into the parts of rs_scene_define_parts: primIds is a range, the rest pose is the mesh, and
+ * rs_build_transformation_matrix of a new translation / rotation / scale re-poses the object with the bits the loader would have
+ * produced.  Pointers stay valid until rs_scene_file_free.  RS_ERR_INVALID_ARGUMENT: a null argument. */
+int  rs_scene_file_objects(const rs_scene_file* file, int* numObjects, const int** firstPrim, const float** transforms16,
+                           const float* const** meshVertices, const float* const** meshNormals);
 /* Math::buildTransformationMatrix (src/mathUtil.cpp:13-20): column-major 4x4, rotation in degrees. */
 int  rs_build_transformation_matrix(const float* translation, const float* rotation, const float* scale, float* out16);
 /* scene.cpp:167-168 for one instance: vec3(transform * vec4(v, 1)) and normalize(transpose(mat3(inverse(transform))) * n). */
 int  rs_bake_instance(const float* translation, const float* rotation, const float* scale, int n,
                       const float* vertsIn, const float* normalsIn, float* vertsOut, float* normalsOut);
+/* The same for a caller-supplied column-major 4x4 (n corners, 3 floats each): rs_bake_instance(t, r, s, ...) and rs_bake_matrix of
+ * rs_build_transformation_matrix(t, r, s) return the same bits, and so does the kernel behind rs_scene_set_part_transforms.  Values
+ * are not checked: a singular matrix yields non-finite normals.  RS_ERR_INVALID_ARGUMENT: a null matrix, n < 0, a null array with n > 0. */
+int  rs_bake_matrix(const float* matrix16, int n, const float* vertsIn, const float* normalsIn, float* vertsOut, float* normalsOut);
 
 /* ---- scene services, batched (for parity tests of DevScene::intersect / testOcclusion) */
 /* DevScene::intersect (src/scene.h:245-284): n rays of 6 floats (origin, direction), device ptrs.

@@ -139,6 +139,7 @@ EXPORTS = [
     "rs_copy_image_to_pbo", "rs_copy_image2_to_pbo", "rs_copy_imagef_to_pbo", "rs_copy_imagei_to_pbo", "rs_eaw_create", "rs_eaw_destroy", "rs_eaw_set_params", "rs_eaw_get_params", "rs_eaw_set_tiled", "rs_eaw_set_fused", "rs_svgf_set_params", "rs_svgf_get_params", "rs_svgf_set_tiled", "rs_svgf_set_fused", "rs_eaw_filter", "rs_eaw_positions_rows", "rs_eaw_level_rows", "rs_modulate_albedo",
     "rs_add_image", "rs_add_image3", "rs_comm_create_rccl", "rs_comm_create_rccl_lib", "rs_comm_create", "rs_comm_destroy", "rs_comm_self_exchange", "rs_strips_create", "rs_strips_destroy", "rs_strips_rows", "rs_strips_set_comm_stream", "rs_strips_set_gbuffer_halo", "rs_strips_set_light_tracking", "rs_strips_frame", "rs_strips_eaw_filter", "rs_strips_svgf_filter", "rs_strips_exchange_svgf_history", "rs_strips_exchange_history", "rs_strips_gather", "rs_strips_gather_begin", "rs_strips_gather_end", "rs_strips_enable_timing", "rs_strips_halo_wait_ms",
     "rs_scene_file_load", "rs_scene_file_get", "rs_scene_file_free", "rs_build_transformation_matrix", "rs_bake_instance",
+    "rs_bake_matrix", "rs_scene_file_objects", "rs_scene_define_parts", "rs_scene_set_part_transforms", "rs_scene_parts_info", "rs_scene_download_part_rest", "rs_debug_scene_staged_bytes",
 ]
 
 _lib = None
@@ -183,6 +184,13 @@ def lib():
     L.rs_scene_file_free.argtypes = [vp]
     L.rs_build_transformation_matrix.argtypes = [vp, vp, vp, vp]
     L.rs_bake_instance.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp]
+    L.rs_bake_matrix.argtypes = [vp, ci, vp, vp, vp, vp]
+    L.rs_scene_file_objects.argtypes = [vp, C.POINTER(ci), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.rs_scene_define_parts.argtypes = [vp, ci, vp, vp, vp, vp]
+    L.rs_scene_set_part_transforms.argtypes = [vp, ci, vp, vp]
+    L.rs_scene_parts_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+    L.rs_scene_download_part_rest.argtypes = [vp, vp, vp, vp]
+    L.rs_debug_scene_staged_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rs_scene_host_desc.argtypes = [vp, C.POINTER(SceneDesc)]
     L.rs_scene_destroy.argtypes = [vp]
     L.rs_scene_set_emission.argtypes = [vp, ci, vp, vp]
@@ -564,6 +572,16 @@ def bake_instance(translation, rotation, scale, vertices, normals):
     return vo, no
 
 
+def bake_matrix(matrix, vertices, normals):
+    """rs_bake_matrix: bake_instance for a caller-supplied (4, 4) float32 matrix, [column][row]."""
+    m = np.ascontiguousarray(matrix, np.float32).reshape(16)
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    vo, no = np.zeros_like(v), np.zeros_like(n)
+    check(lib().rs_bake_matrix(_p(m), len(v), _p(v), _p(n), _p(vo), _p(no)))
+    return vo, no
+
+
 class SceneFile:
     """Scene::Scene(filename) (src/scene.cpp:96-131): the parsed scene as flat host arrays (copies)."""
 
@@ -590,6 +608,20 @@ class SceneFile:
             self.iterations, self.trace_depth = v.iterations, v.traceDepth
             self.image_name = (v.imageName or b"").decode()
             self.num_skipped_objects = v.numSkippedObjects
+            # rs_scene_file_objects: per "Object" block dict(first, count, transform (4, 4), vertices, normals (count, 3, 3) in object space,
+            # mesh = (address of the shared mesh's vertices, of its normals))
+            count, first, tr, mv, mn = C.c_int(0), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+            check(lib().rs_scene_file_objects(h, C.byref(count), C.byref(first), C.byref(tr), C.byref(mv), C.byref(mn)))
+            firsts = arr(first.value, count.value + 1, np.int32)
+            trs = arr(tr.value, count.value * 16, np.float32).reshape(-1, 4, 4)
+            mvp, mnp = C.cast(mv, C.POINTER(C.c_void_p)), C.cast(mn, C.POINTER(C.c_void_p))
+            self.object_first = firsts
+            self.objects = []
+            for i in range(count.value):
+                k = int(firsts[i + 1] - firsts[i])
+                self.objects.append(dict(first=int(firsts[i]), count=k, transform=trs[i], mesh=(mvp[i], mnp[i]),
+                                         vertices=arr(mvp[i], k * 9, np.float32).reshape(k, 3, 3),
+                                         normals=arr(mnp[i], k * 9, np.float32).reshape(k, 3, 3)))
         finally:
             lib().rs_scene_file_free(h)
 
@@ -710,6 +742,47 @@ class Scene:
         """rs_scene_set_geometry: set_triangles that also takes emissive triangles; an edit that names one rebuilds the light sampler and the
         light records and refits the emissive tree at the same point of the library stream."""
         self._set_vertices(lib().rs_scene_set_geometry, "set_geometry", prim_ids, vertices, normals)
+
+    def define_parts(self, parts, rest_vertices=None, rest_normals=None):
+        """rs_scene_define_parts: `parts` is a list of primitive-id lists (an empty list drops the definition); the rest pose is
+        (listed, 3, 3) float32 vertices and normals in the order of the concatenated ids, or None: the scene's current pose."""
+        first = np.zeros(len(parts) + 1, np.int32)
+        first[1:] = np.cumsum([len(p) for p in parts])
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int32).reshape(-1) for p in parts]) if parts else np.zeros(0, np.int32), np.int32)
+        v = None if rest_vertices is None else np.ascontiguousarray(rest_vertices, np.float32).reshape(-1, 9)
+        n = None if rest_normals is None else np.ascontiguousarray(rest_normals, np.float32).reshape(-1, 9)
+        for a in (v, n):
+            if a is not None and a.shape[0] != ids.size:
+                raise ValueError("define_parts: three rest vertices and three rest normals per listed primitive")
+        check(lib().rs_scene_define_parts(self.handle, len(parts), _p(first), _p(ids), None if v is None else _p(v), None if n is None else _p(n)))
+
+    def set_part_transforms(self, part_ids, matrices):
+        """rs_scene_set_part_transforms: one (4, 4) float32 matrix, [column][row], per entry of `part_ids`; does what set_geometry does
+        with the parts' rest pose baked by those matrices, the baking done on the device (one small record per part crosses the bus)."""
+        ids = np.ascontiguousarray(part_ids, np.int32).reshape(-1)
+        m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 16)
+        if m.shape[0] != ids.size:
+            raise ValueError("set_part_transforms: one matrix per part id")
+        check(lib().rs_scene_set_part_transforms(self.handle, int(ids.size), _p(ids), _p(m)))
+
+    def parts_info(self):
+        """rs_scene_parts_info: (number of parts, number of primitives listed in them); (0, 0) when none are defined."""
+        a, b = C.c_int(0), C.c_int(0)
+        check(lib().rs_scene_parts_info(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def part_rest(self):
+        """rs_scene_download_part_rest (test hook): the device copies of (primitive ids, rest vertices, rest normals)."""
+        n = self.parts_info()[1]
+        ids, v, nn = np.zeros(n, np.int32), np.zeros((n, 3, 3), np.float32), np.zeros((n, 3, 3), np.float32)
+        check(lib().rs_scene_download_part_rest(self.handle, _p(ids), _p(v), _p(nn)))
+        return ids, v, nn
+
+    def staged_bytes(self):
+        """rs_debug_scene_staged_bytes (test hook): bytes the last accepted geometry edit copied from the host to the device."""
+        b = C.c_size_t(0)
+        check(lib().rs_debug_scene_staged_bytes(self.handle, C.byref(b)))
+        return b.value
 
     def set_motion_tracking(self, on=True):
         """rs_scene_set_motion_tracking: the scene keeps its pose at the last advance_motion() on the device, and the G-buffer's motion

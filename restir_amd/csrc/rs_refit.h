@@ -9,6 +9,7 @@
 #pragma once
 
 #include "rs_internal.h"
+#include "rs_bake.h"
 
 namespace rs {
 
@@ -47,8 +48,9 @@ struct rs_refit {
     static constexpr int kStaging = 4;
     struct Stage { char* host = nullptr; size_t capacity = 0; hipEvent_t copied = nullptr; bool pending = false; } stage[kStaging];
     int stageNext = 0;
-    char* dStage = nullptr;          // read by the scatter kernel, in the order of the library stream
-    size_t dStageCapacity = 0;
+    char* dStage = nullptr;          // read by the scatter kernel, in the order of the library stream: ids | vertices | normals, copied from a
+    size_t dStageCapacity = 0;       // staging buffer or written by k_bake_parts from the part records, which then follow them in this buffer
+    size_t stagedBytes = 0;          // what the last accepted edit copied from the host (rs_debug_scene_staged_bytes)
     std::vector<unsigned> lastStamp; // [numPrims] the edit that named the primitive last (a repeated id takes its last record)
     std::vector<int> lastIndex;      //            ... and its place in that edit's compacted list
     unsigned stamp = 0;
@@ -61,7 +63,29 @@ struct rs_refit {
     size_t root = 0;
 };
 
+// The rigid parts of a scene (rs_scene_define_parts): which primitives move by one matrix, and their rest pose.  The device copies are
+// read by k_bake_parts alone and never written after the definition; the part offsets stay on the host, whose records (rs::PartRec) carry
+// each named part's range to the device.
+struct rs_parts {
+    std::vector<int> first;          // [numParts + 1] offsets into primIds
+    std::vector<int> primIds;        // the parts' primitives, concatenated; no primitive twice
+    std::vector<float> restVertices, restNormals;       // 9 floats per listed primitive
+    int* dPrimIds = nullptr;
+    float* dRestVertices = nullptr;
+    float* dRestNormals = nullptr;
+    // scratch of one rs_scene_set_part_transforms: the records, and the host's own baking of the named parts (checks, light areas, mirror)
+    std::vector<rs::PartRec> recs;
+    std::vector<int> recOf, ids;     // recOf: [numParts] the record of a part named by the call, by stamp
+    std::vector<unsigned> recStamp;
+    unsigned stamp = 0;
+    std::vector<float> vertices, normals;
+};
+
 // scene_refit.hip
+// one rs_scene_set_part_transforms, on stream st, before rs_refit_enqueue: the triangles of the numRecs parts dRecs baked from the rest
+// arrays into dIds | dVertices | dNormals, m triangles in all, in the layout a staged edit has
+int rs_bake_parts_enqueue(const rs_parts* parts, int numRecs, const rs::PartRec* dRecs, size_t m, int* dIds, float* dVertices, float* dNormals, hipStream_t st);
+void rs_parts_free(rs_parts* parts);                    // (null: nothing to do) rs_scene_destroy, rs_scene_define_parts
 // first edit: builds and uploads the tables, allocates the scratch (waits for the device once: it reads the grid-box trees back)
 int rs_refit_prepare(rs_scene* s);
 // one edit, on stream st: scatters the m staged triangles (ids, 9 floats of vertices each, 9 of normals or null: all device pointers) and refits.

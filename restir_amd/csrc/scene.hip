@@ -516,6 +516,7 @@ extern "C" int rs_scene_destroy(rs_scene* s) {
     for (float*& p : s->dTexData) rs_dev_free(p);
     versions_free(s);
     rs_refit_free(s);
+    rs_parts_free(s->parts);
     motion_free(s);
     delete s;
     return 0;
@@ -702,7 +703,13 @@ int fence_after(hipEvent_t after) {
     return 0;
 }
 
-int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals, bool emitters, const char* name) {
+// parts (rs_scene_set_part_transforms): the edit's records are not copied from the host but written on the device, by k_bake_parts from the
+// numRecs part records `recs` (which alone are staged) and the scene's rest pose; primIds / vertices / normals are then the host's own baking
+// of the same triangles, every id once, in the order the kernel writes them -- for the checks, the light areas and the host's tables.
+struct PartSource { int numRecs; const PartRec* recs; };
+
+int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals, bool emitters, const char* name,
+                 const PartSource* parts = nullptr) {
     if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
     if (count < 0 || (count > 0 && (!primIds || !vertices))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "count < 0 or null arrays");
     const bool bounded = s->dOccNodes != nullptr;       // the 16-bit grid of the grid-box trees lies over the box the scene was created with
@@ -744,29 +751,40 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
     auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t offV = up((size_t)m * sizeof(int)), offN = offV + up((size_t)m * 9 * sizeof(float));
     const size_t bytes = offN + (normals ? up((size_t)m * 9 * sizeof(float)) : 0);
+    // what crosses the bus: the records themselves, or the part records, which follow the records they expand to in the device buffer
+    const size_t staged = parts ? (size_t)parts->numRecs * sizeof(PartRec) : bytes, onDevice = parts ? bytes + staged : bytes;
     rs_refit::Stage& g = r->stage[r->stageNext];
     if (g.pending) { RS_HIP(hipEventSynchronize(g.copied)); g.pending = false; }      // the ring is full of edits whose copies have not finished
-    if (g.capacity < bytes) {
+    if (g.capacity < staged) {
         if (g.host) { (void)hipHostFree(g.host); g.host = nullptr; g.capacity = 0; }
         size_t cap = 4096;
-        while (cap < bytes) cap *= 2;
+        while (cap < staged) cap *= 2;
         RS_HIP(hipHostMalloc((void**)&g.host, cap, hipHostMallocDefault));
         g.capacity = cap;
     }
-    if (r->dStageCapacity < bytes) {                     // (hipFree waits for the device: no earlier edit still reads the old buffer)
+    if (r->dStageCapacity < onDevice) {                  // (hipFree waits for the device: no earlier edit still reads the old buffer)
         rs_dev_free(r->dStage);
         r->dStageCapacity = 0;
-        RS_TRY(rs_dev_alloc(&r->dStage, g.capacity));
-        r->dStageCapacity = g.capacity;
+        size_t cap = 4096;
+        while (cap < onDevice) cap *= 2;
+        RS_TRY(rs_dev_alloc(&r->dStage, cap));
+        r->dStageCapacity = cap;
     }
-    int* ids = reinterpret_cast<int*>(g.host);
-    float* vs = reinterpret_cast<float*>(g.host + offV);
-    float* ns = reinterpret_cast<float*>(g.host + offN);
-    for (int i = 0; i < count; i++) {
-        const size_t p = (size_t)primIds[i], j = (size_t)r->lastIndex[p];
-        ids[j] = primIds[i];
-        std::memcpy(vs + j * 9, vertices + (size_t)i * 9, 9 * sizeof(float));
-        if (normals) std::memcpy(ns + j * 9, normals + (size_t)i * 9, 9 * sizeof(float));
+    const int* ids = primIds;
+    const float* vs = vertices;
+    const float* ns = normals;
+    if (parts) std::memcpy(g.host, parts->recs, staged);
+    else {
+        int* hi = reinterpret_cast<int*>(g.host);
+        float* hv = reinterpret_cast<float*>(g.host + offV);
+        float* hn = reinterpret_cast<float*>(g.host + offN);
+        for (int i = 0; i < count; i++) {
+            const size_t p = (size_t)primIds[i], j = (size_t)r->lastIndex[p];
+            hi[j] = primIds[i];
+            std::memcpy(hv + j * 9, vertices + (size_t)i * 9, 9 * sizeof(float));
+            if (normals) std::memcpy(hn + j * 9, normals + (size_t)i * 9, 9 * sizeof(float));
+        }
+        ids = hi; vs = hv; ns = hn;
     }
     // where a primitive's vertices are once the edit has been applied (so far only the staging buffer has been written)
     auto edited = [&](size_t p) { return r->lastStamp[p] == r->stamp ? vs + (size_t)r->lastIndex[p] * 9 : &s->hVertices[p * 9]; };
@@ -824,10 +842,13 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
     }
     const hipStream_t st = rs_stream();
     RS_TRY(fence_before(r->before));
-    RS_HIP(hipMemcpyAsync(r->dStage, g.host, bytes, hipMemcpyHostToDevice, st));
+    RS_HIP(hipMemcpyAsync(r->dStage + (parts ? bytes : 0), g.host, staged, hipMemcpyHostToDevice, st));
     RS_HIP(hipEventRecord(g.copied, st));
     g.pending = true;
     r->stageNext = (r->stageNext + 1) % rs_refit::kStaging;
+    r->stagedBytes = staged;
+    if (parts) RS_TRY(rs_bake_parts_enqueue(s->parts, parts->numRecs, reinterpret_cast<const PartRec*>(r->dStage + bytes), (size_t)m, reinterpret_cast<int*>(r->dStage),
+                                            reinterpret_cast<float*>(r->dStage + offV), reinterpret_cast<float*>(r->dStage + offN), st));
     RS_TRY(rs_refit_enqueue(s, m, reinterpret_cast<const int*>(r->dStage), reinterpret_cast<const float*>(r->dStage + offV),
                             normals ? reinterpret_cast<const float*>(r->dStage + offN) : nullptr, lamps, emiNodes, st));
     RS_TRY(fence_after(r->after));
@@ -867,6 +888,126 @@ extern "C" int rs_scene_set_triangles(rs_scene* s, int count, const int* primIds
 extern "C" int rs_scene_set_geometry(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals) {
     RS_SCOPE(s);
     return set_geometry(s, count, primIds, vertices, normals, true, "rs_scene_set_geometry");
+}
+
+// ---- rigid parts (include/restir_hip.h) ----
+// The definition is replaced behind a wait for the device (rs_synchronize, as the first edit of a scene waits once): a transform enqueued
+// earlier has finished with the old tables, a later one finds the new.  Nothing of the scene's geometry changes.
+extern "C" int rs_scene_define_parts(rs_scene* s, int numParts, const int* partFirst, const int* primIds, const float* restVertices, const float* restNormals) {
+    RS_SCOPE(s);
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: null scene");
+    if (numParts < 0 || (numParts > 0 && !partFirst)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: numParts < 0 or null offsets");
+    if ((restVertices == nullptr) != (restNormals == nullptr)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: rest vertices without rest normals, or the reverse");
+    if (numParts > 0 && partFirst[0] != 0) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: the first offset is not 0");
+    for (int i = 0; i < numParts; i++)
+        if (partFirst[i + 1] < partFirst[i]) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: offsets that decrease");
+    const size_t listed = numParts > 0 ? (size_t)partFirst[numParts] : 0;
+    if (listed > 0 && !primIds) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: null primitive ids");
+    {
+        std::vector<char> seen((size_t)s->numPrims, 0);
+        for (size_t i = 0; i < listed; i++) {
+            const int p = primIds[i];
+            if (p < 0 || p >= s->numPrims) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: a primitive id out of range");
+            if (seen[(size_t)p]) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: a primitive listed twice");
+            seen[(size_t)p] = 1;
+        }
+    }
+    if (restVertices)
+        for (size_t i = 0; i < listed * 9; i++)
+            if (!std::isfinite(restVertices[i]) || !std::isfinite(restNormals[i])) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: a rest value that is not finite");
+    RS_TRY(refuse_while_capturing("rs_scene_define_parts: the library stream is being captured into a graph"));
+    if (numParts == 0) {
+        if (s->parts) { RS_TRY(rs_synchronize()); rs_parts_free(s->parts); s->parts = nullptr; }
+        return 0;
+    }
+
+    rs_parts* p = new rs_parts();
+    p->first.assign(partFirst, partFirst + numParts + 1);
+    p->primIds.assign(primIds, primIds + listed);
+    p->restVertices.resize(listed * 9); p->restNormals.resize(listed * 9);
+    for (size_t i = 0; i < listed; i++) {
+        // the scene's own pose, or the caller's arrays
+        std::memcpy(&p->restVertices[i * 9], restVertices ? restVertices + i * 9 : &s->hVertices[(size_t)primIds[i] * 9], 9 * sizeof(float));
+        std::memcpy(&p->restNormals[i * 9], restNormals ? restNormals + i * 9 : &s->hNormals[(size_t)primIds[i] * 9], 9 * sizeof(float));
+    }
+    p->recOf.assign((size_t)numParts, 0);
+    p->recStamp.assign((size_t)numParts, 0u);
+    int e = upload(&p->dPrimIds, p->primIds);
+    if (!e) e = upload(&p->dRestVertices, p->restVertices);
+    if (!e) e = upload(&p->dRestNormals, p->restNormals);
+    if (!e && s->parts) e = rs_synchronize();           // a transform in flight reads the tables that are about to be freed
+    if (e) { rs_parts_free(p); return e; }              // (the definition stays what it was)
+    rs_parts_free(s->parts);
+    s->parts = p;
+    return 0;
+}
+
+// The named parts' records (a part named twice keeps its place and takes its last matrix; an empty part has none), the host's own baking of
+// their triangles, and then rs_scene_set_geometry's implementation with the records written on the device.
+extern "C" int rs_scene_set_part_transforms(rs_scene* s, int count, const int* partIds, const float* matrices16) {
+    RS_SCOPE(s);
+    const char* name = "rs_scene_set_part_transforms";
+    if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
+    if (count < 0 || (count > 0 && (!partIds || !matrices16))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "count < 0 or null arrays");
+    rs_parts* p = s->parts;
+    if (!p) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "the scene has no parts (rs_scene_define_parts)");
+    const int numParts = (int)p->first.size() - 1;
+    for (int i = 0; i < count; i++)
+        if (partIds[i] < 0 || partIds[i] >= numParts) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a part id out of range");
+
+    if (++p->stamp == 0u) { std::fill(p->recStamp.begin(), p->recStamp.end(), 0u); p->stamp = 1u; }
+    p->recs.clear();
+    for (int i = 0; i < count; i++) {
+        const size_t part = (size_t)partIds[i];
+        const int first = p->first[part], n = p->first[part + 1] - first;
+        if (n == 0) continue;
+        if (p->recStamp[part] != p->stamp) {
+            p->recStamp[part] = p->stamp;
+            p->recOf[part] = (int)p->recs.size();
+            PartRec rec{};
+            rec.restFirst = first; rec.count = n;
+            p->recs.push_back(rec);
+        }
+        std::memcpy(p->recs[(size_t)p->recOf[part]].m, matrices16 + (size_t)i * 16, 16 * sizeof(float));
+    }
+    size_t m = 0;
+    for (PartRec& rec : p->recs) { rec.outFirst = (int)m; m += (size_t)rec.count; }
+    p->ids.resize(m); p->vertices.resize(m * 9); p->normals.resize(m * 9);
+    for (PartRec& rec : p->recs) {
+        rs_bake_normal_matrix(rec.m, rec.nm);
+        const size_t in = (size_t)rec.restFirst, out = (size_t)rec.outFirst;
+        std::memcpy(&p->ids[out], &p->primIds[in], (size_t)rec.count * sizeof(int));
+        rs_bake_corners(rec.m, rec.nm, (size_t)rec.count * 3, &p->restVertices[in * 9], &p->restNormals[in * 9], &p->vertices[out * 9], &p->normals[out * 9]);
+    }
+    const PartSource src{ (int)p->recs.size(), p->recs.data() };
+    return set_geometry(s, (int)m, p->ids.data(), p->vertices.data(), p->normals.data(), true, name, &src);
+}
+
+extern "C" int rs_scene_parts_info(const rs_scene* s, int* numParts, int* numListedPrims) {
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_parts_info: null scene");
+    if (numParts) *numParts = s->parts ? (int)s->parts->first.size() - 1 : 0;
+    if (numListedPrims) *numListedPrims = s->parts ? (int)s->parts->primIds.size() : 0;
+    return 0;
+}
+
+extern "C" int rs_scene_download_part_rest(const rs_scene* s, int* primIds, float* restVertices, float* restNormals) {
+    RS_SCOPE(s);
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_part_rest: null scene");
+    const rs_parts* p = s->parts;
+    if (!p) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_part_rest: the scene has no parts (rs_scene_define_parts)");
+    RS_TRY(refuse_while_capturing("rs_scene_download_part_rest: the library stream is being captured into a graph"));
+    RS_TRY(rs_synchronize());
+    const size_t n = p->primIds.size();
+    if (n && primIds) RS_HIP(hipMemcpy(primIds, p->dPrimIds, n * sizeof(int), hipMemcpyDeviceToHost));
+    if (n && restVertices) RS_HIP(hipMemcpy(restVertices, p->dRestVertices, n * 9 * sizeof(float), hipMemcpyDeviceToHost));
+    if (n && restNormals) RS_HIP(hipMemcpy(restNormals, p->dRestNormals, n * 9 * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int rs_debug_scene_staged_bytes(const rs_scene* s, size_t* bytes) {
+    if (!s || !bytes) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_scene_staged_bytes: null argument");
+    *bytes = s->refit ? s->refit->stagedBytes : 0;
+    return 0;
 }
 
 // ---- motion tracking: the previous pose of the scene (include/restir_hip.h) ----

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "rs_internal.h"
+#include "rs_bake.h"
 
 using namespace rs;
 
@@ -106,23 +107,11 @@ M4 inverse(const M4& m) {
     return inv;
 }
 
-// scene.cpp:169-170 with transform / normalMat of loadModel (:273-278)
+// scene.cpp:169-170 with transform / normalMat of loadModel (:273-278); the corners' arithmetic is rs_bake.h's, shared with the device
 void bake(const M4& tr, int n, const float* vertsIn, const float* normalsIn, float* vertsOut, float* normalsOut) {
-    const M4 inv = inverse(tr);
-    float nm[3][3];                                                   // transpose(mat3(transfInv)), columns
-    for (int j = 0; j < 3; j++) for (int k = 0; k < 3; k++) nm[j][k] = inv.c[k][j];
-    for (int i = 0; i < n; i++) {
-        const f3 v = ld3(vertsIn + (size_t)i * 3), nn = ld3(normalsIn + (size_t)i * 3);
-        f3 o;                                                         // mat4 * vec4 (type_mat4x4.inl:612-628)
-        o.x = (tr.c[0][0] * v.x + tr.c[1][0] * v.y) + (tr.c[2][0] * v.z + tr.c[3][0] * 1.f);
-        o.y = (tr.c[0][1] * v.x + tr.c[1][1] * v.y) + (tr.c[2][1] * v.z + tr.c[3][1] * 1.f);
-        o.z = (tr.c[0][2] * v.x + tr.c[1][2] * v.y) + (tr.c[2][2] * v.z + tr.c[3][2] * 1.f);
-        st3(vertsOut + (size_t)i * 3, o);
-        const f3 q = mk3(nm[0][0] * nn.x + nm[1][0] * nn.y + nm[2][0] * nn.z,
-                         nm[0][1] * nn.x + nm[1][1] * nn.y + nm[2][1] * nn.z,
-                         nm[0][2] * nn.x + nm[1][2] * nn.y + nm[2][2] * nn.z);
-        st3(normalsOut + (size_t)i * 3, normalize(q));
-    }
+    float nm[9];
+    rs_bake_normal_matrix(&tr.c[0][0], nm);
+    rs_bake_corners(&tr.c[0][0], nm, (size_t)(n > 0 ? n : 0), vertsIn, normalsIn, vertsOut, normalsOut);
 }
 
 // ---- text input ----------------------------------------------------------------------------------------------------
@@ -1410,6 +1399,13 @@ int load_image(const std::string& path, bool flipRows, std::vector<float>& data,
 
 }  // namespace
 
+void rs_bake_normal_matrix(const float* matrix16, float* nm9) {
+    M4 m;
+    std::memcpy(&m, matrix16, sizeof m);
+    const M4 inv = inverse(m);
+    for (int j = 0; j < 3; j++) for (int k = 0; k < 3; k++) nm9[j * 3 + k] = inv.c[k][j];      // transpose(mat3(transfInv)), columns
+}
+
 struct rs_scene_file {
     std::vector<float> vertices, normals, texcoords;
     std::vector<int> materialIds;
@@ -1422,6 +1418,12 @@ struct rs_scene_file {
     int iterations = 0, traceDepth = 0;
     std::string imageName;
     std::vector<std::string> skipped;                                  // objects whose mesh file could not be opened
+    // rs_scene_file_objects: the loaded "Object" blocks in file order -- the first primitive of each (and numPrims last), its load-time
+    // matrix, and its object-space mesh in the pool (objects that name one mesh file share one entry; a map's nodes do not move)
+    std::map<std::string, Mesh> meshPool;                              // Resource::meshDataPool
+    std::vector<int> objFirstPrim;
+    std::vector<float> objTransforms;
+    std::vector<const float*> objMeshVertices, objMeshNormals;
 };
 
 namespace {
@@ -1472,7 +1474,28 @@ int rs_bake_instance(const float* translation, const float* rotation, const floa
     return 0;
 }
 
+int rs_bake_matrix(const float* matrix16, int n, const float* vertsIn, const float* normalsIn, float* vertsOut, float* normalsOut) {
+    if (!matrix16 || n < 0 || (n > 0 && (!vertsIn || !normalsIn || !vertsOut || !normalsOut)))
+        return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_bake_matrix: bad argument");
+    M4 m;
+    std::memcpy(&m, matrix16, sizeof m);
+    bake(m, n, vertsIn, normalsIn, vertsOut, normalsOut);
+    return 0;
+}
+
 int rs_scene_file_free(rs_scene_file* s) { delete s; return 0; }
+
+int rs_scene_file_objects(const rs_scene_file* s, int* numObjects, const int** firstPrim, const float** transforms16,
+                          const float* const** meshVertices, const float* const** meshNormals) {
+    if (!s || !numObjects || !firstPrim || !transforms16 || !meshVertices || !meshNormals)
+        return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_file_objects: null argument");
+    *numObjects = (int)s->objMeshVertices.size();
+    *firstPrim = s->objFirstPrim.data();
+    *transforms16 = s->objTransforms.data();
+    *meshVertices = s->objMeshVertices.data();
+    *meshNormals = s->objMeshNormals.data();
+    return 0;
+}
 
 int rs_scene_file_load(const char* path, rs_scene_file** out) {
     if (!path || !out) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_file_load: null argument");
@@ -1485,7 +1508,7 @@ int rs_scene_file_load(const char* path, rs_scene_file** out) {
 
     rs_scene_file* s = new rs_scene_file();
     auto bail = [&](int e) { delete s; return e; };
-    std::map<std::string, Mesh> meshPool;                              // Resource::meshDataPool
+    std::map<std::string, Mesh>& meshPool = s->meshPool;
     static const std::map<std::string, int> typeOf = { { "Lambertian", 0 }, { "MetallicWorkflow", 1 }, { "Dielectric", 2 }, { "Light", 4 } };   // :16-21
 
     try {
@@ -1571,7 +1594,12 @@ int rs_scene_file_load(const char* path, rs_scene_file** out) {
             const int n = (int)(mesh.v.size() / 3);
             const size_t at = s->vertices.size();
             s->vertices.resize(at + mesh.v.size()); s->normals.resize(at + mesh.n.size());
-            bake(build_transformation_matrix(translation, rotation, scl), n, mesh.v.data(), mesh.n.data(), s->vertices.data() + at, s->normals.data() + at);
+            const M4 transform = build_transformation_matrix(translation, rotation, scl);
+            bake(transform, n, mesh.v.data(), mesh.n.data(), s->vertices.data() + at, s->normals.data() + at);
+            s->objFirstPrim.push_back((int)(at / 9));
+            s->objTransforms.insert(s->objTransforms.end(), &transform.c[0][0], &transform.c[0][0] + 16);
+            s->objMeshVertices.push_back(mesh.v.data());
+            s->objMeshNormals.push_back(mesh.n.data());
             s->texcoords.insert(s->texcoords.end(), mesh.t.begin(), mesh.t.end());
             s->materialIds.insert(s->materialIds.end(), (size_t)(n / 3), materialId);
         }
@@ -1619,6 +1647,7 @@ int rs_scene_file_load(const char* path, rs_scene_file** out) {
     }
     if (s->vertices.empty()) return bail(rs_fail(RS_ERR_INVALID_ARGUMENT, "No mesh data loaded"));      // scene.cpp:192-195
     for (size_t i = 0; i < s->textures.size(); i++) s->textures[i].data = s->texData[i].data();
+    s->objFirstPrim.push_back((int)(s->vertices.size() / 9));
     *out = s;
     return 0;
 }

@@ -19,6 +19,9 @@
 // of other triangles stops short of them and writes no byte of emiNodes / emiTris.  Its grid is its own and moves with the lamps: the host
 // lays it over the new emissive root box before the launches (scene.hip), so base, scale and margin are per record range (GridArgs).
 //
+// In front of the refit, for rs_scene_set_part_transforms alone: k_bake_parts writes the records k_scatter reads -- the staged edit -- from the
+// scene's rest pose and one matrix per part, instead of a copy from the host bringing them.
+//
 // Next to the refit: k_copy_pose, the copy rs_scene_advance_motion makes of the vertices into the scene's previous pose (scene.hip).
 //
 // Hand-off inside a launch (the two climbs): a parent's box is only ever written by agent-scope atomic min / max and only ever read by
@@ -194,6 +197,36 @@ __global__ void __launch_bounds__(256) k_copy_pose(const float* __restrict__ ver
     if (i < count) prevVertices[i] = vertices[i];
 }
 
+// rs_scene_set_part_transforms: the staged edit of rs_scene_set_geometry -- ids | vertices | normals of m triangles -- written on the device
+// from the parts' rest pose instead of copied from the host.  One lane per output corner: consecutive lanes read consecutive 12-byte rest
+// vertices and normals of their part and write consecutive 12-byte results; the lane of corner 0 also writes the primitive id.  A lane finds
+// its part by binary search for the last record whose outFirst is not beyond its triangle (outFirst is non-decreasing, recs[0].outFirst = 0,
+// no record is empty).  A wave that lies inside one part reads the two matrices through the scalar cache.  The arithmetic is rs_bake.h's
+// bake_corner and nothing else: the bits are rs_bake_matrix's.  No hand-off between lanes, nothing shared.
+__device__ __forceinline__ void bake_store(const PartRec* rec, const float* __restrict__ v, const float* __restrict__ n, float* outV, float* outN) {
+    const BakedCorner o = bake_corner(rec->m, rec->nm, ld3(v), ld3(n));
+    st3(outV, o.position);
+    st3(outN, o.normal);
+}
+__global__ void __launch_bounds__(256) k_bake_parts(int numRecs, const PartRec* __restrict__ recs, const int* __restrict__ partPrimIds,
+                                                    const float* __restrict__ restVertices, const float* __restrict__ restNormals,
+                                                    size_t numCorners, int* __restrict__ ids, float* __restrict__ vertices, float* __restrict__ normals) {
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= numCorners) return;
+    const size_t tri = c / 3, corner = c - tri * 3;
+    int lo = 0, hi = numRecs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((size_t)recs[mid].outFirst <= tri) lo = mid; else hi = mid - 1;
+    }
+    const size_t slot = (size_t)recs[lo].restFirst + (tri - (size_t)recs[lo].outFirst);
+    const size_t src = (slot * 3 + corner) * 3;
+    const int first = __builtin_amdgcn_readfirstlane(lo);
+    if (__all(lo == first)) bake_store(recs + first, restVertices + src, restNormals + src, vertices + c * 3, normals + c * 3);
+    else bake_store(recs + lo, restVertices + src, restNormals + src, vertices + c * 3, normals + c * 3);
+    if (corner == 0) ids[tri] = partPrimIds[slot];
+}
+
 template <typename T>
 int upload_table(T** dst, const std::vector<T>& src) {
     RS_TRY(rs_dev_alloc(dst, src.size()));
@@ -283,6 +316,20 @@ int rs_motion_copy_enqueue(const float* vertices, float* prevVertices, size_t nu
     if (count == 0) return 0;
     hipLaunchKernelGGL(k_copy_pose, dim3(blocks_for(count)), dim3(256), 0, st, vertices, prevVertices, count);
     return rs_check_hip(hipGetLastError(), "rs_scene_advance_motion: copy kernel");
+}
+
+int rs_bake_parts_enqueue(const rs_parts* parts, int numRecs, const PartRec* dRecs, size_t m, int* dIds, float* dVertices, float* dNormals, hipStream_t st) {
+    const size_t corners = m * 3;
+    if (corners == 0) return 0;
+    hipLaunchKernelGGL(k_bake_parts, dim3(blocks_for(corners)), dim3(256), 0, st, numRecs, dRecs, (const int*)parts->dPrimIds,
+                       (const float*)parts->dRestVertices, (const float*)parts->dRestNormals, corners, dIds, dVertices, dNormals);
+    return rs_check_hip(hipGetLastError(), "rs_scene_set_part_transforms: bake kernel");
+}
+
+void rs_parts_free(rs_parts* p) {
+    if (!p) return;
+    rs_dev_free(p->dPrimIds); rs_dev_free(p->dRestVertices); rs_dev_free(p->dRestNormals);
+    delete p;
 }
 
 void rs_refit_free(rs_scene* s) {
