@@ -600,6 +600,8 @@ typedef struct rs_phase_a_inputs {
     int chain, smallChain;  /* the frame's turn among two / three chains */
     int idle;               /* the previous frames had finished when this frame began (twice in a row) */
     int numLights, envMap, risGlobalBelow;   /* light table entries; the scene has an environment map; rs_set_ris_table_pixels */
+    int cutState;           /* primary cuts (rs_restir_set_primary_cuts): 0 off, or this call's key differs from the previous frame's; 1 the key is
+                               unchanged and no cut has been built for it; 2 unchanged and built */
 } rs_phase_a_inputs;
 #define RS_RIS_GLOBAL    0  /* light table read from global memory */
 #define RS_RIS_LDS       1  /* whole table in LDS */
@@ -614,9 +616,34 @@ typedef struct rs_phase_a_plan {
     int shadowOnLibrary;    /* the shadow rays go to the library stream, not to the chain's */
     int risForm;            /* RS_RIS_* */
     int tilesX, tilesY, fusedTilesY;   /* blocks of 32 x 8 pixels over the rows; of 32 x 4 over the deferred render's rows when fused */
+    int cut;                /* primary cuts: 0 the primary rays walk the tree; 1 they walk the tree and the build is enqueued behind the chain;
+                               2 they walk the cuts */
 } rs_phase_a_plan;
 /* Test hook: evaluates that function; needs no device. */
 int  rs_debug_phase_a_plan(const rs_phase_a_inputs* in, rs_phase_a_plan* out);
+/* Primary cuts.  While the scene's geometry, the camera, the size and the rows of a phase-A call stay what they were in the previous
+ * frame, the primary rays (not those of the launch fused with GBuffer::render) walk a per-32x8-pixel-block cut of the BVH instead of
+ * the tree: a re-linked copy of the node records that some ray of the block can pass at all (restir_amd/csrc/rs_cuts.h).  Every ray
+ * enters the nodes it would enter in the tree, in the same order: no result changes by a bit.  The second frame with an unchanged key
+ * enqueues the build behind its own kernels (no host wait), the frames after it use the cuts; a camera move, rs_scene_set_triangles,
+ * rs_scene_set_geometry and rs_scene_set_part_transforms forget them, material, texture and emission edits do not.  Memory: the first
+ * build allocates, per phase-A call of a frame, 512 records of 36 bytes per block of its rows (149 MB for 1920x1080, 597 MB for
+ * 3840x2160), kept until rs_restir_free; where that allocation fails the frames keep the tree and no call fails.  on = 1 is the default; the environment variable RS_PRIMARY_CUTS=0
+ * makes 0 the default (A/B measurements). */
+int  rs_restir_set_primary_cuts(rs_restir* r, int on);
+/* Test hooks.  The most records one block's cut may have (default 4096; a block past it walks the tree);
+ * what the last phase-A call's cuts hold -- blocks of its launch, blocks without a cut, records in all cuts (zeros while none is built),
+ * whether that call's primary rays walked them, builds so far (waits for a build in flight);
+ * and containment: each of the n rays { pixel x, pixel y, jitter x, jitter y } walks the whole tree on the geometric part of the
+ * reference's box test, out = { nodes passed that block `cell`'s cut lacks, nodes passed, rays left out (a special case of
+ * AABB::intersect, another traversal order than the cut's, a block without a cut), records in the block's cut }. */
+int  rs_debug_set_primary_cut_cap(rs_restir* r, int records);
+int  rs_debug_primary_cut_info(rs_restir* r, int* cells, int* cellsWithoutCut, unsigned long long* records, int* usedLastFrame, unsigned long long* builds);
+int  rs_debug_primary_cut_missing(rs_restir* r, const rs_scene* scene, int cell, int n, const float* rays, unsigned long long out[4]);
+/* Test hook: the per-pixel state the primary rays of the last ended frame left for the later passes (host arrays of width * height
+ * pixels): 4 floats { hit position, tag bits }, 4 floats { shading normal, metallic }, 2 words { sampler state, tag }.  Waits for the
+ * device. */
+int  rs_debug_restir_surface(rs_restir* r, float* posTag, float* normal, unsigned* rngTag);
 #define RS_SPATIAL_HALO_ROWS 5           /* taps reach y-4..y+5 (src/restir.cu:49-56) */
 /* bytes needed for `rows` rows of published reservoirs */
 size_t rs_restir_halo_bytes(const rs_restir* r, int rows);

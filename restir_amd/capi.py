@@ -111,14 +111,14 @@ class PhaseAInputs(C.Structure):
     _fields_ = [(n, C.c_int) for n in (
         "async_", "chainStreams", "smallChains", "shadowOnMain", "fuseMode", "denoiseStream", "chainsInFlight", "reusedThree", "phaseACalls",
         "width", "y0", "y1", "deferredValid", "deferredMatches", "deferredY0", "deferredY1", "reusedFrame", "tuneChoice", "tuneFrame",
-        "chain", "smallChain", "idle", "numLights", "envMap", "risGlobalBelow")]
+        "chain", "smallChain", "idle", "numLights", "envMap", "risGlobalBelow", "cutState")]
 
 
 class PhaseAPlan(C.Structure):
     """rs_phase_a_plan (include/restir_hip.h): what it decides."""
     _fields_ = [(n, C.c_int) for n in (
         "fuse", "tuneCounted", "tuneRestart", "stream", "lastChains", "splitSlot", "splitCall", "splitMode", "shadowOnLibrary", "risForm",
-        "tilesX", "tilesY", "fusedTilesY")]
+        "tilesX", "tilesY", "fusedTilesY", "cut")]
 
 
 RIS_GLOBAL, RIS_LDS, RIS_ALIAS_LDS = 0, 1, 2
@@ -133,7 +133,7 @@ EXPORTS = [
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
     "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
-    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
+    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
     "rs_path_trace", "rs_path_trace_indirect", "rs_restir_indirect", "rs_restir_download_indirect",
     "rs_svgf_create", "rs_svgf_destroy", "rs_svgf_filter", "rs_svgf_next_frame", "rs_svgf_get_view",
     "rs_copy_image_to_pbo", "rs_copy_image2_to_pbo", "rs_copy_imagef_to_pbo", "rs_copy_imagei_to_pbo", "rs_eaw_create", "rs_eaw_destroy", "rs_eaw_set_params", "rs_eaw_get_params", "rs_eaw_set_tiled", "rs_eaw_set_fused", "rs_svgf_set_params", "rs_svgf_get_params", "rs_svgf_set_tiled", "rs_svgf_set_fused", "rs_eaw_filter", "rs_eaw_positions_rows", "rs_eaw_level_rows", "rs_modulate_albedo",
@@ -243,6 +243,11 @@ def lib():
     L.rs_debug_tap_estimate_error.argtypes = [ci, C.POINTER(cf)]
     L.rs_restir_last_launch.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
     L.rs_debug_phase_a_plan.argtypes = [C.POINTER(PhaseAInputs), C.POINTER(PhaseAPlan)]
+    L.rs_restir_set_primary_cuts.argtypes = [vp, ci]
+    L.rs_debug_set_primary_cut_cap.argtypes = [vp, ci]
+    L.rs_debug_primary_cut_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(ci), C.POINTER(C.c_ulonglong)]
+    L.rs_debug_primary_cut_missing.argtypes = [vp, vp, ci, ci, vp, C.POINTER(C.c_ulonglong * 4)]
+    L.rs_debug_restir_surface.argtypes = [vp, vp, vp, vp]
     L.rs_pbo_register.argtypes = [C.c_uint, C.POINTER(vp)]
     L.rs_pbo_map.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rs_pbo_unmap.argtypes = [vp]
@@ -1045,6 +1050,36 @@ class ReSTIR:
         a, b = C.c_int(), C.c_int()
         check(lib().rs_restir_last_launch(self.handle, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def set_primary_cuts(self, on=True):
+        """rs_restir_set_primary_cuts: still-camera primary rays walk per-block cuts of the BVH (on by default)."""
+        check(lib().rs_restir_set_primary_cuts(self.handle, 1 if on else 0))
+
+    def set_primary_cut_cap(self, records):
+        """rs_debug_set_primary_cut_cap: the most records one block's cut may have."""
+        check(lib().rs_debug_set_primary_cut_cap(self.handle, records))
+
+    def primary_cut_info(self):
+        """dict(cells, without_cut, records, used, builds) of the last phase-A call's cuts (rs_debug_primary_cut_info)."""
+        a, b, u = C.c_int(), C.c_int(), C.c_int()
+        n, k = C.c_ulonglong(), C.c_ulonglong()
+        check(lib().rs_debug_primary_cut_info(self.handle, C.byref(a), C.byref(b), C.byref(n), C.byref(u), C.byref(k)))
+        return dict(cells=a.value, without_cut=b.value, records=n.value, used=bool(u.value), builds=k.value)
+
+    def primary_cut_missing(self, scene, cell, rays):
+        """rs_debug_primary_cut_missing: rays = (n, 4) float32 { pixel x, pixel y, jitter x, jitter y }; returns dict(missing, passed,
+        left_out, records) for block `cell`."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 4)
+        out = (C.c_ulonglong * 4)()
+        check(lib().rs_debug_primary_cut_missing(self.handle, scene.handle, cell, len(rays), _p(rays), C.byref(out)))
+        return dict(missing=out[0], passed=out[1], left_out=out[2], records=out[3])
+
+    def surface(self):
+        """rs_debug_restir_surface: (pos_tag (n, 4) f32, normal (n, 4) f32, rng_tag (n, 2) u32) of the last ended frame."""
+        n = self.width * self.height
+        a, b, c = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32), np.zeros((n, 2), np.uint32)
+        check(lib().rs_debug_restir_surface(self.handle, _p(a), _p(b), _p(c)))
+        return a, b, c
 
     def launch_choice(self):
         """0 two launches, 1 GBuffer::render walked together with the primary rays, -1 still measuring, -2 nothing to choose."""

@@ -26,6 +26,7 @@
 
 #include "rs_row_layouts.h"
 #include "rs_internal.h"
+#include "rs_cuts.h"
 
 using namespace rs;
 
@@ -94,11 +95,15 @@ __device__ __forceinline__ int primary_store(const DevScene& s, const SurfPlanes
 // SPLIT: the launch splits its heavy tiles (rs_tilesplit.h) and counts the nodes of every walk for it; the plain kernel carries none of that
 template <bool TEX, bool SOBOL, bool SPLIT>
 __device__ __forceinline__ void primary_body(const DevScene& s, const CamParams& cam, const SurfPlanes& sp, int looper,
-                                             int y0, int y1, int tilesX, unsigned long long* rayCount, const TileSplit& ts) {
+                                             int y0, int y1, int tilesX, unsigned long long* rayCount, const TileSplit& ts, const PrimaryCuts& cuts) {
     RS_SETPRIO(RS_PRIO_WALK);
     int x, py, tile;
     bool mine, helper;
     if (!tile_split_map<8, 8>(ts, tilesX, threadIdx.x & 63, x, py, mine, tile, helper)) return;     // (a helper block without a tile)
+    const CutRef cut = cut_of_cell(cuts, tile >> 2);             // a block's four tiles are one cell (rs_cuts.h); a helper block takes its tile's
+    // (Touching the cell's records first -- one 128-byte line per thread, an L2 warm-up -- and cells of 64x8 or 32x16 pixels were built
+    // and measured: the warm-up's load alone took the kernel from 45 to 62-64 registers and from 303 to 428 us WITHOUT cuts, and gained
+    // 6 % back with them; the other cell shapes moved it by 1 %.  EXPERIMENTS.md "Primary cuts".)
     const int y = y0 + py;
     const bool inside = mine && x < cam.width && y < y1;
     int shaded = 0;
@@ -107,7 +112,7 @@ __device__ __forceinline__ void primary_body(const DevScene& s, const CamParams&
     f4 r = rng.uniform4();                              // sample4D: all four are drawn, two are used
     Ray ray = camera_sample(cam, x, y, r.x, r.y);
     unsigned unionNodes = 0;
-    Hit h = trace_closest_packet<SPLIT>(s, ray, inside, &unionNodes);       // all 64 lanes take part in the wave's walk
+    Hit h = trace_closest_packet<SPLIT>(s, ray, inside, &unionNodes, cut);       // all 64 lanes take part in the wave's walk
     if (inside) shaded = primary_store<TEX>(s, sp, index, ray, h, rng.word());
     // BVH walks for the Mrays/s metric: one per pixel here, one more per shaded pixel (shadow ray)
     const unsigned long long ballotIn = __ballot(inside), ballotSh = __ballot(shaded);
@@ -120,13 +125,13 @@ __device__ __forceinline__ void primary_body(const DevScene& s, const CamParams&
 
 template <bool TEX, bool SOBOL>
 __global__ void __launch_bounds__(256, RS_WALK_WAVES) k_primary(DevScene s, CamParams cam, SurfPlanes sp, int looper,
-                                                 int y0, int y1, int tilesX, unsigned long long* rayCount) {
-    primary_body<TEX, SOBOL, false>(s, cam, sp, looper, y0, y1, tilesX, rayCount, TileSplit{ nullptr, 0, 0 });
+                                                 int y0, int y1, int tilesX, unsigned long long* rayCount, PrimaryCuts cuts) {
+    primary_body<TEX, SOBOL, false>(s, cam, sp, looper, y0, y1, tilesX, rayCount, TileSplit{ nullptr, 0, 0 }, cuts);
 }
 template <bool TEX, bool SOBOL>
 __global__ void __launch_bounds__(256, RS_WALK_WAVES) k_primary_split(DevScene s, CamParams cam, SurfPlanes sp, int looper,
-                                                 int y0, int y1, int tilesX, unsigned long long* rayCount, TileSplit ts) {
-    primary_body<TEX, SOBOL, true>(s, cam, sp, looper, y0, y1, tilesX, rayCount, ts);
+                                                 int y0, int y1, int tilesX, unsigned long long* rayCount, TileSplit ts, PrimaryCuts cuts) {
+    primary_body<TEX, SOBOL, true>(s, cam, sp, looper, y0, y1, tilesX, rayCount, ts, cuts);
 }
 
 // GBuffer::render and the primary rays of ReSTIRDirect in one launch (asynchronous mode, when the render of this frame is
@@ -874,6 +879,61 @@ int check_frame_args(rs_restir* r, const rs_scene* scene, const rs_camera* cam, 
 // stay where the overlapped mode puts them -- the pass's duration while other frames' kernels share the CUs
 void mark(rs_restir* r, int i) { if (r->timing == 1 || (r->timing == 2 && i >= 3)) (void)hipEventRecord(r->ev[i], rs_stream()); }
 
+// ---- primary cuts (rs_cuts.h; rs_primary_cut in rs_internal.h) -----------------------------------------------------------------------
+constexpr unsigned kCutArenaPerCell = 512;     // the arena holds this many records per cell (or the cap, if smaller); cells that do not fit take no cut
+
+void cut_free(rs_primary_cut& pc) {
+    rs_dev_free(pc.cells); rs_dev_free(pc.records); rs_dev_free(pc.orig); rs_dev_free(pc.counters);
+    pc.cells = nullptr; pc.records = nullptr; pc.orig = nullptr; pc.counters = nullptr;
+    pc.numCells = 0; pc.capacity = 0; pc.built = false;
+}
+
+// rs_phase_a_inputs::cutState for this call, and the call's key left in the slot for the same call of the next frame
+int cut_state(rs_restir* r, rs_primary_cut& pc, const rs_scene* scene, const rs_camera* cam, int y0, int y1) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(rs_stream(), &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
+    if (!r->cutsOn || capturing != hipStreamCaptureStatusNone) { pc.keyValid = false; pc.built = false; return 0; }
+    // (the size is the camera's resolution, which check_frame_args holds to the object's)
+    const bool same = pc.keyValid && pc.sceneId == scene->id && pc.geomEdits == scene->geomEdits && std::memcmp(&pc.cam, cam, sizeof(rs_camera)) == 0 &&
+                      pc.y0 == y0 && pc.y1 == y1 && pc.cap == r->cutCap;
+    if (same) return pc.noMemory ? 0 : pc.built ? 2 : 1;
+    pc.keyValid = true; pc.built = false; pc.noMemory = false;
+    pc.sceneId = scene->id; pc.geomEdits = scene->geomEdits; pc.cam = *cam; pc.y0 = y0; pc.y1 = y1; pc.cap = r->cutCap;
+    return 0;
+}
+
+// enqueues the build of the slot's cuts on st: after every launch that still reads the arena, before every launch that waits for pc.builtEv
+int cut_build(rs_primary_cut& pc, const rs_scene* scene, const CamParams& cp, int y0, int tilesX, int tilesY, hipStream_t st) {
+    const int cellsX = tilesX, numCells = tilesX * tilesY;          // a cell is a block of the launch: 32x8 pixels
+    const unsigned perCell = pc.cap < kCutArenaPerCell ? pc.cap : kCutArenaPerCell;
+    const unsigned long long want = (unsigned long long)numCells * perCell;
+    const unsigned capacity = want < 0x7fffffffull ? (unsigned)want : 0x7fffffffu;
+    if (numCells != pc.numCells || capacity != pc.capacity) {      // another launch geometry (hipFree waits for the device: nothing reads the old arena)
+        cut_free(pc);
+        int e = rs_dev_alloc(&pc.cells, (size_t)numCells);
+        if (!e) e = rs_dev_alloc(&pc.records, (size_t)capacity + 1);
+        if (!e) e = rs_dev_alloc(&pc.orig, (size_t)capacity + 1);
+        if (!e) e = rs_dev_alloc(&pc.counters, 4);
+        if (e) {                                             // no memory for the arena: this key renders through the tree, as the frames before it did
+            (void)hipGetLastError();
+            cut_free(pc);
+            pc.noMemory = true;
+            return 0;
+        }
+        pc.numCells = numCells; pc.capacity = capacity;
+        for (bool& v : pc.usedValid) v = false;
+    }
+    pc.cellsX = cellsX;
+    if (!pc.builtEv) RS_HIP(hipEventCreateWithFlags(&pc.builtEv, hipEventDisableTiming));
+    for (int i = 0; i < 1 + rs_context::kAux; i++) if (pc.usedValid[i]) { RS_HIP(hipStreamWaitEvent(st, pc.usedEv[i], 0)); pc.usedValid[i] = false; }
+    RS_HIP(hipMemsetAsync(pc.counters, 0, 4 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_build_primary_cuts, dim3((numCells + 63) / 64), dim3(64), 0, st, scene->dev, cp, y0, cellsX, numCells, 32, 8, pc.cap, capacity,
+                       pc.cells, pc.records, pc.orig, pc.counters);
+    RS_HIP(hipEventRecord(pc.builtEv, st));
+    pc.built = true; pc.builds++;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -892,6 +952,11 @@ int rs_restir_free(rs_restir* r) {
     rs_dev_free(r->indResv[0]); rs_dev_free(r->indResv[1]);
     rs_dev_free(r->idCur); rs_dev_free(r->idLast); rs_dev_free(r->idTemp);
     for (int*& p : r->candId) rs_dev_free(p);
+    for (rs_primary_cut& pc : r->cut) {
+        cut_free(pc);
+        if (pc.builtEv) (void)hipEventDestroy(pc.builtEv);
+        for (hipEvent_t& e : pc.usedEv) if (e) (void)hipEventDestroy(e);
+    }
     for (auto& e : r->ev) if (e) (void)hipEventDestroy(e);
     for (auto& pair : r->spatialEv) for (hipEvent_t& e : pair) if (e) (void)hipEventDestroy(e);
     for (auto& e : r->surfFree) if (e) (void)hipEventDestroy(e);
@@ -909,6 +974,7 @@ int rs_restir_init(int width, int height, rs_restir** out) {
     r->ctx = rs_ctx();
     rs_ctx_scope scope(r->ctx);
     r->width = width; r->height = height;
+    if (const char* env = std::getenv("RS_PRIMARY_CUTS")) r->cutsOn = std::atoi(env) != 0;     // A/B switch for measurements: the default of rs_restir_set_primary_cuts
     const size_t n = (size_t)width * height;
     int e = 0;
     if (!e) e = alloc_planes(r->cur, n);
@@ -1096,6 +1162,9 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     }
     in.idle = in.async && r->idleFrame;
     in.numLights = scene->numLights; in.envMap = scene->envMapTexId >= 0; in.risGlobalBelow = rs_ris_global_below();
+    const int cutSlot = r->phaseACalls < 2 ? r->phaseACalls : 2;
+    rs_primary_cut& pc = r->cut[cutSlot];
+    in.cutState = cut_state(r, pc, scene, cam, y0, y1);
     rs_phase_a_plan p;
     rs_plan_phase_a(in, p);
     hipStream_t aux = p.stream >= 0 ? rs_aux_stream(p.stream) : nullptr;
@@ -1103,6 +1172,7 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     if (p.tuneCounted) r->tune.count(scene->id);
     if (p.tuneRestart) r->tune.restart();
     r->lastFused = p.fuse; r->lastChains = p.lastChains;
+    r->lastCutSlot = cutSlot; r->lastCutUsed = p.cut == 2;
     const hipStream_t st = aux ? aux : rs_stream();
     const int tilesX = p.tilesX, tilesY = p.tilesY;
     if (aux) {
@@ -1142,10 +1212,21 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     else {
         TileSplit ts; int helpers = 0;
         RS_TRY(rs_tile_split_prepare(hints, (((long long)y0 << 20 | y1) << 12 | tilesX), tilesX * 4 * tilesY, tilesX * tilesY, p.splitMode, st, &ts, &helpers));
+        PrimaryCuts cuts{ nullptr, nullptr };
+        if (p.cut == 2) {                                       // after the build, wherever it was enqueued
+            RS_HIP(hipStreamWaitEvent(st, pc.builtEv, 0));
+            cuts = PrimaryCuts{ pc.cells, pc.records };
+        }
         rs_dispatch([&](auto TEX, auto SOBOL) {
-            if (ts.base) hipLaunchKernelGGL((k_primary_split<TEX(), SOBOL()>), dim3(helpers + tilesX * tilesY), dim3(256), 0, st, scene->dev, cp, sp, looper, y0, y1, tilesX, rayCounter, ts);
-            else hipLaunchKernelGGL((k_primary<TEX(), SOBOL()>), dim3(tilesX * tilesY), dim3(256), 0, st, scene->dev, cp, sp, looper, y0, y1, tilesX, rayCounter);
+            if (ts.base) hipLaunchKernelGGL((k_primary_split<TEX(), SOBOL()>), dim3(helpers + tilesX * tilesY), dim3(256), 0, st, scene->dev, cp, sp, looper, y0, y1, tilesX, rayCounter, ts, cuts);
+            else hipLaunchKernelGGL((k_primary<TEX(), SOBOL()>), dim3(tilesX * tilesY), dim3(256), 0, st, scene->dev, cp, sp, looper, y0, y1, tilesX, rayCounter, cuts);
         }, tex, sobol);
+        if (p.cut == 2) {                                       // a later build into this arena waits for this reader
+            const int k = aux ? 1 + p.stream : 0;
+            if (!pc.usedEv[k]) RS_HIP(hipEventCreateWithFlags(&pc.usedEv[k], hipEventDisableTiming));
+            RS_HIP(hipEventRecord(pc.usedEv[k], st));
+            pc.usedValid[k] = true;
+        }
     }
     mark(r, 1);
     const int npx = (y1 - y0) * W;
@@ -1158,6 +1239,8 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
         RS_HIP(hipEventRecord(r->auxDone, aux));
         RS_HIP(hipStreamWaitEvent(rs_stream(), r->auxDone, 0));
     }
+    // (behind the chain's end event: this frame's temporal pass does not wait for the build, the chain's next frame does)
+    if (p.cut == 1) RS_TRY(cut_build(pc, scene, cp, y0, tilesX, tilesY, st));
     if (p.shadowOnLibrary) hipLaunchKernelGGL(k_shadow, dim3(tilesX * tilesY), dim3(256), 0, rs_stream(), scene->dev, sp, W, y0, y1, tilesX);
     RS_TRY(rs_gbuffer_join(g));                                 // first consumer of the G-buffer planes
     LightIds ids{ nullptr, nullptr, nullptr, nullptr, nullptr, 0, -1 };
@@ -1248,6 +1331,78 @@ int rs_restir_last_launch(const rs_restir* r, int* fused, int* chains) {
     RS_SCOPE(r);
     if (!r || !fused || !chains) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_last_launch: null argument");
     *fused = r->lastFused; *chains = r->lastChains;
+    return 0;
+}
+
+// Primary cuts (rs_cuts.h): 1 on (the default; RS_PRIMARY_CUTS=0 makes 0 the default), 0 off -- the cuts are forgotten, their memory stays
+int rs_restir_set_primary_cuts(rs_restir* r, int on) {
+    RS_SCOPE(r);
+    if (!r) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_set_primary_cuts: null");
+    r->cutsOn = on != 0;
+    if (!r->cutsOn) for (rs_primary_cut& pc : r->cut) { pc.keyValid = false; pc.built = false; }
+    return 0;
+}
+
+// test hook: the most records a cell's cut may have (1 .. 2^24; the default is 4096); cuts built under another cap are forgotten
+int rs_debug_set_primary_cut_cap(rs_restir* r, int records) {
+    RS_SCOPE(r);
+    if (!r || records < 1 || records > (1 << 24)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_set_primary_cut_cap: bad argument");
+    r->cutCap = (unsigned)records;
+    return 0;
+}
+
+// of the last phase-A call's slot: cells of its launch, cells without a cut, records in all cuts (zeros while nothing is built), whether
+// that call's primary rays walked the cuts, and how many builds the slot has seen.  Waits for the build.
+int rs_debug_primary_cut_info(rs_restir* r, int* cells, int* cellsWithoutCut, unsigned long long* records, int* usedLastFrame, unsigned long long* builds) {
+    RS_SCOPE(r);
+    if (!r || !cells || !cellsWithoutCut || !records || !usedLastFrame || !builds) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_primary_cut_info: null argument");
+    const rs_primary_cut& pc = r->cut[r->lastCutSlot];
+    *cells = 0; *cellsWithoutCut = 0; *records = 0; *usedLastFrame = r->lastCutUsed ? 1 : 0; *builds = pc.builds;
+    if (!pc.built) return 0;
+    RS_HIP(hipEventSynchronize(pc.builtEv));
+    unsigned long long h[4];
+    RS_HIP(hipMemcpy(h, pc.counters, sizeof h, hipMemcpyDeviceToHost));
+    *cells = pc.numCells; *cellsWithoutCut = (int)h[1]; *records = h[2];
+    return 0;
+}
+
+// test hook: containment of the last phase-A call's cuts, ray by ray (k_primary_cut_missing).  rays: n x { pixel x, pixel y, jitter x,
+// jitter y } on the host; the camera is the one the cut was built for.  out[4]: nodes a ray passes geometrically that the cell's cut
+// lacks, nodes passed, rays left out (special-case direction, another order than the cut's, no cut), records in the cell's cut.
+int rs_debug_primary_cut_missing(rs_restir* r, const rs_scene* scene, int cell, int n, const float* rays, unsigned long long out[4]) {
+    RS_SCOPE(r);
+    if (!r || !scene || !rays || !out || n <= 0) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_primary_cut_missing: bad argument");
+    const rs_primary_cut& pc = r->cut[r->lastCutSlot];
+    if (!pc.built || scene->id != pc.sceneId || scene->geomEdits != pc.geomEdits) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_primary_cut_missing: no cut has been built for this scene");
+    if (cell < 0 || cell >= pc.numCells) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_primary_cut_missing: no such cell");
+    RS_HIP(hipEventSynchronize(pc.builtEv));
+    float* dRays = nullptr; unsigned long long* dOut = nullptr;
+    RS_TRY(rs_dev_alloc(&dRays, (size_t)n * 4));
+    int e = rs_dev_alloc(&dOut, 4);
+    if (!e) e = rs_check_hip(hipMemcpy(dRays, rays, (size_t)n * 16, hipMemcpyHostToDevice), "hipMemcpy");
+    if (!e) e = rs_check_hip(hipMemset(dOut, 0, 32), "hipMemset");
+    if (!e) {
+        hipLaunchKernelGGL(k_primary_cut_missing, dim3((n + 63) / 64), dim3(64), 0, rs_stream(), scene->dev, rs_make_cam_params(&pc.cam),
+                           PrimaryCuts{ pc.cells, pc.records }, pc.orig, cell, n, dRays, dOut);
+        e = rs_check_hip(hipStreamSynchronize(rs_stream()), "rs_debug_primary_cut_missing");
+    }
+    if (!e) e = rs_check_hip(hipMemcpy(out, dOut, 32, hipMemcpyDeviceToHost), "hipMemcpy");
+    rs_dev_free(dRays); rs_dev_free(dOut);
+    return e;
+}
+
+// test hook: what the primary rays of the frame that rs_restir_end_frame ended last left for the later passes -- per pixel 4 floats
+// { hit position, tag }, 4 floats { shading normal, metallic } and 2 words { sampler state, tag } (SurfPlanes).  Rows no phase-A call of
+// that frame covered hold whatever the set held before.
+int rs_debug_restir_surface(rs_restir* r, float* posTag, float* normal, unsigned* rngTag) {
+    RS_SCOPE(r);
+    if (!r || !posTag || !normal || !rngTag) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_restir_surface: null argument");
+    RS_TRY(rs_synchronize());
+    const rs_restir::Surf& f = r->surf[(r->surfSet + rs_restir::kSurfSets - 1) % rs_restir::kSurfSets];
+    const size_t n = (size_t)r->width * r->height;
+    RS_HIP(hipMemcpy(posTag, f.posKind, n * 16, hipMemcpyDeviceToHost));
+    RS_HIP(hipMemcpy(normal, f.norm, n * 16, hipMemcpyDeviceToHost));
+    RS_HIP(hipMemcpy(rngTag, f.rngMat, n * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1,0 +1,239 @@
+// rs_cuts.h -- static cuts of the MTBVH for the primary rays of a camera that stands still.
+//
+// Of the union nodes a tile's packet walk visits, about two in five are rejected by EVERY lane on geometry alone (EXPERIMENTS.md "Primary
+// cuts") -- the camera and the box decide that, the same way in every frame.  A CELL is the 32x8 pixels of one primary-ray block
+// (four 8x8 tiles, one wave each).  Its cut is a copy, in nodesAll's record format, of the records of one threaded order that some ray of
+// the cell may pass geometrically, re-linked among themselves; packet_walk_fast (rs_walk.h) walks it with `base` and `end` set to the
+// cell's records and nothing else changed.
+//
+// Which records.  A node is kept iff all its ancestors are kept and the conservative cell test below passes on its box; kept records keep
+// their pre-order, and the link of a kept record is next' = the index within the cut of the first kept record whose original index is >=
+// the original miss link (the cut's length if there is none).
+//
+// Why every lane computes the same bits.  Take one lane and its walk through the whole tree: a sequence of visited nodes, each entered
+// (box test passed with tMin < closest: go to the next record) or rejected (go to the miss link).  It visits a node only after entering
+// all its ancestors.  Entering needs the geometric part of the test, and a node on which that part passes for some ray of the cell passes
+// the cell test (containment, below): by induction from the root every entered node is kept, so a visited node that is NOT kept has kept
+// ancestors only, fails the cell test itself and is rejected -- the lane goes to its miss link, past a subtree that holds no kept record
+// (kept sets are closed under ancestors).  Unkept nodes are therefore only ever stepped over, one subtree at a time, forwards.
+//   * entered -> next record: the whole-tree walk goes from kept node n to n + 1 and from there steps over unkept subtrees until it
+//     stands on the first kept node of index > n; the cut walk goes to the record after n's, which is that node.
+//   * rejected -> next': the whole-tree walk goes to link(n) and steps over unkept subtrees until it stands on the first kept node of
+//     index >= link(n), or leaves the tree; the cut walk goes to next', which is that node, or to the cut's end.
+// The kept nodes a lane visits, their order, the boxes and triangles it tests and the `closest` it tests them against are the same in
+// both walks, and a stepped-over node changes nothing in a lane's state.  For the wave: packet_walk_fast needs nested links, and next'
+// is monotone in the original link, so c inside (a, next'(a)) is a kept node inside (a, link(a)) and next'(c) <= next'(a).
+//
+// The cell test.  All rays of a cell start at cam.position, and the unnormalised direction of camera_sample (rs_scene.h) is affine in
+// the screen coordinate, so per world axis it lies between its values at the cell's four extreme (pixel, jitter) corners -- jitter 0 of
+// the first pixel, jitter 1 of the last (Rng::uniform reaches 1).  The slab test is invariant under a positive scale of the direction,
+// so nothing is normalised: with D.c in [dlo.c, dhi.c], all of one sign, the near and far slab distances (p - o.c) / D.c of a box have
+// exact interval bounds, and the test is the interval form of tMax >= max(tMin, 0):
+//     min over axes of (largest far distance)  >=  max(max over axes of (smallest near distance), 0) - margin.
+// Evaluated in double, so that its own rounding (2^-52) does not count.  What the margin and the widening of D cover is the lane's float
+// arithmetic:
+//   * its direction.  camera_sample's sum right * X + up * Y + view * Z has absolute error below 2^-20 |D| per component (a dozen float
+//     roundings of terms below |D|), and normalisation and the reciprocal scale all three components alike up to 2^-22: the lane's
+//     direction is a positive multiple of some D + e, |e.c| < 2^-20 |D|.  The intervals are widened by 2^-16 M, M = the largest
+//     |component| of the corner directions (>= |D| / sqrt 3).  (The rounding of the screen coordinate, 2^-23, enters X scaled by aspect *
+//     tanFovY * focalDist while |D| >= focalDist: the bound holds while aspect * tanFovY and tanFovY stay below 16, and a camera beyond
+//     that -- a half angle above 86 degrees -- takes no cut at all.)  A cell whose widened interval reaches within 2^-10 M of zero takes no
+//     cut: that covers the sign change, AABB::intersect's near-zero and axis-aligned cases (the wave checks ray_is_special itself
+//     and ignores the cut), and keeps the widening below 2^-6 of the interval's ends.
+//   * its slab distances.  (p - o) * dinv is a rounded difference times a rounded reciprocal, rounded: relative error below 2^-22.  A
+//     lane whose float test passes has far.a >= near.b in float for every pair of axes, hence in real arithmetic far.a - near.b >=
+//     -2^-21 T, T = the largest |slab distance| of the ROOT box (root_extent, rs_walk.h: it bounds those of every box).  The margin is
+//     2^-16 R with R >= T the interval maximum of the root's |slab distances|: 32 times the rounding it has to cover.
+// A cell takes no cut -- and walks the tree as before -- if its four corners do not share one mtbvh_order, if a bound is not finite,
+// if its cut is empty or longer than the cap, or if the arena is full.  The wave still compares its own order with the cell's.
+#pragma once
+
+#include "rs_walk.h"
+
+namespace rs {
+
+// the cuts of one launch geometry: cells[c] = { first record, count | order << 28 } (count 0: no cut), `records` the arena they index
+struct PrimaryCuts { const uint2* cells; const BvhNode* records; };
+constexpr unsigned kCutCountMask = (1u << 28) - 1u;
+
+// what the conservative test of a cell needs: per axis the interval of the unnormalised direction mapped to the POSITIVE case (a negative
+// axis is mirrored: planes and origin change sign), so that the near plane is always `a` and the far plane always `b`
+struct CutCell {
+    double o[3], dlo[3], dhi[3];
+    bool neg[3];
+    int order;              // -1: the cell takes no cut
+    double margin;          // 2^-16 R, set from the root box (cut_cell_margin)
+};
+
+// Camera::sample's unnormalised direction for screen position (sx, sy) in pixels (jitter included), in double
+RS_HD void cut_corner_dir(const CamParams& c, double sx, double sy, double D[3]) {
+    const double ruvx = 1.0 - (sx * (double)c.pixelSizeX) * 2.0, ruvy = 1.0 - (sy * (double)c.pixelSizeY) * 2.0;
+    const double X = ruvx * (double)c.aspect * (double)c.tanFovY * (double)c.focalDist, Y = ruvy * (double)c.tanFovY * (double)c.focalDist, Z = (double)c.focalDist;
+    D[0] = (double)c.right.x * X + (double)c.up.x * Y + (double)c.view.x * Z;
+    D[1] = (double)c.right.y * X + (double)c.up.y * Y + (double)c.view.y * Z;
+    D[2] = (double)c.right.z * X + (double)c.up.z * Y + (double)c.view.z * Z;
+}
+
+// the cell of pixels [x0, x0 + w) x [y0, y0 + h)
+RS_HD CutCell cut_cell(const CamParams& c, int x0, int y0, int w, int h) {
+    CutCell cell;
+    cell.order = -1; cell.margin = 0.0;
+    double lo[3], hi[3], M = 0.0;
+    int order = -1;
+    bool ok = c.aspect * c.tanFovY <= 16.f && c.tanFovY <= 16.f;       // (the widening's bound, above; false for NaN)
+    for (int k = 0; k < 4; k++) {
+        double D[3];
+        cut_corner_dir(c, (double)(x0 + ((k & 1) ? w : 0)), (double)(y0 + ((k & 2) ? h : 0)), D);
+        for (int a = 0; a < 3; a++) {
+            if (!(D[a] - D[a] == 0.0)) ok = false;                  // not finite
+            lo[a] = k == 0 ? D[a] : (D[a] < lo[a] ? D[a] : lo[a]);
+            hi[a] = k == 0 ? D[a] : (D[a] > hi[a] ? D[a] : hi[a]);
+            const double m = D[a] < 0.0 ? -D[a] : D[a];
+            M = m > M ? m : M;
+        }
+        const int ord = mtbvh_order(mk3((float)-D[0], (float)-D[1], (float)-D[2]));
+        if (k == 0) order = ord; else if (ord != order) ok = false;
+    }
+    const double o[3] = { (double)c.position.x, (double)c.position.y, (double)c.position.z };
+    const double widen = M * (1.0 / 65536.0), keepOff = M * (1.0 / 1024.0);
+    for (int a = 0; a < 3; a++) {
+        if (!(o[a] - o[a] == 0.0)) ok = false;
+        const double l = lo[a] - widen, h2 = hi[a] + widen;
+        if (l > keepOff) { cell.neg[a] = false; cell.dlo[a] = l; cell.dhi[a] = h2; cell.o[a] = o[a]; }
+        else if (h2 < -keepOff) { cell.neg[a] = true; cell.dlo[a] = -h2; cell.dhi[a] = -l; cell.o[a] = -o[a]; }
+        else { ok = false; cell.neg[a] = false; cell.dlo[a] = cell.dhi[a] = 1.0; cell.o[a] = 0.0; }
+    }
+    if (ok && M > 0.0) cell.order = order;
+    return cell;
+}
+
+// near / far plane of a record's box on axis a, mirrored with the axis
+RS_HD void cut_planes(const CutCell& cell, const BvhNode& n, double pa[3], double pb[3]) {
+    const double lo[3] = { (double)n.bminx, (double)n.bminy, (double)n.bminz }, hi[3] = { (double)n.bmaxx, (double)n.bmaxy, (double)n.bmaxz };
+    for (int a = 0; a < 3; a++) {
+        pa[a] = (cell.neg[a] ? -hi[a] : lo[a]) - cell.o[a];
+        pb[a] = (cell.neg[a] ? -lo[a] : hi[a]) - cell.o[a];
+    }
+}
+
+// R = the interval maximum of the root box's |slab distances|; false: not finite (no cut)
+RS_HD bool cut_cell_margin(CutCell& cell, const BvhNode& root) {
+    double pa[3], pb[3], R = 0.0;
+    cut_planes(cell, root, pa, pb);
+    for (int a = 0; a < 3; a++) {
+        const double fa = pa[a] < 0.0 ? -pa[a] : pa[a], fb = pb[a] < 0.0 ? -pb[a] : pb[a];
+        const double t = (fa > fb ? fa : fb) / cell.dlo[a];
+        R = t > R ? t : R;
+    }
+    cell.margin = R * (1.0 / 65536.0);
+    return R - R == 0.0;
+}
+
+// may some ray of the cell pass the geometric part of the box test on this record?  (anything that is not a number: yes)
+RS_HD bool cut_cell_test(const CutCell& cell, const BvhNode& n) {
+    double pa[3], pb[3];
+    cut_planes(cell, n, pa, pb);
+    double tMinLo = 0.0, tMaxHi = 0.0;
+    for (int a = 0; a < 3; a++) {
+        const double nearLo = pa[a] >= 0.0 ? pa[a] / cell.dhi[a] : pa[a] / cell.dlo[a];
+        const double farHi = pb[a] >= 0.0 ? pb[a] / cell.dlo[a] : pb[a] / cell.dhi[a];
+        tMinLo = nearLo > tMinLo ? nearLo : tMinLo;               // (starts at 0: max(tMin, 0))
+        tMaxHi = (a == 0 || farHi < tMaxHi) ? farHi : tMaxHi;
+        if (!(nearLo == nearLo) || !(farHi == farHi)) return true;
+    }
+    return !(tMaxHi < tMinLo - cell.margin);
+}
+
+#if defined(__HIPCC__)
+// the cut of block `cell` of a primary-ray launch (wave-uniform)
+__device__ __forceinline__ CutRef cut_of_cell(const PrimaryCuts& cuts, int cell) {
+    if (!cuts.cells) return CutRef{ nullptr, 0u, 0 };
+    // (the index and the entry are the same in every lane; said explicitly, because a record base the compiler cannot prove uniform
+    // turns the walk's scalar fetches into per-lane loads: 64 registers and scratch instead of 44)
+    const uint2 c = cuts.cells[__builtin_amdgcn_readfirstlane(cell)];
+    const unsigned first = (unsigned)__builtin_amdgcn_readfirstlane((int)c.x), word = (unsigned)__builtin_amdgcn_readfirstlane((int)c.y);
+    return CutRef{ reinterpret_cast<const char*>(cuts.records + first), word & kCutCountMask, (int)(word >> 28) };
+}
+
+// counters (64-bit: a large cap times many cells must not wrap): [0] records handed out, [1] cells without a cut, [2] records of the cells that have one
+// One thread per cell: a walk that counts, a reservation in the arena, the same walk again to write, then the links.  orig[]: the original
+// index of every cut record (the links' binary search here; rs_debug_primary_cut_missing)
+static __global__ void __launch_bounds__(64) k_build_primary_cuts(DevScene s, CamParams cam, int y0, int cellsX, int numCells, int cellW, int cellH, unsigned cap, unsigned capacity,
+                                                                  uint2* cells, BvhNode* records, unsigned* orig, unsigned long long* counters) {
+    const int ci = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ci >= numCells) return;
+    CutCell cell = cut_cell(cam, (ci % cellsX) * cellW, y0 + (ci / cellsX) * cellH, cellW, cellH);
+    unsigned count = 0;
+    const unsigned end = (unsigned)s.bvhSize;
+    const BvhNode* nodes = s.nodesAll + (size_t)(cell.order < 0 ? 0 : cell.order) * (size_t)s.bvhSize;
+    bool ok = cell.order >= 0 && s.axisCull && s.linksNested && end > 0u && cut_cell_margin(cell, nodes[0]);
+    if (ok) {
+        for (unsigned cur = 0; cur != end && count <= cap;) {
+            const BvhNode n = nodes[cur];
+            if (cut_cell_test(cell, n)) { count++; cur++; }
+            else cur = (unsigned)n.next;
+        }
+        ok = count > 0u && count <= cap;
+    }
+    // (space is handed out in the order the cells ask: which cells go without when the arena is too small depends on that order --
+    // the results never do)
+    unsigned off = 0;
+    if (ok) {
+        const unsigned long long at = atomicAdd(counters, (unsigned long long)count);
+        ok = at + count <= (unsigned long long)capacity;
+        off = ok ? (unsigned)at : 0u;
+    }
+    if (!ok) { cells[ci] = make_uint2(0u, 0u); atomicAdd(counters + 1, 1ull); return; }
+    unsigned i = 0;
+    for (unsigned cur = 0; cur != end && i < count;) {
+        const BvhNode n = nodes[cur];
+        if (cut_cell_test(cell, n)) { records[off + i] = n; orig[off + i] = cur; i++; cur++; }
+        else cur = (unsigned)n.next;
+    }
+    for (i = 0; i < count; i++) {
+        const unsigned link = (unsigned)records[off + i].next;
+        unsigned lo = i + 1u, hi = count;                       // first record in (i, count) of original index >= link
+        while (lo < hi) { const unsigned mid = (lo + hi) >> 1; if (orig[off + mid] < link) lo = mid + 1u; else hi = mid; }
+        records[off + i].next = (int)lo;
+    }
+    cells[ci] = make_uint2(off, count | ((unsigned)cell.order << 28));
+    atomicAdd(counters + 2, (unsigned long long)count);
+}
+
+// Containment, ray by ray: every ray walks the WHOLE tree of its order on the geometric part of the reference's test alone (no distance
+// cull), and each node it passes is looked up in the cell's cut.  rays: n x { pixel x, pixel y, jitter x, jitter y } as floats.
+// out: [0] passed nodes absent from the cut, [1] passed nodes, [2] rays left out (special-case direction, another order than the cut's, or
+// a cell without a cut), [3] records in the cell's cut
+static __global__ void k_primary_cut_missing(DevScene s, CamParams cam, PrimaryCuts cuts, const unsigned* orig, int cellIndex, int n, const float* rays, unsigned long long* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint2 entry = cuts.cells[cellIndex];
+    const CutRef cut{ reinterpret_cast<const char*>(cuts.records + entry.x), entry.y & kCutCountMask, (int)(entry.y >> 28) };
+    const unsigned off = entry.x;
+    if (i == 0) out[3] = cut.end;
+    const Ray ray = camera_sample(cam, (int)rays[4 * i], (int)rays[4 * i + 1], rays[4 * i + 2], rays[4 * i + 3]);
+    RayBoxCtx ctx = make_box_ctx(ray);
+    ctx.cull = s.axisCull;
+    const int order = mtbvh_order(-ray.d);
+    if (ray_is_special(ctx, ray) || order != cut.order || cut.end == 0u) { atomicAdd(out + 2, 1ull); return; }
+    const BvhNode* nodes = s.nodesAll + (size_t)order * (size_t)s.bvhSize;
+    unsigned long long passed = 0, missing = 0;
+    for (unsigned cur = 0; cur != (unsigned)s.bvhSize;) {
+        const float4* rec = reinterpret_cast<const float4*>(nodes + cur);
+        float4 lo, hi;
+        node_unpack(rec[0], rec[1], lo, hi);
+        float tb;
+        if (box_hit_general(ctx.o, ctx.dinv, lo, hi, tb)) {
+            unsigned a = 0, b = cut.end;
+            while (a < b) { const unsigned mid = (a + b) >> 1; if (orig[off + mid] < cur) a = mid + 1u; else b = mid; }
+            passed++;
+            if (a == cut.end || orig[off + a] != cur) missing++;
+            cur++;
+        }
+        else cur = (unsigned)__float_as_int(hi.w);
+    }
+    atomicAdd(out, missing); atomicAdd(out + 1, passed);
+}
+#endif  // __HIPCC__
+
+}  // namespace rs

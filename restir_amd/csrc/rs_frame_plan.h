@@ -95,4 +95,9 @@ inline void rs_plan_phase_a(const rs_phase_a_inputs& in, rs_phase_a_plan& p) {
     const bool tableFits = !in.envMap && (long long)(rows ? in.y1 - in.y0 : 0) * in.width >= in.risGlobalBelow;   // (64 Ki pixels unless rs_set_ris_table_pixels says otherwise)
     p.risForm = tableFits && in.numLights > 0 && in.numLights <= kRisLdsLights ? RS_RIS_LDS
               : tableFits && in.numLights > kRisLdsLights && in.numLights <= kRisAliasLdsLights && alone ? RS_RIS_ALIAS_LDS : RS_RIS_GLOBAL;
+    // Primary cuts (rs_cuts.h) belong to k_primary / k_primary_split: the fused launch walks two rays per pixel from 8x4 tiles and keeps
+    // the tree (it only runs when something moved, or after an emission edit, which leaves the cut alone for the frames after it).  A key
+    // that has just been seen unchanged for the first time builds -- behind this call's chain, so the frame itself still walks the tree --
+    // and every later call with that key walks the cuts, whatever its rows (a strip), its stream or the number of frames in flight.
+    p.cut = rows && !fuse ? in.cutState : 0;
 }

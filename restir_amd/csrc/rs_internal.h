@@ -237,6 +237,7 @@ struct rs_scene {
     float sumLightPower = 0.f;
     int numPrims = 0, bvhSize = 0, numLights = 0;
     unsigned long long id = 0;       // unique per rs_scene_create (a freed scene's address can come back; its id cannot)
+    unsigned long long geomEdits = 0;   // counts the edits that refit the box tables (set_geometry, scene.hip): part of a primary cut's key (rs_primary_cut)
     unsigned long long edits = 0;    // counts the edits that change what GBuffer::render writes (rs_scene_set_emission: baseColor, hence the albedo plane); part of a G-buffer set's content key
     // Edits (rs_scene_set_emission, rs_scene_set_materials, rs_scene_set_texture): a ring of versions of { materials, light records,
     // alias table, texture table }.  Kernels capture
@@ -516,8 +517,38 @@ struct rs_fuse_tuner {
     int reported() const { return choice >= 0 ? choice : (frame > 0 || counted) ? -1 : -2; }     // rs_restir_launch_choice
 };
 
+// Static cuts of the tree for the primary rays of a still camera (rs_cuts.h), one per phase-A call of a frame (as the tile-split
+// hints: a strip driver's calls have rows of their own).  The KEY is what the cut was built from: the scene and its geometry edits
+// (rs_scene::geomEdits -- materials and emission do not count), every byte of the camera, the size and the rows.  Every call compares
+// its key with the one the same call of the previous frame left; the first call that finds it unchanged enqueues the build behind its
+// chain, the calls after that walk the cut, a call that finds another key forgets the cut.  Nothing here waits on the host: `built` orders
+// the readers' streams after the build, used[] orders a later build into the same arena after its readers.
+struct rs_primary_cut {
+    bool keyValid = false, built = false;
+    unsigned long long sceneId = 0, geomEdits = 0;
+    rs_camera cam{};
+    int y0 = 0, y1 = 0;
+    unsigned cap = 0;
+    bool noMemory = false;                   // the arena could not be allocated for this key: it keeps the tree
+    uint2* cells = nullptr;                  // per cell { first record, count | order << 28 }
+    rs::BvhNode* records = nullptr;          // the arena: `capacity` records and one more that is only ever read
+    unsigned* orig = nullptr;                // original index of every record (the builder's links; the containment test hook)
+    unsigned long long* counters = nullptr;  // [0] records handed out, [1] cells without a cut, [2] records in cuts
+    int numCells = 0, cellsX = 0;
+    unsigned capacity = 0;
+    hipEvent_t builtEv = nullptr;
+    hipEvent_t usedEv[1 + rs_context::kAux] = {};
+    bool usedValid[1 + rs_context::kAux] = {};
+    unsigned long long builds = 0;
+};
+
 struct rs_restir {
     rs_context* ctx = nullptr;
+    rs_primary_cut cut[3];
+    bool cutsOn = true;                      // rs_restir_set_primary_cuts (RS_PRIMARY_CUTS=0: off from the start)
+    unsigned cutCap = 4096;                  // records a cell's cut may have (rs_debug_set_primary_cut_cap)
+    int lastCutSlot = 0;                     // of the last phase-A call
+    bool lastCutUsed = false;                // the last phase-A call's primary rays walked cuts
     // The chain primary rays -> RIS -> shadow rays of a frame depends on no other frame.  Frames put theirs on kChains auxiliary
     // streams in turn, so that consecutive frames' chains overlap: on a 1/8 strip a chain lasts 0.4 ms however few rows it has.
     // A chain writes one of kSurfSets sets of surface planes, which the frame's temporal / spatial passes read afterwards; with as

@@ -712,10 +712,10 @@ __device__ __forceinline__ bool slab_overlap_part(const SlabT& t, bool near) {
     return dx + dy > (ok ? fy - nx : __builtin_inff());
 }
 
+// base, end: the records the wave walks and how many -- one threaded order of nodesAll (bvhSize records), or a cell's cut of it
+// (rs_cuts.h: the same records re-linked, first record the same root box); the record at `end` is readable either way
 template <int NEG, bool COUNT>
-__device__ __forceinline__ void packet_walk_fast(const DevScene& s, int order, bool mine, const Ray& ray, const RayBoxCtx& ctx, WalkResult& r) {
-    const char* __restrict__ base = reinterpret_cast<const char*>(s.nodesAll + (size_t)order * (size_t)s.bvhSize);
-    const unsigned end = (unsigned)s.bvhSize;
+__device__ __forceinline__ void packet_walk_fast(const DevScene& s, const char* __restrict__ base, unsigned end, bool mine, const Ray& ray, const RayBoxCtx& ctx, WalkResult& r) {
     const vf2 oxy = { ctx.o.x, ctx.o.y }, ozz = { ctx.o.z, ctx.o.z }, dxy = { ctx.dinv.x, ctx.dinv.y }, dzz = { ctx.dinv.z, ctx.dinv.z };
     unsigned myNext = mine ? 0u : end;
     unsigned c = 0;                                           // wave-uniform
@@ -826,23 +826,28 @@ __device__ __forceinline__ void packet_walk_order(const DevScene& s, int order, 
 
 // the bits of `neg`: a direction component is negative in the lanes that take part (the same in all of them)
 template <bool COUNT>
-__device__ __forceinline__ void packet_walk_fast_dispatch(int neg, const DevScene& s, int order, bool mine, const Ray& ray, const RayBoxCtx& ctx, WalkResult& r) {
+__device__ __forceinline__ void packet_walk_fast_dispatch(int neg, const DevScene& s, const char* base, unsigned end, bool mine, const Ray& ray, const RayBoxCtx& ctx, WalkResult& r) {
     switch (neg) {
-        case 0: packet_walk_fast<0, COUNT>(s, order, mine, ray, ctx, r); break;
-        case 1: packet_walk_fast<1, COUNT>(s, order, mine, ray, ctx, r); break;
-        case 2: packet_walk_fast<2, COUNT>(s, order, mine, ray, ctx, r); break;
-        case 3: packet_walk_fast<3, COUNT>(s, order, mine, ray, ctx, r); break;
-        case 4: packet_walk_fast<4, COUNT>(s, order, mine, ray, ctx, r); break;
-        case 5: packet_walk_fast<5, COUNT>(s, order, mine, ray, ctx, r); break;
-        case 6: packet_walk_fast<6, COUNT>(s, order, mine, ray, ctx, r); break;
-        default: packet_walk_fast<7, COUNT>(s, order, mine, ray, ctx, r); break;
+        case 0: packet_walk_fast<0, COUNT>(s, base, end, mine, ray, ctx, r); break;
+        case 1: packet_walk_fast<1, COUNT>(s, base, end, mine, ray, ctx, r); break;
+        case 2: packet_walk_fast<2, COUNT>(s, base, end, mine, ray, ctx, r); break;
+        case 3: packet_walk_fast<3, COUNT>(s, base, end, mine, ray, ctx, r); break;
+        case 4: packet_walk_fast<4, COUNT>(s, base, end, mine, ray, ctx, r); break;
+        case 5: packet_walk_fast<5, COUNT>(s, base, end, mine, ray, ctx, r); break;
+        case 6: packet_walk_fast<6, COUNT>(s, base, end, mine, ray, ctx, r); break;
+        default: packet_walk_fast<7, COUNT>(s, base, end, mine, ray, ctx, r); break;
     }
 }
 
+// A cell's cut of one threaded order (rs_cuts.h): `end` records at `base`, cut from order `order`; end == 0: the cell has none
+struct CutRef { const char* base; unsigned end; int order; };
+
 // closest hit for a wave of coherent rays; lanes with active == false carry no ray
 // unionNodes (may be null): the number of nodes the wave visited, the length of its chain of dependent fetches (tile splitting, rs_tilesplit.h)
+// cut (wave-uniform): the walk of order cut.order goes through the cut's records instead of the tree's when it takes the fast form --
+// every other walk (special-case rays, mixed signs, another order, a table without nested links) ignores it
 template <bool COUNT = false>
-__device__ inline Hit trace_closest_packet(const DevScene& s, const Ray& ray, bool active, unsigned* unionNodes = nullptr) {
+__device__ inline Hit trace_closest_packet(const DevScene& s, const Ray& ray, bool active, unsigned* unionNodes = nullptr, CutRef cut = CutRef{ nullptr, 0u, 0 }) {
     WalkResult w;
     RayBoxCtx ctx = make_box_ctx(ray);
     ctx.cull = s.axisCull;
@@ -866,7 +871,11 @@ __device__ inline Hit trace_closest_packet(const DevScene& s, const Ray& ray, bo
         const unsigned long long sx = __ballot(mine && ray.d.x < 0.f), sy = __ballot(mine && ray.d.y < 0.f), sz = __ballot(mine && ray.d.z < 0.f);
         const bool uniformSigns = (sx == 0 || sx == mm) && (sy == 0 || sy == mm) && (sz == 0 || sz == mm);
         if (anySpecial) packet_walk_order<false, COUNT>(s, k, mine, ray, ctx, w);
-        else if (uniformSigns && s.axisCull && s.linksNested) packet_walk_fast_dispatch<COUNT>((sx ? 1 : 0) | (sy ? 2 : 0) | (sz ? 4 : 0), s, k, mine, ray, ctx, w);
+        else if (uniformSigns && s.axisCull && s.linksNested) {
+            const bool cutHere = cut.end != 0u && k == cut.order;
+            const char* base = cutHere ? cut.base : reinterpret_cast<const char*>(s.nodesAll + (size_t)k * (size_t)s.bvhSize);
+            packet_walk_fast_dispatch<COUNT>((sx ? 1 : 0) | (sy ? 2 : 0) | (sz ? 4 : 0), s, base, cutHere ? cut.end : (unsigned)s.bvhSize, mine, ray, ctx, w);
+        }
         else packet_walk_order<true, COUNT>(s, k, mine, ray, ctx, w);
     }
 #ifdef RS_WALK_STATS

@@ -868,6 +868,7 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
         s->dev.occRootHi = ld3(&s->hBoxes[r->root * 6 + 3]);
     }
     s->edits++;                                                  // retained G-buffer planes are not this scene's any more
+    s->geomEdits++;                                              // ... and cuts of the tree carry boxes the refit has just changed
     if (s->dev.prevVertices) s->motionDirty = true;              // rs_scene_advance_motion has something to copy
     if (!lamps) return rs_after_launch(name);
     // the lights' version: light_records reads the vertices just written; launches from here on see new geometry and new lights alike
