@@ -374,6 +374,45 @@ int  rs_scene_parts_info(const rs_scene* scene, int* numParts, int* numListedPri
  * geometry edit of either kind copied from the host to the device (0 before the first); host only. */
 int  rs_scene_download_part_rest(const rs_scene* scene, int* primIds, float* restVertices, float* restNormals);
 int  rs_debug_scene_staged_bytes(const rs_scene* scene, size_t* bytes);
+/* What a geometry edit of any of the three kinds decides on the host before it touches the device, as functions of plain arrays and
+ * integers (restir_amd/csrc/rs_geometry_plan.h).  The view is what they read of a scene; flags are 0 / 1. */
+typedef struct rs_geometry_edit_view {
+    int numPrims;
+    const int* materialIds;         /* [numPrims] */
+    const rs_material* materials;   /* a triangle is an emitter when its material's type is Light */
+    int bounded;                    /* the scene has grid-box trees: a vertex must stay inside [gridLo, gridHi], the creation-time root box */
+    float gridLo[3], gridHi[3];
+    /* read only when the edit names an emitter */
+    const float* vertices;          /* [numPrims * 9] before the edit */
+    int numLights, numLightPrims;   /* sampler entries; light primitives (one less when the environment map has the last entry) */
+    const int* lightPrimIds;        /* [numLightPrims] */
+    const float* lightRadiance;     /* [numLightPrims * 3] */
+    const float* lightArea;         /* [numLightPrims] Math::triangleArea before the edit */
+    float envPower;                 /* the environment map's sampler entry */
+    int emissiveTree, numEmissive;  /* the scene has a tree of its emissive triangles; how many they are */
+    const int* emiLeafPrims;        /* [numEmissive] */
+} rs_geometry_edit_view;
+typedef struct rs_geometry_edit_plan {
+    int m;                          /* distinct primitives named: the records staged (a repeated id keeps its last record and its first place) */
+    int lamps;                      /* the edit names an emitter */
+    size_t offV, offN, bytes;       /* ids | vertices | normals, each part 16-byte aligned; without normals bytes == offN */
+    size_t staged, onDevice;        /* copied from the host / held in the device buffer when the records themselves are staged */
+    size_t partStaged, partOnDevice;   /* ... when numPartRecs 112-byte part records are staged and follow the records a kernel expands them to */
+} rs_geometry_edit_plan;
+typedef struct rs_geometry_edit_lights {
+    float sumAll;                   /* the new light sampler's total power */
+    int emiGrid;                    /* a grid could be laid over the emissive root box (0: no emissive tree, or no extent) */
+    float emiLo[3], emiHi[3];       /* the emissive root box after the edit (emissiveTree only) */
+    float emiBase[3], emiScale[3];
+    double emiMargin;
+} rs_geometry_edit_lights;
+/* Test hook: evaluates those functions for an edit of `count` records made through the entry point `name` (emitters: it takes Light
+ * triangles); needs no device.  Returns the refusal the entry point would return, with its text.  slots (may be NULL): [count] the place
+ * of every input record among the m staged.  When the plan says lamps and lights is not NULL: *lights, and area [numLightPrims], prob and
+ * failId [numLights] (each may be NULL). */
+int  rs_debug_plan_geometry_edit(const rs_geometry_edit_view* view, const char* name, int emitters, int count, const int* primIds,
+                                 const float* vertices, const float* normals, int numPartRecs, rs_geometry_edit_plan* plan, int* slots,
+                                 rs_geometry_edit_lights* lights, float* area, float* prob, int* failId);
 /* Motion tracking: the previous pose of the scene, for the G-buffer's motion plane.  (The reference has no moving geometry: there is no
  * reference line to cite.  Its renderGBuffer, src/gbuffer.cu:49-54, asks where the hit's world point was on last frame's screen.)
  * A tracked scene keeps a second vertex array on the device, 36 bytes per triangle: the vertices as they stood at the last

@@ -10,6 +10,7 @@ import os
 import numpy as np
 
 from .ctypes_structs import Camera, Material, Reservoir, MATERIAL_DTYPE, RESERVOIR_DTYPE, INDIRECT_RESERVOIR_DTYPE, copy_camera
+from .ctypes_structs import GeometryEditLights, GeometryEditPlan, GeometryEditView
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RESTIR_HIP_LIB") or os.path.join(_HERE, "librestir_hip.so")   # env override: A/B builds
@@ -139,7 +140,7 @@ EXPORTS = [
     "rs_copy_image_to_pbo", "rs_copy_image2_to_pbo", "rs_copy_imagef_to_pbo", "rs_copy_imagei_to_pbo", "rs_eaw_create", "rs_eaw_destroy", "rs_eaw_set_params", "rs_eaw_get_params", "rs_eaw_set_tiled", "rs_eaw_set_fused", "rs_svgf_set_params", "rs_svgf_get_params", "rs_svgf_set_tiled", "rs_svgf_set_fused", "rs_eaw_filter", "rs_eaw_positions_rows", "rs_eaw_level_rows", "rs_modulate_albedo",
     "rs_add_image", "rs_add_image3", "rs_comm_create_rccl", "rs_comm_create_rccl_lib", "rs_comm_create", "rs_comm_destroy", "rs_comm_self_exchange", "rs_strips_create", "rs_strips_destroy", "rs_strips_rows", "rs_strips_set_comm_stream", "rs_strips_set_gbuffer_halo", "rs_strips_set_light_tracking", "rs_strips_frame", "rs_strips_eaw_filter", "rs_strips_svgf_filter", "rs_strips_exchange_svgf_history", "rs_strips_exchange_history", "rs_strips_gather", "rs_strips_gather_begin", "rs_strips_gather_end", "rs_strips_enable_timing", "rs_strips_halo_wait_ms",
     "rs_scene_file_load", "rs_scene_file_get", "rs_scene_file_free", "rs_build_transformation_matrix", "rs_bake_instance",
-    "rs_bake_matrix", "rs_scene_file_objects", "rs_scene_define_parts", "rs_scene_set_part_transforms", "rs_scene_parts_info", "rs_scene_download_part_rest", "rs_debug_scene_staged_bytes",
+    "rs_bake_matrix", "rs_scene_file_objects", "rs_scene_define_parts", "rs_scene_set_part_transforms", "rs_scene_parts_info", "rs_scene_download_part_rest", "rs_debug_scene_staged_bytes", "rs_debug_plan_geometry_edit",
 ]
 
 _lib = None
@@ -243,6 +244,8 @@ def lib():
     L.rs_debug_tap_estimate_error.argtypes = [ci, C.POINTER(cf)]
     L.rs_restir_last_launch.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
     L.rs_debug_phase_a_plan.argtypes = [C.POINTER(PhaseAInputs), C.POINTER(PhaseAPlan)]
+    L.rs_debug_plan_geometry_edit.argtypes = [C.POINTER(GeometryEditView), C.c_char_p, ci, ci, vp, vp, vp, ci, C.POINTER(GeometryEditPlan), vp,
+                                              C.POINTER(GeometryEditLights), vp, vp, vp]
     L.rs_restir_set_primary_cuts.argtypes = [vp, ci]
     L.rs_debug_set_primary_cut_cap.argtypes = [vp, ci]
     L.rs_debug_primary_cut_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(ci), C.POINTER(C.c_ulonglong)]
@@ -407,6 +410,47 @@ def phase_a_plan(**inputs):
     i, o = PhaseAInputs(**inputs), PhaseAPlan()
     check(lib().rs_debug_phase_a_plan(C.byref(i), C.byref(o)))
     return o
+
+
+def geometry_edit_view(material_ids, materials, vertices, grid=None, light_prim_ids=(), light_radiance=(), light_area=(), env_power=None,
+                       emi_leaf_prims=None):
+    """rs_geometry_edit_view of plain arrays: grid = (lo, hi) of a bounded scene or None; env_power: the environment map's sampler entry
+    or None for a scene without one; emi_leaf_prims: the emissive tree's primitives by slot, or None for a scene without that tree."""
+    keep = dict(materialIds=np.ascontiguousarray(material_ids, np.int32), materials=np.ascontiguousarray(materials, MATERIAL_DTYPE),
+                vertices=np.ascontiguousarray(vertices, np.float32).reshape(-1), lightPrimIds=np.ascontiguousarray(light_prim_ids, np.int32),
+                lightRadiance=np.ascontiguousarray(light_radiance, np.float32).reshape(-1), lightArea=np.ascontiguousarray(light_area, np.float32),
+                emiLeafPrims=np.ascontiguousarray(() if emi_leaf_prims is None else emi_leaf_prims, np.int32))
+    v = GeometryEditView(**{k: a.ctypes.data for k, a in keep.items()})
+    v.keep = keep                                    # (the view points into these arrays)
+    v.numPrims = len(keep["materialIds"])
+    v.bounded = int(grid is not None)
+    if grid is not None:
+        v.gridLo[:], v.gridHi[:] = [float(x) for x in grid[0]], [float(x) for x in grid[1]]
+    v.numLightPrims = len(keep["lightPrimIds"])
+    v.numLights = v.numLightPrims + int(env_power is not None)
+    v.envPower = 0.0 if env_power is None else float(env_power)
+    v.emissiveTree, v.numEmissive = int(emi_leaf_prims is not None), len(keep["emiLeafPrims"])
+    return v
+
+
+def plan_geometry_edit(view, name, emitters, prim_ids, vertices, normals=None, num_part_recs=0, count=None):
+    """The plans of a geometry edit made through the entry point `name` (rs_debug_plan_geometry_edit): needs no device.  Returns
+    (GeometryEditPlan, slots, lights): slots [count] the place of every record among the m staged; lights None unless the edit names an
+    emitter, else a dict of the fields of GeometryEditLights and area, prob, fail.  A refusal raises as the entry point's would."""
+    ids = np.ascontiguousarray(prim_ids, np.int32)
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1)
+    n = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1)
+    count = len(ids) if count is None else count
+    plan, lights, slots = GeometryEditPlan(), GeometryEditLights(), np.full(max(count, 0), -1, np.int32)
+    area, prob, fail = np.zeros(view.numLightPrims, np.float32), np.zeros(view.numLights, np.float32), np.zeros(view.numLights, np.int32)
+    check(lib().rs_debug_plan_geometry_edit(C.byref(view), name.encode(), int(emitters), count, _p(ids), _p(v), None if n is None else _p(n),
+                                            num_part_recs, C.byref(plan), _p(slots), C.byref(lights), _p(area), _p(prob), _p(fail)))
+    if not plan.lamps:
+        return plan, slots, None
+    out = dict(sumAll=np.float32(lights.sumAll), emiGrid=lights.emiGrid, emiMargin=lights.emiMargin, area=area, prob=prob, fail=fail)
+    for k in ("emiLo", "emiHi", "emiBase", "emiScale"):
+        out[k] = np.array(getattr(lights, k)[:], np.float32)
+    return plan, slots, out
 
 
 def prepare_streams():

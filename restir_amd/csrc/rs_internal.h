@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "rs_scene.h"
+#include "rs_geometry_plan.h"
 #include "rs_walk.h"
 #include "rs_bsdf.h"
 #include "rs_tilesplit.h"
@@ -126,6 +127,13 @@ template <typename T>
 static inline void rs_dev_free(T*& p) {
     if (p) { (void)hipFree((void*)p); p = nullptr; }
 }
+// a host table as a device array of its own
+template <typename T>
+int upload(T** dst, const std::vector<T>& src) {
+    RS_TRY(rs_dev_alloc(dst, src.size()));
+    if (!src.empty()) RS_HIP(hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
+    return 0;
+}
 
 // Run-time booleans as template arguments: f is called once, with a std::true_type / std::false_type per boolean --
 //   rs_dispatch([&](auto TEX, auto SOBOL) { hipLaunchKernelGGL((kernel<TEX(), SOBOL()>), grid, block, 0, stream, args...); }, tex, sobol);
@@ -216,7 +224,9 @@ struct rs_scene {
     bool properBoxes = false;            // the box table is a proper hierarchy (rs_scene_create); DevScene::axisCull also asks for small triangles
     // Geometry edits (rs_scene_set_triangles, rs_scene_set_geometry; rs_refit.h, scene_refit.hip).  Kept from creation, on the host only: the primitive in every
     // slot of occTris, the box the shadow tree's grid was laid over (a moved vertex must stay inside it) and the grid's margin.
-    // Everything else -- device tables, scratch, staging -- belongs to `refit`, which the first edit allocates.
+    // Everything else -- device tables, scratch, staging -- belongs to `refit`, which the first edit allocates, but for the scratch of
+    // the edit's plan (rs_geometry_plan.h), which needs no device.
+    rs_edit_stamps editStamps;
     std::vector<int> hOccLeafPrims;
     float gridLo[3] = {}, gridHi[3] = {};
     double gridMargin = 0.0;
@@ -237,7 +247,7 @@ struct rs_scene {
     float sumLightPower = 0.f;
     int numPrims = 0, bvhSize = 0, numLights = 0;
     unsigned long long id = 0;       // unique per rs_scene_create (a freed scene's address can come back; its id cannot)
-    unsigned long long geomEdits = 0;   // counts the edits that refit the box tables (set_geometry, scene.hip): part of a primary cut's key (rs_primary_cut)
+    unsigned long long geomEdits = 0;   // counts the edits that refit the box tables (set_geometry, scene_edits.hip): part of a primary cut's key (rs_primary_cut)
     unsigned long long edits = 0;    // counts the edits that change what GBuffer::render writes (rs_scene_set_emission: baseColor, hence the albedo plane); part of a G-buffer set's content key
     // Edits (rs_scene_set_emission, rs_scene_set_materials, rs_scene_set_texture): a ring of versions of { materials, light records,
     // alias table, texture table }.  Kernels capture
@@ -650,10 +660,21 @@ rs::CamParams rs_make_cam_params(const rs_camera* cam);
 // occlusion_bvh.cpp
 int rs_build_occlusion_bvh(int numPrims, const float* primBoxes, std::vector<rs::BvhNode>& nodes, std::vector<int>& leafPrims);
 int rs_quantize_occlusion_bvh(const std::vector<rs::BvhNode>& nodes, float base[3], float scale[3], std::vector<unsigned>& out, double* margin = nullptr);
-// the 16-bit grid a grid-box tree with root box [lo, hi] is quantised on (rs_quantize_occlusion_bvh lays it; an edit that moves emitters
-// lays the emissive tree's anew); false: the box has no finite, positive extent
-bool rs_grid_over_box(const float lo[3], const float hi[3], float base[3], float scale[3], double* margin);
+// (rs_grid_over_box: rs_geometry_plan.h)
 int rs_build_ordered_bvh(int numPrims, const float* primBoxes, const int* seq, std::vector<rs::BvhNode>& forward, std::vector<rs::BvhNode>& mirrored);
 int rs_reference_chain_tables(int bvhSize, const int* order0, std::vector<int>& parent, std::vector<int>& leafOfPrim, int numPrims);
 // scene_refit.hip
 void rs_refit_free(rs_scene* s);                        // rs_scene_destroy: what the first geometry edit allocated (nothing without one)
+// scene.hip, for scene_edits.hip as well
+// map ids of n materials against a table of numTextures; the two refusal texts carry the entry point's name
+int check_materials(int n, const rs_material* m, int numTextures, bool* anyMap,
+                    const char* beyond = "rs_scene_create: material map id beyond the texture table",
+                    const char* invalid = "rs_scene_create: invalid material map id");
+// the light records and alias records of the scene's host arrays
+void light_records(const rs_scene* s, float sumInv, rs::LightRec* rec, rs::AliasRec* al);
+std::vector<rs::AliasRec> alias_records(const std::vector<float>& prob, const std::vector<int>& fail);
+bool far_skip_allowed(const float* vertices, size_t count);   // may skip_far_on_axis (rs_intersect.h) run on a scene with these triangles?
+// scene_edits.hip, for rs_scene_destroy as well
+int refuse_while_capturing(const char* name);           // edits are not recorded into graphs: RS_ERR_UNSUPPORTED while the library stream is captured
+void versions_free(rs_scene* s);                        // what the first edit of materials, lights or textures allocated
+void motion_free(rs_scene* s);                          // what rs_scene_set_motion_tracking allocated

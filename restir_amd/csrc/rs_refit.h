@@ -1,4 +1,4 @@
-// rs_refit.h -- what rs_scene_set_triangles / rs_scene_set_geometry keep per scene (scene.hip: the entry points; scene_refit.hip: tables,
+// rs_refit.h -- what rs_scene_set_triangles / rs_scene_set_geometry keep per scene (scene_edits.hip: the entry points; rs_geometry_plan.h: their host decisions; scene_refit.hip: tables,
 // kernels, rs_refit_boxes).
 //
 // A refit keeps every tree's topology and recomputes every box from the vertices: the reference tree (nodesAll's six orders, occChain)
@@ -51,9 +51,6 @@ struct rs_refit {
     char* dStage = nullptr;          // read by the scatter kernel, in the order of the library stream: ids | vertices | normals, copied from a
     size_t dStageCapacity = 0;       // staging buffer or written by k_bake_parts from the part records, which then follow them in this buffer
     size_t stagedBytes = 0;          // what the last accepted edit copied from the host (rs_debug_scene_staged_bytes)
-    std::vector<unsigned> lastStamp; // [numPrims] the edit that named the primitive last (a repeated id takes its last record)
-    std::vector<int> lastIndex;      //            ... and its place in that edit's compacted list
-    unsigned stamp = 0;
     // ---- fences ----
     hipEvent_t before[rs_context::kAux] = {};      // what an internal stream has been handed so far
     hipEvent_t after = nullptr;                    // the edit's kernels

@@ -50,6 +50,19 @@ struct __attribute__((aligned(16))) LightRec {
     float v2x, v2y, v2z, nz;
     float Lx, Ly, Lz, pdfArea;
 };
+// The pre-differenced triangle of nine floats: the one place the subtraction is written, for the host builders and the device refit alike
+struct TriEdges { f3 v0, e1, e2; };
+RS_HD TriEdges tri_edges(const float* t) {
+    const f3 v0 = ld3(t), v1 = ld3(t + 3), v2 = ld3(t + 6);
+    return TriEdges{ v0, v1 - v0, v2 - v0 };
+}
+// ... as a record; the pads are a table's own (bit patterns of ints, see the layout above)
+inline TriRec tri_rec(const float* t, int pad0 = 0, int pad1 = 0) {
+    const TriEdges d = tri_edges(t);
+    float b0, b1;
+    __builtin_memcpy(&b0, &pad0, 4); __builtin_memcpy(&b1, &pad1, 4);
+    return TriRec{ d.v0.x, d.v0.y, d.v0.z, b0, d.e1.x, d.e1.y, d.e1.z, b1, d.e2.x, d.e2.y, d.e2.z, 0.f };
+}
 struct AliasRec { float prob; int failId; };
 struct TexRec { const float* data; int width, height; };       // DevTextureObj (src/image.h:76-97): packed float[3] texels
 

@@ -361,7 +361,7 @@ __device__ __forceinline__ bool walk_occlusion_tree(const DevScene& s, const Ray
               if (s.walkStats && __lane_id() == 0) { const int b = wst[5] / 24 < 9 ? (int)(wst[5] / 24) : 9; atomicAdd(&s.walkStats[44 + b], (unsigned long long)__popcll(walkers)); atomicAdd(&s.walkStats[54 + b], 1ull); } }
 #endif
 #endif
-            {   // every lane, also one whose walk has ended: it reads the record past the end, an empty box linked to itself (scene.hip)
+            {   // every lane, also one whose walk has ended: it reads the record past the end, an empty box linked to itself (scene.hip put_end_record)
                 const uint4 n = *reinterpret_cast<const uint4*>(nodes + cur);
 #if defined(RS_WALK_STATS) && !defined(RS_WALK_STATS_TIME)
                 if (s.walkStats && s.occDepth && cur != endOff) { const int dep = s.occDepth[cur >> 4]; atomicAdd(&s.walkStats[44 + (dep < 19 ? dep : 19)], 1ull); }

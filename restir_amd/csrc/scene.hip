@@ -1,5 +1,6 @@
 // scene.hip -- DevScene::create / destroy (src/scene.cpp:435-532) re-laid-out for CDNA4 (see
-// rs_scene.h), Scene::buildDevData as one call, and batched ray entry points for parity tests.
+// rs_scene.h), Scene::buildDevData as one call, the builders of the three grid-box tree sides, the debug hooks of the
+// tables and grids, and batched ray entry points for parity tests.  Edits of a live scene: scene_edits.hip.
 #include <atomic>
 #include <algorithm>
 #include <cmath>
@@ -14,13 +15,9 @@
 
 using namespace rs;
 
-namespace {
-
 // Map ids as getTexturedMaterialAndSurface reads them (src/scene.h:78-99): baseColor -1 none / -2 procedural / index;
 // metallic and roughness are used only when > -1; a normal map id other than -1 indexes `textures` directly.
-int check_materials(int n, const rs_material* m, int numTextures, bool* anyMap,
-                    const char* beyond = "rs_scene_create: material map id beyond the texture table",
-                    const char* invalid = "rs_scene_create: invalid material map id") {
+int check_materials(int n, const rs_material* m, int numTextures, bool* anyMap, const char* beyond, const char* invalid) {
     *anyMap = false;
     for (int i = 0; i < n; i++) {
         const int ids[4] = { m[i].baseColorMapId, m[i].metallicMapId, m[i].roughnessMapId, m[i].normalMapId };
@@ -29,13 +26,6 @@ int check_materials(int n, const rs_material* m, int numTextures, bool* anyMap,
         if (ids[0] < -2 || ids[3] < -1) return rs_fail(RS_ERR_INVALID_ARGUMENT, invalid);
         if (ids[0] != -1 || ids[1] > -1 || ids[2] > -1 || ids[3] != -1) *anyMap = true;
     }
-    return 0;
-}
-
-template <typename T>
-int upload(T** dst, const std::vector<T>& src) {
-    RS_TRY(rs_dev_alloc(dst, src.size()));
-    if (!src.empty()) RS_HIP(hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -65,6 +55,27 @@ bool far_skip_allowed(const float* vertices, size_t count) {
     return true;
 }
 
+namespace {
+
+// the reference leaf boxes of n primitives (prims null: of primitives 0 .. n - 1), which is what the grid-box trees are built over
+std::vector<float> leaf_boxes(const rs_scene* s, size_t n, const int* prims = nullptr) {
+    std::vector<float> boxes(n * 6);
+    for (size_t i = 0; i < n; i++) std::memcpy(&boxes[i * 6], &s->hBoxes[(size_t)s->hLeafOf[prims ? (size_t)prims[i] : i] * 6], 6 * sizeof(float));
+    return boxes;
+}
+
+// The end record of an array of 16-byte grid-box records: an empty box (lo = 65535 > hi = 0 on every axis fails the slab test for either
+// sign of the direction) whose link is its own byte offset -- a lane whose walk has ended stays there, so the walk loop needs no "has this
+// lane ended" region.  (build_ordered_side also pads with it: empty inner records linked to the end record.)
+void put_end_record(unsigned* rec, size_t endOffset) {
+    rec[0] = 0xffffffffu; rec[1] = 0x0000ffffu; rec[2] = 0u; rec[3] = (unsigned)endOffset;
+}
+void push_end_record(std::vector<unsigned>& packed) {
+    const size_t at = packed.size();
+    packed.resize(at + 4);
+    put_end_record(&packed[at], at * 4);
+}
+
 // The shadow-ray tree and the reference chain records (rs_walk.h walk_occlusion_tree).  Needs every
 // reference box finite with min <= max (always true for boxes from rs_build_bvh; a caller-supplied table
 // that is not leaves the fast path off and shadow rays walk the reference's tree).
@@ -76,8 +87,7 @@ int build_occlusion_side(rs_scene* s) {
         for (int k = 0; k < 3; k++) if (s->hBoxes[i * 6 + k] > s->hBoxes[i * 6 + 3 + k]) return 0;
     const std::vector<int>& parent = s->hParent;
     const std::vector<int>& leafOf = s->hLeafOf;
-    std::vector<float> primBoxes(np * 6);
-    for (size_t p = 0; p < np; p++) std::memcpy(&primBoxes[p * 6], &s->hBoxes[(size_t)leafOf[p] * 6], 6 * sizeof(float));
+    const std::vector<float> primBoxes = leaf_boxes(s, np);
     std::vector<BvhNode> nodes;
     std::vector<int> leafPrims;
     // a scene the second tree cannot be built for (RS_ERR_UNSUPPORTED: e.g. all vertices in one point, so that the grid has no
@@ -102,21 +112,14 @@ int build_occlusion_side(rs_scene* s) {
     std::vector<TriRec> rec(np);
     for (size_t i = 0; i < np; i++) {
         const size_t p = (size_t)leafPrims[i];
-        const float* t = &s->hVertices[p * 9];
-        f3 v0 = ld3(t), v1 = ld3(t + 3), v2 = ld3(t + 6);
-        f3 e1 = v1 - v0, e2 = v2 - v0;
-        float leafBits;
-        std::memcpy(&leafBits, &leafOf[p], 4);
-        rec[i] = TriRec{ v0.x, v0.y, v0.z, leafBits, e1.x, e1.y, e1.z, 0.f, e2.x, e2.y, e2.z, 0.f };
+        rec[i] = tri_rec(&s->hVertices[p * 9], leafOf[p]);
     }
     int root = 0;
     for (size_t i = 0; i < nn; i++) if (parent[i] < 0) root = (int)i;
     s->dev.occNested = s->properBoxes;           // a proper hierarchy is in particular nested
     s->dev.occRootLo = ld3(&s->hBoxes[(size_t)root * 6]);
     s->dev.occRootHi = ld3(&s->hBoxes[(size_t)root * 6 + 3]);
-    // one record past the end: an empty box (lo = 65535 > hi = 0 on every axis fails the slab test for either sign of the direction)
-    // whose link is its own offset -- a lane whose walk has ended stays there, so the walk loop needs no "has this lane ended" region
-    packed.push_back(0xffffffffu); packed.push_back(0x0000ffffu); packed.push_back(0u); packed.push_back((unsigned)(no * 16));
+    push_end_record(packed);                     // one record past the end
     RS_TRY(rs_dev_alloc(&s->dOccNodes, no + 1));
     RS_HIP(hipMemcpy(s->dOccNodes, packed.data(), (no + 1) * 16, hipMemcpyHostToDevice));
     RS_TRY(upload(&s->dOccChain, chain));
@@ -163,8 +166,7 @@ int build_emissive_side(rs_scene* s) {
         if (m >= 0 && m < (int)s->hMaterials.size() && s->hMaterials[(size_t)m].type == 4) prims.push_back(p);
     }
     if (prims.empty()) { s->dev.emiState = 1; s->dev.emiCount = 0; return 0; }      // no emissive triangle: no closest hit is one
-    std::vector<float> boxes(prims.size() * 6);
-    for (size_t i = 0; i < prims.size(); i++) std::memcpy(&boxes[i * 6], &s->hBoxes[(size_t)s->hLeafOf[(size_t)prims[i]] * 6], 6 * sizeof(float));
+    const std::vector<float> boxes = leaf_boxes(s, prims.size(), prims.data());
     std::vector<BvhNode> nodes;
     std::vector<int> leafPrims;
     if (int e = rs_build_occlusion_bvh((int)prims.size(), boxes.data(), nodes, leafPrims)) return e == RS_ERR_UNSUPPORTED ? 0 : e;
@@ -172,16 +174,12 @@ int build_emissive_side(rs_scene* s) {
     std::vector<unsigned> packed;
     if (int e = rs_quantize_occlusion_bvh(nodes, base, scale, packed, &s->emiMargin)) return e == RS_ERR_UNSUPPORTED ? 0 : e;
     const size_t no = nodes.size();
-    packed.push_back(0xffffffffu); packed.push_back(0x0000ffffu); packed.push_back(0u); packed.push_back((unsigned)(no * 16));      // the end record
+    push_end_record(packed);
     // kept on the host for rs_scene_set_geometry: the primitive in every slot of emiTris
     s->hEmiLeafPrims.resize(prims.size());
     for (size_t i = 0; i < prims.size(); i++) s->hEmiLeafPrims[i] = prims[(size_t)leafPrims[i]];
     std::vector<TriRec> rec(prims.size());
-    for (size_t i = 0; i < prims.size(); i++) {
-        const float* t = &s->hVertices[(size_t)prims[(size_t)leafPrims[i]] * 9];
-        const f3 v0 = ld3(t), v1 = ld3(t + 3), v2 = ld3(t + 6), e1 = v1 - v0, e2 = v2 - v0;
-        rec[i] = TriRec{ v0.x, v0.y, v0.z, 0.f, e1.x, e1.y, e1.z, 0.f, e2.x, e2.y, e2.z, 0.f };
-    }
+    for (size_t i = 0; i < prims.size(); i++) rec[i] = tri_rec(&s->hVertices[(size_t)prims[(size_t)leafPrims[i]] * 9]);
     RS_TRY(rs_dev_alloc(&s->dEmiNodes, no + 1));
     RS_HIP(hipMemcpy(s->dEmiNodes, packed.data(), (no + 1) * 16, hipMemcpyHostToDevice));
     RS_TRY(upload(&s->dEmiTris, rec));
@@ -211,8 +209,7 @@ int build_ordered_side(rs_scene* s) {
         for (size_t i = 0; i < nn; i++) { const int p = s->hNodes[2 * a + 1][i * 3]; if (p >= 0) { if (j == 0 || seq[a][--j] != p) return 0; } }
         if (j != 0) return 0;
     }
-    std::vector<float> primBoxes(np * 6);
-    for (size_t p = 0; p < np; p++) std::memcpy(&primBoxes[p * 6], &s->hBoxes[(size_t)s->hLeafOf[p] * 6], 6 * sizeof(float));
+    const std::vector<float> primBoxes = leaf_boxes(s, np);
     std::vector<unsigned> packed[6];
     size_t maxCount = 0;
     {   // the three axes are independent: one host thread each (2.8 M triangles: 2.5 s -> 0.9 s of scene set-up)
@@ -252,20 +249,14 @@ int build_ordered_side(rs_scene* s) {
             unsigned& w = o[i * 4 + 3];
             if ((int)w >= 0) w = (w == count * 16) ? (unsigned)endOff : (unsigned)(first + w);       // inner: miss link, relative -> absolute
         }
-        for (size_t i = count; i <= maxCount; i++) { o[i * 4] = 0xffffffffu; o[i * 4 + 1] = 0x0000ffffu; o[i * 4 + 2] = 0u; o[i * 4 + 3] = (unsigned)endOff; }
+        for (size_t i = count; i <= maxCount; i++) put_end_record(o + i * 4, endOff);
     }
     // triangles in the even orders' sequence: pad0 = reference leaf node (the chain check starts there), pad1 = primitive id
     std::vector<TriRec> rec(np * 3);
     for (int a = 0; a < 3; a++)
         for (size_t i = 0; i < np; i++) {
             const size_t p = (size_t)seq[a][i];
-            const float* t = &s->hVertices[p * 9];
-            f3 v0 = ld3(t), v1 = ld3(t + 3), v2 = ld3(t + 6);
-            f3 e1 = v1 - v0, e2 = v2 - v0;
-            float leafBits, primBits;
-            const int prim = (int)p;
-            std::memcpy(&leafBits, &s->hLeafOf[p], 4); std::memcpy(&primBits, &prim, 4);
-            rec[(size_t)a * np + i] = TriRec{ v0.x, v0.y, v0.z, leafBits, e1.x, e1.y, e1.z, primBits, e2.x, e2.y, e2.z, 0.f };
+            rec[(size_t)a * np + i] = tri_rec(&s->hVertices[p * 9], s->hLeafOf[p], (int)p);
         }
     RS_TRY(rs_dev_alloc(&s->dOrdNodes, all.size() / 4));
     RS_HIP(hipMemcpy(s->dOrdNodes, all.data(), all.size() * 4, hipMemcpyHostToDevice));
@@ -275,6 +266,8 @@ int build_ordered_side(rs_scene* s) {
     s->dev.ordStride = (unsigned)stride;
     return 0;
 }
+
+}  // namespace
 
 // The light records and alias records of the scene's host arrays (hLightPrimIds, hLightRadiance, hLightProb, hLightFailId); rs_scene_create
 // and rs_scene_set_emission fill them alike.
@@ -296,213 +289,12 @@ void light_records(const rs_scene* s, float sumInv, LightRec* rec, AliasRec* al)
     }
 }
 
-// Byte offsets of one version's tables in its staging buffer (each 64-byte aligned)
-struct VersionLayout { size_t mat, light, alias, tex, total; };
-VersionLayout version_layout(const rs_scene* s) {
-    auto up = [](size_t b) { return (b + 63) & ~(size_t)63; };
-    VersionLayout l;
-    l.mat = 0;
-    l.light = up(s->hMaterials.size() * sizeof(rs_material));
-    l.alias = l.light + up((size_t)s->numLights * sizeof(LightRec));
-    l.tex = l.alias + up((size_t)s->numLights * sizeof(AliasRec));
-    l.total = l.tex + up(s->hTextures.size() * sizeof(TexRec));
-    return l;
+// a sampler's two host arrays as the records the device reads (the environment map's: rs_scene_create, rs_scene_set_texture)
+std::vector<AliasRec> alias_records(const std::vector<float>& prob, const std::vector<int>& fail) {
+    std::vector<AliasRec> al(prob.size());
+    for (size_t i = 0; i < al.size(); i++) { al[i].prob = prob[i]; al[i].failId = fail[i]; }
+    return al;
 }
-
-float triangle_area(const float* t) {
-    const f3 v0 = ld3(t), v1 = ld3(t + 3), v2 = ld3(t + 6);
-    return length(cross(v1 - v0, v2 - v0)) * .5f;
-}
-
-// First edit: slots 1.. of the version ring, every slot's staging buffer and events, the per-light areas and the environment map's power
-int versions_prepare(rs_scene* s) {
-    if (s->verReady) return 0;
-    const VersionLayout l = version_layout(s);
-    const size_t nm = s->hMaterials.size(), nl = (size_t)s->numLights, nt = s->hTextures.size();
-    s->ver[0].materials = s->dMaterials; s->ver[0].lights = s->dLights; s->ver[0].alias = s->dAlias; s->ver[0].textures = s->dTextures;
-    for (int v = 0; v < rs_scene::kVersions; v++) {
-        rs_scene::Version& x = s->ver[v];
-        if (v > 0) {
-            RS_TRY(rs_dev_alloc(&x.materials, nm));
-            RS_TRY(rs_dev_alloc(&x.lights, nl));
-            RS_TRY(rs_dev_alloc(&x.alias, nl));
-            if (nt) RS_TRY(rs_dev_alloc(&x.textures, nt));
-        }
-        RS_HIP(hipHostMalloc((void**)&x.staging, l.total, hipHostMallocDefault));
-        for (hipEvent_t& e : x.retired) RS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    s->texEdited.assign(nt, rs_scene::Edited{});
-    for (size_t i = 0; i < nt; i++) s->texEdited[i].dev[0] = s->dTexData[i];
-    s->envEdited = rs_scene::Edited{};
-    s->envEdited.dev[0] = s->dEnvAlias;
-    RS_HIP(hipEventCreateWithFlags(&s->verFilled, hipEventDisableTiming));
-    RS_HIP(hipStreamCreateWithFlags(&s->verStream, hipStreamNonBlocking));
-    // Math::triangleArea of every light primitive, as rs_build_light_table computes it (scene_build.cpp)
-    s->hLightArea.resize(s->hLightPrimIds.size());
-    for (size_t i = 0; i < s->hLightArea.size(); i++) s->hLightArea[i] = triangle_area(&s->hVertices[(size_t)s->hLightPrimIds[i] * 9]);
-    // the environment map's sampler entry keeps its power: the sum of its pdf, as rs_scene_build_textured passes it on (a scene made by
-    // rs_scene_create from a description does not carry it)
-    if (s->envMapTexId >= 0 && !s->envPowerKnown) {
-        const rs_texture& env = s->hTextures[(size_t)s->envMapTexId];
-        std::vector<float> pdf((size_t)env.width * env.height);
-        RS_TRY(rs_build_envmap_pdf(env.width, env.height, env.data, pdf.data()));
-        float total = 0.f;
-        for (float p : pdf) total += p;                           // rs_build_alias_table's sum, in its order
-        s->envPower = total; s->envPowerKnown = true;
-    }
-    s->verReady = true;
-    return 0;
-}
-
-void edited_free(rs_scene::Edited& e) {
-    for (int k = 0; k < rs_scene::kEditedCopies; k++) {
-        if (k > 0 && e.dev[k]) (void)hipFree(e.dev[k]);           // ([0] is the scene's own array)
-        if (e.staging[k]) (void)hipHostFree(e.staging[k]);
-        e.dev[k] = nullptr; e.staging[k] = nullptr;
-    }
-}
-
-void versions_free(rs_scene* s) {
-    for (int v = 0; v < rs_scene::kVersions; v++) {
-        rs_scene::Version& x = s->ver[v];
-        if (v > 0) { rs_dev_free(x.materials); rs_dev_free(x.lights); rs_dev_free(x.alias); rs_dev_free(x.textures); }
-        if (x.staging) { (void)hipHostFree(x.staging); x.staging = nullptr; }
-        for (hipEvent_t& e : x.retired) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    }
-    for (rs_scene::Edited& e : s->texEdited) edited_free(e);
-    edited_free(s->envEdited);
-    if (s->verFilled) { (void)hipEventDestroy(s->verFilled); s->verFilled = nullptr; }
-    if (s->verStream) { (void)hipStreamDestroy(s->verStream); s->verStream = nullptr; }
-}
-
-// what rs_scene_set_motion_tracking allocated
-void motion_free(rs_scene* s) {
-    rs_dev_free(s->dPrevVertices);
-    for (hipEvent_t& e : s->motionBefore) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    if (s->motionAfter) { (void)hipEventDestroy(s->motionAfter); s->motionAfter = nullptr; }
-}
-
-// Edits are not recorded into graphs: a captured frame keeps the tables it was captured with
-int refuse_while_capturing(const char* msg) {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(rs_stream(), &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
-    if (capturing != hipStreamCaptureStatusNone) return rs_fail(RS_ERR_UNSUPPORTED, msg);
-    return 0;
-}
-
-// An edit, first half (the new host tables have been built and checked; nothing of the scene has changed yet): launches what has only
-// been recorded, with the old tables, and frees the slot the edit will fill.
-int version_begin(rs_scene* s) {
-    // frames in flight: a render that has only been recorded captures `dev` when it is launched -- launch it now, with the old tables
-    RS_TRY(rs_gbuffer_release_scene(s));
-    rs_scene::Version& nv = s->ver[(s->verCur + 1) % rs_scene::kVersions];
-    for (int k = 0; k < rs_scene::kVersionStreams; k++)          // the ring has run out only if a launch that captured the slot still runs
-        if (nv.retiredValid[k]) { RS_HIP(hipEventSynchronize(nv.retired[k])); nv.retiredValid[k] = false; }
-    return 0;
-}
-
-// Between version_begin and version_commit: the edit replaces the contents of `e` (`bytes`).  They go, on the fills' stream, to an array
-// that no version in flight points at -- edited_reserve finds it, edited_fill writes it, so that an edit that replaces two (the
-// environment map's texels and its alias table) has reserved both before it changes either.  version_begin has waited for version
-// verSeq + 1 - kVersions, and versions retire in order, so an array last used kVersions edits back is free; failing that a new one is
-// allocated while the Edited may grow; failing that the host waits for the versions that read the array left longest ago.
-int edited_reserve(rs_scene* s, rs_scene::Edited& e, size_t bytes, int* which) {
-    const unsigned long long newSeq = s->verSeq + 1;
-    int k = -1;
-    for (int i = 0; i < e.count && k < 0; i++)
-        if (i != e.cur && e.lastSeq[i] + rs_scene::kVersions <= newSeq) k = i;
-    if (k < 0 && e.count < rs_scene::kEditedCopies) {
-        RS_HIP(hipMalloc(&e.dev[e.count], bytes ? bytes : 1));
-        e.lastSeq[e.count] = 0;                                  // (never pointed at yet)
-        k = e.count++;
-    }
-    if (k < 0) {
-        for (int i = 0; i < e.count; i++)
-            if (i != e.cur && (k < 0 || e.lastSeq[i] < e.lastSeq[k])) k = i;
-        // the versions up to lastSeq[k] retire in order, and the events of lastSeq[k] are still in its slot (less than kVersions edits back)
-        rs_scene::Version& x = s->ver[e.lastSeq[k] % rs_scene::kVersions];
-        for (int j = 0; j < rs_scene::kVersionStreams; j++)
-            if (x.retiredValid[j]) { RS_HIP(hipEventSynchronize(x.retired[j])); x.retiredValid[j] = false; }
-    }
-    if (!e.staging[k]) RS_HIP(hipHostMalloc((void**)&e.staging[k], bytes ? bytes : 1, hipHostMallocDefault));
-    *which = k;
-    return 0;
-}
-int edited_fill(rs_scene* s, rs_scene::Edited& e, int k, const void* src, size_t bytes) {
-    std::memcpy(e.staging[k], src, bytes);
-    RS_HIP(hipMemcpyAsync(e.dev[k], e.staging[k], bytes, hipMemcpyHostToDevice, s->verStream));
-    e.lastSeq[e.cur] = s->verSeq;
-    e.cur = k;
-    return 0;
-}
-
-// An edit, second half (the scene's host tables are the new ones): fills the next slot from them and moves the scene there.
-int version_commit(rs_scene* s, const char* what) {
-    const int next = (s->verCur + 1) % rs_scene::kVersions;
-    rs_scene::Version& nv = s->ver[next];
-    const size_t nl = (size_t)s->numLights, nt = s->hTextures.size();
-    const float sumInv = 1.f / s->sumLightPower;                         // scene.cpp:489
-    const VersionLayout l = version_layout(s);
-    std::memcpy(nv.staging + l.mat, s->hMaterials.data(), s->hMaterials.size() * sizeof(rs_material));
-    light_records(s, sumInv, reinterpret_cast<LightRec*>(nv.staging + l.light), reinterpret_cast<AliasRec*>(nv.staging + l.alias));
-    TexRec* recs = reinterpret_cast<TexRec*>(nv.staging + l.tex);
-    for (size_t i = 0; i < nt; i++) {
-        const rs_scene::Edited& e = s->texEdited[i];
-        recs[i] = TexRec{ static_cast<float*>(e.dev[e.cur]), s->hTextures[i].width, s->hTextures[i].height };
-    }
-
-    // the current slot is retired by what has been enqueued so far on the library stream and on every auxiliary stream
-    rs_context* c = rs_ctx();
-    const hipStream_t st = rs_stream();
-    rs_scene::Version& ov = s->ver[s->verCur];
-    RS_HIP(hipEventRecord(ov.retired[0], st)); ov.retiredValid[0] = true;
-    for (int i = 0; i < rs_context::kAux; i++)
-        if (c->aux[i]) { RS_HIP(hipEventRecord(ov.retired[1 + i], c->aux[i])); ov.retiredValid[1 + i] = true; }
-    // The slot is free (no launch reads it), so its fill waits for nothing: it goes to a stream of the scene's own and the library and
-    // auxiliary streams wait for that copy alone.  (Filled on the library stream, the edit would order the auxiliary streams after the
-    // frames in flight there and end the overlap of consecutive frames: config 5 with an edit per frame 1.69 -> 3.12 ms.)
-    RS_HIP(hipMemcpyAsync(nv.materials, nv.staging + l.mat, s->hMaterials.size() * sizeof(rs_material), hipMemcpyHostToDevice, s->verStream));
-    if (nl) {
-        RS_HIP(hipMemcpyAsync(nv.lights, nv.staging + l.light, nl * sizeof(LightRec), hipMemcpyHostToDevice, s->verStream));
-        RS_HIP(hipMemcpyAsync(nv.alias, nv.staging + l.alias, nl * sizeof(AliasRec), hipMemcpyHostToDevice, s->verStream));
-    }
-    if (nt) RS_HIP(hipMemcpyAsync(nv.textures, nv.staging + l.tex, nt * sizeof(TexRec), hipMemcpyHostToDevice, s->verStream));
-    RS_HIP(hipEventRecord(s->verFilled, s->verStream));
-    RS_HIP(hipStreamWaitEvent(st, s->verFilled, 0));             // launches from now on see the new tables
-    for (int i = 0; i < rs_context::kAux; i++)
-        if (c->aux[i]) RS_HIP(hipStreamWaitEvent(c->aux[i], s->verFilled, 0));
-    s->dev.materials = nv.materials;
-    s->dev.lights = nv.lights;
-    s->dev.alias = nv.alias;
-    if (nt) s->dev.textures = nv.textures;
-    if (s->envMapTexId >= 0) s->dev.envAlias = static_cast<AliasRec*>(s->envEdited.dev[s->envEdited.cur]);
-    s->dev.sumLightPowerInv = sumInv;
-    s->verCur = next;
-    s->verSeq++;
-    s->edits++;                                                  // retained G-buffer planes are not this scene's any more
-    return rs_after_launch(what);
-}
-
-// The light sampler of the scene's light primitives with radiance `rad` (3 floats each), areas `area` and the environment entry's power envPower, as
-// rs_scene_build_textured builds it (rs_build_light_table's powers, the environment map's entry last, rs_build_alias_table)
-int light_sampler(const rs_scene* s, const float* rad, const float* area, float envPower, std::vector<float>& prob, std::vector<int>& fail, float* sumAll, const char* noPower) {
-    const size_t nl = (size_t)s->numLights, nlp = s->hLightPrimIds.size();
-    std::vector<float> power(nl);
-    prob.assign(nl, 0.f); fail.assign(nl, 0);
-    for (size_t i = 0; i < nlp; i++) {
-        const float perArea = luminance(ld3(rad + i * 3)) * 2.f * kGlmPi;       // rs_build_light_table (scene.cpp:164)
-        power[i] = perArea * area[i];
-    }
-    if (nlp < nl) power[nlp] = envPower;
-    *sumAll = 0.f;
-    if (nl) {
-        RS_TRY(rs_build_alias_table((int)nl, power.data(), prob.data(), fail.data(), sumAll));
-        if (!(*sumAll > 0.f) || std::isinf(*sumAll)) return rs_fail(RS_ERR_INVALID_ARGUMENT, noPower);
-    }
-    return 0;
-}
-
-}  // namespace
 
 extern "C" int rs_scene_destroy(rs_scene* s) {
     RS_SCOPE(s);
@@ -545,535 +337,6 @@ extern "C" int rs_scene_set_sample_sequence(rs_scene* s, const uint32_t* data, i
     return 0;
 }
 
-// Emission of Light-type materials, stream-ordered (include/restir_hip.h).  The host tables are rebuilt as rs_scene_build_textured builds
-// them (rs_build_light_table's powers over the scene's light primitives, the environment map's entry last, rs_build_alias_table), so
-// that the scene equals, bit for bit, one built afresh from the edited materials.  The device tables go to the next slot of the version
-// ring (rs_internal.h rs_scene::Version): launches enqueued before the call keep reading the slot they captured.
-extern "C" int rs_scene_set_emission(rs_scene* s, int count, const int* materialIds, const float* radiance) {
-    RS_SCOPE(s);
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_emission: null scene");
-    if (count < 0 || (count > 0 && (!materialIds || !radiance))) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_emission: count < 0 or null arrays");
-    const int nm = (int)s->hMaterials.size();
-    for (int i = 0; i < count; i++) {
-        const int m = materialIds[i];
-        if (m < 0 || m >= nm || s->hMaterials[(size_t)m].type != 4)
-            return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_emission: a material id out of range or of a material that is not a Light");
-        for (int k = 0; k < 3; k++) {
-            const float x = radiance[(size_t)i * 3 + k];
-            if (!(x >= 0.f) || std::isinf(x)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_emission: radiance must be finite and >= 0");
-        }
-    }
-    RS_TRY(refuse_while_capturing("rs_scene_set_emission: the library stream is being captured into a graph"));
-    RS_TRY(versions_prepare(s));
-
-    // the new host tables (nothing of the scene changes before all of them have been built and checked)
-    std::vector<rs_material> mats = s->hMaterials;
-    for (int i = 0; i < count; i++) std::memcpy(mats[(size_t)materialIds[i]].baseColor, radiance + (size_t)i * 3, 3 * sizeof(float));
-    const size_t nlp = s->hLightPrimIds.size();
-    std::vector<float> rad(nlp * 3), prob;
-    std::vector<int> fail;
-    for (size_t i = 0; i < nlp; i++) st3(&rad[i * 3], ld3(mats[(size_t)s->hMaterialIds[(size_t)s->hLightPrimIds[i]]].baseColor));
-    float sumAll = 0.f;
-    RS_TRY(light_sampler(s, rad.data(), s->hLightArea.data(), s->envPower, prob, fail, &sumAll,
-                         "rs_scene_set_emission: the edit leaves the light sampler without a finite, positive total power"));
-
-    RS_TRY(version_begin(s));
-    s->hMaterials.swap(mats);
-    s->hLightRadiance.swap(rad);
-    s->hLightProb.swap(prob);
-    s->hLightFailId.swap(fail);
-    s->sumLightPower = sumAll;
-    return version_commit(s, "rs_scene_set_emission");
-}
-
-// Material records, stream-ordered like the emission (include/restir_hip.h).  Light materials stay with rs_scene_set_emission: the light
-// list, the emissive tree and the G-buffer's -2 ids are built from which materials are Lights.
-extern "C" int rs_scene_set_materials(rs_scene* s, int count, const int* materialIds, const rs_material* records) {
-    RS_SCOPE(s);
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_materials: null scene");
-    if (count < 0 || (count > 0 && (!materialIds || !records))) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_materials: count < 0 or null arrays");
-    const int nm = (int)s->hMaterials.size();
-    for (int i = 0; i < count; i++) {
-        const int m = materialIds[i];
-        if (m < 0 || m >= nm) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_materials: a material id out of range");
-        if (s->hMaterials[(size_t)m].type == 4 || records[i].type < 0 || records[i].type > 3)
-            return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_materials: a material that is a Light or would become one (or of an unknown type); emission is edited by rs_scene_set_emission");
-    }
-    RS_TRY(refuse_while_capturing("rs_scene_set_materials: the library stream is being captured into a graph"));
-    if (count == 0) return 0;
-    std::vector<rs_material> mats = s->hMaterials;
-    for (int i = 0; i < count; i++) mats[(size_t)materialIds[i]] = records[i];           // a repeated id: the last record wins
-    bool anyMap = false;
-    RS_TRY(check_materials(nm, mats.data(), (int)s->hTextures.size(), &anyMap, "rs_scene_set_materials: material map id beyond the texture table",
-                           "rs_scene_set_materials: invalid material map id"));
-    if (anyMap && !s->hasTexcoords) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_materials: texture maps need texcoords, and the scene was created without");
-    RS_TRY(versions_prepare(s));
-
-    RS_TRY(version_begin(s));
-    if (anyMap && !s->textured) {
-        // the scene's first map: so far it ran the kernels that read no texture coordinates, and none are on the device
-        if (!s->dTexcoords) RS_TRY(rs_dev_alloc(&s->dTexcoords, s->hTexcoords.size()));
-        RS_HIP(hipMemcpyAsync(s->dTexcoords, s->hTexcoords.data(), s->hTexcoords.size() * sizeof(float), hipMemcpyHostToDevice, s->verStream));
-        s->dev.texcoords = s->dTexcoords;
-        s->textured = true;
-    }
-    s->hMaterials.swap(mats);
-    return version_commit(s, "rs_scene_set_materials");
-}
-
-// The texels of one texture, stream-ordered like the emission (include/restir_hip.h).  For the environment map the host rebuilds what
-// rs_scene_build_textured builds from it: the pdf, the map's alias table, its entry in the light sampler and with it the light sampler.
-extern "C" int rs_scene_set_texture(rs_scene* s, int texId, int width, int height, const float* data) {
-    RS_SCOPE(s);
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_texture: null scene");
-    if (texId < 0 || texId >= (int)s->hTextures.size()) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_texture: texture id out of range");
-    const rs_texture& t = s->hTextures[(size_t)texId];
-    if (width != t.width || height != t.height || !data) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_texture: null data, or dimensions other than the texture's");
-    RS_TRY(refuse_while_capturing("rs_scene_set_texture: the library stream is being captured into a graph"));
-    RS_TRY(versions_prepare(s));
-    const size_t n = (size_t)width * height;
-    const bool env = texId == s->envMapTexId;
-    std::vector<float> envProb, prob;
-    std::vector<int> envFail, fail;
-    float envSum = 0.f, sumAll = 0.f;
-    if (env) {
-        std::vector<float> pdf(n);
-        RS_TRY(rs_build_envmap_pdf(width, height, data, pdf.data()));
-        for (float p : pdf) envSum += p;                                 // rs_build_alias_table's sum, in its order
-        if (!(envSum > 0.f) || std::isinf(envSum)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_texture: the environment map's pdf has no finite, positive sum");
-        envProb.resize(n); envFail.resize(n);
-        RS_TRY(rs_build_alias_table((int)n, pdf.data(), envProb.data(), envFail.data(), &envSum));
-        RS_TRY(light_sampler(s, s->hLightRadiance.data(), s->hLightArea.data(), envSum, prob, fail, &sumAll,
-                             "rs_scene_set_texture: the edit leaves the light sampler without a finite, positive total power"));
-    }
-
-    RS_TRY(version_begin(s));
-    int texels = 0, alias = 0;
-    RS_TRY(edited_reserve(s, s->texEdited[(size_t)texId], n * 3 * sizeof(float), &texels));
-    if (env) RS_TRY(edited_reserve(s, s->envEdited, n * sizeof(AliasRec), &alias));
-    RS_TRY(edited_fill(s, s->texEdited[(size_t)texId], texels, data, n * 3 * sizeof(float)));
-    std::memcpy(s->hTexData[(size_t)texId].data(), data, n * 3 * sizeof(float));
-    if (env) {
-        std::vector<AliasRec> al(n);
-        for (size_t i = 0; i < n; i++) { al[i].prob = envProb[i]; al[i].failId = envFail[i]; }
-        RS_TRY(edited_fill(s, s->envEdited, alias, al.data(), n * sizeof(AliasRec)));
-        s->hEnvProb.swap(envProb);
-        s->hEnvFail.swap(envFail);
-        s->hLightProb.swap(prob);
-        s->hLightFailId.swap(fail);
-        s->sumLightPower = sumAll;
-        s->envPower = envSum; s->envPowerKnown = true;
-    }
-    return version_commit(s, "rs_scene_set_texture");
-}
-
-// Triangles, stream-ordered (include/restir_hip.h).  Geometry is too large for the ring of versions (nodesAll alone is 6 x 32 bytes per
-// node), so this edit works in place behind device-side fences: the library stream waits for what the internal streams have been handed
-// so far, the edit's kernels (scene_refit.hip) run on the library stream, and the next launch of every internal stream waits for them.
-// The host's tables follow at once: hVertices, hNormals, and hBoxes = rs_refit_boxes of the edited vertices.
-//
-// One implementation behind two entry points.  rs_scene_set_triangles refuses emitters and thereby guarantees that the light sampler, the
-// light records and the emissive tree are untouched.  rs_scene_set_geometry takes them: an edit that names one also rebuilds the light
-// sampler from the new areas (as rs_scene_set_emission does from new radiance), fills the next slot of the version ring -- light_records
-// derives LightRec from hVertices -- and refits the emissive tree on a grid laid anew over the new emissive root box.  Both transitions
-// are made at the same point of the library stream: the in-place edit behind before[] / after, the version switch behind verFilled, with
-// no launch between them.  An edit through rs_scene_set_geometry that names no emitter does exactly what rs_scene_set_triangles does.
-namespace {
-
-int fail_named(int code, const char* name, const char* text) {
-    static thread_local std::string msg;
-    msg = std::string(name) + ": " + text;
-    return rs_fail(code, msg.c_str());
-}
-
-// An edit in place of arrays that launches on the library's internal streams read (the geometry; the previous pose): the library stream waits,
-// by events, for what those streams have been handed so far (fence_before), the edit's kernels run on the library stream, and the next
-// launch of every internal stream waits for them (fence_after).  Launches enqueued before the edit read the old arrays, launches after it the new.
-int fence_before(hipEvent_t* before) {
-    rs_context* c = rs_ctx();
-    for (int i = 0; i < rs_context::kAux; i++)
-        if (c->aux[i]) { RS_HIP(hipEventRecord(before[i], c->aux[i])); RS_HIP(hipStreamWaitEvent(rs_stream(), before[i], 0)); }
-    return 0;
-}
-int fence_after(hipEvent_t after) {
-    rs_context* c = rs_ctx();
-    RS_HIP(hipEventRecord(after, rs_stream()));
-    for (int i = 0; i < rs_context::kAux; i++)
-        if (c->aux[i]) RS_HIP(hipStreamWaitEvent(c->aux[i], after, 0));
-    return 0;
-}
-
-// parts (rs_scene_set_part_transforms): the edit's records are not copied from the host but written on the device, by k_bake_parts from the
-// numRecs part records `recs` (which alone are staged) and the scene's rest pose; primIds / vertices / normals are then the host's own baking
-// of the same triangles, every id once, in the order the kernel writes them -- for the checks, the light areas and the host's tables.
-struct PartSource { int numRecs; const PartRec* recs; };
-
-int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals, bool emitters, const char* name,
-                 const PartSource* parts = nullptr) {
-    if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
-    if (count < 0 || (count > 0 && (!primIds || !vertices))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "count < 0 or null arrays");
-    const bool bounded = s->dOccNodes != nullptr;       // the 16-bit grid of the grid-box trees lies over the box the scene was created with
-    bool lamps = false;
-    for (int i = 0; i < count; i++) {
-        const int p = primIds[i];
-        if (p < 0 || p >= s->numPrims) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a primitive id out of range");
-        if (s->hMaterials[(size_t)s->hMaterialIds[(size_t)p]].type == 4) {
-            if (!emitters)
-                return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a triangle whose material is a Light (the light table, the sampler's powers and the emissive tree are built over the emitters' geometry; rs_scene_set_geometry moves emitters)");
-            lamps = true;
-        }
-        for (int k = 0; k < 9; k++) {
-            const float x = vertices[(size_t)i * 9 + k];
-            if (!std::isfinite(x) || (normals && !std::isfinite(normals[(size_t)i * 9 + k])))
-                return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a vertex or normal that is not finite");
-            if (bounded && !(x >= s->gridLo[k % 3] && x <= s->gridHi[k % 3]))
-                return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a vertex outside the root box the scene was created with (the grid of its shadow-ray tree lies over that box); build a new scene");
-        }
-    }
-    {
-        static thread_local std::string msg;
-        msg = std::string(name) + ": the library stream is being captured into a graph";
-        RS_TRY(refuse_while_capturing(msg.c_str()));
-    }
-    if (count == 0) return 0;
-    RS_TRY(rs_refit_prepare(s));
-    if (lamps) RS_TRY(versions_prepare(s));             // (the ring's slots, hLightArea, the environment entry's power)
-    rs_refit* r = s->refit;
-    const size_t np = (size_t)s->numPrims, nn = (size_t)s->bvhSize;
-
-    // the edit's records, a repeated id keeping its last: ids | vertices | normals, each part 16-byte aligned
-    if (++r->stamp == 0u) { std::fill(r->lastStamp.begin(), r->lastStamp.end(), 0u); r->stamp = 1u; }
-    int m = 0;
-    for (int i = 0; i < count; i++) {
-        const size_t p = (size_t)primIds[i];
-        if (r->lastStamp[p] != r->stamp) { r->lastStamp[p] = r->stamp; r->lastIndex[p] = m++; }
-    }
-    auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t offV = up((size_t)m * sizeof(int)), offN = offV + up((size_t)m * 9 * sizeof(float));
-    const size_t bytes = offN + (normals ? up((size_t)m * 9 * sizeof(float)) : 0);
-    // what crosses the bus: the records themselves, or the part records, which follow the records they expand to in the device buffer
-    const size_t staged = parts ? (size_t)parts->numRecs * sizeof(PartRec) : bytes, onDevice = parts ? bytes + staged : bytes;
-    rs_refit::Stage& g = r->stage[r->stageNext];
-    if (g.pending) { RS_HIP(hipEventSynchronize(g.copied)); g.pending = false; }      // the ring is full of edits whose copies have not finished
-    if (g.capacity < staged) {
-        if (g.host) { (void)hipHostFree(g.host); g.host = nullptr; g.capacity = 0; }
-        size_t cap = 4096;
-        while (cap < staged) cap *= 2;
-        RS_HIP(hipHostMalloc((void**)&g.host, cap, hipHostMallocDefault));
-        g.capacity = cap;
-    }
-    if (r->dStageCapacity < onDevice) {                  // (hipFree waits for the device: no earlier edit still reads the old buffer)
-        rs_dev_free(r->dStage);
-        r->dStageCapacity = 0;
-        size_t cap = 4096;
-        while (cap < onDevice) cap *= 2;
-        RS_TRY(rs_dev_alloc(&r->dStage, cap));
-        r->dStageCapacity = cap;
-    }
-    const int* ids = primIds;
-    const float* vs = vertices;
-    const float* ns = normals;
-    if (parts) std::memcpy(g.host, parts->recs, staged);
-    else {
-        int* hi = reinterpret_cast<int*>(g.host);
-        float* hv = reinterpret_cast<float*>(g.host + offV);
-        float* hn = reinterpret_cast<float*>(g.host + offN);
-        for (int i = 0; i < count; i++) {
-            const size_t p = (size_t)primIds[i], j = (size_t)r->lastIndex[p];
-            hi[j] = primIds[i];
-            std::memcpy(hv + j * 9, vertices + (size_t)i * 9, 9 * sizeof(float));
-            if (normals) std::memcpy(hn + j * 9, normals + (size_t)i * 9, 9 * sizeof(float));
-        }
-        ids = hi; vs = hv; ns = hn;
-    }
-    // where a primitive's vertices are once the edit has been applied (so far only the staging buffer has been written)
-    auto edited = [&](size_t p) { return r->lastStamp[p] == r->stamp ? vs + (size_t)r->lastIndex[p] * 9 : &s->hVertices[p * 9]; };
-
-    // An emitter moves: the new light sampler and the emissive tree's new grid, built and checked before anything of the scene changes
-    std::vector<float> area, prob;
-    std::vector<int> fail;
-    float sumAll = 0.f, emiBase[3] = {}, emiScale[3] = {};
-    double emiMargin = 0.0;
-    bool emiGrid = false;
-    if (lamps) {
-        area = s->hLightArea;
-        for (size_t i = 0; i < area.size(); i++) {
-            const size_t p = (size_t)s->hLightPrimIds[i];
-            if (r->lastStamp[p] == r->stamp) area[i] = triangle_area(edited(p));
-        }
-        static thread_local std::string msg;
-        msg = std::string(name) + ": the edit leaves the light sampler without a finite, positive total power";
-        RS_TRY(light_sampler(s, s->hLightRadiance.data(), area.data(), s->envPower, prob, fail, &sumAll, msg.c_str()));
-        if (r->emiRecords) {
-            // the emissive root box: the union of the emissive triangles' boxes, which is what a fresh build_emissive_side starts from
-            float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-            for (int p : s->hEmiLeafPrims) {
-                const float* t = edited((size_t)p);
-                for (int k = 0; k < 9; k++) { lo[k % 3] = std::min(lo[k % 3], t[k]); hi[k % 3] = std::max(hi[k % 3], t[k]); }
-            }
-            emiGrid = rs_grid_over_box(lo, hi, emiBase, emiScale, &emiMargin);
-        }
-    }
-
-    // frames in flight: a render that has only been recorded is launched now, with the old geometry (and the old lights)
-    if (lamps) RS_TRY(version_begin(s));
-    else RS_TRY(rs_gbuffer_release_scene(s));
-    if (!r->boxesExact) {
-        // Boxes that were not the exact unions (a caller-supplied table): from now on they are.  The emissive tree was built over the boxes
-        // as given, so it no longer answers for the new ones: the last bounce asks the scene's trees again, for good.
-        std::vector<float> exact(nn * 6);
-        rs_refit_boxes_host(s->bvhSize, s->hVertices.data(), s->hNodes[0].data(), s->hParent.data(), exact.data());
-        bool same = true;
-        for (size_t i = 0; i < nn * 6 && same; i++) same = exact[i] == s->hBoxes[i];
-        if (!same) { s->dev.emiState = 0; r->emiSticky = true; }
-        s->hBoxes.swap(exact);                           // (also when equal as values: rs_refit_boxes' signs of zero from here on)
-        r->boxesExact = true;
-    }
-    // The emissive tree's grid moves with the lamps (DevScene travels by value; the fences keep earlier launches on the old tree).  Emitters
-    // collapsed to a box without extent: a fresh build has no emissive tree either (the quantiser refuses), so the last bounce asks the
-    // scene's trees until an edit brings an extent back -- that edit refits every emissive record, whichever emitters it names.
-    const bool emiNodes = lamps && r->emiRecords && emiGrid && !r->emiSticky;
-    if (lamps && r->emiRecords && !r->emiSticky) {
-        s->dev.emiState = emiGrid ? 1 : 0;
-        if (emiGrid) {
-            s->dev.emiBase = mk3(emiBase[0], emiBase[1], emiBase[2]); s->dev.emiScale = mk3(emiScale[0], emiScale[1], emiScale[2]);
-            s->emiMargin = emiMargin;
-        }
-    }
-    const hipStream_t st = rs_stream();
-    RS_TRY(fence_before(r->before));
-    RS_HIP(hipMemcpyAsync(r->dStage + (parts ? bytes : 0), g.host, staged, hipMemcpyHostToDevice, st));
-    RS_HIP(hipEventRecord(g.copied, st));
-    g.pending = true;
-    r->stageNext = (r->stageNext + 1) % rs_refit::kStaging;
-    r->stagedBytes = staged;
-    if (parts) RS_TRY(rs_bake_parts_enqueue(s->parts, parts->numRecs, reinterpret_cast<const PartRec*>(r->dStage + bytes), (size_t)m, reinterpret_cast<int*>(r->dStage),
-                                            reinterpret_cast<float*>(r->dStage + offV), reinterpret_cast<float*>(r->dStage + offN), st));
-    RS_TRY(rs_refit_enqueue(s, m, reinterpret_cast<const int*>(r->dStage), reinterpret_cast<const float*>(r->dStage + offV),
-                            normals ? reinterpret_cast<const float*>(r->dStage + offN) : nullptr, lamps, emiNodes, st));
-    RS_TRY(fence_after(r->after));
-
-    // the host's tables
-    for (int j = 0; j < m; j++) {
-        std::memcpy(&s->hVertices[(size_t)ids[j] * 9], vs + (size_t)j * 9, 9 * sizeof(float));
-        if (normals) std::memcpy(&s->hNormals[(size_t)ids[j] * 9], ns + (size_t)j * 9, 9 * sizeof(float));
-    }
-    // ... hBoxes = rs_refit_boxes of the edited vertices.  They hold exact unions already (before the first edit: checked above), so an edit
-    // of few triangles recomputes only the moved leaves' ancestors: the same min / max, hence the same bits
-    if ((size_t)m * 16 < np) rs_refit_boxes_host_some(m, ids, s->hVertices.data(), s->hLeafOf.data(), s->hParent.data(), r->hChild.data(), s->hBoxes.data());
-    else rs_refit_boxes_host(s->bvhSize, s->hVertices.data(), s->hNodes[0].data(), s->hParent.data(), s->hBoxes.data());
-    if (s->dev.axisCull && !far_skip_allowed(vs, (size_t)m)) s->dev.axisCull = false;      // (never back on: that would need every triangle again)
-    if (bounded) {
-        s->dev.occRootLo = ld3(&s->hBoxes[r->root * 6]);
-        s->dev.occRootHi = ld3(&s->hBoxes[r->root * 6 + 3]);
-    }
-    s->edits++;                                                  // retained G-buffer planes are not this scene's any more
-    s->geomEdits++;                                              // ... and cuts of the tree carry boxes the refit has just changed
-    if (s->dev.prevVertices) s->motionDirty = true;              // rs_scene_advance_motion has something to copy
-    if (!lamps) return rs_after_launch(name);
-    // the lights' version: light_records reads the vertices just written; launches from here on see new geometry and new lights alike
-    s->hLightArea.swap(area);
-    s->hLightProb.swap(prob);
-    s->hLightFailId.swap(fail);
-    s->sumLightPower = sumAll;
-    return version_commit(s, name);
-}
-
-}  // namespace
-
-extern "C" int rs_scene_set_triangles(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals) {
-    RS_SCOPE(s);
-    return set_geometry(s, count, primIds, vertices, normals, false, "rs_scene_set_triangles");
-}
-
-extern "C" int rs_scene_set_geometry(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals) {
-    RS_SCOPE(s);
-    return set_geometry(s, count, primIds, vertices, normals, true, "rs_scene_set_geometry");
-}
-
-// ---- rigid parts (include/restir_hip.h) ----
-// The definition is replaced behind a wait for the device (rs_synchronize, as the first edit of a scene waits once): a transform enqueued
-// earlier has finished with the old tables, a later one finds the new.  Nothing of the scene's geometry changes.
-extern "C" int rs_scene_define_parts(rs_scene* s, int numParts, const int* partFirst, const int* primIds, const float* restVertices, const float* restNormals) {
-    RS_SCOPE(s);
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: null scene");
-    if (numParts < 0 || (numParts > 0 && !partFirst)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: numParts < 0 or null offsets");
-    if ((restVertices == nullptr) != (restNormals == nullptr)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: rest vertices without rest normals, or the reverse");
-    if (numParts > 0 && partFirst[0] != 0) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: the first offset is not 0");
-    for (int i = 0; i < numParts; i++)
-        if (partFirst[i + 1] < partFirst[i]) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: offsets that decrease");
-    const size_t listed = numParts > 0 ? (size_t)partFirst[numParts] : 0;
-    if (listed > 0 && !primIds) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: null primitive ids");
-    {
-        std::vector<char> seen((size_t)s->numPrims, 0);
-        for (size_t i = 0; i < listed; i++) {
-            const int p = primIds[i];
-            if (p < 0 || p >= s->numPrims) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: a primitive id out of range");
-            if (seen[(size_t)p]) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: a primitive listed twice");
-            seen[(size_t)p] = 1;
-        }
-    }
-    if (restVertices)
-        for (size_t i = 0; i < listed * 9; i++)
-            if (!std::isfinite(restVertices[i]) || !std::isfinite(restNormals[i])) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: a rest value that is not finite");
-    RS_TRY(refuse_while_capturing("rs_scene_define_parts: the library stream is being captured into a graph"));
-    if (numParts == 0) {
-        if (s->parts) { RS_TRY(rs_synchronize()); rs_parts_free(s->parts); s->parts = nullptr; }
-        return 0;
-    }
-
-    rs_parts* p = new rs_parts();
-    p->first.assign(partFirst, partFirst + numParts + 1);
-    p->primIds.assign(primIds, primIds + listed);
-    p->restVertices.resize(listed * 9); p->restNormals.resize(listed * 9);
-    for (size_t i = 0; i < listed; i++) {
-        // the scene's own pose, or the caller's arrays
-        std::memcpy(&p->restVertices[i * 9], restVertices ? restVertices + i * 9 : &s->hVertices[(size_t)primIds[i] * 9], 9 * sizeof(float));
-        std::memcpy(&p->restNormals[i * 9], restNormals ? restNormals + i * 9 : &s->hNormals[(size_t)primIds[i] * 9], 9 * sizeof(float));
-    }
-    p->recOf.assign((size_t)numParts, 0);
-    p->recStamp.assign((size_t)numParts, 0u);
-    int e = upload(&p->dPrimIds, p->primIds);
-    if (!e) e = upload(&p->dRestVertices, p->restVertices);
-    if (!e) e = upload(&p->dRestNormals, p->restNormals);
-    if (!e && s->parts) e = rs_synchronize();           // a transform in flight reads the tables that are about to be freed
-    if (e) { rs_parts_free(p); return e; }              // (the definition stays what it was)
-    rs_parts_free(s->parts);
-    s->parts = p;
-    return 0;
-}
-
-// The named parts' records (a part named twice keeps its place and takes its last matrix; an empty part has none), the host's own baking of
-// their triangles, and then rs_scene_set_geometry's implementation with the records written on the device.
-extern "C" int rs_scene_set_part_transforms(rs_scene* s, int count, const int* partIds, const float* matrices16) {
-    RS_SCOPE(s);
-    const char* name = "rs_scene_set_part_transforms";
-    if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
-    if (count < 0 || (count > 0 && (!partIds || !matrices16))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "count < 0 or null arrays");
-    rs_parts* p = s->parts;
-    if (!p) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "the scene has no parts (rs_scene_define_parts)");
-    const int numParts = (int)p->first.size() - 1;
-    for (int i = 0; i < count; i++)
-        if (partIds[i] < 0 || partIds[i] >= numParts) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a part id out of range");
-
-    if (++p->stamp == 0u) { std::fill(p->recStamp.begin(), p->recStamp.end(), 0u); p->stamp = 1u; }
-    p->recs.clear();
-    for (int i = 0; i < count; i++) {
-        const size_t part = (size_t)partIds[i];
-        const int first = p->first[part], n = p->first[part + 1] - first;
-        if (n == 0) continue;
-        if (p->recStamp[part] != p->stamp) {
-            p->recStamp[part] = p->stamp;
-            p->recOf[part] = (int)p->recs.size();
-            PartRec rec{};
-            rec.restFirst = first; rec.count = n;
-            p->recs.push_back(rec);
-        }
-        std::memcpy(p->recs[(size_t)p->recOf[part]].m, matrices16 + (size_t)i * 16, 16 * sizeof(float));
-    }
-    size_t m = 0;
-    for (PartRec& rec : p->recs) { rec.outFirst = (int)m; m += (size_t)rec.count; }
-    p->ids.resize(m); p->vertices.resize(m * 9); p->normals.resize(m * 9);
-    for (PartRec& rec : p->recs) {
-        rs_bake_normal_matrix(rec.m, rec.nm);
-        const size_t in = (size_t)rec.restFirst, out = (size_t)rec.outFirst;
-        std::memcpy(&p->ids[out], &p->primIds[in], (size_t)rec.count * sizeof(int));
-        rs_bake_corners(rec.m, rec.nm, (size_t)rec.count * 3, &p->restVertices[in * 9], &p->restNormals[in * 9], &p->vertices[out * 9], &p->normals[out * 9]);
-    }
-    const PartSource src{ (int)p->recs.size(), p->recs.data() };
-    return set_geometry(s, (int)m, p->ids.data(), p->vertices.data(), p->normals.data(), true, name, &src);
-}
-
-extern "C" int rs_scene_parts_info(const rs_scene* s, int* numParts, int* numListedPrims) {
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_parts_info: null scene");
-    if (numParts) *numParts = s->parts ? (int)s->parts->first.size() - 1 : 0;
-    if (numListedPrims) *numListedPrims = s->parts ? (int)s->parts->primIds.size() : 0;
-    return 0;
-}
-
-extern "C" int rs_scene_download_part_rest(const rs_scene* s, int* primIds, float* restVertices, float* restNormals) {
-    RS_SCOPE(s);
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_part_rest: null scene");
-    const rs_parts* p = s->parts;
-    if (!p) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_part_rest: the scene has no parts (rs_scene_define_parts)");
-    RS_TRY(refuse_while_capturing("rs_scene_download_part_rest: the library stream is being captured into a graph"));
-    RS_TRY(rs_synchronize());
-    const size_t n = p->primIds.size();
-    if (n && primIds) RS_HIP(hipMemcpy(primIds, p->dPrimIds, n * sizeof(int), hipMemcpyDeviceToHost));
-    if (n && restVertices) RS_HIP(hipMemcpy(restVertices, p->dRestVertices, n * 9 * sizeof(float), hipMemcpyDeviceToHost));
-    if (n && restNormals) RS_HIP(hipMemcpy(restNormals, p->dRestNormals, n * 9 * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int rs_debug_scene_staged_bytes(const rs_scene* s, size_t* bytes) {
-    if (!s || !bytes) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_scene_staged_bytes: null argument");
-    *bytes = s->refit ? s->refit->stagedBytes : 0;
-    return 0;
-}
-
-// ---- motion tracking: the previous pose of the scene (include/restir_hip.h) ----
-namespace {
-
-// prevVertices = vertices, for every launch enqueued after this call.  Launches already handed to an auxiliary stream may read prevVertices
-// (a render that was deferred to it), so the copy sits behind the fences of a geometry edit (fence_before / fence_after).  A render that has only been recorded was launched before (rs_gbuffer_release_scene).
-int motion_copy(rs_scene* s, const char* name) {
-    RS_TRY(fence_before(s->motionBefore));
-    RS_TRY(rs_motion_copy_enqueue(s->dVertices, s->dPrevVertices, (size_t)s->numPrims, rs_stream()));
-    RS_TRY(fence_after(s->motionAfter));
-    s->motionDirty = false;
-    return rs_after_launch(name);
-}
-
-}  // namespace
-
-extern "C" int rs_scene_set_motion_tracking(rs_scene* s, int on) {
-    RS_SCOPE(s);
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_motion_tracking: null scene");
-    RS_TRY(refuse_while_capturing("rs_scene_set_motion_tracking: the library stream is being captured into a graph"));
-    const bool tracked = s->dev.prevVertices != nullptr;
-    if ((on != 0) == tracked) return 0;
-    if (on && !s->dPrevVertices) {
-        // everything that can fail comes first: a failure leaves the scene untracked and unchanged
-        int e = rs_dev_alloc(&s->dPrevVertices, (size_t)s->numPrims * 9);
-        for (hipEvent_t& ev : s->motionBefore) if (!e) e = rs_check_hip(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-        if (!e) e = rs_check_hip(hipEventCreateWithFlags(&s->motionAfter, hipEventDisableTiming), "hipEventCreate");
-        if (e) { motion_free(s); return e; }
-    }
-    // a render that has only been recorded captures `dev` when it is launched: launch it now, in the form it was requested in
-    RS_TRY(rs_gbuffer_release_scene(s));
-    if (on) {
-        RS_TRY(motion_copy(s, "rs_scene_set_motion_tracking"));      // previous pose = current pose: the motion plane of an untracked scene
-        s->dev.prevVertices = s->dPrevVertices;
-        return 0;
-    }
-    s->dev.prevVertices = nullptr;
-    if (s->motionDirty) s->edits++;                     // the previous pose differed: the camera-only plane is not the retained one
-    s->motionDirty = false;
-    return 0;
-}
-
-extern "C" int rs_scene_advance_motion(rs_scene* s) {
-    RS_SCOPE(s);
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_advance_motion: null scene");
-    RS_TRY(refuse_while_capturing("rs_scene_advance_motion: the library stream is being captured into a graph"));
-    // untracked: nothing to do.  No accepted geometry edit since the last advance: prevVertices equals the vertices already, nothing is
-    // enqueued and retained G-buffer planes stay this scene's
-    if (!s->dev.prevVertices || !s->motionDirty) return 0;
-    RS_TRY(rs_gbuffer_release_scene(s));                // with the old previous pose
-    RS_TRY(motion_copy(s, "rs_scene_advance_motion"));
-    s->edits++;                                         // the motion plane of the frame after a move is not the one of the frame of the move
-    return 0;
-}
-
-extern "C" int rs_scene_download_prev_vertices(const rs_scene* s, float* out) {
-    RS_SCOPE(s);
-    if (!s || !out) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_prev_vertices: null argument");
-    if (!s->dev.prevVertices) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_prev_vertices: the scene does not track motion (rs_scene_set_motion_tracking)");
-    RS_TRY(refuse_while_capturing("rs_scene_download_prev_vertices: the library stream is being captured into a graph"));
-    RS_TRY(rs_synchronize());
-    RS_HIP(hipMemcpy(out, s->dPrevVertices, (size_t)s->numPrims * 9 * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
 
 // Test hooks of the refit (include/restir_hip.h): the device tables as they are, the grid they are quantised on, and grid_box itself.
 extern "C" int rs_debug_scene_table(const rs_scene* s, int which, void* host, size_t capacity, size_t* bytes) {
@@ -1100,7 +363,7 @@ extern "C" int rs_debug_scene_table(const rs_scene* s, int which, void* host, si
     }
     if (!src) size = 0;
     if (host && capacity < size) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_scene_table: the host buffer is smaller than the table");
-    RS_TRY(refuse_while_capturing("rs_debug_scene_table: the library stream is being captured into a graph"));
+    RS_TRY(refuse_while_capturing("rs_debug_scene_table"));
     if (host && size) {
         RS_TRY(rs_synchronize());
         RS_HIP(hipMemcpy(host, src, size, hipMemcpyDeviceToHost));
@@ -1254,12 +517,7 @@ extern "C" int rs_scene_create(const rs_scene_desc* d, rs_scene** out) {
     // pre-differenced triangles
     {
         std::vector<TriRec> rec(np);
-        for (size_t i = 0; i < np; i++) {
-            const float* t = &s->hVertices[i * 9];
-            f3 v0 = ld3(t), v1 = ld3(t + 3), v2 = ld3(t + 6);
-            f3 e1 = v1 - v0, e2 = v2 - v0;
-            rec[i] = TriRec{ v0.x, v0.y, v0.z, 0.f, e1.x, e1.y, e1.z, 0.f, e2.x, e2.y, e2.z, 0.f };
-        }
+        for (size_t i = 0; i < np; i++) rec[i] = tri_rec(&s->hVertices[i * 9]);
         if (int e = upload(&s->dTris, rec)) { rs_scene_destroy(s); return e; }
     }
     // light records with the per-light constants of sampleDirectLightNoVisibility (scene.h:411-424)
@@ -1286,9 +544,7 @@ extern "C" int rs_scene_create(const rs_scene_desc* d, rs_scene** out) {
         if (int e = upload(&s->dTextures, recs)) { rs_scene_destroy(s); return e; }
     }
     if (hasEnv) {
-        std::vector<AliasRec> al(s->hEnvProb.size());
-        for (size_t i = 0; i < al.size(); i++) { al[i].prob = s->hEnvProb[i]; al[i].failId = s->hEnvFail[i]; }
-        if (int e = upload(&s->dEnvAlias, al)) { rs_scene_destroy(s); return e; }
+        if (int e = upload(&s->dEnvAlias, alias_records(s->hEnvProb, s->hEnvFail))) { rs_scene_destroy(s); return e; }
     }
     if (s->textured) { if (int e = upload(&s->dTexcoords, s->hTexcoords)) { rs_scene_destroy(s); return e; } }
     s->dev.texcoords = s->dTexcoords;

@@ -1,5 +1,5 @@
-// scene_refit.hip -- the device side of rs_scene_set_triangles and rs_scene_set_geometry (their entry points, checks, staging and fences:
-// scene.hip) and rs_refit_boxes, the same definition on the host.
+// scene_refit.hip -- the device side of rs_scene_set_triangles and rs_scene_set_geometry (their entry points, staging and fences:
+// scene_edits.hip; their checks and layout: rs_geometry_plan.h) and rs_refit_boxes, the same definition on the host.
 //
 // Every edit refits everything: O(numPrims), one code path, no ancestor can be left stale.  In the order of one stream:
 //   k_refit_clear   every box of the index space of rs_refit.h to the empty box (keys: min = all ones, max = 0), every counter to 0
@@ -17,12 +17,12 @@
 // The emissive tree (emiNodes: the shadow tree's kind over the reference leaf boxes of the emissive triangles alone) takes part in the last
 // two launches when, and only when, the edit names an emitter (rs_scene_set_geometry): its records come last in the index space, so an edit
 // of other triangles stops short of them and writes no byte of emiNodes / emiTris.  Its grid is its own and moves with the lamps: the host
-// lays it over the new emissive root box before the launches (scene.hip), so base, scale and margin are per record range (GridArgs).
+// lays it over the new emissive root box before the launches (scene_edits.hip), so base, scale and margin are per record range (GridArgs).
 //
 // In front of the refit, for rs_scene_set_part_transforms alone: k_bake_parts writes the records k_scatter reads -- the staged edit -- from the
 // scene's rest pose and one matrix per part, instead of a copy from the host bringing them.
 //
-// Next to the refit: k_copy_pose, the copy rs_scene_advance_motion makes of the vertices into the scene's previous pose (scene.hip).
+// Next to the refit: k_copy_pose, the copy rs_scene_advance_motion makes of the vertices into the scene's previous pose (scene_edits.hip).
 //
 // Hand-off inside a launch (the two climbs): a parent's box is only ever written by agent-scope atomic min / max and only ever read by
 // agent-scope atomic loads, both of which act on the one copy all eight XCDs agree on, never on a CU's L1; a child's merges are ordered
@@ -105,11 +105,11 @@ __global__ void __launch_bounds__(256) k_scatter(ScatterArgs a, int m, const int
     const float* v = vertices + (size_t)i * 9;
     for (int k = 0; k < 9; k++) a.vertices[p * 9 + k] = v[k];
     if (normals) for (int k = 0; k < 9; k++) a.normals[p * 9 + k] = normals[(size_t)i * 9 + k];
-    const f3 v0 = ld3(v), v1 = ld3(v + 3), v2 = ld3(v + 6), e1 = v1 - v0, e2 = v2 - v0;      // as rs_scene_create differences them
-    put_triangle(a.tris + p, v0, e1, e2);
-    if (a.occTris) put_triangle(a.occTris + a.slotOf[p], v0, e1, e2);
-    if (a.ordTris) for (size_t s = 0; s < 3; s++) put_triangle(a.ordTris + s * np + (size_t)a.slotOf[(1 + s) * np + p], v0, e1, e2);
-    if (a.emiTris) { const int slot = a.slotOf[4 * np + p]; if (slot >= 0) put_triangle(a.emiTris + slot, v0, e1, e2); }
+    const TriEdges d = tri_edges(v);                     // as rs_scene_create differences them
+    put_triangle(a.tris + p, d.v0, d.e1, d.e2);
+    if (a.occTris) put_triangle(a.occTris + a.slotOf[p], d.v0, d.e1, d.e2);
+    if (a.ordTris) for (size_t s = 0; s < 3; s++) put_triangle(a.ordTris + s * np + (size_t)a.slotOf[(1 + s) * np + p], d.v0, d.e1, d.e2);
+    if (a.emiTris) { const int slot = a.slotOf[4 * np + p]; if (slot >= 0) put_triangle(a.emiTris + slot, d.v0, d.e1, d.e2); }
 }
 
 __global__ void __launch_bounds__(256) k_ref_leaves(int numPrims, const float* __restrict__ vertices, const int* __restrict__ leafOf,
@@ -225,13 +225,6 @@ __global__ void __launch_bounds__(256) k_bake_parts(int numRecs, const PartRec* 
     if (__all(lo == first)) bake_store(recs + first, restVertices + src, restNormals + src, vertices + c * 3, normals + c * 3);
     else bake_store(recs + lo, restVertices + src, restNormals + src, vertices + c * 3, normals + c * 3);
     if (corner == 0) ids[tri] = partPrimIds[slot];
-}
-
-template <typename T>
-int upload_table(T** dst, const std::vector<T>& src) {
-    RS_TRY(rs_dev_alloc(dst, src.size()));
-    if (!src.empty()) RS_HIP(hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
-    return 0;
 }
 
 inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
@@ -419,19 +412,17 @@ int rs_refit_prepare(rs_scene* s) {
     }
     if (!trees) { rs_refit_free(s); return rs_fail(RS_ERR_INTERNAL, "rs_scene_set_triangles: a grid-box tree is not a binary tree in pre-order"); }
 
-    int e = upload_table(&r->dSlotOf, slotOf);
-    if (!e) e = upload_table(&r->dEmiLeaf, emiLeaf);
-    if (!e) e = upload_table(&r->dLeafOf, s->hLeafOf);
-    if (!e) e = upload_table(&r->dBoxId, boxId);
-    if (!e) e = upload_table(&r->dParent, parent);
+    int e = upload(&r->dSlotOf, slotOf);
+    if (!e) e = upload(&r->dEmiLeaf, emiLeaf);
+    if (!e) e = upload(&r->dLeafOf, s->hLeafOf);
+    if (!e) e = upload(&r->dBoxId, boxId);
+    if (!e) e = upload(&r->dParent, parent);
     if (!e) e = rs_dev_alloc(&r->dKeys, r->numNodes * 6);
     if (!e) e = rs_dev_alloc(&r->dArrived, r->numNodes);
     for (rs_refit::Stage& g : r->stage) if (!e) e = rs_check_hip(hipEventCreateWithFlags(&g.copied, hipEventDisableTiming), "hipEventCreate");
     for (hipEvent_t& ev : r->before) if (!e) e = rs_check_hip(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
     if (!e) e = rs_check_hip(hipEventCreateWithFlags(&r->after, hipEventDisableTiming), "hipEventCreate");
     if (e) { rs_refit_free(s); return e; }
-    r->lastStamp.assign(np, 0u);
-    r->lastIndex.assign(np, 0);
     r->hChild.assign(nn * 2, -1);
     for (size_t i = 0; i < nn; i++) {
         const int p = s->hParent[i];

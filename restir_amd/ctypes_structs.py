@@ -53,6 +53,40 @@ class Reservoir(C.Structure):
     ]
 
 
+class GeometryEditView(C.Structure):
+    """rs_geometry_edit_view (include/restir_hip.h): what the plan of a geometry edit reads of a scene."""
+    _fields_ = [
+        ("numPrims", C.c_int),
+        ("materialIds", C.c_void_p),
+        ("materials", C.c_void_p),
+        ("bounded", C.c_int),
+        ("gridLo", C.c_float * 3),
+        ("gridHi", C.c_float * 3),
+        ("vertices", C.c_void_p),
+        ("numLights", C.c_int),
+        ("numLightPrims", C.c_int),
+        ("lightPrimIds", C.c_void_p),
+        ("lightRadiance", C.c_void_p),
+        ("lightArea", C.c_void_p),
+        ("envPower", C.c_float),
+        ("emissiveTree", C.c_int),
+        ("numEmissive", C.c_int),
+        ("emiLeafPrims", C.c_void_p),
+    ]
+
+
+class GeometryEditPlan(C.Structure):
+    """rs_geometry_edit_plan: the records of the edit and the layout they are staged in."""
+    _fields_ = [("m", C.c_int), ("lamps", C.c_int)] + [(n, C.c_size_t) for n in (
+        "offV", "offN", "bytes", "staged", "onDevice", "partStaged", "partOnDevice")]
+
+
+class GeometryEditLights(C.Structure):
+    """rs_geometry_edit_lights: the light sampler's total and the emissive tree's grid after an edit that names an emitter."""
+    _fields_ = [("sumAll", C.c_float), ("emiGrid", C.c_int), ("emiLo", C.c_float * 3), ("emiHi", C.c_float * 3),
+                ("emiBase", C.c_float * 3), ("emiScale", C.c_float * 3), ("emiMargin", C.c_double)]
+
+
 assert C.sizeof(Material) == 44
 assert C.sizeof(Camera) == 196
 assert C.sizeof(Reservoir) == 36

@@ -61,6 +61,28 @@ class EmissiveSnapshot(Snapshot):
         return out
 
 
+def triangle_area(vertices):
+    """Math::triangleArea of (n, 3, 3) float32 triangles: length(cross(v1 - v0, v2 - v0)) / 2, one float32 rounding per operation, sums
+    from the left."""
+    v = np.asarray(vertices, np.float32).reshape(-1, 3, 3)
+    a, b = v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]
+    c = np.stack([a[:, 1] * b[:, 2] - b[:, 1] * a[:, 2], a[:, 2] * b[:, 0] - b[:, 2] * a[:, 0], a[:, 0] * b[:, 1] - b[:, 0] * a[:, 1]], 1)
+    return np.sqrt(c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1] + c[:, 2] * c[:, 2]) * np.float32(0.5)
+
+
+def light_sampler_tables(capi, vertices, light_prims, radiance, env_power=None):
+    """(area, prob, fail, sumAll) of the light sampler over the light primitives of `vertices`: rs_build_light_table's power per light,
+    luminance(radiance) * 2 * pi * area in float32, the environment map's entry (env_power, if any) last, then the library's alias table."""
+    area = triangle_area(np.asarray(vertices, np.float32).reshape(-1, 3, 3)[np.asarray(light_prims, np.int64)])
+    r = np.asarray(radiance, np.float32).reshape(-1, 3)
+    lum = r[:, 0] * np.float32(0.2126) + r[:, 1] * np.float32(0.7152) + r[:, 2] * np.float32(0.0722)
+    power = lum * np.float32(2.0) * np.float32(np.pi) * area
+    if env_power is not None:
+        power = np.concatenate([power, np.float32([env_power])])
+    prob, fail, total = capi.build_alias_table(power)
+    return area, prob, fail, total
+
+
 def grid_over_box(lo, hi):
     """The grid a grid-box tree with root box [lo, hi] lies on, as the library's one function lays it: the largest extent over 65 000
     steps on every axis, 200 steps of apron below lo, a margin of 2^-17 of the extent.  float32 arithmetic, one rounding per operation."""

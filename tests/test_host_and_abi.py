@@ -29,6 +29,10 @@ def test_library_exports_every_declared_symbol():
 def test_struct_layouts_match_reference_sizes():
     from restir_amd.ctypes_structs import Camera, Material, Reservoir
     assert C.sizeof(Material) == 44 and C.sizeof(Camera) == 196 and C.sizeof(Reservoir) == 36
+    # rs_geometry_edit_view / _plan / _lights (include/restir_hip.h): pointers and size_t of 8 bytes, each aligned to 8
+    from restir_amd.ctypes_structs import GeometryEditLights, GeometryEditPlan, GeometryEditView
+    assert (C.sizeof(GeometryEditView), C.sizeof(GeometryEditPlan), C.sizeof(GeometryEditLights)) == (120, 64, 64)
+    assert (GeometryEditView.vertices.offset, GeometryEditView.emiLeafPrims.offset, GeometryEditPlan.offV.offset) == (56, 112, 8)
 
 
 @pytest.mark.parametrize("name", ["cornell", "sponza:0.02", "sponza:0.1"])
