@@ -679,6 +679,25 @@ int  rs_restir_set_primary_cuts(rs_restir* r, int on);
 int  rs_debug_set_primary_cut_cap(rs_restir* r, int records);
 int  rs_debug_primary_cut_info(rs_restir* r, int* cells, int* cellsWithoutCut, unsigned long long* records, int* usedLastFrame, unsigned long long* builds);
 int  rs_debug_primary_cut_missing(rs_restir* r, const rs_scene* scene, int cell, int n, const float* rays, unsigned long long out[4]);
+/* Primary leaf lists, on top of the cuts: every 8x8 tile of such a launch also gets the LEAVES of the cut of its own 8x8 pixels, box and
+ * triangle side by side in 64-byte records in the traversal order, and a wave whose tile has a list tests those records one after the
+ * other instead of walking its block's cut (a tile without a list -- no common traversal order, an empty list or one past the cap, a
+ * full arena, a scene without nested reference boxes -- keeps the cut, as do the quarter-tile waves of a split tile).  A triangle that
+ * would become the closest hit while its leaf box is only grazed is confirmed by the reference's own box test up its ancestors: no
+ * result changes by a bit.  Same key, build and lifetime as the cuts, and off whenever they are off.  Memory: per phase-A call 32
+ * records of 68 bytes per tile (71 MB for 1920x1080); where that allocation fails the frames keep the cuts.  on = 1 is the default;
+ * RS_PRIMARY_LEAF_LISTS=0 makes 0 the default (A/B measurements). */
+int  rs_restir_set_primary_leaf_lists(rs_restir* r, int on);
+/* Test hooks, as the cuts': the most records one tile's list may have (default 192; 0: no tile takes a list); tiles of the last phase-A
+ * call's launch, tiles without a list, records in all lists, whether that call walked lists, list builds so far; containment of every
+ * ray's own tile's list, out = { leaves passed that the list lacks, leaves passed, rays left out, 0 }; and, on the host alone, the list
+ * the builder makes for the tile at pixel (x0, y0) over rs_build_bvh's outputs: *order (-1: the tile takes none), *count (cap + 1: more
+ * than cap), positions[min(*count, cap)] = the leaves' record indices in that order's table. */
+int  rs_debug_set_primary_leaf_list_cap(rs_restir* r, int records);
+int  rs_debug_primary_leaf_list_info(rs_restir* r, int* tiles, int* tilesWithoutList, unsigned long long* records, int* usedLastFrame, unsigned long long* builds);
+int  rs_debug_primary_leaf_list_missing(rs_restir* r, const rs_scene* scene, int n, const float* rays, unsigned long long out[4]);
+int  rs_debug_plan_primary_leaf_list(const rs_camera* cam, int x0, int y0, int bvhSize, const float* boundingBoxes, const int* const bvhNodes[6], int cap,
+                                     int* order, int* count, int* positions);
 /* Test hook: the per-pixel state the primary rays of the last ended frame left for the later passes (host arrays of width * height
  * pixels): 4 floats { hit position, tag bits }, 4 floats { shading normal, metallic }, 2 words { sampler state, tag }.  Waits for the
  * device. */

@@ -134,7 +134,7 @@ EXPORTS = [
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
     "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
-    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
+    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_restir_set_primary_leaf_lists", "rs_debug_set_primary_leaf_list_cap", "rs_debug_primary_leaf_list_info", "rs_debug_primary_leaf_list_missing", "rs_debug_plan_primary_leaf_list", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
     "rs_path_trace", "rs_path_trace_indirect", "rs_restir_indirect", "rs_restir_download_indirect",
     "rs_svgf_create", "rs_svgf_destroy", "rs_svgf_filter", "rs_svgf_next_frame", "rs_svgf_get_view",
     "rs_copy_image_to_pbo", "rs_copy_image2_to_pbo", "rs_copy_imagef_to_pbo", "rs_copy_imagei_to_pbo", "rs_eaw_create", "rs_eaw_destroy", "rs_eaw_set_params", "rs_eaw_get_params", "rs_eaw_set_tiled", "rs_eaw_set_fused", "rs_svgf_set_params", "rs_svgf_get_params", "rs_svgf_set_tiled", "rs_svgf_set_fused", "rs_eaw_filter", "rs_eaw_positions_rows", "rs_eaw_level_rows", "rs_modulate_albedo",
@@ -250,6 +250,11 @@ def lib():
     L.rs_debug_set_primary_cut_cap.argtypes = [vp, ci]
     L.rs_debug_primary_cut_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(ci), C.POINTER(C.c_ulonglong)]
     L.rs_debug_primary_cut_missing.argtypes = [vp, vp, ci, ci, vp, C.POINTER(C.c_ulonglong * 4)]
+    L.rs_restir_set_primary_leaf_lists.argtypes = [vp, ci]
+    L.rs_debug_set_primary_leaf_list_cap.argtypes = [vp, ci]
+    L.rs_debug_primary_leaf_list_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(ci), C.POINTER(C.c_ulonglong)]
+    L.rs_debug_primary_leaf_list_missing.argtypes = [vp, vp, ci, vp, C.POINTER(C.c_ulonglong * 4)]
+    L.rs_debug_plan_primary_leaf_list.argtypes = [vp, ci, ci, ci, vp, C.POINTER(vp * 6), ci, C.POINTER(ci), C.POINTER(ci), vp]
     L.rs_debug_restir_surface.argtypes = [vp, vp, vp, vp]
     L.rs_pbo_register.argtypes = [C.c_uint, C.POINTER(vp)]
     L.rs_pbo_map.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -517,6 +522,18 @@ def synchronize():
 def camera_update(cam):
     check(lib().rs_camera_update(C.byref(cam)))
     return cam
+
+
+def plan_primary_leaf_list(cam, x0, y0, boxes, nodes, cap):
+    """rs_debug_plan_primary_leaf_list (host only): the leaf list of the 8x8 tile at pixel (x0, y0) over build_bvh's outputs.  Returns
+    (order, count, positions): order -1 when the tile takes no list; count = cap + 1 when it has more than cap leaves; positions = the
+    record indices of the first min(count, cap) leaves in nodes[order]."""
+    boxes = np.ascontiguousarray(boxes, np.float32); nodes = np.ascontiguousarray(nodes, np.int32)
+    arr = (C.c_void_p * 6)(*[nodes[i].ctypes.data for i in range(6)])
+    order, count = C.c_int(), C.c_int()
+    pos = np.zeros(max(int(cap), 1), np.int32)
+    check(lib().rs_debug_plan_primary_leaf_list(C.byref(cam), int(x0), int(y0), nodes.shape[1], _p(boxes), C.byref(arr), int(cap), C.byref(order), C.byref(count), _p(pos)))
+    return order.value, count.value, pos[:min(count.value, int(cap))].copy()
 
 
 # ---- host builders (no GPU needed) ----------------------------------------------------------------
@@ -1117,6 +1134,29 @@ class ReSTIR:
         out = (C.c_ulonglong * 4)()
         check(lib().rs_debug_primary_cut_missing(self.handle, scene.handle, cell, len(rays), _p(rays), C.byref(out)))
         return dict(missing=out[0], passed=out[1], left_out=out[2], records=out[3])
+
+    def set_primary_leaf_lists(self, on=True):
+        """rs_restir_set_primary_leaf_lists: whole tiles of such a launch walk the leaf lists of their own 8x8 pixels (on by default)."""
+        check(lib().rs_restir_set_primary_leaf_lists(self.handle, 1 if on else 0))
+
+    def set_primary_leaf_list_cap(self, records):
+        """rs_debug_set_primary_leaf_list_cap: the most records one tile's leaf list may have (0: no tile takes a list)."""
+        check(lib().rs_debug_set_primary_leaf_list_cap(self.handle, records))
+
+    def primary_leaf_list_info(self):
+        """dict(tiles, without_list, records, used, builds) of the last phase-A call's leaf lists (rs_debug_primary_leaf_list_info)."""
+        a, b, u = C.c_int(), C.c_int(), C.c_int()
+        n, k = C.c_ulonglong(), C.c_ulonglong()
+        check(lib().rs_debug_primary_leaf_list_info(self.handle, C.byref(a), C.byref(b), C.byref(n), C.byref(u), C.byref(k)))
+        return dict(tiles=a.value, without_list=b.value, records=n.value, used=bool(u.value), builds=k.value)
+
+    def primary_leaf_list_missing(self, scene, rays):
+        """rs_debug_primary_leaf_list_missing: rays = (n, 4) float32 { pixel x, pixel y, jitter x, jitter y }, each looked up in its own
+        tile's list; returns dict(missing, passed, left_out)."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 4)
+        out = (C.c_ulonglong * 4)()
+        check(lib().rs_debug_primary_leaf_list_missing(self.handle, scene.handle, len(rays), _p(rays), C.byref(out)))
+        return dict(missing=out[0], passed=out[1], left_out=out[2])
 
     def surface(self):
         """rs_debug_restir_surface: (pos_tag (n, 4) f32, normal (n, 4) f32, rng_tag (n, 2) u32) of the last ended frame."""

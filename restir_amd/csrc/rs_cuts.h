@@ -46,6 +46,16 @@
 //     2^-16 R with R >= T the interval maximum of the root's |slab distances|: 32 times the rounding it has to cover.
 // A cell takes no cut -- and walks the tree as before -- if its four corners do not share one mtbvh_order, if a bound is not finite,
 // if its cut is empty or longer than the cap, or if the arena is full.  The wave still compares its own order with the cell's.
+//
+// Leaf lists.  Nine in ten of the steps a wave still takes through its cell's cut are inner nodes (EXPERIMENTS.md "Primary leaf lists"), and
+// for a still camera an inner node only lets the wave skip leaves -- which the camera and the boxes decide as well, once.  The reference
+// tree has one triangle per leaf, so an 8x8 TILE (one wave) gets the LEAF records of the cut of its own 8x8 cell, in the threaded order,
+// box and triangle side by side in 64 bytes (LeafListRef, rs_walk.h), and packet_walk_leaves walks them one after the other: no links, the
+// same triangle tests as before, a quarter of the box tests.  Containment is the cut's, for the tile's own cell: the list is made by the cut's walk,
+// which descends through kept nodes only, and the cut's induction shows that every node some ray of the cell passes geometrically after
+// passing all its ancestors is kept -- the reference enters no other.  Why the lane's bits stay although the inner nodes are gone is packet_walk_leaves' argument (rs_walk.h).
+// A tile takes no list -- and keeps its block's cut, or the tree -- if cut_cell gives it no order, if its list is empty or longer than the
+// cap, if the arena is full, or if the scene lacks occChain / nested boxes.  Same key and lifetime as the cuts; built by the same call.
 #pragma once
 
 #include "rs_walk.h"
@@ -53,7 +63,9 @@
 namespace rs {
 
 // the cuts of one launch geometry: cells[c] = { first record, count | order << 28 } (count 0: no cut), `records` the arena they index
-struct PrimaryCuts { const uint2* cells; const BvhNode* records; };
+// tiles[t] = { first record, count | order << 28 } of tile t's leaf list (tiles numbered as primary_body numbers them: row-major over the
+// launch's 8x8 tiles), leafRecords / leafOf the arena they index (LeafListRef, rs_walk.h); tiles == null: no lists
+struct PrimaryCuts { const uint2* cells; const BvhNode* records; const uint2* tiles; const float4* leafRecords; const int* leafOf; };
 constexpr unsigned kCutCountMask = (1u << 28) - 1u;
 
 // what the conservative test of a cell needs: per axis the interval of the unnormalised direction mapped to the POSITIVE case (a negative
@@ -144,7 +156,108 @@ RS_HD bool cut_cell_test(const CutCell& cell, const BvhNode& n) {
     return !(tMaxHi < tMinLo - cell.margin);
 }
 
+// The leaves of a cell's list: the cut's walk over records [0, end) of the cell's order (rec(i): record i), emit(i, record) for every kept
+// LEAF in threaded order.  Returns how many there are, or cap + 1 as soon as there are more than `cap` (nothing is emitted past the cap).
+// Host and device: the device builder and the host's planning hook (rs_debug_plan_primary_leaf_list) run this very function.
+template <class Rec, class Emit>
+RS_HD unsigned leaf_list_walk(const CutCell& cell, Rec rec, unsigned end, unsigned cap, Emit emit) {
+    unsigned count = 0;
+    for (unsigned cur = 0; cur != end;) {
+        const BvhNode n = rec(cur);
+        if (cut_cell_test(cell, n)) {
+            if (n.primId != kNullPrim) { if (count == cap) return cap + 1u; emit(count, cur, n); count++; }
+            cur++;
+        }
+        else cur = (unsigned)n.next;
+    }
+    return count;
+}
+
 #if defined(__HIPCC__)
+// the leaf list of tile `tile` of a primary-ray launch (wave-uniform; tile < 0: none)
+__device__ __forceinline__ LeafListRef leaf_list_of_tile(const PrimaryCuts& cuts, int tile) {
+    if (!cuts.tiles || tile < 0) return LeafListRef{ nullptr, nullptr, 0u, 0 };
+    const uint2 t = cuts.tiles[__builtin_amdgcn_readfirstlane(tile)];                    // (uniform, said explicitly: cut_of_cell)
+    const unsigned first = (unsigned)__builtin_amdgcn_readfirstlane((int)t.x), word = (unsigned)__builtin_amdgcn_readfirstlane((int)t.y);
+    return LeafListRef{ reinterpret_cast<const char*>(cuts.leafRecords + (size_t)first * 4u), cuts.leafOf + first, word & kCutCountMask, (int)(word >> 28) };
+}
+
+// One thread per tile: the walk that counts, a reservation in the arena, the same walk again to write.  leafOfPrim: the reference node of
+// every primitive's leaf.  counters: [0] records handed out, [1] tiles without a list, [2] records of the tiles that have one
+static __global__ void __launch_bounds__(64) k_build_primary_leaf_lists(DevScene s, CamParams cam, int y0, int tilesPerRow, int numTiles, unsigned cap, unsigned capacity,
+                                                                        const int* leafOfPrim, uint2* tiles, float4* records, int* leafOf, unsigned long long* counters) {
+    const int ti = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ti >= numTiles) return;
+    CutCell cell = cut_cell(cam, (ti % tilesPerRow) * 8, y0 + (ti / tilesPerRow) * 8, 8, 8);
+    const unsigned end = (unsigned)s.bvhSize;
+    const BvhNode* nodes = s.nodesAll + (size_t)(cell.order < 0 ? 0 : cell.order) * (size_t)s.bvhSize;
+    bool ok = cell.order >= 0 && s.axisCull && s.linksNested && s.occChain && s.occNested && end > 0u && cut_cell_margin(cell, nodes[0]);
+    unsigned count = 0;
+    if (ok) {
+        count = leaf_list_walk(cell, [&](unsigned i) { return nodes[i]; }, end, cap, [](unsigned, unsigned, const BvhNode&) {});
+        ok = count > 0u && count <= cap;
+    }
+    unsigned off = 0;
+    if (ok) {           // (first come, first served, as the cuts' arena: the results never depend on who goes without)
+        const unsigned long long at = atomicAdd(counters, (unsigned long long)count);
+        ok = at + count <= (unsigned long long)capacity;
+        off = ok ? (unsigned)at : 0u;
+    }
+    if (!ok) { tiles[ti] = make_uint2(0u, 0u); atomicAdd(counters + 1, 1ull); return; }
+    leaf_list_walk(cell, [&](unsigned i) { return nodes[i]; }, end, cap, [&](unsigned k, unsigned, const BvhNode& n) {
+        const float4* tp = reinterpret_cast<const float4*>(s.tris + n.primId);
+        const float4 a = tp[0], b = tp[1], e = tp[2];
+        float4* r = records + (size_t)(off + k) * 4u;
+        r[0] = make_float4(n.bminx, n.bminy, n.bminz, n.bmaxz);
+        r[1] = make_float4(n.bmaxx, n.bmaxy, __int_as_float(n.primId), a.x);
+        r[2] = make_float4(a.y, a.z, b.x, b.y);
+        r[3] = make_float4(b.z, e.x, e.y, e.z);
+        leafOf[off + k] = leafOfPrim[n.primId];
+    });
+    tiles[ti] = make_uint2(off, count | ((unsigned)cell.order << 28));
+    atomicAdd(counters + 2, (unsigned long long)count);
+}
+
+// Containment of the lists, ray by ray, as k_primary_cut_missing: every ray walks the WHOLE tree of its order on the geometric part of the
+// reference's test alone, and each LEAF it passes is looked up in the list of the ray's own tile.  rays as there.  out: [0] passed leaves
+// absent from the list, [1] passed leaves, [2] rays left out (special-case direction, another order than the list's, a tile without a list)
+static __global__ void k_primary_leaf_list_missing(DevScene s, CamParams cam, PrimaryCuts cuts, int y0, int tilesPerRow, int numTiles, int n, const float* rays, unsigned long long* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int px = (int)rays[4 * i], py = (int)rays[4 * i + 1];
+    const int tile = py >= y0 && px >= 0 ? ((py - y0) / 8) * tilesPerRow + px / 8 : -1;
+    if (tile < 0 || tile >= numTiles || px / 8 >= tilesPerRow) { atomicAdd(out + 2, 1ull); return; }
+    const uint2 entry = cuts.tiles[tile];
+    const unsigned count = entry.y & kCutCountMask;
+    const float4* list = cuts.leafRecords + (size_t)entry.x * 4u;
+    const Ray ray = camera_sample(cam, px, py, rays[4 * i + 2], rays[4 * i + 3]);
+    RayBoxCtx ctx = make_box_ctx(ray);
+    ctx.cull = s.axisCull;
+    const int order = mtbvh_order(-ray.d);
+    if (ray_is_special(ctx, ray) || count == 0u || order != (int)(entry.y >> 28)) { atomicAdd(out + 2, 1ull); return; }
+    const BvhNode* nodes = s.nodesAll + (size_t)order * (size_t)s.bvhSize;
+    unsigned long long passed = 0, missing = 0;
+    unsigned at = 0;                                        // the list is in the walk's order: the search never goes back
+    for (unsigned cur = 0; cur != (unsigned)s.bvhSize;) {
+        const float4* rec = reinterpret_cast<const float4*>(nodes + cur);
+        float4 lo, hi;
+        node_unpack(rec[0], rec[1], lo, hi);
+        float tb;
+        if (box_hit_general(ctx.o, ctx.dinv, lo, hi, tb)) {
+            const int prim = __float_as_int(lo.w);
+            if (prim != kNullPrim) {
+                passed++;
+                unsigned j = at;
+                while (j < count && __float_as_int(list[(size_t)j * 4u + 1u].z) != prim) j++;
+                if (j == count) missing++; else at = j + 1u;
+            }
+            cur++;
+        }
+        else cur = (unsigned)__float_as_int(hi.w);
+    }
+    atomicAdd(out, missing); atomicAdd(out + 1, passed);
+}
+
 // the cut of block `cell` of a primary-ray launch (wave-uniform)
 __device__ __forceinline__ CutRef cut_of_cell(const PrimaryCuts& cuts, int cell) {
     if (!cuts.cells) return CutRef{ nullptr, 0u, 0 };

@@ -99,5 +99,7 @@ inline void rs_plan_phase_a(const rs_phase_a_inputs& in, rs_phase_a_plan& p) {
     // the tree (it only runs when something moved, or after an emission edit, which leaves the cut alone for the frames after it).  A key
     // that has just been seen unchanged for the first time builds -- behind this call's chain, so the frame itself still walks the tree --
     // and every later call with that key walks the cuts, whatever its rows (a strip), its stream or the number of frames in flight.
+    // The tiles' leaf lists (rs_cuts.h "Leaf lists") have no field of their own: they are built by the same build and walked by the same
+    // launches as the cuts, wherever the slot holds them.
     p.cut = rows && !fuse ? in.cutState : 0;
 }

@@ -211,6 +211,7 @@ struct rs_scene {
     uint32_t* dSampleSeq = nullptr;  // the Sobol table (rs_scene_set_sample_sequence); null: the default thrust engine
     uint4* dOccNodes = nullptr;      // shadow-ray tree (occlusion_bvh.cpp)
     rs::BvhNode* dOccChain = nullptr;   // reference boxes + parent links by original node id
+    int* dLeafOfPrim = nullptr;         // reference leaf node of every primitive (hLeafOf), with dOccChain: the leaf lists' builder reads it (rs_cuts.h)
     rs::TriRec* dOccTris = nullptr;
     uint4* dEmiNodes = nullptr;      // tree of the emissive triangles alone (scene.hip build_emissive_side)
     rs::TriRec* dEmiTris = nullptr;
@@ -543,9 +544,18 @@ struct rs_primary_cut {
     uint2* cells = nullptr;                  // per cell { first record, count | order << 28 }
     rs::BvhNode* records = nullptr;          // the arena: `capacity` records and one more that is only ever read
     unsigned* orig = nullptr;                // original index of every record (the builder's links; the containment test hook)
-    unsigned long long* counters = nullptr;  // [0] records handed out, [1] cells without a cut, [2] records in cuts
+    unsigned long long* counters = nullptr;  // [0] records handed out, [1] cells without a cut, [2] records in cuts; [4..6] the same of the leaf lists and tiles
     int numCells = 0, cellsX = 0;
     unsigned capacity = 0;
+    // the tiles' leaf lists (rs_cuts.h "Leaf lists"): same key, built by the same call behind the cuts, read by the same launches
+    bool listsWanted = false, listsBuilt = false, listsNoMemory = false;
+    unsigned listCap = 0;                    // part of the key
+    uint2* tiles = nullptr;                  // per tile { first record, count | order << 28 }
+    float4* leafRecords = nullptr;           // the arena: `listCapacity` 64-byte records and one more that is only ever read
+    int* leafOf = nullptr;                   // reference node of every record's leaf
+    int numTiles = 0, tilesPerRow = 0;
+    unsigned listCapacity = 0;
+    unsigned long long listBuilds = 0;
     hipEvent_t builtEv = nullptr;
     hipEvent_t usedEv[1 + rs_context::kAux] = {};
     bool usedValid[1 + rs_context::kAux] = {};
@@ -557,8 +567,11 @@ struct rs_restir {
     rs_primary_cut cut[3];
     bool cutsOn = true;                      // rs_restir_set_primary_cuts (RS_PRIMARY_CUTS=0: off from the start)
     unsigned cutCap = 4096;                  // records a cell's cut may have (rs_debug_set_primary_cut_cap)
+    bool listsOn = true;                     // rs_restir_set_primary_leaf_lists (RS_PRIMARY_LEAF_LISTS=0: off from the start); lists need the cuts' switch too
+    unsigned listCap = 192;                  // records a tile's leaf list may have (rs_debug_set_primary_leaf_list_cap; 0: no tile takes a list)
     int lastCutSlot = 0;                     // of the last phase-A call
     bool lastCutUsed = false;                // the last phase-A call's primary rays walked cuts
+    bool lastListsUsed = false;              // ... and its whole tiles their leaf lists
     // The chain primary rays -> RIS -> shadow rays of a frame depends on no other frame.  Frames put theirs on kChains auxiliary
     // streams in turn, so that consecutive frames' chains overlap: on a 1/8 strip a chain lasts 0.4 ms however few rows it has.
     // A chain writes one of kSurfSets sets of surface planes, which the frame's temporal / spatial passes read afterwards; with as

@@ -50,6 +50,7 @@ struct WalkResult {
 #ifdef RS_WALK_STATS
     unsigned steps, nearSteps, enteredSteps, leafSteps, clearSteps;   // clearSteps: entered without evaluating the overlap part
     unsigned myVisits;                                                // nodes this lane's own walk visited (packet walks)
+    unsigned chainSteps, listSteps;                                   // leaf lists: wave steps up occChain, records walked
 #endif
 };
 
@@ -842,12 +843,118 @@ __device__ __forceinline__ void packet_walk_fast_dispatch(int neg, const DevScen
 // A cell's cut of one threaded order (rs_cuts.h): `end` records at `base`, cut from order `order`; end == 0: the cell has none
 struct CutRef { const char* base; unsigned end; int order; };
 
+// ---- the walk through a tile's leaf list (rs_cuts.h "Leaf lists") ---------------------------------------------------------------------
+// A tile's list: `end` 64-byte records at `base`, one per leaf that some ray of the tile may pass geometrically, in the threaded order
+// `order`; leafOf[c] = the reference node of record c (its record in occChain).  end == 0: the tile has none.  Record c, four float4:
+//   { min.x, min.y, min.z, max.z } { max.x, max.y, bits(prim), v0.x } { v0.y, v0.z, e1.x, e1.y } { e1.z, e2.x, e2.y, e2.z }
+// -- the box half laid out as a BvhNode's, the triangle as s.tris holds it, so that a step is one scalar fetch of the record after.
+struct LeafListRef { const char* base; const int* leafOf; unsigned end; int order; };
+
+// Why the bits stay.  A lane's result depends only on the sequence of triangles it tests and the `closest` it tests each against.  The
+// reference tests leaf L's triangle iff it enters L and, before it, every ancestor of L (box test passed with tMin < closest at that
+// moment).  Here every lane of the order visits every record of the list, in the threaded order:
+//   * entered = the reference's own test on L's box with tMin < closest: slabs + slab_distance_part, then the chord > margin shortcut
+//     or slab_overlap_part, exactly as packet_walk_fast decides it;
+//   * boxes are nested (DevScene::occNested, checked at scene build) and (p - o) * dinv rounds monotonically, so an ancestor's near
+//     distances are <= and its far distances >= the leaf's: tMax >= 0, tMax >= tMin and tMin < closest carry from L to every ancestor
+//     -- also to the moment the reference stood on that ancestor, because `closest` only falls.  Conversely an ancestor the reference
+//     rejected on those three had tMin >= its closest then >= closest now, and so has L;
+//   * the overlap part alone is not monotone in float.  A lane whose leaf clears it by chain_step's margin (2^-18 tRoot) has settled it for
+//     the whole path; any other lane with a candidate runs the reference's test up occChain, from the leaf's own record (its `open`
+//     is `entered` again, its `clear` the exact form of the margin -- a flat leaf box has chord <= 0 and still clears more often than
+//     not) to the first clear ancestor, and accepts only if every record on the way is open.  This is the rule walk_ordered_tree lives
+//     by; only triangles that would lower `closest` pay for it, a rejected triangle changes nothing whether the reference met it or not;
+//   * a leaf absent from the list is one no ray of the tile passes geometrically (containment, as for the cut: rs_cuts.h), so the
+//     reference never enters it;
+//   * the list keeps the threaded order, so ties under the strict `<` fall as before.
+// Needs what packet_walk_fast needs (general-case rays of one sign pattern, a proper box table) and occChain with nested boxes; the
+// builder makes no list otherwise.  There are no links: the record after is requested at the top of every step.
+template <int NEG, bool COUNT>
+__device__ __forceinline__ void packet_walk_leaves(const DevScene& s, const LeafListRef& list, bool mine, const Ray& ray, const RayBoxCtx& ctx, WalkResult& r) {
+    const vf2 oxy = { ctx.o.x, ctx.o.y }, ozz = { ctx.o.z, ctx.o.z }, dxy = { ctx.dinv.x, ctx.dinv.y }, dzz = { ctx.dinv.z, ctx.dinv.z };
+    const float tRoot = root_extent(ctx.o, ctx.dinv, s.occRootLo, s.occRootHi);
+    const float margin = tRoot * 1.9073486328125e-6f, clearMargin = tRoot * 3.814697265625e-6f;      // 2^-19 (overlap_margin), 2^-18 (chain_step)
+    const char* __restrict__ base = list.base;
+    const unsigned end = list.end;
+    const float4* first = reinterpret_cast<const float4*>(base);      // uniform addresses -> scalar loads
+    float4 q0 = first[0], q1 = first[1], q2 = first[2], q3 = first[3];
+    for (unsigned c = 0; c != end; c++) {
+        const float4* np = reinterpret_cast<const float4*>(base + (c + 1u) * 64u);       // (the record at `end` is readable)
+        const float4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
+        if (COUNT) r.nodes++;
+#ifdef RS_WALK_STATS
+        r.steps++; if (mine) r.myVisits++;
+#endif
+        const SlabT t = slabs(oxy, ozz, dxy, dzz, q0, q1);
+        float chord;
+        const bool near = slab_distance_part<NEG>(t, mine, r.closest, chord);
+        const unsigned long long nearMask = __builtin_amdgcn_ballot_w64(near);
+        if (nearMask != 0ull) {
+#ifdef RS_WALK_STATS
+            r.nearSteps++;
+#endif
+            bool entered = near;
+            unsigned long long enteredMask = nearMask;
+            if ((nearMask & __builtin_amdgcn_ballot_w64(!(chord > margin))) != 0ull) {
+                entered = slab_overlap_part<NEG>(t, near);
+                enteredMask = __builtin_amdgcn_ballot_w64(entered);
+            }
+#ifdef RS_WALK_STATS
+            else r.clearSteps++;
+#endif
+            if (enteredMask != 0ull) {
+#ifdef RS_WALK_STATS
+                r.enteredSteps++; r.leafSteps++;
+#endif
+                float bx, by, dist;
+                const bool hit = tri_hit<true>(ray.o, ray.d, mk3(q1.w, q2.x, q2.y), mk3(q2.z, q2.w, q3.x), mk3(q3.y, q3.z, q3.w), bx, by, dist);
+                const bool candidate = entered && hit && dist < r.closest;
+                bool accept = candidate && chord > clearMargin;
+                int verify = -1;
+                if (__builtin_amdgcn_ballot_w64(candidate && !(chord > clearMargin)) != 0ull) {
+                    const int leaf = list.leafOf[c];                  // uniform -> scalar
+                    verify = (candidate && !accept) ? leaf : -1;
+                    while (__any(verify >= 0)) {
+#ifdef RS_WALK_STATS
+                        r.chainSteps++;
+#endif
+                        if (verify >= 0) {
+                            const ChainStep cs = chain_step(s.occChain + verify, ctx, r.closest, tRoot);
+                            const bool done = cs.open & ((cs.parent < 0) | cs.clear);
+                            accept = accept | done;
+                            verify = (cs.open & !done) ? cs.parent : -1;          // closed: the reference never reaches the triangle
+                        }
+                    }
+                }
+                if (accept) { r.closest = dist; r.bx = bx; r.by = by; r.prim = __float_as_int(q1.z); }
+            }
+        }
+        q0 = n0; q1 = n1; q2 = n2; q3 = n3;
+    }
+}
+
+template <bool COUNT>
+__device__ __forceinline__ void packet_walk_leaves_dispatch(int neg, const DevScene& s, const LeafListRef& list, bool mine, const Ray& ray, const RayBoxCtx& ctx, WalkResult& r) {
+    switch (neg) {
+        case 0: packet_walk_leaves<0, COUNT>(s, list, mine, ray, ctx, r); break;
+        case 1: packet_walk_leaves<1, COUNT>(s, list, mine, ray, ctx, r); break;
+        case 2: packet_walk_leaves<2, COUNT>(s, list, mine, ray, ctx, r); break;
+        case 3: packet_walk_leaves<3, COUNT>(s, list, mine, ray, ctx, r); break;
+        case 4: packet_walk_leaves<4, COUNT>(s, list, mine, ray, ctx, r); break;
+        case 5: packet_walk_leaves<5, COUNT>(s, list, mine, ray, ctx, r); break;
+        case 6: packet_walk_leaves<6, COUNT>(s, list, mine, ray, ctx, r); break;
+        default: packet_walk_leaves<7, COUNT>(s, list, mine, ray, ctx, r); break;
+    }
+}
+
 // closest hit for a wave of coherent rays; lanes with active == false carry no ray
 // unionNodes (may be null): the number of nodes the wave visited, the length of its chain of dependent fetches (tile splitting, rs_tilesplit.h)
 // cut (wave-uniform): the walk of order cut.order goes through the cut's records instead of the tree's when it takes the fast form --
 // every other walk (special-case rays, mixed signs, another order, a table without nested links) ignores it
 template <bool COUNT = false>
-__device__ inline Hit trace_closest_packet(const DevScene& s, const Ray& ray, bool active, unsigned* unionNodes = nullptr, CutRef cut = CutRef{ nullptr, 0u, 0 }) {
+// list (wave-uniform): under the same conditions the walk of order list.order goes through the tile's leaf list instead of either
+__device__ inline Hit trace_closest_packet(const DevScene& s, const Ray& ray, bool active, unsigned* unionNodes = nullptr, CutRef cut = CutRef{ nullptr, 0u, 0 },
+                                           LeafListRef list = LeafListRef{ nullptr, nullptr, 0u, 0 }) {
     WalkResult w;
     RayBoxCtx ctx = make_box_ctx(ray);
     ctx.cull = s.axisCull;
@@ -856,7 +963,7 @@ __device__ inline Hit trace_closest_packet(const DevScene& s, const Ray& ray, bo
     const int order = mtbvh_order(-ray.d);
     unsigned long long todo = __ballot(active);
 #ifdef RS_WALK_STATS
-    w.steps = w.nearSteps = w.enteredSteps = w.leafSteps = w.clearSteps = 0; w.myVisits = 0;
+    w.steps = w.nearSteps = w.enteredSteps = w.leafSteps = w.clearSteps = 0; w.myVisits = 0; w.chainSteps = w.listSteps = 0;
     unsigned norders = 0;
 #endif
     while (todo) {                                            // one pass per threaded order present in the wave
@@ -872,9 +979,17 @@ __device__ inline Hit trace_closest_packet(const DevScene& s, const Ray& ray, bo
         const bool uniformSigns = (sx == 0 || sx == mm) && (sy == 0 || sy == mm) && (sz == 0 || sz == mm);
         if (anySpecial) packet_walk_order<false, COUNT>(s, k, mine, ray, ctx, w);
         else if (uniformSigns && s.axisCull && s.linksNested) {
+            const int neg = (sx ? 1 : 0) | (sy ? 2 : 0) | (sz ? 4 : 0);
+            if (list.end != 0u && k == list.order) {
+#ifdef RS_WALK_STATS
+                w.listSteps += list.end;
+#endif
+                packet_walk_leaves_dispatch<COUNT>(neg, s, list, mine, ray, ctx, w);
+                continue;
+            }
             const bool cutHere = cut.end != 0u && k == cut.order;
             const char* base = cutHere ? cut.base : reinterpret_cast<const char*>(s.nodesAll + (size_t)k * (size_t)s.bvhSize);
-            packet_walk_fast_dispatch<COUNT>((sx ? 1 : 0) | (sy ? 2 : 0) | (sz ? 4 : 0), s, base, cutHere ? cut.end : (unsigned)s.bvhSize, mine, ray, ctx, w);
+            packet_walk_fast_dispatch<COUNT>(neg, s, base, cutHere ? cut.end : (unsigned)s.bvhSize, mine, ray, ctx, w);
         }
         else packet_walk_order<true, COUNT>(s, k, mine, ray, ctx, w);
     }
@@ -886,6 +1001,7 @@ __device__ inline Hit trace_closest_packet(const DevScene& s, const Ray& ray, bo
         atomicAdd(&s.walkStats[21], (unsigned long long)w.nearSteps); atomicAdd(&s.walkStats[22], (unsigned long long)w.enteredSteps);
         atomicAdd(&s.walkStats[23], (unsigned long long)w.leafSteps); atomicAdd(&s.walkStats[15], (unsigned long long)w.clearSteps);
         atomicAdd(&s.walkStats[24 + (w.steps ? 31 - __clz((int)w.steps) : 0)], 1ull);
+        atomicAdd(&s.walkStats[94], (unsigned long long)w.listSteps); atomicAdd(&s.walkStats[95], (unsigned long long)w.chainSteps);       // (88..93: the RIS loop's, restir.hip)
     }
     {   // is a heavy tile heavy because its rays diverge (large union) or because single rays visit that many nodes?
         unsigned mv = w.myVisits;

@@ -123,6 +123,7 @@ int build_occlusion_side(rs_scene* s) {
     RS_TRY(rs_dev_alloc(&s->dOccNodes, no + 1));
     RS_HIP(hipMemcpy(s->dOccNodes, packed.data(), (no + 1) * 16, hipMemcpyHostToDevice));
     RS_TRY(upload(&s->dOccChain, chain));
+    RS_TRY(upload(&s->dLeafOfPrim, leafOf));
     RS_TRY(upload(&s->dOccTris, rec));
 #ifdef RS_WALK_STATS
     {   // depth of every record of the pre-order array (spans nest: a stack of span ends)
@@ -301,7 +302,7 @@ extern "C" int rs_scene_destroy(rs_scene* s) {
     if (!s) return 0;
     (void)rs_gbuffer_release_scene(s);                  // asynchronous mode: a GBuffer::render of this scene that has only been recorded so far
     (void)rs_synchronize();                             // ... and kernels on the library / auxiliary streams may still read the scene
-    rs_dev_free(s->dNodesAll); rs_dev_free(s->dWalkStats); rs_dev_free(s->dOccNodes); rs_dev_free(s->dEmiNodes); rs_dev_free(s->dEmiTris); rs_dev_free(s->dOccChain); rs_dev_free(s->dOccTris); rs_dev_free(s->dOrdNodes); rs_dev_free(s->dOrdTris);
+    rs_dev_free(s->dNodesAll); rs_dev_free(s->dWalkStats); rs_dev_free(s->dOccNodes); rs_dev_free(s->dEmiNodes); rs_dev_free(s->dEmiTris); rs_dev_free(s->dOccChain); rs_dev_free(s->dLeafOfPrim); rs_dev_free(s->dOccTris); rs_dev_free(s->dOrdNodes); rs_dev_free(s->dOrdTris);
     rs_dev_free(s->dTris); rs_dev_free(s->dVertices); rs_dev_free(s->dNormals);
     rs_dev_free(s->dMaterialIds); rs_dev_free(s->dMaterials); rs_dev_free(s->dLights); rs_dev_free(s->dAlias);
     rs_dev_free(s->dTextures); rs_dev_free(s->dEnvAlias); rs_dev_free(s->dTexcoords); rs_dev_free(s->dSampleSeq);

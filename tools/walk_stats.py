@@ -63,6 +63,8 @@ print("  histogram of union nodes per wave (log2 buckets):", " ".join("%d:%d" % 
 try:
     o2 = (C.c_ulonglong * 32)()
     assert L.rs_debug_walk_stats_ordered(scene.handle, o2, 0) == 0
+    if o2[30]:      # leaf lists (rs_cuts.h): slots 94, 95
+        print("  leaf lists: %.1f of the mean union nodes above are list records; ancestor-chain steps (wave iterations) %.4f per wave" % (o2[30] / pw, o2[31] / pw))
     if o2[23]:
         print("  the slowest ray of a wave visits %.1f nodes on average (fast form only); waves with >= 1024 union nodes: %d, union %.0f, slowest ray %.0f nodes" %
               (o2[23] / pw, o2[20], o2[21] / max(o2[20], 1), o2[22] / max(o2[20], 1)))
