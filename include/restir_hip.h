@@ -698,6 +698,30 @@ int  rs_debug_primary_leaf_list_info(rs_restir* r, int* tiles, int* tilesWithout
 int  rs_debug_primary_leaf_list_missing(rs_restir* r, const rs_scene* scene, int n, const float* rays, unsigned long long out[4]);
 int  rs_debug_plan_primary_leaf_list(const rs_camera* cam, int x0, int y0, int bvhSize, const float* boundingBoxes, const int* const bvhNodes[6], int cap,
                                      int* order, int* count, int* positions);
+/* The same for the node cut of the w x h pixels at (x0, y0) (a block is 32 x 8): *order, *count (cap + 1: more than cap),
+ * positions[min(*count, cap)] = the kept records' indices in that order's table and, when *count <= cap, links[*count] = their miss links
+ * within the cut (*count: the cut's end).  The walk and the re-linking are the functions the device builder runs. */
+int  rs_debug_plan_primary_cut(const rs_camera* cam, int x0, int y0, int w, int h, int bvhSize, const float* boundingBoxes, const int* const bvhNodes[6], int cap,
+                               int* order, int* count, int* positions, int* links);
+/* What one phase-A call of a frame keeps about its cuts between frames, as plain data (restir_amd/csrc/rs_cut_plan.h).  The key is what
+ * the cuts and lists were built from; listCap is 0 while the lists' switch is off.  `cuts` and `lists` say what became of each arena
+ * under that key. */
+typedef struct rs_primary_cut_key {
+    unsigned long long sceneId, geomEdits;
+    rs_camera cam;
+    int y0, y1;
+    unsigned cap, listCap;
+} rs_primary_cut_key;
+#define RS_CUT_ARENA_NOTHING   0   /* nothing built for the key */
+#define RS_CUT_ARENA_NO_MEMORY 1   /* the arena could not be allocated: the key goes without */
+#define RS_CUT_ARENA_BUILT     2
+typedef struct rs_primary_cut_slot { int keyValid, cuts, lists; rs_primary_cut_key key; } rs_primary_cut_slot;
+typedef struct rs_primary_cut_sizes { int numCells; unsigned capacity; int numTiles; unsigned listCapacity; } rs_primary_cut_sizes;
+/* Test hook, host only: a call with key *key, the cuts' switch `on` and the library stream `capturing` or not meets *slot -- *cutState as
+ * rs_phase_a_inputs has it, *slot as the call leaves it -- and the arenas of a launch of tilesX x tilesY blocks under the key's caps:
+ * cells, records, tiles (0: no lists), list records. */
+int  rs_debug_plan_primary_cut_slot(int on, int capturing, rs_primary_cut_slot* slot, const rs_primary_cut_key* key, int tilesX, int tilesY,
+                                    int* cutState, rs_primary_cut_sizes* sizes);
 /* Test hook: the per-pixel state the primary rays of the last ended frame left for the later passes (host arrays of width * height
  * pixels): 4 floats { hit position, tag bits }, 4 floats { shading normal, metallic }, 2 words { sampler state, tag }.  Waits for the
  * device. */

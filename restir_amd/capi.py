@@ -125,6 +125,25 @@ class PhaseAPlan(C.Structure):
 RIS_GLOBAL, RIS_LDS, RIS_ALIAS_LDS = 0, 1, 2
 
 
+class PrimaryCutKey(C.Structure):
+    """rs_primary_cut_key (include/restir_hip.h): what a slot's cuts and leaf lists were built from."""
+    _fields_ = [("sceneId", C.c_ulonglong), ("geomEdits", C.c_ulonglong), ("cam", Camera), ("y0", C.c_int), ("y1", C.c_int),
+                ("cap", C.c_uint), ("listCap", C.c_uint)]
+
+
+class PrimaryCutSlot(C.Structure):
+    """rs_primary_cut_slot: the stored key and what became of the two arenas under it (CUT_ARENA_*)."""
+    _fields_ = [("keyValid", C.c_int), ("cuts", C.c_int), ("lists", C.c_int), ("key", PrimaryCutKey)]
+
+
+class PrimaryCutSizes(C.Structure):
+    """rs_primary_cut_sizes: the arenas of one launch geometry."""
+    _fields_ = [("numCells", C.c_int), ("capacity", C.c_uint), ("numTiles", C.c_int), ("listCapacity", C.c_uint)]
+
+
+CUT_ARENA_NOTHING, CUT_ARENA_NO_MEMORY, CUT_ARENA_BUILT = 0, 1, 2
+
+
 # every symbol include/restir_hip.h declares; tests check that the library exports all of them
 EXPORTS = [
     "rs_last_error", "rs_context_create", "rs_context_destroy", "rs_context_set_current", "rs_init", "rs_set_stream", "rs_set_sync", "rs_set_side_stream", "rs_set_ris_table_pixels", "rs_set_internal_stream_priority", "rs_internal_streams_info", "rs_choose_internal_streams_again", "rs_prepare_streams", "rs_set_stream_plan", "rs_set_denoise_stream", "rs_join_denoise_stream", "rs_set_tile_split", "rs_debug_split_tiles", "rs_synchronize",
@@ -134,7 +153,7 @@ EXPORTS = [
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
     "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
-    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_restir_set_primary_leaf_lists", "rs_debug_set_primary_leaf_list_cap", "rs_debug_primary_leaf_list_info", "rs_debug_primary_leaf_list_missing", "rs_debug_plan_primary_leaf_list", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
+    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_restir_set_primary_leaf_lists", "rs_debug_set_primary_leaf_list_cap", "rs_debug_primary_leaf_list_info", "rs_debug_primary_leaf_list_missing", "rs_debug_plan_primary_leaf_list", "rs_debug_plan_primary_cut", "rs_debug_plan_primary_cut_slot", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
     "rs_path_trace", "rs_path_trace_indirect", "rs_restir_indirect", "rs_restir_download_indirect",
     "rs_svgf_create", "rs_svgf_destroy", "rs_svgf_filter", "rs_svgf_next_frame", "rs_svgf_get_view",
     "rs_copy_image_to_pbo", "rs_copy_image2_to_pbo", "rs_copy_imagef_to_pbo", "rs_copy_imagei_to_pbo", "rs_eaw_create", "rs_eaw_destroy", "rs_eaw_set_params", "rs_eaw_get_params", "rs_eaw_set_tiled", "rs_eaw_set_fused", "rs_svgf_set_params", "rs_svgf_get_params", "rs_svgf_set_tiled", "rs_svgf_set_fused", "rs_eaw_filter", "rs_eaw_positions_rows", "rs_eaw_level_rows", "rs_modulate_albedo",
@@ -255,6 +274,8 @@ def lib():
     L.rs_debug_primary_leaf_list_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(ci), C.POINTER(C.c_ulonglong)]
     L.rs_debug_primary_leaf_list_missing.argtypes = [vp, vp, ci, vp, C.POINTER(C.c_ulonglong * 4)]
     L.rs_debug_plan_primary_leaf_list.argtypes = [vp, ci, ci, ci, vp, C.POINTER(vp * 6), ci, C.POINTER(ci), C.POINTER(ci), vp]
+    L.rs_debug_plan_primary_cut.argtypes = [vp, ci, ci, ci, ci, ci, vp, C.POINTER(vp * 6), ci, C.POINTER(ci), C.POINTER(ci), vp, vp]
+    L.rs_debug_plan_primary_cut_slot.argtypes = [ci, ci, C.POINTER(PrimaryCutSlot), C.POINTER(PrimaryCutKey), ci, ci, C.POINTER(ci), C.POINTER(PrimaryCutSizes)]
     L.rs_debug_restir_surface.argtypes = [vp, vp, vp, vp]
     L.rs_pbo_register.argtypes = [C.c_uint, C.POINTER(vp)]
     L.rs_pbo_map.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -534,6 +555,28 @@ def plan_primary_leaf_list(cam, x0, y0, boxes, nodes, cap):
     pos = np.zeros(max(int(cap), 1), np.int32)
     check(lib().rs_debug_plan_primary_leaf_list(C.byref(cam), int(x0), int(y0), nodes.shape[1], _p(boxes), C.byref(arr), int(cap), C.byref(order), C.byref(count), _p(pos)))
     return order.value, count.value, pos[:min(count.value, int(cap))].copy()
+
+
+def plan_primary_cut(cam, x0, y0, w, h, boxes, nodes, cap):
+    """rs_debug_plan_primary_cut (host only): the node cut of the w x h pixels at (x0, y0) over build_bvh's outputs.  Returns (order,
+    count, positions, links): order -1 when the cell takes no cut; count = cap + 1 when it has more than cap records; positions = the
+    record indices of the first min(count, cap) kept records in nodes[order]; links = their miss links within the cut (empty past the cap)."""
+    boxes = np.ascontiguousarray(boxes, np.float32); nodes = np.ascontiguousarray(nodes, np.int32)
+    arr = (C.c_void_p * 6)(*[nodes[i].ctypes.data for i in range(6)])
+    order, count = C.c_int(), C.c_int()
+    pos, links = np.zeros(max(int(cap), 1), np.int32), np.zeros(max(int(cap), 1), np.int32)
+    check(lib().rs_debug_plan_primary_cut(C.byref(cam), int(x0), int(y0), int(w), int(h), nodes.shape[1], _p(boxes), C.byref(arr), int(cap),
+                                          C.byref(order), C.byref(count), _p(pos), _p(links)))
+    kept = min(count.value, int(cap))
+    return order.value, count.value, pos[:kept].copy(), links[:kept if count.value <= int(cap) else 0].copy()
+
+
+def plan_primary_cut_slot(slot, key, on=True, capturing=False, tiles=(1, 1)):
+    """rs_debug_plan_primary_cut_slot (host only): a phase-A call with PrimaryCutKey `key` meets PrimaryCutSlot `slot`, which is updated
+    as the call leaves it.  Returns (cutState, PrimaryCutSizes of a launch of tiles[0] x tiles[1] blocks under the key's caps)."""
+    state, sizes = C.c_int(), PrimaryCutSizes()
+    check(lib().rs_debug_plan_primary_cut_slot(int(on), int(capturing), C.byref(slot), C.byref(key), int(tiles[0]), int(tiles[1]), C.byref(state), C.byref(sizes)))
+    return state.value, sizes
 
 
 # ---- host builders (no GPU needed) ----------------------------------------------------------------

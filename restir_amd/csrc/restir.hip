@@ -880,91 +880,6 @@ int check_frame_args(rs_restir* r, const rs_scene* scene, const rs_camera* cam, 
 // stay where the overlapped mode puts them -- the pass's duration while other frames' kernels share the CUs
 void mark(rs_restir* r, int i) { if (r->timing == 1 || (r->timing == 2 && i >= 3)) (void)hipEventRecord(r->ev[i], rs_stream()); }
 
-// ---- primary cuts (rs_cuts.h; rs_primary_cut in rs_internal.h) -----------------------------------------------------------------------
-constexpr unsigned kCutArenaPerCell = 512;     // the arena holds this many records per cell (or the cap, if smaller); cells that do not fit take no cut
-constexpr unsigned kListArenaPerTile = 32;     // the lists' arena: this many 64-byte records per tile (the model's mean is 20 / 29 at the default cap); tiles that do not fit take no list
-
-void list_free(rs_primary_cut& pc) {
-    rs_dev_free(pc.tiles); rs_dev_free(pc.leafRecords); rs_dev_free(pc.leafOf);
-    pc.tiles = nullptr; pc.leafRecords = nullptr; pc.leafOf = nullptr;
-    pc.numTiles = 0; pc.listCapacity = 0; pc.listsBuilt = false;
-}
-
-void cut_free(rs_primary_cut& pc) {
-    rs_dev_free(pc.cells); rs_dev_free(pc.records); rs_dev_free(pc.orig); rs_dev_free(pc.counters);
-    pc.cells = nullptr; pc.records = nullptr; pc.orig = nullptr; pc.counters = nullptr;
-    pc.numCells = 0; pc.capacity = 0; pc.built = false;
-    list_free(pc);
-}
-
-// rs_phase_a_inputs::cutState for this call, and the call's key left in the slot for the same call of the next frame
-int cut_state(rs_restir* r, rs_primary_cut& pc, const rs_scene* scene, const rs_camera* cam, int y0, int y1) {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(rs_stream(), &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
-    if (!r->cutsOn || capturing != hipStreamCaptureStatusNone) { pc.keyValid = false; pc.built = false; pc.listsBuilt = false; return 0; }
-    const unsigned listCap = r->listsOn ? r->listCap : 0u;          // (lists off: cap 0, no tile takes one)
-    // (the size is the camera's resolution, which check_frame_args holds to the object's)
-    const bool same = pc.keyValid && pc.sceneId == scene->id && pc.geomEdits == scene->geomEdits && std::memcmp(&pc.cam, cam, sizeof(rs_camera)) == 0 &&
-                      pc.y0 == y0 && pc.y1 == y1 && pc.cap == r->cutCap && pc.listCap == listCap;
-    if (same) return pc.noMemory ? 0 : pc.built ? 2 : 1;
-    pc.keyValid = true; pc.built = false; pc.noMemory = false; pc.listsBuilt = false; pc.listsNoMemory = false; pc.listCap = listCap;
-    pc.sceneId = scene->id; pc.geomEdits = scene->geomEdits; pc.cam = *cam; pc.y0 = y0; pc.y1 = y1; pc.cap = r->cutCap;
-    return 0;
-}
-
-// enqueues the build of the slot's cuts on st: after every launch that still reads the arena, before every launch that waits for pc.builtEv
-int cut_build(rs_primary_cut& pc, const rs_scene* scene, const CamParams& cp, int y0, int tilesX, int tilesY, hipStream_t st) {
-    const int cellsX = tilesX, numCells = tilesX * tilesY;          // a cell is a block of the launch: 32x8 pixels
-    const unsigned perCell = pc.cap < kCutArenaPerCell ? pc.cap : kCutArenaPerCell;
-    const unsigned long long want = (unsigned long long)numCells * perCell;
-    const unsigned capacity = want < 0x7fffffffull ? (unsigned)want : 0x7fffffffu;
-    if (numCells != pc.numCells || capacity != pc.capacity) {      // another launch geometry (hipFree waits for the device: nothing reads the old arena)
-        cut_free(pc);
-        int e = rs_dev_alloc(&pc.cells, (size_t)numCells);
-        if (!e) e = rs_dev_alloc(&pc.records, (size_t)capacity + 1);
-        if (!e) e = rs_dev_alloc(&pc.orig, (size_t)capacity + 1);
-        if (!e) e = rs_dev_alloc(&pc.counters, 8);
-        if (e) {                                             // no memory for the arena: this key renders through the tree, as the frames before it did
-            (void)hipGetLastError();
-            cut_free(pc);
-            pc.noMemory = true;
-            return 0;
-        }
-        pc.numCells = numCells; pc.capacity = capacity;
-        for (bool& v : pc.usedValid) v = false;
-    }
-    pc.cellsX = cellsX;
-    // the tiles' leaf lists: an arena of their own; without memory, or on a scene without the chain records, the launches keep the cuts alone
-    const int numTiles = numCells * 4;
-    const unsigned perTile = pc.listCap < kListArenaPerTile ? pc.listCap : kListArenaPerTile;
-    const unsigned long long wantList = (unsigned long long)numTiles * perTile;
-    const unsigned listCapacity = wantList < 0x3ffffffull ? (unsigned)wantList : 0x3ffffffu;       // (byte offsets of 64-byte records stay below 2^32)
-    const bool lists = pc.listCap > 0u && scene->dLeafOfPrim && scene->dev.occChain && scene->dev.occNested && !pc.listsNoMemory;
-    if (!lists) pc.listsBuilt = false;
-    else if (numTiles != pc.numTiles || listCapacity != pc.listCapacity) {
-        list_free(pc);
-        int e = rs_dev_alloc(&pc.tiles, (size_t)numTiles);
-        if (!e) e = rs_dev_alloc(&pc.leafRecords, ((size_t)listCapacity + 1) * 4);
-        if (!e) e = rs_dev_alloc(&pc.leafOf, (size_t)listCapacity + 1);
-        if (e) { (void)hipGetLastError(); list_free(pc); pc.listsNoMemory = true; }
-        else { pc.numTiles = numTiles; pc.listCapacity = listCapacity; }
-    }
-    pc.tilesPerRow = tilesX * 4;
-    if (!pc.builtEv) RS_HIP(hipEventCreateWithFlags(&pc.builtEv, hipEventDisableTiming));
-    for (int i = 0; i < 1 + rs_context::kAux; i++) if (pc.usedValid[i]) { RS_HIP(hipStreamWaitEvent(st, pc.usedEv[i], 0)); pc.usedValid[i] = false; }
-    RS_HIP(hipMemsetAsync(pc.counters, 0, 8 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_build_primary_cuts, dim3((numCells + 63) / 64), dim3(64), 0, st, scene->dev, cp, y0, cellsX, numCells, 32, 8, pc.cap, capacity,
-                       pc.cells, pc.records, pc.orig, pc.counters);
-    if (lists && pc.tiles) {
-        hipLaunchKernelGGL(k_build_primary_leaf_lists, dim3((numTiles + 63) / 64), dim3(64), 0, st, scene->dev, cp, y0, pc.tilesPerRow, numTiles, pc.listCap, listCapacity,
-                           scene->dLeafOfPrim, pc.tiles, pc.leafRecords, pc.leafOf, pc.counters + 4);
-        pc.listsBuilt = true; pc.listBuilds++;
-    }
-    RS_HIP(hipEventRecord(pc.builtEv, st));
-    pc.built = true; pc.builds++;
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -983,11 +898,7 @@ int rs_restir_free(rs_restir* r) {
     rs_dev_free(r->indResv[0]); rs_dev_free(r->indResv[1]);
     rs_dev_free(r->idCur); rs_dev_free(r->idLast); rs_dev_free(r->idTemp);
     for (int*& p : r->candId) rs_dev_free(p);
-    for (rs_primary_cut& pc : r->cut) {
-        cut_free(pc);
-        if (pc.builtEv) (void)hipEventDestroy(pc.builtEv);
-        for (hipEvent_t& e : pc.usedEv) if (e) (void)hipEventDestroy(e);
-    }
+    rs_primary_cuts_destroy(r->cuts);
     for (auto& e : r->ev) if (e) (void)hipEventDestroy(e);
     for (auto& pair : r->spatialEv) for (hipEvent_t& e : pair) if (e) (void)hipEventDestroy(e);
     for (auto& e : r->surfFree) if (e) (void)hipEventDestroy(e);
@@ -1005,8 +916,7 @@ int rs_restir_init(int width, int height, rs_restir** out) {
     r->ctx = rs_ctx();
     rs_ctx_scope scope(r->ctx);
     r->width = width; r->height = height;
-    if (const char* env = std::getenv("RS_PRIMARY_CUTS")) r->cutsOn = std::atoi(env) != 0;     // A/B switch for measurements: the default of rs_restir_set_primary_cuts
-    if (const char* env = std::getenv("RS_PRIMARY_LEAF_LISTS")) r->listsOn = std::atoi(env) != 0;     // the same for rs_restir_set_primary_leaf_lists
+    rs_primary_cuts_init(r->cuts);
     const size_t n = (size_t)width * height;
     int e = 0;
     if (!e) e = alloc_planes(r->cur, n);
@@ -1194,9 +1104,7 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     }
     in.idle = in.async && r->idleFrame;
     in.numLights = scene->numLights; in.envMap = scene->envMapTexId >= 0; in.risGlobalBelow = rs_ris_global_below();
-    const int cutSlot = r->phaseACalls < 2 ? r->phaseACalls : 2;
-    rs_primary_cut& pc = r->cut[cutSlot];
-    in.cutState = cut_state(r, pc, scene, cam, y0, y1);
+    in.cutState = rs_primary_cuts_begin(r->cuts, r->phaseACalls, scene, cam, y0, y1);
     rs_phase_a_plan p;
     rs_plan_phase_a(in, p);
     hipStream_t aux = p.stream >= 0 ? rs_aux_stream(p.stream) : nullptr;
@@ -1204,7 +1112,6 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     if (p.tuneCounted) r->tune.count(scene->id);
     if (p.tuneRestart) r->tune.restart();
     r->lastFused = p.fuse; r->lastChains = p.lastChains;
-    r->lastCutSlot = cutSlot; r->lastCutUsed = p.cut == 2; r->lastListsUsed = false;
     const hipStream_t st = aux ? aux : rs_stream();
     const int tilesX = p.tilesX, tilesY = p.tilesY;
     if (aux) {
@@ -1244,23 +1151,13 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     else {
         TileSplit ts; int helpers = 0;
         RS_TRY(rs_tile_split_prepare(hints, (((long long)y0 << 20 | y1) << 12 | tilesX), tilesX * 4 * tilesY, tilesX * tilesY, p.splitMode, st, &ts, &helpers));
-        PrimaryCuts cuts{ nullptr, nullptr, nullptr, nullptr, nullptr };
-        if (p.cut == 2) {                                       // after the build, wherever it was enqueued
-            RS_HIP(hipStreamWaitEvent(st, pc.builtEv, 0));
-            cuts = PrimaryCuts{ pc.cells, pc.records, nullptr, nullptr, nullptr };
-            if (pc.listsBuilt) { cuts.tiles = pc.tiles; cuts.leafRecords = pc.leafRecords; cuts.leafOf = pc.leafOf; }
-        }
-        r->lastListsUsed = cuts.tiles != nullptr;
+        PrimaryCuts cuts{};                                     // (no cells: the tree)
+        if (p.cut == 2) RS_TRY(rs_primary_cuts_view(r->cuts, st, &cuts));      // st waits for the build, wherever it was enqueued
         rs_dispatch([&](auto TEX, auto SOBOL) {
             if (ts.base) hipLaunchKernelGGL((k_primary_split<TEX(), SOBOL()>), dim3(helpers + tilesX * tilesY), dim3(256), 0, st, scene->dev, cp, sp, looper, y0, y1, tilesX, rayCounter, ts, cuts);
             else hipLaunchKernelGGL((k_primary<TEX(), SOBOL()>), dim3(tilesX * tilesY), dim3(256), 0, st, scene->dev, cp, sp, looper, y0, y1, tilesX, rayCounter, cuts);
         }, tex, sobol);
-        if (p.cut == 2) {                                       // a later build into this arena waits for this reader
-            const int k = aux ? 1 + p.stream : 0;
-            if (!pc.usedEv[k]) RS_HIP(hipEventCreateWithFlags(&pc.usedEv[k], hipEventDisableTiming));
-            RS_HIP(hipEventRecord(pc.usedEv[k], st));
-            pc.usedValid[k] = true;
-        }
+        if (p.cut == 2) RS_TRY(rs_primary_cuts_launched(r->cuts, aux ? 1 + p.stream : 0, st));     // a later build into this arena waits for this reader
     }
     mark(r, 1);
     const int npx = (y1 - y0) * W;
@@ -1274,7 +1171,7 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
         RS_HIP(hipStreamWaitEvent(rs_stream(), r->auxDone, 0));
     }
     // (behind the chain's end event: this frame's temporal pass does not wait for the build, the chain's next frame does)
-    if (p.cut == 1) RS_TRY(cut_build(pc, scene, cp, y0, tilesX, tilesY, st));
+    if (p.cut == 1) RS_TRY(rs_primary_cuts_build(r->cuts, scene, cp, y0, tilesX, tilesY, st));
     if (p.shadowOnLibrary) hipLaunchKernelGGL(k_shadow, dim3(tilesX * tilesY), dim3(256), 0, rs_stream(), scene->dev, sp, W, y0, y1, tilesX);
     RS_TRY(rs_gbuffer_join(g));                                 // first consumer of the G-buffer planes
     LightIds ids{ nullptr, nullptr, nullptr, nullptr, nullptr, 0, -1 };
@@ -1365,139 +1262,6 @@ int rs_restir_last_launch(const rs_restir* r, int* fused, int* chains) {
     RS_SCOPE(r);
     if (!r || !fused || !chains) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_last_launch: null argument");
     *fused = r->lastFused; *chains = r->lastChains;
-    return 0;
-}
-
-// Primary cuts (rs_cuts.h): 1 on (the default; RS_PRIMARY_CUTS=0 makes 0 the default), 0 off -- the cuts are forgotten, their memory stays
-int rs_restir_set_primary_cuts(rs_restir* r, int on) {
-    RS_SCOPE(r);
-    if (!r) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_set_primary_cuts: null");
-    r->cutsOn = on != 0;
-    if (!r->cutsOn) for (rs_primary_cut& pc : r->cut) { pc.keyValid = false; pc.built = false; }
-    return 0;
-}
-
-// test hook: the most records a cell's cut may have (1 .. 2^24; the default is 4096); cuts built under another cap are forgotten
-int rs_debug_set_primary_cut_cap(rs_restir* r, int records) {
-    RS_SCOPE(r);
-    if (!r || records < 1 || records > (1 << 24)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_set_primary_cut_cap: bad argument");
-    r->cutCap = (unsigned)records;
-    return 0;
-}
-
-// of the last phase-A call's slot: cells of its launch, cells without a cut, records in all cuts (zeros while nothing is built), whether
-// that call's primary rays walked the cuts, and how many builds the slot has seen.  Waits for the build.
-int rs_debug_primary_cut_info(rs_restir* r, int* cells, int* cellsWithoutCut, unsigned long long* records, int* usedLastFrame, unsigned long long* builds) {
-    RS_SCOPE(r);
-    if (!r || !cells || !cellsWithoutCut || !records || !usedLastFrame || !builds) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_primary_cut_info: null argument");
-    const rs_primary_cut& pc = r->cut[r->lastCutSlot];
-    *cells = 0; *cellsWithoutCut = 0; *records = 0; *usedLastFrame = r->lastCutUsed ? 1 : 0; *builds = pc.builds;
-    if (!pc.built) return 0;
-    RS_HIP(hipEventSynchronize(pc.builtEv));
-    unsigned long long h[4];
-    RS_HIP(hipMemcpy(h, pc.counters, sizeof h, hipMemcpyDeviceToHost));
-    *cells = pc.numCells; *cellsWithoutCut = (int)h[1]; *records = h[2];
-    return 0;
-}
-
-// test hook: containment of the last phase-A call's cuts, ray by ray (k_primary_cut_missing).  rays: n x { pixel x, pixel y, jitter x,
-// jitter y } on the host; the camera is the one the cut was built for.  out[4]: nodes a ray passes geometrically that the cell's cut
-// lacks, nodes passed, rays left out (special-case direction, another order than the cut's, no cut), records in the cell's cut.
-int rs_debug_primary_cut_missing(rs_restir* r, const rs_scene* scene, int cell, int n, const float* rays, unsigned long long out[4]) {
-    RS_SCOPE(r);
-    if (!r || !scene || !rays || !out || n <= 0) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_primary_cut_missing: bad argument");
-    const rs_primary_cut& pc = r->cut[r->lastCutSlot];
-    if (!pc.built || scene->id != pc.sceneId || scene->geomEdits != pc.geomEdits) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_primary_cut_missing: no cut has been built for this scene");
-    if (cell < 0 || cell >= pc.numCells) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_primary_cut_missing: no such cell");
-    RS_HIP(hipEventSynchronize(pc.builtEv));
-    float* dRays = nullptr; unsigned long long* dOut = nullptr;
-    RS_TRY(rs_dev_alloc(&dRays, (size_t)n * 4));
-    int e = rs_dev_alloc(&dOut, 4);
-    if (!e) e = rs_check_hip(hipMemcpy(dRays, rays, (size_t)n * 16, hipMemcpyHostToDevice), "hipMemcpy");
-    if (!e) e = rs_check_hip(hipMemset(dOut, 0, 32), "hipMemset");
-    if (!e) {
-        hipLaunchKernelGGL(k_primary_cut_missing, dim3((n + 63) / 64), dim3(64), 0, rs_stream(), scene->dev, rs_make_cam_params(&pc.cam),
-                           PrimaryCuts{ pc.cells, pc.records, nullptr, nullptr, nullptr }, pc.orig, cell, n, dRays, dOut);
-        e = rs_check_hip(hipStreamSynchronize(rs_stream()), "rs_debug_primary_cut_missing");
-    }
-    if (!e) e = rs_check_hip(hipMemcpy(out, dOut, 32, hipMemcpyDeviceToHost), "hipMemcpy");
-    rs_dev_free(dRays); rs_dev_free(dOut);
-    return e;
-}
-
-// Primary leaf lists (rs_cuts.h "Leaf lists"): 1 on (the default; RS_PRIMARY_LEAF_LISTS=0 makes 0 the default), 0 off -- whole tiles walk
-// their block's cut again.  The lists live and die with the cuts (rs_restir_set_primary_cuts off: no lists either); a change here forgets both.
-int rs_restir_set_primary_leaf_lists(rs_restir* r, int on) {
-    RS_SCOPE(r);
-    if (!r) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_set_primary_leaf_lists: null");
-    r->listsOn = on != 0;
-    return 0;
-}
-
-// test hook: the most records a tile's leaf list may have (0 .. 2^24; the default is 192; 0: no tile takes a list); lists and cuts built
-// under another cap are forgotten
-int rs_debug_set_primary_leaf_list_cap(rs_restir* r, int records) {
-    RS_SCOPE(r);
-    if (!r || records < 0 || records > (1 << 24)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_set_primary_leaf_list_cap: bad argument");
-    r->listCap = (unsigned)records;
-    return 0;
-}
-
-// of the last phase-A call's slot: tiles of its launch, tiles without a list, records in all lists (zeros while nothing is built), whether
-// that call's primary rays walked lists, and how many list builds the slot has seen.  Waits for the build.
-int rs_debug_primary_leaf_list_info(rs_restir* r, int* tiles, int* tilesWithoutList, unsigned long long* records, int* usedLastFrame, unsigned long long* builds) {
-    RS_SCOPE(r);
-    if (!r || !tiles || !tilesWithoutList || !records || !usedLastFrame || !builds) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_primary_leaf_list_info: null argument");
-    const rs_primary_cut& pc = r->cut[r->lastCutSlot];
-    *tiles = 0; *tilesWithoutList = 0; *records = 0; *usedLastFrame = r->lastListsUsed ? 1 : 0; *builds = pc.listBuilds;
-    if (!pc.built || !pc.listsBuilt) return 0;
-    RS_HIP(hipEventSynchronize(pc.builtEv));
-    unsigned long long h[4];
-    RS_HIP(hipMemcpy(h, pc.counters + 4, sizeof h, hipMemcpyDeviceToHost));
-    *tiles = pc.numTiles; *tilesWithoutList = (int)h[1]; *records = h[2];
-    return 0;
-}
-
-// test hook: containment of the last phase-A call's leaf lists, ray by ray (k_primary_leaf_list_missing).  rays as for
-// rs_debug_primary_cut_missing; every ray is looked up in its own tile's list.  out[4]: leaves a ray passes geometrically that its
-// tile's list lacks, leaves passed, rays left out (special-case direction, another order than the list's, a tile without a list), 0.
-int rs_debug_primary_leaf_list_missing(rs_restir* r, const rs_scene* scene, int n, const float* rays, unsigned long long out[4]) {
-    RS_SCOPE(r);
-    if (!r || !scene || !rays || !out || n <= 0) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_primary_leaf_list_missing: bad argument");
-    const rs_primary_cut& pc = r->cut[r->lastCutSlot];
-    if (!pc.built || !pc.listsBuilt || scene->id != pc.sceneId || scene->geomEdits != pc.geomEdits)
-        return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_primary_leaf_list_missing: no lists have been built for this scene");
-    RS_HIP(hipEventSynchronize(pc.builtEv));
-    float* dRays = nullptr; unsigned long long* dOut = nullptr;
-    RS_TRY(rs_dev_alloc(&dRays, (size_t)n * 4));
-    int e = rs_dev_alloc(&dOut, 4);
-    if (!e) e = rs_check_hip(hipMemcpy(dRays, rays, (size_t)n * 16, hipMemcpyHostToDevice), "hipMemcpy");
-    if (!e) e = rs_check_hip(hipMemset(dOut, 0, 32), "hipMemset");
-    if (!e) {
-        hipLaunchKernelGGL(k_primary_leaf_list_missing, dim3((n + 63) / 64), dim3(64), 0, rs_stream(), scene->dev, rs_make_cam_params(&pc.cam),
-                           PrimaryCuts{ pc.cells, pc.records, pc.tiles, pc.leafRecords, pc.leafOf }, pc.y0, pc.tilesPerRow, pc.numTiles, n, dRays, dOut);
-        e = rs_check_hip(hipStreamSynchronize(rs_stream()), "rs_debug_primary_leaf_list_missing");
-    }
-    if (!e) e = rs_check_hip(hipMemcpy(out, dOut, 32, hipMemcpyDeviceToHost), "hipMemcpy");
-    rs_dev_free(dRays); rs_dev_free(dOut);
-    return e;
-}
-
-// test hook, host only (no device call): the leaf list the builder would make for the 8x8 tile at pixel (x0, y0) of `cam`, over a
-// reference table (rs_build_bvh's outputs).  *order: the tile's threaded order (-1: cut_cell gives none, nothing else is written);
-// *count: the leaves of its list, or cap + 1 if there are more than `cap`; positions[0 .. min(*count, cap)): their record indices in
-// that order's table, in list order.  leaf_list_walk of rs_cuts.h, the function the device builder runs.
-int rs_debug_plan_primary_leaf_list(const rs_camera* cam, int x0, int y0, int bvhSize, const float* boundingBoxes, const int* const bvhNodes[6], int cap,
-                                    int* order, int* count, int* positions) {
-    if (!cam || !boundingBoxes || !bvhNodes || !order || !count || !positions || bvhSize <= 0 || cap < 0) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_plan_primary_leaf_list: bad argument");
-    *order = -1; *count = 0;
-    CutCell cell = cut_cell(rs_make_cam_params(cam), x0, y0, 8, 8);
-    if (cell.order < 0 || !bvhNodes[cell.order]) return 0;
-    const int* table = bvhNodes[cell.order];
-    auto rec = [&](unsigned i) { const int* n = table + (size_t)i * 3; const float* b = boundingBoxes + (size_t)n[1] * 6; return BvhNode{ b[0], b[1], b[2], b[5], b[3], b[4], n[0], n[2] }; };
-    if (!cut_cell_margin(cell, rec(0))) return 0;
-    *order = cell.order;
-    *count = (int)leaf_list_walk(cell, rec, (unsigned)bvhSize, (unsigned)cap, [&](unsigned k, unsigned at, const BvhNode&) { positions[k] = (int)at; });
     return 0;
 }
 

@@ -56,6 +56,10 @@
 // passing all its ancestors is kept -- the reference enters no other.  Why the lane's bits stay although the inner nodes are gone is packet_walk_leaves' argument (rs_walk.h).
 // A tile takes no list -- and keeps its block's cut, or the tree -- if cut_cell gives it no order, if its list is empty or longer than the
 // cap, if the arena is full, or if the scene lacks occChain / nested boxes.  Same key and lifetime as the cuts; built by the same call.
+//
+// This header: what k_primary / k_primary_split read (PrimaryCuts, cut_of_cell, leaf_list_of_tile) and the geometry, the walk and the
+// re-linking as host-and-device functions.  The slots, the build, its kernels and the entry points: primary_cuts.hip; the key and the
+// slot's state: rs_cut_plan.h.
 #pragma once
 
 #include "rs_walk.h"
@@ -156,21 +160,40 @@ RS_HD bool cut_cell_test(const CutCell& cell, const BvhNode& n) {
     return !(tMaxHi < tMinLo - cell.margin);
 }
 
-// The leaves of a cell's list: the cut's walk over records [0, end) of the cell's order (rec(i): record i), emit(i, record) for every kept
-// LEAF in threaded order.  Returns how many there are, or cap + 1 as soon as there are more than `cap` (nothing is emitted past the cap).
-// Host and device: the device builder and the host's planning hook (rs_debug_plan_primary_leaf_list) run this very function.
-template <class Rec, class Emit>
-RS_HD unsigned leaf_list_walk(const CutCell& cell, Rec rec, unsigned end, unsigned cap, Emit emit) {
+// The cut's walk over records [0, end) of the cell's order (rec(i): record i): it descends through kept records only, emit(k, i, record)
+// for the k-th kept record -- LEAVES: for the k-th kept LEAF, a tile's list -- in threaded order.  Returns how many there are, or cap + 1
+// as soon as there are more than `cap` (nothing is emitted past the cap).  stopAt: a caller that knows the count (the builders' writing
+// pass: cap = stopAt = the count) ends the walk with the last emitted record instead of stepping over the rest of the tree.  Host and
+// device: the device builders (primary_cuts.hip) and the host's planning hooks (rs_debug_plan_primary_cut,
+// rs_debug_plan_primary_leaf_list) run this very function.
+// (One thread walks one cell, a dependent load and a double-precision test per step: the loop keeps ONE exit, on `limit`.  With a second
+// exit from its middle -- "return cap + 1" where the record past the cap is met -- the cuts' builder took 5 % longer on configs 3 and 5.)
+template <bool LEAVES, class Rec, class Emit>
+RS_HD unsigned cut_walk(const CutCell& cell, Rec rec, unsigned end, unsigned cap, Emit emit, unsigned stopAt = 0xffffffffu) {
+    const unsigned limit = stopAt <= cap ? stopAt : cap + 1u;
     unsigned count = 0;
-    for (unsigned cur = 0; cur != end;) {
+    for (unsigned cur = 0; cur != end && count != limit;) {
         const BvhNode n = rec(cur);
         if (cut_cell_test(cell, n)) {
-            if (n.primId != kNullPrim) { if (count == cap) return cap + 1u; emit(count, cur, n); count++; }
+            if (!LEAVES || n.primId != kNullPrim) { if (count != cap) emit(count, cur, n); count++; }
             cur++;
         }
         else cur = (unsigned)n.next;
     }
     return count;
+}
+
+// The links of a cut of `count` records ("Which records", above): orig(j) is the original index of kept record j (rising), link(i) the
+// original miss link of kept record i; set(i, next') with next' = the first kept record after i whose original index is >= link(i),
+// or count.  Host and device, as the walk.
+template <class Orig, class Link, class Set>
+RS_HD void cut_relink(Orig orig, Link link, unsigned count, Set set) {
+    for (unsigned i = 0; i < count; i++) {
+        const unsigned to = link(i);
+        unsigned lo = i + 1u, hi = count;
+        while (lo < hi) { const unsigned mid = (lo + hi) >> 1; if (orig(mid) < to) lo = mid + 1u; else hi = mid; }
+        set(i, lo);
+    }
 }
 
 #if defined(__HIPCC__)
@@ -182,82 +205,6 @@ __device__ __forceinline__ LeafListRef leaf_list_of_tile(const PrimaryCuts& cuts
     return LeafListRef{ reinterpret_cast<const char*>(cuts.leafRecords + (size_t)first * 4u), cuts.leafOf + first, word & kCutCountMask, (int)(word >> 28) };
 }
 
-// One thread per tile: the walk that counts, a reservation in the arena, the same walk again to write.  leafOfPrim: the reference node of
-// every primitive's leaf.  counters: [0] records handed out, [1] tiles without a list, [2] records of the tiles that have one
-static __global__ void __launch_bounds__(64) k_build_primary_leaf_lists(DevScene s, CamParams cam, int y0, int tilesPerRow, int numTiles, unsigned cap, unsigned capacity,
-                                                                        const int* leafOfPrim, uint2* tiles, float4* records, int* leafOf, unsigned long long* counters) {
-    const int ti = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ti >= numTiles) return;
-    CutCell cell = cut_cell(cam, (ti % tilesPerRow) * 8, y0 + (ti / tilesPerRow) * 8, 8, 8);
-    const unsigned end = (unsigned)s.bvhSize;
-    const BvhNode* nodes = s.nodesAll + (size_t)(cell.order < 0 ? 0 : cell.order) * (size_t)s.bvhSize;
-    bool ok = cell.order >= 0 && s.axisCull && s.linksNested && s.occChain && s.occNested && end > 0u && cut_cell_margin(cell, nodes[0]);
-    unsigned count = 0;
-    if (ok) {
-        count = leaf_list_walk(cell, [&](unsigned i) { return nodes[i]; }, end, cap, [](unsigned, unsigned, const BvhNode&) {});
-        ok = count > 0u && count <= cap;
-    }
-    unsigned off = 0;
-    if (ok) {           // (first come, first served, as the cuts' arena: the results never depend on who goes without)
-        const unsigned long long at = atomicAdd(counters, (unsigned long long)count);
-        ok = at + count <= (unsigned long long)capacity;
-        off = ok ? (unsigned)at : 0u;
-    }
-    if (!ok) { tiles[ti] = make_uint2(0u, 0u); atomicAdd(counters + 1, 1ull); return; }
-    leaf_list_walk(cell, [&](unsigned i) { return nodes[i]; }, end, cap, [&](unsigned k, unsigned, const BvhNode& n) {
-        const float4* tp = reinterpret_cast<const float4*>(s.tris + n.primId);
-        const float4 a = tp[0], b = tp[1], e = tp[2];
-        float4* r = records + (size_t)(off + k) * 4u;
-        r[0] = make_float4(n.bminx, n.bminy, n.bminz, n.bmaxz);
-        r[1] = make_float4(n.bmaxx, n.bmaxy, __int_as_float(n.primId), a.x);
-        r[2] = make_float4(a.y, a.z, b.x, b.y);
-        r[3] = make_float4(b.z, e.x, e.y, e.z);
-        leafOf[off + k] = leafOfPrim[n.primId];
-    });
-    tiles[ti] = make_uint2(off, count | ((unsigned)cell.order << 28));
-    atomicAdd(counters + 2, (unsigned long long)count);
-}
-
-// Containment of the lists, ray by ray, as k_primary_cut_missing: every ray walks the WHOLE tree of its order on the geometric part of the
-// reference's test alone, and each LEAF it passes is looked up in the list of the ray's own tile.  rays as there.  out: [0] passed leaves
-// absent from the list, [1] passed leaves, [2] rays left out (special-case direction, another order than the list's, a tile without a list)
-static __global__ void k_primary_leaf_list_missing(DevScene s, CamParams cam, PrimaryCuts cuts, int y0, int tilesPerRow, int numTiles, int n, const float* rays, unsigned long long* out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int px = (int)rays[4 * i], py = (int)rays[4 * i + 1];
-    const int tile = py >= y0 && px >= 0 ? ((py - y0) / 8) * tilesPerRow + px / 8 : -1;
-    if (tile < 0 || tile >= numTiles || px / 8 >= tilesPerRow) { atomicAdd(out + 2, 1ull); return; }
-    const uint2 entry = cuts.tiles[tile];
-    const unsigned count = entry.y & kCutCountMask;
-    const float4* list = cuts.leafRecords + (size_t)entry.x * 4u;
-    const Ray ray = camera_sample(cam, px, py, rays[4 * i + 2], rays[4 * i + 3]);
-    RayBoxCtx ctx = make_box_ctx(ray);
-    ctx.cull = s.axisCull;
-    const int order = mtbvh_order(-ray.d);
-    if (ray_is_special(ctx, ray) || count == 0u || order != (int)(entry.y >> 28)) { atomicAdd(out + 2, 1ull); return; }
-    const BvhNode* nodes = s.nodesAll + (size_t)order * (size_t)s.bvhSize;
-    unsigned long long passed = 0, missing = 0;
-    unsigned at = 0;                                        // the list is in the walk's order: the search never goes back
-    for (unsigned cur = 0; cur != (unsigned)s.bvhSize;) {
-        const float4* rec = reinterpret_cast<const float4*>(nodes + cur);
-        float4 lo, hi;
-        node_unpack(rec[0], rec[1], lo, hi);
-        float tb;
-        if (box_hit_general(ctx.o, ctx.dinv, lo, hi, tb)) {
-            const int prim = __float_as_int(lo.w);
-            if (prim != kNullPrim) {
-                passed++;
-                unsigned j = at;
-                while (j < count && __float_as_int(list[(size_t)j * 4u + 1u].z) != prim) j++;
-                if (j == count) missing++; else at = j + 1u;
-            }
-            cur++;
-        }
-        else cur = (unsigned)__float_as_int(hi.w);
-    }
-    atomicAdd(out, missing); atomicAdd(out + 1, passed);
-}
-
 // the cut of block `cell` of a primary-ray launch (wave-uniform)
 __device__ __forceinline__ CutRef cut_of_cell(const PrimaryCuts& cuts, int cell) {
     if (!cuts.cells) return CutRef{ nullptr, 0u, 0 };
@@ -266,86 +213,6 @@ __device__ __forceinline__ CutRef cut_of_cell(const PrimaryCuts& cuts, int cell)
     const uint2 c = cuts.cells[__builtin_amdgcn_readfirstlane(cell)];
     const unsigned first = (unsigned)__builtin_amdgcn_readfirstlane((int)c.x), word = (unsigned)__builtin_amdgcn_readfirstlane((int)c.y);
     return CutRef{ reinterpret_cast<const char*>(cuts.records + first), word & kCutCountMask, (int)(word >> 28) };
-}
-
-// counters (64-bit: a large cap times many cells must not wrap): [0] records handed out, [1] cells without a cut, [2] records of the cells that have one
-// One thread per cell: a walk that counts, a reservation in the arena, the same walk again to write, then the links.  orig[]: the original
-// index of every cut record (the links' binary search here; rs_debug_primary_cut_missing)
-static __global__ void __launch_bounds__(64) k_build_primary_cuts(DevScene s, CamParams cam, int y0, int cellsX, int numCells, int cellW, int cellH, unsigned cap, unsigned capacity,
-                                                                  uint2* cells, BvhNode* records, unsigned* orig, unsigned long long* counters) {
-    const int ci = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ci >= numCells) return;
-    CutCell cell = cut_cell(cam, (ci % cellsX) * cellW, y0 + (ci / cellsX) * cellH, cellW, cellH);
-    unsigned count = 0;
-    const unsigned end = (unsigned)s.bvhSize;
-    const BvhNode* nodes = s.nodesAll + (size_t)(cell.order < 0 ? 0 : cell.order) * (size_t)s.bvhSize;
-    bool ok = cell.order >= 0 && s.axisCull && s.linksNested && end > 0u && cut_cell_margin(cell, nodes[0]);
-    if (ok) {
-        for (unsigned cur = 0; cur != end && count <= cap;) {
-            const BvhNode n = nodes[cur];
-            if (cut_cell_test(cell, n)) { count++; cur++; }
-            else cur = (unsigned)n.next;
-        }
-        ok = count > 0u && count <= cap;
-    }
-    // (space is handed out in the order the cells ask: which cells go without when the arena is too small depends on that order --
-    // the results never do)
-    unsigned off = 0;
-    if (ok) {
-        const unsigned long long at = atomicAdd(counters, (unsigned long long)count);
-        ok = at + count <= (unsigned long long)capacity;
-        off = ok ? (unsigned)at : 0u;
-    }
-    if (!ok) { cells[ci] = make_uint2(0u, 0u); atomicAdd(counters + 1, 1ull); return; }
-    unsigned i = 0;
-    for (unsigned cur = 0; cur != end && i < count;) {
-        const BvhNode n = nodes[cur];
-        if (cut_cell_test(cell, n)) { records[off + i] = n; orig[off + i] = cur; i++; cur++; }
-        else cur = (unsigned)n.next;
-    }
-    for (i = 0; i < count; i++) {
-        const unsigned link = (unsigned)records[off + i].next;
-        unsigned lo = i + 1u, hi = count;                       // first record in (i, count) of original index >= link
-        while (lo < hi) { const unsigned mid = (lo + hi) >> 1; if (orig[off + mid] < link) lo = mid + 1u; else hi = mid; }
-        records[off + i].next = (int)lo;
-    }
-    cells[ci] = make_uint2(off, count | ((unsigned)cell.order << 28));
-    atomicAdd(counters + 2, (unsigned long long)count);
-}
-
-// Containment, ray by ray: every ray walks the WHOLE tree of its order on the geometric part of the reference's test alone (no distance
-// cull), and each node it passes is looked up in the cell's cut.  rays: n x { pixel x, pixel y, jitter x, jitter y } as floats.
-// out: [0] passed nodes absent from the cut, [1] passed nodes, [2] rays left out (special-case direction, another order than the cut's, or
-// a cell without a cut), [3] records in the cell's cut
-static __global__ void k_primary_cut_missing(DevScene s, CamParams cam, PrimaryCuts cuts, const unsigned* orig, int cellIndex, int n, const float* rays, unsigned long long* out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint2 entry = cuts.cells[cellIndex];
-    const CutRef cut{ reinterpret_cast<const char*>(cuts.records + entry.x), entry.y & kCutCountMask, (int)(entry.y >> 28) };
-    const unsigned off = entry.x;
-    if (i == 0) out[3] = cut.end;
-    const Ray ray = camera_sample(cam, (int)rays[4 * i], (int)rays[4 * i + 1], rays[4 * i + 2], rays[4 * i + 3]);
-    RayBoxCtx ctx = make_box_ctx(ray);
-    ctx.cull = s.axisCull;
-    const int order = mtbvh_order(-ray.d);
-    if (ray_is_special(ctx, ray) || order != cut.order || cut.end == 0u) { atomicAdd(out + 2, 1ull); return; }
-    const BvhNode* nodes = s.nodesAll + (size_t)order * (size_t)s.bvhSize;
-    unsigned long long passed = 0, missing = 0;
-    for (unsigned cur = 0; cur != (unsigned)s.bvhSize;) {
-        const float4* rec = reinterpret_cast<const float4*>(nodes + cur);
-        float4 lo, hi;
-        node_unpack(rec[0], rec[1], lo, hi);
-        float tb;
-        if (box_hit_general(ctx.o, ctx.dinv, lo, hi, tb)) {
-            unsigned a = 0, b = cut.end;
-            while (a < b) { const unsigned mid = (a + b) >> 1; if (orig[off + mid] < cur) a = mid + 1u; else b = mid; }
-            passed++;
-            if (a == cut.end || orig[off + a] != cur) missing++;
-            cur++;
-        }
-        else cur = (unsigned)__float_as_int(hi.w);
-    }
-    atomicAdd(out, missing); atomicAdd(out + 1, passed);
 }
 #endif  // __HIPCC__
 

@@ -12,6 +12,7 @@
 #define RS_SPLIT_SMALL_ROUNDS 3
 #endif
 #include "rs_frame_plan.h"
+#include "rs_cut_plan.h"
 #ifndef RS_GBUF_SETS
 #define RS_GBUF_SETS (RS_AUX_STREAMS + 2)
 #endif
@@ -248,7 +249,7 @@ struct rs_scene {
     float sumLightPower = 0.f;
     int numPrims = 0, bvhSize = 0, numLights = 0;
     unsigned long long id = 0;       // unique per rs_scene_create (a freed scene's address can come back; its id cannot)
-    unsigned long long geomEdits = 0;   // counts the edits that refit the box tables (set_geometry, scene_edits.hip): part of a primary cut's key (rs_primary_cut)
+    unsigned long long geomEdits = 0;   // counts the edits that refit the box tables (set_geometry, scene_edits.hip): part of a primary cut's key (rs_primary_cut_key, rs_cut_plan.h)
     unsigned long long edits = 0;    // counts the edits that change what GBuffer::render writes (rs_scene_set_emission: baseColor, hence the albedo plane); part of a G-buffer set's content key
     // Edits (rs_scene_set_emission, rs_scene_set_materials, rs_scene_set_texture): a ring of versions of { materials, light records,
     // alias table, texture table }.  Kernels capture
@@ -528,50 +529,57 @@ struct rs_fuse_tuner {
     int reported() const { return choice >= 0 ? choice : (frame > 0 || counted) ? -1 : -2; }     // rs_restir_launch_choice
 };
 
-// Static cuts of the tree for the primary rays of a still camera (rs_cuts.h), one per phase-A call of a frame (as the tile-split
-// hints: a strip driver's calls have rows of their own).  The KEY is what the cut was built from: the scene and its geometry edits
-// (rs_scene::geomEdits -- materials and emission do not count), every byte of the camera, the size and the rows.  Every call compares
-// its key with the one the same call of the previous frame left; the first call that finds it unchanged enqueues the build behind its
-// chain, the calls after that walk the cut, a call that finds another key forgets the cut.  Nothing here waits on the host: `built` orders
-// the readers' streams after the build, used[] orders a later build into the same arena after its readers.
+// Static cuts of the tree for the primary rays of a still camera (rs_cuts.h), one slot per phase-A call of a frame (as the tile-split
+// hints: a strip driver's calls have rows of their own).  primary_cuts.hip owns every field; the host decisions are rs_cut_plan.h's.
+// slot.key is what the cut was built from: the scene and its geometry edits (rs_scene::geomEdits -- materials and emission do not
+// count), every byte of the camera, the size, the rows and the caps.  Every call compares its key with the one the same call of the
+// previous frame left; the first call that finds it unchanged enqueues the build behind its chain, the calls after that walk the cut, a
+// call that finds another key forgets the cut.  Nothing here waits on the host: builtEv orders the readers' streams after the build,
+// usedEv[] orders a later build into the same arena after its readers.
 struct rs_primary_cut {
-    bool keyValid = false, built = false;
-    unsigned long long sceneId = 0, geomEdits = 0;
-    rs_camera cam{};
-    int y0 = 0, y1 = 0;
-    unsigned cap = 0;
-    bool noMemory = false;                   // the arena could not be allocated for this key: it keeps the tree
+    rs_primary_cut_slot slot{};
+    rs_primary_cut_sizes size{};             // of the arenas below (zeros: none)
     uint2* cells = nullptr;                  // per cell { first record, count | order << 28 }
-    rs::BvhNode* records = nullptr;          // the arena: `capacity` records and one more that is only ever read
+    rs::BvhNode* records = nullptr;          // the arena: size.capacity records and one more that is only ever read
     unsigned* orig = nullptr;                // original index of every record (the builder's links; the containment test hook)
     unsigned long long* counters = nullptr;  // [0] records handed out, [1] cells without a cut, [2] records in cuts; [4..6] the same of the leaf lists and tiles
-    int numCells = 0, cellsX = 0;
-    unsigned capacity = 0;
     // the tiles' leaf lists (rs_cuts.h "Leaf lists"): same key, built by the same call behind the cuts, read by the same launches
-    bool listsWanted = false, listsBuilt = false, listsNoMemory = false;
-    unsigned listCap = 0;                    // part of the key
     uint2* tiles = nullptr;                  // per tile { first record, count | order << 28 }
-    float4* leafRecords = nullptr;           // the arena: `listCapacity` 64-byte records and one more that is only ever read
+    float4* leafRecords = nullptr;           // the arena: size.listCapacity 64-byte records and one more that is only ever read
     int* leafOf = nullptr;                   // reference node of every record's leaf
-    int numTiles = 0, tilesPerRow = 0;
-    unsigned listCapacity = 0;
-    unsigned long long listBuilds = 0;
+    int tilesPerRow = 0;
     hipEvent_t builtEv = nullptr;
     hipEvent_t usedEv[1 + rs_context::kAux] = {};
     bool usedValid[1 + rs_context::kAux] = {};
-    unsigned long long builds = 0;
+    unsigned long long builds = 0, listBuilds = 0;
 };
+
+// the cuts of one rs_restir: the slots, the switches and what the last phase-A call did
+struct rs_primary_cuts {
+    rs_primary_cut slot[3];
+    bool on = true;                          // rs_restir_set_primary_cuts (RS_PRIMARY_CUTS=0: off from the start)
+    unsigned cap = 4096;                     // records a cell's cut may have (rs_debug_set_primary_cut_cap)
+    bool listsOn = true;                     // rs_restir_set_primary_leaf_lists (RS_PRIMARY_LEAF_LISTS=0: off from the start); lists need the cuts' switch too
+    unsigned listCap = 192;                  // records a tile's leaf list may have (rs_debug_set_primary_leaf_list_cap; 0: no tile takes a list)
+    int last = 0;                            // the last phase-A call's slot
+    bool lastUsed = false;                   // the last phase-A call's primary rays walked cuts
+    bool lastListsUsed = false;              // ... and its whole tiles their leaf lists
+};
+namespace rs { struct PrimaryCuts; }
+// What phase_a_impl (restir.hip) asks of primary_cuts.hip, in the order it asks: the call's rs_phase_a_inputs::cutState (call: phase-A
+// calls of this frame before this one); when the plan says 2, the cuts to hand to the launch, `st` ordered after their build, and after
+// the launch the reader's event for stream index k (0 the library stream, 1 + the internal stream); when it says 1, the build, enqueued
+// on st after every launch that still reads the arena.
+void rs_primary_cuts_init(rs_primary_cuts& c);
+int  rs_primary_cuts_begin(rs_primary_cuts& c, int call, const rs_scene* scene, const rs_camera* cam, int y0, int y1);
+int  rs_primary_cuts_view(rs_primary_cuts& c, hipStream_t st, rs::PrimaryCuts* out);
+int  rs_primary_cuts_launched(rs_primary_cuts& c, int k, hipStream_t st);
+int  rs_primary_cuts_build(rs_primary_cuts& c, const rs_scene* scene, const rs::CamParams& cp, int y0, int tilesX, int tilesY, hipStream_t st);
+void rs_primary_cuts_destroy(rs_primary_cuts& c);
 
 struct rs_restir {
     rs_context* ctx = nullptr;
-    rs_primary_cut cut[3];
-    bool cutsOn = true;                      // rs_restir_set_primary_cuts (RS_PRIMARY_CUTS=0: off from the start)
-    unsigned cutCap = 4096;                  // records a cell's cut may have (rs_debug_set_primary_cut_cap)
-    bool listsOn = true;                     // rs_restir_set_primary_leaf_lists (RS_PRIMARY_LEAF_LISTS=0: off from the start); lists need the cuts' switch too
-    unsigned listCap = 192;                  // records a tile's leaf list may have (rs_debug_set_primary_leaf_list_cap; 0: no tile takes a list)
-    int lastCutSlot = 0;                     // of the last phase-A call
-    bool lastCutUsed = false;                // the last phase-A call's primary rays walked cuts
-    bool lastListsUsed = false;              // ... and its whole tiles their leaf lists
+    rs_primary_cuts cuts;
     // The chain primary rays -> RIS -> shadow rays of a frame depends on no other frame.  Frames put theirs on kChains auxiliary
     // streams in turn, so that consecutive frames' chains overlap: on a 1/8 strip a chain lasts 0.4 ms however few rows it has.
     // A chain writes one of kSurfSets sets of surface planes, which the frame's temporal / spatial passes read afterwards; with as

@@ -21,14 +21,14 @@ import types
 import numpy as np
 import pytest
 
-from oracle import binding as ob
 from restir_amd import scenes
 from restir_amd.ctypes_structs import LAMBERTIAN, LIGHT, make_materials
 from tests import extreme_cases as xc
 from tests import geometric_cases as gc
-from tests import part_transforms as pt
-from tests.common import EmissionEdits, HipRenderer, OracleRenderer, bits_equal, get_scene, hip_scene, oracle_scene
-from tests.geometry_edits import geometry_edit
+from tests.common import EmissionEdits, hip_scene, oracle_scene
+from tests.primary_cuts import (TURNED, Side, fast_form as _fast_form, frames_of as _frames, move_camera as _move_camera,
+                                move_one_triangle as _move_one_triangle, sides as _sides, small as _small, three_way as _three_way,
+                                turn_a_part as _turn_a_part, used_after_build as _used_after_build, view as _view)
 from tests.scene_edits import assert_same
 
 pytestmark = pytest.mark.gpu
@@ -38,120 +38,6 @@ pytestmark = pytest.mark.gpu
 def _libm():
     with xc.correctly_rounded_libm():                # the oracle's cos / sin as the device evaluates them: every bit must agree
         yield
-
-
-# ---- one side of a comparison: frames over rows [y0, y1) ------------------------------------------------------------------------------
-SCALE = {"cornell": 0.45, "sponza:0.03": 0.25}
-
-
-def _fast_form(sd):
-    """scene.hip far_skip_allowed: the largest product of a triangle's two edge extents is at most 1."""
-    v = sd.vertices.reshape(-1, 3, 3)
-    return float((np.abs(v[:, 1] - v[:, 0]).max(1) * np.abs(v[:, 2] - v[:, 0]).max(1)).max()) <= 1.0
-
-
-def _small(name):
-    sd = get_scene(name)
-    gc._affine(sd, scale=(SCALE[name],) * 3)
-    assert _fast_form(sd)
-    return sd
-
-
-# The Sponza-class scene seen at an angle through a narrow lens: no direction component changes sign inside the frame and one traversal
-# order covers nearly all of it, so most blocks take a cut (its own camera looks along -z: two thirds of the blocks straddle a sign
-# change or an order change and keep the tree)
-TURNED = dict(rotation=(-65.0, -15.0, 0.0), fov_y=12.0)
-
-
-def _view(sd, **camera):
-    sd = _small(sd) if isinstance(sd, str) else sd
-    if camera:
-        sd.camera_args = dict(sd.camera_args, **camera)
-    return sd
-
-
-def _set_axes(cam, view, right, up):
-    """The camera's basis written exactly (rs_camera_update derives it from angles, whose cosines are never exactly 0)."""
-    for i in range(3):
-        cam.view[i], cam.right[i], cam.up[i] = view[i], right[i], up[i]
-    for col in range(3):                             # the inverse of an orthonormal basis is its transpose; [col * 3 + row]
-        for row, axis in enumerate((right, up, view)):
-            cam.rotationMatInv[col * 3 + row] = axis[col]
-
-
-class Side:
-    def __init__(self, hip, sd, size, rows=None, scene=None, cuts=True, cap=None, axes=None):
-        self.hip, self.W, self.H = hip, size[0], size[1]
-        self.rows = rows or (0, size[1])
-        self.r = HipRenderer(hip, sd, *size, scene=scene) if hip else OracleRenderer(sd, *size, scene=scene)
-        if axes:
-            _set_axes(self.r.cam, *axes)
-        if hip:
-            self.r.restir.set_primary_cuts(cuts)
-            if cap:
-                self.r.restir.set_primary_cut_cap(cap)
-        self.info = []
-
-    def frame(self):
-        r, (y0, y1) = self.r, self.rows
-        r.gbuf.render(r.scene, r.cam, y0, y1)
-        r.restir.phase_a(r.scene, r.cam, r.gbuf, r.looper, 3, y0, y1)
-        r.restir.phase_b(r.scene, r.cam, r.gbuf, r.image.data_ptr() if self.hip else r.image, 0, 3, y0, y1)
-        r.restir.end_frame()
-        if self.hip:
-            r.rays = r.restir.ray_count()
-            self.info.append(r.restir.primary_cut_info())
-        else:
-            r.rays = r.restir.rays
-        r.looper += 1
-        r.gbuf.update(r.cam)
-        return self.state()
-
-    def _rows(self, a):
-        return np.ascontiguousarray(a[self.rows[0] * self.W:self.rows[1] * self.W])
-
-    def state(self):
-        r = self.r
-        if self.hip:
-            planes = dict(image=r.image.cpu().numpy(), cur=r.restir.download(0), last=r.restir.download(1), temp=r.restir.download(2))
-        else:
-            planes = dict(image=r.image.copy(), cur=r.restir.reservoir.copy(), last=r.restir.last.copy(), temp=r.restir.temp.copy())
-        return dict(rays=int(r.rays), **{k: self._rows(v) for k, v in planes.items()})
-
-    def surface(self):
-        return [self._rows(a) for a in self.r.restir.surface()]
-
-
-def _used_after_build(info, frames):
-    """The one build of a still camera, and the cuts walked by exactly the frames after it."""
-    builds = [i["builds"] for i in info]
-    assert builds[-1] == 1 and builds[0] == 0, builds
-    built_in = builds.index(1)
-    assert [i["used"] for i in info] == [f > built_in for f in range(frames)], (builds, [i["used"] for i in info])
-    assert built_in + 1 < frames
-    return built_in
-
-
-def _three_way(hip, sd, size, rows=None, frames=6, overlapped=False, **kw):
-    scene_h, scene_o = hip_scene(hip, sd), oracle_scene(sd)
-    scene_h.set_sample_sequence(None); scene_o.set_sample_sequence(None)
-    on = Side(hip, sd, size, rows, scene=scene_h, **kw)
-    off = Side(hip, sd, size, rows, scene=scene_h, cuts=False, **{k: v for k, v in kw.items() if k != "cap"})
-    ref = Side(None, sd, size, rows, scene=scene_o, **{k: v for k, v in kw.items() if k != "cap"})
-    hip.set_sync(not overlapped)
-    try:
-        for f in range(frames):
-            a, b, c = on.frame(), off.frame(), ref.frame()
-            assert_same(c, a, "cuts on against the oracle, frame %d" % f)
-            assert_same(c, b, "cuts off against the oracle, frame %d" % f)
-            for k, (x, y) in enumerate(zip(on.surface(), off.surface())):
-                assert bits_equal(x, y), ("surface plane %d, frame %d" % (k, f))
-    finally:
-        hip.synchronize()
-        hip.set_sync(True)
-    assert a["image"].any() and a["rays"] > 0
-    assert all(i["builds"] == 0 and not i["used"] and i["records"] == 0 for i in off.info)
-    return on
 
 
 # ---- equality -------------------------------------------------------------------------------------------------------------------------
@@ -284,48 +170,6 @@ def test_cap_of_eight_records_overflows(hip):
 
 
 # ---- invalidation ---------------------------------------------------------------------------------------------------------------------
-SIZE = (96, 54)
-BOX = list(range(10, 22))                            # the tall box of the Cornell scene
-
-
-def _sides(hip):
-    from tests import emitter_edits as ee
-    sd = _small("cornell")
-    h, o = ee.HipSide(hip, sd, *SIZE), ee.OracleSide(hip, sd, *SIZE)
-    h.r.scene.define_parts([BOX])
-    return sd, h, o
-
-
-def _frames(h, o, n, tag):
-    out = []
-    for f in range(n):
-        h.r.frame(3); o.r.frame(3)
-        assert_same(o.direct_state(), h.direct_state(), "%s, frame %d" % (tag, f))
-        out.append(h.r.restir.primary_cut_info())
-    return out
-
-
-def _move_camera(hip, sd, h, o):
-    p = sd.camera_args["position"]
-    for s in (h, o):
-        s.r.set_camera_position((p[0] + 0.02, p[1], p[2]))
-
-
-def _move_one_triangle(hip, sd, h, o):
-    ids, v, n = geometry_edit(sd, sd.vertices, "one")
-    for s in (h, o):
-        s.set_triangles(ids, v, n)
-
-
-def _turn_a_part(hip, sd, h, o):
-    """rs_scene_set_part_transforms on the library; on the oracle the geometry edit that equals it (rs_bake_matrix of the rest pose)."""
-    v, n = pt.rest_of(sd, BOX)
-    m = pt.rotation_about(v.reshape(-1, 3).astype(np.float64).mean(0), (0, 1, 0), 3.0, (0.01, 0.005, 0.01))
-    bv, bn = hip.bake_matrix(m, v, n)
-    h.r.scene.set_part_transforms([0], [m])
-    o.set_geometry(np.asarray(BOX, np.int32), bv.reshape(-1, 3, 3), bn.reshape(-1, 3, 3))
-
-
 @pytest.mark.parametrize("change", [_move_camera, _move_one_triangle, _turn_a_part], ids=["camera", "set_triangles", "part_transform"])
 def test_a_change_drops_the_cut_and_the_next_still_frame_rebuilds(hip, change):
     sd, h, o = _sides(hip)

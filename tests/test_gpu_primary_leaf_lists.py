@@ -6,7 +6,7 @@ image, both reservoir buffers, the published copy, the ray count -- and between 
 write (rs_debug_restir_surface).  rs_debug_primary_leaf_list_info says which frame built, which frames walked lists and how many tiles
 have one; rs_debug_primary_leaf_list_missing is the containment check, ray by ray.
 
-Scenes, sizes and helpers are those of tests/test_gpu_primary_cuts.py (the Cornell box and the Sponza-class scene scaled down so that the
+Scenes, sizes and helpers are those of tests/primary_cuts.py, shared with tests/test_gpu_primary_cuts.py (the Cornell box and the Sponza-class scene scaled down so that the
 packet walk takes its fast form, the only one that walks cuts or lists), plus the Bistro-class scene scaled the same way: half of its
 leaf boxes are flat, as every one of the Cornell box's is, so accepted hits go up the ancestor chain there."""
 import numpy as np
@@ -14,14 +14,22 @@ import pytest
 
 from tests import extreme_cases as xc
 from tests import geometric_cases as gc
-from tests.common import EmissionEdits, get_scene, hip_scene, oracle_scene, bits_equal
-from tests.scene_edits import assert_same
-from tests.test_gpu_primary_cuts import (TURNED, Side, _fast_form, _move_camera, _move_one_triangle, _sides, _small, _turn_a_part,
-                                         _view)
+from tests.common import EmissionEdits, get_scene
+from tests.primary_cuts import (TURNED, Side, fast_form as _fast_form, frames_of, move_camera as _move_camera,
+                                move_one_triangle as _move_one_triangle, refit as _refit, sides as _sides, small as _small, three_way,
+                                turn_a_part as _turn_a_part, used_after_build as _lists_after_build, view as _view)
 
 pytestmark = pytest.mark.gpu
 
 DEFAULT_CAP = 192
+
+
+def _three_way(hip, sd, size, rows=None, frames=4, **kw):
+    return three_way(hip, sd, size, rows, frames, toggle="lists", **kw)
+
+
+def _list_frames(h, o, n, tag):
+    return frames_of(h, o, n, tag, lists=True)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -42,59 +50,9 @@ def _bistro():
     return sd
 
 
-class ListSide(Side):
-    """tests.test_gpu_primary_cuts.Side with the lists' switch, cap and counters (`lists`: per frame, next to `info`)."""
-
-    def __init__(self, hip, sd, size, rows=None, scene=None, lists=True, list_cap=None, axes=None):
-        super().__init__(hip, sd, size, rows, scene=scene, axes=axes)
-        if hip:
-            self.r.restir.set_primary_leaf_lists(lists)
-            if list_cap is not None:
-                self.r.restir.set_primary_leaf_list_cap(list_cap)
-        self.lists = []
-
-    def frame(self):
-        state = super().frame()
-        if self.hip:
-            self.lists.append(self.r.restir.primary_leaf_list_info())
-        return state
-
-
-def _three_way(hip, sd, size, rows=None, frames=4, overlapped=False, list_cap=None, axes=None):
-    scene_h, scene_o = hip_scene(hip, sd), oracle_scene(sd)
-    scene_h.set_sample_sequence(None); scene_o.set_sample_sequence(None)
-    on = ListSide(hip, sd, size, rows, scene=scene_h, list_cap=list_cap, axes=axes)
-    off = ListSide(hip, sd, size, rows, scene=scene_h, lists=False, axes=axes)
-    ref = ListSide(None, sd, size, rows, scene=scene_o, axes=axes)
-    hip.set_sync(not overlapped)
-    try:
-        for f in range(frames):
-            a, b, c = on.frame(), off.frame(), ref.frame()
-            assert_same(c, a, "lists on against the oracle, frame %d" % f)
-            assert_same(c, b, "lists off against the oracle, frame %d" % f)
-            for k, (x, y) in enumerate(zip(on.surface(), off.surface())):
-                assert bits_equal(x, y), ("surface plane %d, frame %d" % (k, f))
-    finally:
-        hip.synchronize()
-        hip.set_sync(True)
-    assert a["image"].any() and a["rays"] > 0
-    assert all(i["builds"] == 0 and not i["used"] and i["records"] == 0 for i in off.lists), off.lists
-    assert all(i["used"] == j["used"] for i, j in zip(on.info, off.info))                 # the cuts themselves are built and walked on both sides
-    return on
-
-
 def _tiles(size, rows=None):
     rows = rows or (0, size[1])
     return ((size[0] + 31) // 32) * 4 * ((rows[1] - rows[0] + 7) // 8)
-
-
-def _lists_after_build(lists, frames):
-    builds = [i["builds"] for i in lists]
-    assert builds[0] == 0 and builds[-1] == 1, builds
-    built_in = builds.index(1)
-    assert [i["used"] for i in lists] == [f > built_in for f in range(frames)], lists
-    assert built_in + 1 < frames
-    return built_in
 
 
 # ---- sizes and cameras ----------------------------------------------------------------------------------------------------------------
@@ -135,15 +93,7 @@ def test_a_row_of_special_case_rays_ignores_the_lists(hip):
 # ---- temporal sequence ----------------------------------------------------------------------------------------------------------------
 def test_eight_still_frames_a_move_and_still_again(hip):
     sd, h, o = _sides(hip)
-    lists = []
-
-    def frames(n, tag):
-        for f in range(n):
-            h.r.frame(3); o.r.frame(3)
-            assert_same(o.direct_state(), h.direct_state(), "%s, frame %d" % (tag, f))
-            lists.append(h.r.restir.primary_leaf_list_info())
-        return lists[-n:]
-
+    frames = lambda n, tag: _list_frames(h, o, n, tag)
     still = frames(8, "still")
     assert [i["used"] for i in still] == [False, False] + [True] * 6, still          # lists from the third frame on
     assert [i["builds"] for i in still] == [0] + [1] * 7
@@ -190,23 +140,6 @@ def test_flat_boxes_and_grazing_views(hip, name):
 
 
 # ---- edits ----------------------------------------------------------------------------------------------------------------------------
-def _list_frames(h, o, n, tag):
-    out = []
-    for f in range(n):
-        h.r.frame(3); o.r.frame(3)
-        assert_same(o.direct_state(), h.direct_state(), "%s, frame %d" % (tag, f))
-        out.append(h.r.restir.primary_leaf_list_info())
-    return out
-
-
-def _refit(hip, sd, h, o):
-    """rs_scene_set_geometry of the tall box's triangles, moved a little: the device refit."""
-    ids = np.arange(10, 22, dtype=np.int32)
-    v = sd.vertices.reshape(-1, 3, 3)[ids] + np.float32(0.004)
-    for s in (h, o):
-        s.set_geometry(ids, v)
-
-
 @pytest.mark.parametrize("change", [_move_one_triangle, _refit, _turn_a_part], ids=["set_triangles", "set_geometry", "part_transform"])
 def test_a_geometry_change_forgets_the_lists(hip, change):
     sd, h, o = _sides(hip)
@@ -241,7 +174,7 @@ def test_no_passed_leaf_is_absent_from_its_tile_s_list(hip, scene):
     """10^4 rays: every pixel corner of the frame's tiles with jitters of exactly 0 and 1, the rest random (pixel, jitter)."""
     sd = {"sponza": lambda: _view("sponza:0.03", **TURNED), "bistro": _bistro, "cornell": lambda: _small("cornell")}[scene]()
     size = (96, 54)
-    side = ListSide(hip, sd, size)
+    side = Side(hip, sd, size, lists=True)
     for _ in range(3):
         side.frame()
     info = side.lists[-1]
