@@ -334,8 +334,12 @@ int  rs_scene_set_triangles(rs_scene* scene, int count, const int* primIds, cons
  * Refused with RS_ERR_INVALID_ARGUMENT, the scene unchanged: everything rs_scene_set_triangles refuses except emitters, and an edit that
  * leaves the light sampler without a finite, positive total power.  RS_ERR_UNSUPPORTED while the library stream is being captured.
  * Temporal reservoirs keep the direction, distance and radiance they were drawn with for up to the M clamp's 20 frames, as in the
- * reference; rs_restir_reset drops them.  Adding or removing emitters still takes a new scene. */
+ * reference; rs_restir_reset drops them, and rs_restir_set_light_retargeting evaluates the samples of the moved lamps again instead.
+ * Adding or removing emitters still takes a new scene. */
 int  rs_scene_set_geometry(rs_scene* scene, int count, const int* primIds, const float* vertices, const float* normals);
+/* How many accepted geometry edits (rs_scene_set_geometry, rs_scene_set_part_transforms) have named an emitter so far.  Host only: no
+ * wait, no launch.  An edit that names no emitter does not count.  (Per light: RS_TABLE_LIGHT_MOVED of rs_debug_scene_table.) */
+int  rs_scene_light_moves(const rs_scene* scene, unsigned long long* moves);
 /* Rigid parts: sets of triangles that each move by one matrix (a door, a prop, a swinging lamp), with a rest pose the scene keeps on the
  * host and on the device.  (The reference has no moving geometry: there is no reference line to cite.)
  * rs_scene_define_parts: partFirst holds numParts + 1 offsets into primIds (0 first, non-decreasing; an empty part is allowed), primIds
@@ -461,6 +465,8 @@ int  rs_refit_boxes(int numPrims, const float* vertices, int bvhSize, const int*
 #define RS_TABLE_ORD_TRIS  8   /* triangle records [3 * numPrims] */
 #define RS_TABLE_EMI_NODES 9   /* 16-byte grid-box records of the emissive tree and its end record */
 #define RS_TABLE_EMI_TRIS  10  /* triangle records, one per emissive triangle */
+/* (tables of the scene's edit history, which a scene built afresh from the edited arrays does not share, are numbered from 32) */
+#define RS_TABLE_LIGHT_MOVED 32 /* uint32 per light-sampler entry: rs_scene_light_moves at the last edit that named the light's primitive, 0 = never; size 0 before the first edit that names an emitter */
 int  rs_debug_scene_table(const rs_scene* scene, int which, void* host, size_t capacity, size_t* bytes);
 /* The 16-bit grid of the scene's grid-box trees: plane q of axis k lies at base[k] + q * scale[k]; the margin boxes are cleared by; the
  * box the grid was laid over (a moved vertex must stay inside it); the shadow tree's record count and the byte stride of the ordered
@@ -726,6 +732,9 @@ int  rs_debug_plan_primary_cut_slot(int on, int capturing, rs_primary_cut_slot* 
  * pixels): 4 floats { hit position, tag bits }, 4 floats { shading normal, metallic }, 2 words { sampler state, tag }.  Waits for the
  * device. */
 int  rs_debug_restir_surface(rs_restir* r, float* posTag, float* normal, unsigned* rngTag);
+/* ... and the plane next to them: 4 floats { wo, roughness }, written only for pixels of a MetallicWorkflow material (the others hold
+ * whatever the set held before). */
+int  rs_debug_restir_surface_wo(rs_restir* r, float* wo4);
 #define RS_SPATIAL_HALO_ROWS 5           /* taps reach y-4..y+5 (src/restir.cu:49-56) */
 /* bytes needed for `rows` rows of published reservoirs */
 size_t rs_restir_halo_bytes(const rs_restir* r, int rows);
@@ -762,6 +771,35 @@ int  rs_restir_download_light_ids(const rs_restir* r, int which, int* host);
 size_t rs_restir_light_rows_bytes(const rs_restir* r, int rows);
 int  rs_restir_light_rows_pack(const rs_restir* r, int which, int y0, int rows, void* devBuffer);
 int  rs_restir_light_rows_unpack(rs_restir* r, int which, int y0, int rows, const void* devBuffer);
+/* Light retargeting: temporal reuse follows lamps that rs_scene_set_geometry / rs_scene_set_part_transforms moved.  On top of light
+ * tracking (switching it on switches tracking on; rs_restir_set_light_tracking(r, 0) switches both off).  Every reservoir's sample
+ * carries a record { light-sampler index, the barycentric pair (u, v) it was drawn at, the solid-angle pdf it last had }; light = -1:
+ * none or unknown.  In the temporal merge of a shaded pixel whose history slot passes the reference's neighbour test, a candidate of a
+ * light that an edit has named since this rs_restir's previous frame -- not the environment map's entry, not an unknown light, not W = 0
+ * -- is evaluated again from the pixel's own surface on the current light records before it is merged:
+ *   (Li', wi', dist', pdf') = the light's sample at (u, v) seen from the pixel; W = 0 if it faces away now or pdf' is not finite and positive;
+ *   W = (W * (pNew / pOld)) * (pdfOld / pdf'), p = luminance(Li * BSDF(wi) * cos) of the old and the new sample (0 unless pOld, pdfOld
+ *   are finite and positive); Li, wi, dist and the record's pdf become the new ones; M stays; a sample left with W != 0 walks its shadow
+ *   segment (one ray in rs_restir_ray_count) and is cleared when occluded.
+ * Every other candidate takes today's path, the emission rescale of tracking included.  The history buffers are not written.  Slots of
+ * pixels that shade nothing this frame, and the published copies they keep, have no surface to evaluate from: they are treated as
+ * tracking treats them (emission rescale only).  Moved occluders do not trigger anything.
+ * With no emitter moved since the previous frame nothing extra is launched, and the results equal tracking's bit for bit.
+ * Stream-ordered like tracking; a failed allocation leaves it off with nothing changed.  Switching on marks every record AND every tracked light id
+ * unknown (ids that tracking carried so far have no record to go with), and edits made before the switch are taken as seen;
+ * rs_restir_upload and a change of scene mark records unknown.  Memory: 164 B/px.  While it is on, rs_restir_light_rows_pack / _unpack,
+ * rs_strips_frame and rs_strips_exchange_history are refused with RS_ERR_UNSUPPORTED: their 4 B/px do not carry the records. */
+int  rs_restir_set_light_retargeting(rs_restir* r, int enable);
+int  rs_restir_get_light_retargeting(const rs_restir* r, int* enabled);
+typedef struct rs_light_sample { int light; float u, v, pdf; } rs_light_sample;
+/* The record of every reservoir's sample, width x height; which as rs_restir_download_light_ids.  All { -1, 0, 0, 0 } while retargeting
+ * is off.  Waits for the library stream. */
+int  rs_restir_download_light_samples(const rs_restir* r, int which, rs_light_sample* host);
+/* Test hook: what the retargeting kernel did in the last ended frame: out[0] samples evaluated again, out[1] shadow segments walked,
+ * out[2] samples left with W = 0.  All 0 when the frame launched no such kernel (no lamp moved since the frame before). */
+int  rs_debug_restir_retarget(rs_restir* r, unsigned long long out[3]);
+/* ... and whether that frame launched the kernel at all: 1 or 0.  Host only. */
+int  rs_debug_restir_retarget_launched(rs_restir* r, int* launched);
 /* BVH walks (intersect + testOcclusion calls) performed by the last rs_restir_direct / phase_a,
  * for the Mrays/s metric. Synchronises. */
 int  rs_restir_ray_count(rs_restir* r, unsigned long long* rays);

@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from .ctypes_structs import Camera, Material, Reservoir, MATERIAL_DTYPE, RESERVOIR_DTYPE, INDIRECT_RESERVOIR_DTYPE, copy_camera
+from .ctypes_structs import Camera, Material, Reservoir, MATERIAL_DTYPE, RESERVOIR_DTYPE, INDIRECT_RESERVOIR_DTYPE, LIGHT_SAMPLE_DTYPE, copy_camera
 from .ctypes_structs import GeometryEditLights, GeometryEditPlan, GeometryEditView
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -152,7 +152,7 @@ EXPORTS = [
     "rs_gbuffer_create", "rs_gbuffer_destroy", "rs_gbuffer_render", "rs_gbuffer_render_rows", "rs_gbuffer_update",
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
-    "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
+    "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_set_light_retargeting", "rs_restir_get_light_retargeting", "rs_restir_download_light_samples", "rs_debug_restir_retarget", "rs_debug_restir_retarget_launched", "rs_debug_restir_surface_wo", "rs_scene_light_moves", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
     "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_restir_set_primary_leaf_lists", "rs_debug_set_primary_leaf_list_cap", "rs_debug_primary_leaf_list_info", "rs_debug_primary_leaf_list_missing", "rs_debug_plan_primary_leaf_list", "rs_debug_plan_primary_cut", "rs_debug_plan_primary_cut_slot", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
     "rs_path_trace", "rs_path_trace_indirect", "rs_restir_indirect", "rs_restir_download_indirect",
     "rs_svgf_create", "rs_svgf_destroy", "rs_svgf_filter", "rs_svgf_next_frame", "rs_svgf_get_view",
@@ -228,6 +228,14 @@ def lib():
     L.rs_debug_grid_box.argtypes = [vp, vp, vp, vp, C.c_double, vp, C.POINTER(ci)]
     L.rs_restir_set_light_tracking.argtypes = [vp, ci]
     L.rs_restir_download_light_ids.argtypes = [vp, ci, vp]
+    if hasattr(L, "rs_restir_set_light_retargeting"):     # (an A/B build from before retargeting, RESTIR_HIP_LIB: tools/bench_light_retarget.py)
+        L.rs_restir_set_light_retargeting.argtypes = [vp, ci]
+        L.rs_restir_get_light_retargeting.argtypes = [vp, C.POINTER(ci)]
+        L.rs_restir_download_light_samples.argtypes = [vp, ci, vp]
+        L.rs_debug_restir_retarget.argtypes = [vp, C.POINTER(C.c_ulonglong * 3)]
+        L.rs_debug_restir_retarget_launched.argtypes = [vp, C.POINTER(ci)]
+        L.rs_debug_restir_surface_wo.argtypes = [vp, vp]
+        L.rs_scene_light_moves.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.rs_restir_light_rows_bytes.argtypes = [vp, ci]
     L.rs_restir_light_rows_bytes.restype = C.c_size_t
     L.rs_restir_light_rows_pack.argtypes = [vp, ci, ci, ci, vp]
@@ -622,6 +630,8 @@ SCENE_TABLES = {
     "nodesAll": (3, NODE_DTYPE), "occNodes": (4, GRID_DTYPE), "occChain": (5, NODE_DTYPE), "occTris": (6, TRI_DTYPE),
     "ordNodes": (7, GRID_DTYPE), "ordTris": (8, TRI_DTYPE), "emiNodes": (9, GRID_DTYPE), "emiTris": (10, TRI_DTYPE),
 }
+# ... and the tables that record the scene's history of edits, which a scene built afresh from the edited arrays does not share
+HISTORY_TABLES = {"lightMoved": (32, np.dtype(np.uint32))}
 
 
 def ordered_bvh_host_check(boxes, nodes):
@@ -865,6 +875,12 @@ class Scene:
                 raise ValueError("define_parts: three rest vertices and three rest normals per listed primitive")
         check(lib().rs_scene_define_parts(self.handle, len(parts), _p(first), _p(ids), None if v is None else _p(v), None if n is None else _p(n)))
 
+    def light_moves(self):
+        """rs_scene_light_moves: accepted geometry edits that named an emitter so far (host only)."""
+        n = C.c_ulonglong(0)
+        check(lib().rs_scene_light_moves(self.handle, C.byref(n)))
+        return int(n.value)
+
     def set_part_transforms(self, part_ids, matrices):
         """rs_scene_set_part_transforms: one (4, 4) float32 matrix, [column][row], per entry of `part_ids`; does what set_geometry does
         with the parts' rest pose baked by those matrices, the baking done on the device (one small record per part crosses the bus)."""
@@ -921,7 +937,7 @@ class Scene:
     def debug_table(self, name):
         """rs_debug_scene_table (test hook): a copy of one device array of the scene, after everything enqueued so far, as a NumPy array of
         its records (SCENE_TABLES; pads and grid-box dwords as uint32 so that they compare bit for bit); length 0 when the scene has none."""
-        which, dtype = SCENE_TABLES[name]
+        which, dtype = SCENE_TABLES[name] if name in SCENE_TABLES else HISTORY_TABLES[name]
         size = C.c_size_t(0)
         check(lib().rs_debug_scene_table(self.handle, which, None, 0, C.byref(size)))
         raw = np.zeros(size.value, np.uint8)
@@ -1208,6 +1224,12 @@ class ReSTIR:
         check(lib().rs_debug_restir_surface(self.handle, _p(a), _p(b), _p(c)))
         return a, b, c
 
+    def surface_wo(self):
+        """rs_debug_restir_surface_wo: the (n, 4) f32 plane { wo, roughness } beside surface()'s; only MetallicWorkflow pixels wrote it."""
+        out = np.zeros((self.width * self.height, 4), np.float32)
+        check(lib().rs_debug_restir_surface_wo(self.handle, _p(out)))
+        return out
+
     def launch_choice(self):
         """0 two launches, 1 GBuffer::render walked together with the primary rays, -1 still measuring, -2 nothing to choose."""
         c = C.c_int(-1)
@@ -1250,6 +1272,34 @@ class ReSTIR:
         out = np.zeros(self.width * self.height, np.int32)
         check(lib().rs_restir_download_light_ids(self.handle, which, _p(out)))
         return out
+
+    def set_light_retargeting(self, on=True):
+        """rs_restir_set_light_retargeting: temporal candidates of lamps moved since the previous frame are evaluated again (switches
+        tracking on too; set_light_tracking(False) switches both off)."""
+        check(lib().rs_restir_set_light_retargeting(self.handle, 1 if on else 0))
+
+    def get_light_retargeting(self):
+        on = C.c_int(0)
+        check(lib().rs_restir_get_light_retargeting(self.handle, C.byref(on)))
+        return bool(on.value)
+
+    def download_light_samples(self, which):
+        """rs_restir_download_light_samples: LIGHT_SAMPLE_DTYPE record of every reservoir's sample (which as download); light -1 = none / unknown."""
+        out = np.zeros(self.width * self.height, LIGHT_SAMPLE_DTYPE)
+        check(lib().rs_restir_download_light_samples(self.handle, which, _p(out)))
+        return out
+
+    def retarget_stats(self):
+        """rs_debug_restir_retarget: (samples evaluated again, shadow segments walked, samples left with W = 0) of the last ended frame."""
+        out = (C.c_ulonglong * 3)()
+        check(lib().rs_debug_restir_retarget(self.handle, C.byref(out)))
+        return tuple(int(x) for x in out)
+
+    def retarget_launched(self):
+        """rs_debug_restir_retarget_launched: did the last ended frame launch the retargeting kernel?"""
+        on = C.c_int(0)
+        check(lib().rs_debug_restir_retarget_launched(self.handle, C.byref(on)))
+        return bool(on.value)
 
     def light_rows_bytes(self, rows):
         return int(lib().rs_restir_light_rows_bytes(self.handle, rows))

@@ -222,8 +222,11 @@ __device__ __forceinline__ float ris_candidate(const DevScene& s, AliasPtr alias
 // k_ris, reading the scene's table, would pay for per candidate what it saves: it scales its second draw as before.  The Sobol sampler's
 // draws come as they are (scale 1).
 template <bool SOBOL> constexpr float kRisRawScale = SOBOL ? 1.f : kRngRawScale;
-template <bool ENV, bool SOBOL, bool TRACK, bool SCALED_ALIAS, typename AliasPtr, typename LightPtr>
-__device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& sp, AliasPtr alias, LightPtr lights, int index, int looper, int* candId) {
+// REC (rs_restir_set_light_retargeting, with TRACK): the winner's record { light, u, v, pdf } goes to candRec -- the pair is the one the loop
+// carries already; the pdf is evaluated again after the loop with the pair (light_sample_at), or carried where the loop carries the sample (ENV)
+template <bool ENV, bool SOBOL, bool TRACK, bool SCALED_ALIAS, typename AliasPtr, typename LightPtr, bool REC = false>
+__device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& sp, AliasPtr alias, LightPtr lights, int index, int looper, int* candId,
+                                          float4* candRec = nullptr) {
     RS_SETPRIO(RS_PRIO_RIS);
     const float4 pm = sp.posMat[index];
     const int mk = __float_as_int(pm.w);
@@ -242,7 +245,7 @@ __device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& s
     // Without an environment map every winner is a triangle-light sample: the loop carries its light and barycentric pair (three
     // conditional moves per candidate instead of seven) and the sample is evaluated again after the loop (light_sample_again).
     int selId = -1;
-    float selU = 0.f, selV = 0.f;
+    float selU = 0.f, selV = 0.f, selPdf = 0.f;
     // The candidate is evaluated with the short forms of rs_exact.h unguarded, and the wave is asked once whether every operand that a
     // lane used was in their range (ExactSpeculative); if not, the candidate is evaluated again from the same draws with the compiler's
     // operators.  Either way the bits are the IEEE results.
@@ -288,7 +291,7 @@ __device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& s
             float u = uniform();
             wsum += weight;                                    // Reservoir::update (restir.h:38-44)
             if (u * wsum < weight) {
-                if (ENV) { selLi = c.Li; selWi = c.wi; selDist = c.dist; if (TRACK) selId = c.id; }
+                if (ENV) { selLi = c.Li; selWi = c.wi; selDist = c.dist; if (TRACK) selId = c.id; if (REC) { selU = c.bu; selV = c.bv; selPdf = c.pdf; } }
                 else { selId = c.id; selU = c.bu; selV = c.bv; }
             }
         }
@@ -297,32 +300,39 @@ __device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& s
     if (s.numLights <= 0) { for (int i = 0; i < kReservoirSize; i++) { rng.uniform4(); rng.uniform(); } }     // no candidate has a weight: the draws alone
     else if (__all(m.type == 0)) loop(std::true_type{});
     else loop(std::false_type{});
-    if (!ENV && selId >= 0) light_sample_again(lights, selId, selU, selV, pos, selLi, selWi, selDist);
+    if (!ENV && !REC && selId >= 0) light_sample_again(lights, selId, selU, selV, pos, selLi, selWi, selDist);
+    if (!ENV && REC && selId >= 0) light_sample_at(lights, selId, selU, selV, pos, selLi, selWi, selDist, selPdf);      // (a winner faces pos: the same bits)
     sp.candLi[index] = make_float4(selLi.x, selLi.y, selLi.z, selDist);
     sp.candWi[index] = make_float4(selWi.x, selWi.y, selWi.z, wsum);
     reinterpret_cast<unsigned*>(sp.rngMat + index)[0] = rng.word();
     if (TRACK) candId[index] = selId;
+    if (REC) candRec[index] = make_float4(__int_as_float(selId), selU, selV, selPdf);
 }
 
-template <bool ENV, bool SOBOL, bool TRACK>
-__device__ __forceinline__ void ris_rows(const DevScene& s, const SurfPlanes& sp, int width, int y0, int y1, int looper, int* candId) {
+template <bool ENV, bool SOBOL, bool TRACK, bool REC = false>
+__device__ __forceinline__ void ris_rows(const DevScene& s, const SurfPlanes& sp, int width, int y0, int y1, int looper, int* candId, float4* candRec = nullptr) {
     const int n0 = y0 * width, n1 = y1 * width;
     const int index = n0 + blockIdx.x * blockDim.x + threadIdx.x;
     if (index >= n1) return;
-    ris_pixel<ENV, SOBOL, TRACK, false, const AliasRec*, const LightRec*>(s, sp, s.alias, s.lights, index, looper, candId);
+    ris_pixel<ENV, SOBOL, TRACK, false, const AliasRec*, const LightRec*, REC>(s, sp, s.alias, s.lights, index, looper, candId, candRec);
 }
 
 template <bool ENV, bool SOBOL, bool TRACK>
 __global__ void __launch_bounds__(256) k_ris(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
     ris_rows<ENV, SOBOL, TRACK>(s, sp, width, y0, y1, looper, candId);
 }
+// ... with the winners' records (retargeting): a form of its own, so that the forms above keep their code
+template <bool ENV, bool SOBOL>
+__global__ void __launch_bounds__(256) k_ris_rec(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId, float4* candRec) {
+    ris_rows<ENV, SOBOL, true, true>(s, sp, width, y0, y1, looper, candId, candRec);
+}
 
 // amdgpu_waves_per_eu(8): two 1 024-thread blocks per CU are 8 waves per SIMD, i.e. 64 registers at most, and nothing but this attribute
 // tells the register allocator so (the block size alone allows 128).  Left to itself the single-guard loop takes 67 and the kernel
 // loses half its waves.  The kernel now sits AT 64: a value added to the loop shows as scratch, not as a 65th register -- check the
 // scratch column of tools/kernel_resources.sh restir.hip after every change here (0 bytes today).
-template <bool SOBOL, bool TRACK>
-__global__ void __launch_bounds__(kRisThreads) __attribute__((amdgpu_waves_per_eu(8))) k_ris_lds(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
+template <bool SOBOL, bool TRACK, bool REC = false>
+__device__ __forceinline__ void ris_lds_block(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId, float4* candRec = nullptr) {
     // The copy is laid out by quarter: the lanes of a wave read the same quarter of 64 random records, and in record order those
     // 16 bytes lie in 2 of the 8 four-bank groups whatever the light (a 4-fold bank conflict; SQ_LDS_BANK_CONFLICT was 80 % of the
     // LDS cycles); by quarter, light i's lies in group i mod 8.
@@ -354,7 +364,16 @@ __global__ void __launch_bounds__(kRisThreads) __attribute__((amdgpu_waves_per_e
     const int n0 = y0 * width, n1 = y1 * width;
     const int index = n0 + blockIdx.x * kRisThreads + threadIdx.x;
     if (index >= n1) return;
-    ris_pixel<false, SOBOL, TRACK, true, const AliasRec*, LightQuarters<kRisLdsLights>>(s, sp, sAlias, LightQuarters<kRisLdsLights>{ sQuarters }, index, looper, candId);
+    ris_pixel<false, SOBOL, TRACK, true, const AliasRec*, LightQuarters<kRisLdsLights>, REC>(s, sp, sAlias, LightQuarters<kRisLdsLights>{ sQuarters }, index, looper, candId, candRec);
+}
+template <bool SOBOL, bool TRACK>
+__global__ void __launch_bounds__(kRisThreads) __attribute__((amdgpu_waves_per_eu(8))) k_ris_lds(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
+    ris_lds_block<SOBOL, TRACK>(s, sp, width, y0, y1, looper, candId);
+}
+// (the retargeting form: the record's pdf lives only after the loop, the loop's registers are those of the tracked form)
+template <bool SOBOL>
+__global__ void __launch_bounds__(kRisThreads) __attribute__((amdgpu_waves_per_eu(8))) k_ris_lds_rec(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId, float4* candRec) {
+    ris_lds_block<SOBOL, true, true>(s, sp, width, y0, y1, looper, candId, candRec);
 }
 
 // More lights than the LDS copy of the whole table holds (config 5: 10 240): the alias records alone (8 B per light) still fit -- one
@@ -369,6 +388,16 @@ __global__ void __launch_bounds__(kRisThreads) k_ris_alias_lds(DevScene s, SurfP
     const int index = n0 + blockIdx.x * kRisThreads + threadIdx.x;
     if (index >= n1) return;
     ris_pixel<false, SOBOL, TRACK, true, const AliasRec*, const LightRec*>(s, sp, sAliasDyn, s.lights, index, looper, candId);
+}
+template <bool SOBOL>
+__global__ void __launch_bounds__(kRisThreads) k_ris_alias_lds_rec(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId, float4* candRec) {
+    extern __shared__ AliasRec sAliasDyn[];
+    for (int i = threadIdx.x; i < s.numLights; i += kRisThreads) { AliasRec al = s.alias[i]; al.prob *= kRisRawScale<SOBOL>; sAliasDyn[i] = al; }
+    __syncthreads();
+    const int n0 = y0 * width, n1 = y1 * width;
+    const int index = n0 + blockIdx.x * kRisThreads + threadIdx.x;
+    if (index >= n1) return;
+    ris_pixel<false, SOBOL, true, true, const AliasRec*, const LightRec*, true>(s, sp, sAliasDyn, s.lights, index, looper, candId, candRec);
 }
 
 // ---- phase A.3: shadow ray, temporal merge, publish -------------------------------------------------
@@ -436,9 +465,19 @@ struct LightIds {
 // with luminance(Li) (the DI path evaluates the BSDF with baseColor 1, restir.cu:141), so W takes the ratio of the luminances and Li the
 // light's current radiance.  Not for an unknown light (-1), the environment map's entry or W = 0.  The published copy of a pixel that shades
 // nothing this frame keeps an older frame's reservoir (Q1) and is still a spatial tap: it is re-evaluated in place the same way.
-template <bool SOBOL, bool TRACK>
-__global__ void __launch_bounds__(256) k_temporal(SurfPlanes sp, GBufView g, ResvPlanes last, ResvPlanes cur, TempPlanes temp, const uint32_t* sampleSeq, int looper,
-                                                  int first, int reuse, int n0, int n1, unsigned long long* rayWork, unsigned long long* rayDone, LightIds ids) {
+// Retargeting (rs_restir_set_light_retargeting): the records { light, u, v, pdf } of the RIS winners (cand), of the reservoirs the merge
+// reads (last) and publishes (cur, temp), and what k_retarget left for this frame: flag[i] != 0 -- pixel i's temporal candidate is
+// { rtLi | rtWi (w = W) | rtRec }[i] instead of last[motion[i]]; M stays the slot's.  flag null: k_retarget was not launched.
+struct LightRecs {
+    const float4* cand; const float4* last; float4* cur; float4* temp;
+    const float4* rtLi; const float4* rtWi; const float4* rtRec; const int* flag;
+};
+
+// RETARGET (with TRACK): the merge carries the records, and takes the flagged candidates from k_retarget's planes
+template <bool SOBOL, bool TRACK, bool RETARGET>
+__device__ __forceinline__ void temporal_body(const SurfPlanes& sp, const GBufView& g, const ResvPlanes& last, const ResvPlanes& cur, const TempPlanes& temp, const uint32_t* sampleSeq, int looper,
+                                              int first, int reuse, int n0, int n1, unsigned long long* rayWork, unsigned long long* rayDone, const LightIds& ids,
+                                              const LightRecs& recs) {
     RS_SETPRIO(RS_PRIO_STREAM);
     // this call's BVH-walk counters are complete (the launch is ordered after the chain that counted): publish them and leave the
     // working slot zero for its next user, so that the chain itself needs no clearing launch
@@ -481,6 +520,8 @@ __global__ void __launch_bounds__(256) k_temporal(SurfPlanes sp, GBufView g, Res
     r.Li = mk3(cl.x, cl.y, cl.z); r.wi = mk3(cw.x, cw.y, cw.z); r.dist = cl.w;
     r.M = kReservoirSize; r.W = cw.w;                             // 0 if the shadow ray was blocked (k_shadow)
     int id = TRACK ? ld_stream(ids.cand + index) : -1;
+    float4 rec = make_float4(__int_as_float(-1), 0.f, 0.f, 0.f);
+    if (RETARGET) rec = ld_stream(recs.cand + index);
 
     if (!first && (reuse & 1)) {                                  // findTemporalNeighbor, restir.cu:20-45 (gi.hip write_sample: the same test with plain loads)
         const int primId = gid;
@@ -497,7 +538,18 @@ __global__ void __launch_bounds__(256) k_temporal(SurfPlanes sp, GBufView g, Res
         Resv t;
         t.Li = splat(0.f); t.wi = splat(0.f); t.dist = 0.f; t.M = 0; t.W = 0.f;
         int tid = -1;
-        if (!diff) {
+        float4 trec = make_float4(__int_as_float(-1), 0.f, 0.f, 0.f);
+        bool retargeted = false;
+        if (RETARGET) retargeted = !diff && recs.flag != nullptr && ld_stream(recs.flag + index) != 0;
+        if (RETARGET && retargeted) {
+            const float4 a = ld_stream(recs.rtLi + index), b = ld_stream(recs.rtWi + index);
+            t.Li = mk3(a.x, a.y, a.z); t.dist = a.w; t.wi = mk3(b.x, b.y, b.z);
+            t.W = b.w; t.M = ld_stream(last.m + lastIdx);
+            trec = ld_stream(recs.rtRec + index);
+            tid = __float_as_int(trec.x);
+        }
+        else if (!diff) {
+            if (RETARGET) trec = ld_stream(recs.last + lastIdx);
             const float4 a = ld_stream(last.li + lastIdx), b = ld_stream(last.wi + lastIdx);
             t.Li = mk3(a.x, a.y, a.z); t.dist = a.w; t.wi = mk3(b.x, b.y, b.z);
             t.W = ld_stream(last.w + lastIdx); t.M = ld_stream(last.m + lastIdx);
@@ -523,19 +575,119 @@ __global__ void __launch_bounds__(256) k_temporal(SurfPlanes sp, GBufView g, Res
             }
             r.W += t.W;
             r.M += t.M;
-            if (u * r.W < t.W) { r.Li = t.Li; r.wi = t.wi; r.dist = t.dist; if (TRACK) id = tid; }
+            if (u * r.W < t.W) { r.Li = t.Li; r.wi = t.wi; r.dist = t.dist; if (TRACK) id = tid; if (RETARGET) rec = trec; }
         }
     }
     // checkValidity (restir.h:55-59); the temp copy and the stored copy are the same value
-    if (resv_invalid(r.W)) { r.W = 0.f; r.M = 0; if (TRACK) id = -1; }
+    if (resv_invalid(r.W)) { r.W = 0.f; r.M = 0; if (TRACK) id = -1; if (RETARGET) rec = make_float4(__int_as_float(-1), 0.f, 0.f, 0.f); }
     if (TRACK) __builtin_nontemporal_store(id, ids.cur + index);
+    if (RETARGET) st_stream(recs.cur + index, rec.x, rec.y, rec.z, rec.w);
     if (reuse & 2) {
         if (TRACK) ids.temp[index] = id;
+        if (RETARGET) recs.temp[index] = rec;
         temp.li[index] = make_float4(r.Li.x, r.Li.y, r.Li.z, r.dist);
         temp.wi[index] = make_float4(r.wi.x, r.wi.y, r.wi.z, 0.f);
         temp.tap[index] = make_float4(r.W, __int_as_float(r.M), __int_as_float(gid), gdepth);
     }
     resv_store(cur, index, r);
+}
+
+template <bool SOBOL, bool TRACK>
+__global__ void __launch_bounds__(256) k_temporal(SurfPlanes sp, GBufView g, ResvPlanes last, ResvPlanes cur, TempPlanes temp, const uint32_t* sampleSeq, int looper,
+                                                  int first, int reuse, int n0, int n1, unsigned long long* rayWork, unsigned long long* rayDone, LightIds ids) {
+    temporal_body<SOBOL, TRACK, false>(sp, g, last, cur, temp, sampleSeq, looper, first, reuse, n0, n1, rayWork, rayDone, ids, LightRecs{});
+}
+template <bool SOBOL>
+__global__ void __launch_bounds__(256) k_temporal_retarget(SurfPlanes sp, GBufView g, ResvPlanes last, ResvPlanes cur, TempPlanes temp, const uint32_t* sampleSeq, int looper,
+                                                           int first, int reuse, int n0, int n1, unsigned long long* rayWork, unsigned long long* rayDone, LightIds ids, LightRecs recs) {
+    temporal_body<SOBOL, true, true>(sp, g, last, cur, temp, sampleSeq, looper, first, reuse, n0, n1, rayWork, rayDone, ids, recs);
+}
+
+// Retargeting: the temporal candidates whose lamp has moved since the previous frame, evaluated again on this frame's light records
+// before the merge.  One lane per pixel, tiles and walk as k_shadow.  For a shaded pixel whose history slot j = motion[i] passes
+// findTemporalNeighbor and holds a sample of a light with moved[light] > seenMoves (not the environment's entry, not W = 0):
+//   1  (Li', wi', dist', pdf') of the light at the sample's (u, v) seen from the pixel's position; a sample that now faces away, or a pdf'
+//      that is not finite and positive: W = 0
+//   2  pOld, pNew: luminance(Li * bsdf(wi) * sat_dot(n, wi)) of the old and the new sample on the pixel's surface (ris_candidate's g)
+//   3  W = (W * (pNew / pOld)) * (pdfOld / pdf') when pOld and pdfOld are positive and finite, else 0
+//   5  a sample left with W != 0 walks its shadow segment, pos -> pos + wi' * dist', and is cleared when occluded
+// The candidate goes to planes of this kernel's own; the history buffers are not written (with a moving camera two pixels read one slot).
+// Registers: everything but W and the index is stored before the walk, which then carries what k_shadow's carries.
+struct RetargetOut { float4* li; float4* wi; float4* rec; int* flag; };
+__global__ void __launch_bounds__(256, RS_WALK_WAVES) k_retarget(DevScene s, SurfPlanes sp, GBufView g, ResvPlanes last, const float4* recLast, const uint32_t* moved,
+                                                                 uint32_t seenMoves, int envId, RetargetOut out, int width, int y0, int y1, int tilesX,
+                                                                 unsigned long long* rayCount, unsigned long long* stats) {
+    RS_SETPRIO(RS_PRIO_WALK);
+    int x, y;
+    const int lane = pixel_of_lane(tilesX, y0, x, y);
+    const bool inside = x < width && y < y1;
+    const int index = inside ? y * width + x : 0;
+    const float4 pm = inside ? sp.posMat[index] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const int mk = __float_as_int(pm.w);
+    const bool shaded = inside && mk_kind(mk) == kKindShaded;
+    const f3 pos = mk3(pm.x, pm.y, pm.z);
+    bool take = false;
+    int lastIdx = 0;
+    if (shaded) {                                               // findTemporalNeighbor, as k_temporal
+        const int primId = g.primId[index];
+        lastIdx = g.motion[index];
+        bool diff = false;
+        if (lastIdx < 0) diff = true;
+        else if (primId <= kNullPrim) diff = true;
+        else if (g.lastPrimId[lastIdx] != primId) diff = true;
+        else {
+            const f3 n = ld3(g.normal + (size_t)index * 3), ln = ld3(g.lastNormal + (size_t)lastIdx * 3);
+            const float depth = g.depth[index], pdepth = g.lastDepth[lastIdx];
+            if (abs_dot(n, ln) < .9f || gabs(pdepth - depth) > depth * .1f) diff = true;
+        }
+        take = !diff;
+    }
+    float W = 0.f;
+    f3 wi = splat(0.f);
+    float dist = 0.f;
+    if (take) {
+        const float4 rc = recLast[lastIdx];
+        const int id = __float_as_int(rc.x);
+        W = last.w[lastIdx];
+        take = id >= 0 && id < s.numLights && id != envId && W != 0.f;
+        if (take) take = moved[id] > seenMoves;
+        if (take) {
+            const float4 a = last.li[lastIdx], b = last.wi[lastIdx], nr = sp.norm[index];
+            const f3 oldLi = mk3(a.x, a.y, a.z), oldWi = mk3(b.x, b.y, b.z), norm = mk3(nr.x, nr.y, nr.z);
+            const int type = mk_type(mk);
+            f3 wo = splat(0.f);
+            float roughness = 0.f;
+            if (type == 1) { const float4 w4 = sp.wo[index]; wo = mk3(w4.x, w4.y, w4.z); roughness = w4.w; }
+            f3 Li;
+            float pdf;
+            light_sample_at(s.lights, id, rc.y, rc.z, pos, Li, wi, dist, pdf);
+            if (!(pdf > 0.f) || is_nan_or_inf(pdf)) W = 0.f;                                  // step 1
+            else {
+                const f3 one = splat(1.f);
+                const float pOld = luminance(oldLi * eval_bsdf(type, one, nr.w, roughness, norm, wo, oldWi) * sat_dot(norm, oldWi));
+                const float pNew = luminance(Li * eval_bsdf(type, one, nr.w, roughness, norm, wo, wi) * sat_dot(norm, wi));
+                const float pdfOld = rc.w;
+                if (pOld > 0.f && pdfOld > 0.f && !is_nan_or_inf(pOld) && !is_nan_or_inf(pdfOld)) W = (W * (pNew / pOld)) * (pdfOld / pdf);
+                else W = 0.f;                                                                 // step 3
+            }
+            out.li[index] = make_float4(Li.x, Li.y, Li.z, dist);
+            out.wi[index] = make_float4(wi.x, wi.y, wi.z, W);
+            out.rec[index] = make_float4(rc.x, rc.y, rc.z, pdf);
+        }
+    }
+    if (inside) out.flag[index] = take ? 1 : 0;
+    const bool walk = take && W != 0.f;
+    const bool occluded = trace_occluded_wave(s, pos, pos + wi * dist, walk);                 // every lane of the wave takes part
+    if (walk && occluded) { reinterpret_cast<float*>(out.wi + index)[3] = 0.f; W = 0.f; }    // step 5
+    const unsigned long long bTake = __ballot(take), bWalk = __ballot(walk), bZero = __ballot(take && W == 0.f);
+    if (lane == 0 && bTake) {
+        atomicAdd(stats, (unsigned long long)__popcll(bTake));
+        atomicAdd(stats + 2, (unsigned long long)__popcll(bZero));
+        if (bWalk) {
+            atomicAdd(stats + 1, (unsigned long long)__popcll(bWalk));
+            atomicAdd(rayCount + (blockIdx.x % kRaySub) * kRayStride, (unsigned long long)__popcll(bWalk));
+        }
+    }
 }
 
 // ---- phase B: spatial reuse + shade --------------------------------------------------------------
@@ -898,6 +1050,9 @@ int rs_restir_free(rs_restir* r) {
     rs_dev_free(r->indResv[0]); rs_dev_free(r->indResv[1]);
     rs_dev_free(r->idCur); rs_dev_free(r->idLast); rs_dev_free(r->idTemp);
     for (int*& p : r->candId) rs_dev_free(p);
+    rs_dev_free(r->recCur); rs_dev_free(r->recLast); rs_dev_free(r->recTemp);
+    for (float4*& p : r->candRec) rs_dev_free(p);
+    rs_dev_free(r->rtLi); rs_dev_free(r->rtWi); rs_dev_free(r->rtRec); rs_dev_free(r->rtFlag); rs_dev_free(r->dRetarget);
     rs_primary_cuts_destroy(r->cuts);
     for (auto& e : r->ev) if (e) (void)hipEventDestroy(e);
     for (auto& pair : r->spatialEv) for (hipEvent_t& e : pair) if (e) (void)hipEventDestroy(e);
@@ -996,7 +1151,88 @@ int rs_restir_set_light_tracking(rs_restir* r, int enable) {
         r->trackSceneId = 0;             // (the RIS winners' planes need no clearing: a frame writes its set before it reads it)
     }
     r->track = on;
+    if (!on) r->retarget = false;        // retargeting rides on tracking
     return rs_after_launch("rs_restir_set_light_tracking");
+}
+
+// Light retargeting (include/restir_hip.h), on top of tracking.  The planes are allocated before anything of the object changes, and
+// `retarget` is set last: a failed allocation leaves it off with nothing changed, and so does a failure of the tracking switch (which
+// leaves tracking as that call leaves it).  A clear that fails to enqueue leaves retargeting off as well.  Every record AND every tracked
+// id starts unknown, in the order of the library stream -- ids that tracking carried so far have no record to go with -- and the next frame
+// takes the scene's count of moves as seen (trackSceneId = 0): nothing that happened before the switch is evaluated again.
+int rs_restir_set_light_retargeting(rs_restir* r, int enable) {
+    RS_SCOPE(r);
+    if (!r) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_set_light_retargeting: null");
+    const bool on = enable != 0;
+    if (on == r->retarget) return 0;
+    if (!on) { r->retarget = false; return 0; }
+    const size_t n = (size_t)r->width * r->height;
+    constexpr int kPlanes = 3 + rs_restir::kSurfSets + 3;
+    float4* f[kPlanes] = {};
+    int* flag = nullptr;
+    unsigned long long* counters = nullptr;
+    const bool fresh = !r->recCur;
+    auto drop = [&]() { for (float4*& p : f) rs_dev_free(p); rs_dev_free(flag); rs_dev_free(counters); };
+    if (fresh) {
+        int e = 0;
+        for (float4*& p : f) if (!e) e = rs_dev_alloc(&p, n);
+        if (!e) e = rs_dev_alloc(&flag, n);
+        if (!e) e = rs_dev_alloc(&counters, 3);
+        if (!e) e = rs_check_hip(hipMemset(counters, 0, 3 * sizeof(unsigned long long)), "memset");
+        if (e) { drop(); return e; }
+    }
+    const bool tracked = r->track;
+    if (!tracked) if (int e = rs_restir_set_light_tracking(r, 1)) { drop(); return e; }
+    if (fresh) {
+        r->recCur = f[0]; r->recLast = f[1]; r->recTemp = f[2];
+        for (int k = 0; k < rs_restir::kSurfSets; k++) r->candRec[k] = f[3 + k];
+        r->rtLi = f[3 + rs_restir::kSurfSets]; r->rtWi = f[4 + rs_restir::kSurfSets]; r->rtRec = f[5 + rs_restir::kSurfSets];
+        r->rtFlag = flag; r->dRetarget = counters;
+    }
+    if (tracked)                          // (a switch-on of tracking has just cleared them)
+        for (int* p : { r->idCur, r->idLast, r->idTemp }) RS_HIP(hipMemsetAsync(p, 0xff, n * sizeof(int), rs_stream()));
+    for (float4* p : { r->recCur, r->recLast, r->recTemp }) RS_HIP(hipMemsetAsync(p, 0xff, n * sizeof(float4), rs_stream()));      // light = -1
+    r->trackSceneId = 0;
+    r->retarget = true;
+    r->rtLaunched = r->rtLaunchedLast = false;
+    return rs_after_launch("rs_restir_set_light_retargeting");
+}
+
+int rs_restir_get_light_retargeting(const rs_restir* r, int* enabled) {
+    if (!r || !enabled) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_get_light_retargeting: null argument");
+    *enabled = r->retarget ? 1 : 0;
+    return 0;
+}
+
+int rs_restir_download_light_samples(const rs_restir* rc, int which, rs_light_sample* host) {
+    RS_SCOPE(rc);
+    rs_restir* r = const_cast<rs_restir*>(rc);
+    if (!r || !host || which < 0 || which > 2) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_download_light_samples: bad argument");
+    const size_t n = (size_t)r->width * r->height;
+    static_assert(sizeof(rs_light_sample) == sizeof(float4), "a record is one 16-byte element of the planes");
+    if (!r->retarget || !r->recCur) { for (size_t i = 0; i < n; i++) host[i] = rs_light_sample{ -1, 0.f, 0.f, 0.f }; return 0; }
+    RS_HIP(hipStreamSynchronize(rs_stream()));
+    RS_HIP(hipMemcpy(host, which == 0 ? r->recCur : which == 1 ? r->recLast : r->recTemp, n * sizeof(float4), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// test hook: what k_retarget did in the frame that rs_restir_end_frame ended last -- { samples re-evaluated, shadow segments walked,
+// samples left with W = 0 }; zeros when that frame did not launch it
+int rs_debug_restir_retarget(rs_restir* r, unsigned long long out[3]) {
+    RS_SCOPE(r);
+    if (!r || !out) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_restir_retarget: null argument");
+    out[0] = out[1] = out[2] = 0;
+    if (!r->retarget || !r->rtLaunchedLast) return 0;
+    RS_HIP(hipStreamSynchronize(rs_stream()));
+    RS_HIP(hipMemcpy(out, r->dRetarget, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ... and whether that frame launched it at all (a launch that found nothing to evaluate reports zeros too)
+int rs_debug_restir_retarget_launched(rs_restir* r, int* launched) {
+    if (!r || !launched) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_restir_retarget_launched: null argument");
+    *launched = r->retarget && r->rtLaunchedLast ? 1 : 0;
+    return 0;
 }
 
 int rs_restir_download_light_ids(const rs_restir* rc, int which, int* host) {
@@ -1033,11 +1269,27 @@ int rs_restir_spatial_times(rs_restir* r, float* ms, int capacity, int* count) {
 namespace {
 // RIS over the light table for rows [y0, y1) on stream st in the form the plan names (RS_RIS_*, rs_frame_plan.h)
 // candId: the winners' light-sampler indices (light tracking), null = not tracked
-int launch_ris(const rs_scene* scene, const SurfPlanes& sp, int W, int y0, int y1, int looper, bool sobol, hipStream_t st, int form, int* candId) {
+// candRec: the winners' records (retargeting, with candId), null = none
+int launch_ris(const rs_scene* scene, const SurfPlanes& sp, int W, int y0, int y1, int looper, bool sobol, hipStream_t st, int form, int* candId, float4* candRec) {
     const bool track = candId != nullptr;
     const int npx = (y1 - y0) * W;
     const dim3 grid((npx + kRisThreads - 1) / kRisThreads);
-    if (form == RS_RIS_LDS)
+    if (candRec && form == RS_RIS_LDS)
+        rs_dispatch([&](auto SOBOL) { hipLaunchKernelGGL((k_ris_lds_rec<SOBOL()>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, candId, candRec); }, sobol);
+    else if (candRec && form == RS_RIS_ALIAS_LDS) {
+        static const bool ldsAllowed = []{      // more than 64 KB of dynamic LDS is opt-in
+            bool ok = true;
+            for (const void* k : { reinterpret_cast<const void*>(&k_ris_alias_lds_rec<true>), reinterpret_cast<const void*>(&k_ris_alias_lds_rec<false>) })
+                ok = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kRisAliasLdsLights * (int)sizeof(AliasRec)) == hipSuccess && ok;
+            (void)hipGetLastError();
+            return ok; }();
+        (void)ldsAllowed;
+        rs_dispatch([&](auto SOBOL) { hipLaunchKernelGGL((k_ris_alias_lds_rec<SOBOL()>), grid, dim3(kRisThreads), (size_t)scene->numLights * sizeof(AliasRec), st, scene->dev, sp, W, y0, y1, looper, candId, candRec); }, sobol);
+    }
+    else if (candRec)
+        rs_dispatch([&](auto ENV, auto SOBOL) { hipLaunchKernelGGL((k_ris_rec<ENV(), SOBOL()>), dim3((npx + 255) / 256), dim3(256), 0, st, scene->dev, sp, W, y0, y1, looper, candId, candRec); },
+                    scene->envMapTexId >= 0, sobol);
+    else if (form == RS_RIS_LDS)
         // (one block per CU instead of two -- half of the wave slots left to the latency-bound kernels of the other streams -- measured
         // slower: frame 1.088 -> 1.142 ms, profiles/r03_ab_ris_blocks_per_cu.log)
         rs_dispatch([&](auto SOBOL, auto TRACK) { hipLaunchKernelGGL((k_ris_lds<SOBOL(), TRACK()>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, candId); }, sobol, track);
@@ -1161,7 +1413,8 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     }
     mark(r, 1);
     const int npx = (y1 - y0) * W;
-    RS_TRY(launch_ris(scene, sp, W, y0, y1, looper, sobol, st, p.risForm, r->track ? r->candId[r->surfSet] : nullptr));
+    RS_TRY(launch_ris(scene, sp, W, y0, y1, looper, sobol, st, p.risForm, r->track ? r->candId[r->surfSet] : nullptr,
+                      r->retarget ? r->candRec[r->surfSet] : nullptr));
     mark(r, 2);
     // (the shadow rays of a launch that fills the chip several times over go to the library stream: rs_frame_plan.h)
     if (!p.shadowOnLibrary) hipLaunchKernelGGL(k_shadow, dim3(tilesX * tilesY), dim3(256), 0, st, scene->dev, sp, W, y0, y1, tilesX);
@@ -1180,10 +1433,36 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
         if (r->trackSceneId != scene->id) {
             RS_HIP(hipMemsetAsync(r->idLast, 0xff, (size_t)W * r->height * sizeof(int), rs_stream()));
             RS_HIP(hipMemsetAsync(r->idTemp, 0xff, (size_t)W * r->height * sizeof(int), rs_stream()));
+            if (r->retarget) {
+                RS_HIP(hipMemsetAsync(r->recLast, 0xff, (size_t)W * r->height * sizeof(float4), rs_stream()));
+                RS_HIP(hipMemsetAsync(r->recTemp, 0xff, (size_t)W * r->height * sizeof(float4), rs_stream()));
+            }
             r->trackSceneId = scene->id;
+            r->seenMoves = scene->lightMoves;                   // (no record names a light of this scene yet)
         }
         ids = LightIds{ r->candId[r->surfSet], r->idLast, r->idCur, r->idTemp, scene->dev.lights, scene->numLights, scene->envMapTexId >= 0 ? scene->numLights - 1 : -1 };
     }
+    if (r->retarget) {
+        // Lamps moved since the previous frame: their samples are evaluated again before the merge, on the library stream behind the
+        // chain's join.  A frame after which none moved launches nothing extra (the merge's retargeting form carries the records).
+        r->frameMoves = scene->lightMoves;
+        const bool moved = !r->firstFrame && (reuse & 1) && scene->lightMoves != r->seenMoves;
+        LightRecs recs{ r->candRec[r->surfSet], r->recLast, r->recCur, r->recTemp, r->rtLi, r->rtWi, r->rtRec, moved ? r->rtFlag : nullptr };
+        if (moved) {
+            if (!r->rtLaunched) {
+                RS_HIP(hipMemsetAsync(r->dRetarget, 0, 3 * sizeof(unsigned long long), rs_stream()));
+                r->rtLaunched = true;
+            }
+            hipLaunchKernelGGL(k_retarget, dim3(tilesX * tilesY), dim3(256), 0, rs_stream(), scene->dev, sp, gbuf_view(g), r->last, r->recLast,
+                               scene->ver[scene->verCur].moved, (uint32_t)r->seenMoves, ids.envId, RetargetOut{ r->rtLi, r->rtWi, r->rtRec, r->rtFlag },
+                               W, y0, y1, tilesX, rayCounter, r->dRetarget);
+        }
+        rs_dispatch([&](auto SOBOL) {
+            hipLaunchKernelGGL((k_temporal_retarget<SOBOL()>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g),
+                               r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, ids, recs);
+        }, sobol);
+    }
+    else
     rs_dispatch([&](auto SOBOL, auto TRACK) {
         hipLaunchKernelGGL((k_temporal<SOBOL(), TRACK()>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g),
                            r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, ids);
@@ -1280,6 +1559,16 @@ int rs_debug_restir_surface(rs_restir* r, float* posTag, float* normal, unsigned
     return 0;
 }
 
+// ... and its { wo, roughness } plane, which only the pixels of a MetallicWorkflow material wrote
+int rs_debug_restir_surface_wo(rs_restir* r, float* wo4) {
+    RS_SCOPE(r);
+    if (!r || !wo4) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_restir_surface_wo: null argument");
+    RS_TRY(rs_synchronize());
+    const rs_restir::Surf& f = r->surf[(r->surfSet + rs_restir::kSurfSets - 1) % rs_restir::kSurfSets];
+    RS_HIP(hipMemcpy(wo4, f.wo, (size_t)r->width * r->height * 16, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // the plan of a phase-A call (rs_frame_plan.h) for inputs the caller fills in: no device, no context, no object
 int rs_debug_phase_a_plan(const rs_phase_a_inputs* in, rs_phase_a_plan* out) {
     if (!in || !out) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_phase_a_plan: null argument");
@@ -1301,6 +1590,9 @@ int rs_restir_end_frame(rs_restir* r) {
     if (!r) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_end_frame: null");
     ResvPlanes t = r->cur; r->cur = r->last; r->last = t;       // std::swap(devDirectReservoir, devLastDirectReservoir)
     int* ti = r->idCur; r->idCur = r->idLast; r->idLast = ti;   // (light tracking: the reservoirs' light indices travel with them)
+    float4* tr = r->recCur; r->recCur = r->recLast; r->recLast = tr;      // (retargeting: so do their records)
+    if (r->retarget && r->phaseACalls > 0) r->seenMoves = r->frameMoves;
+    r->rtLaunchedLast = r->rtLaunched; r->rtLaunched = false;
     r->firstFrame = false;
     // every reader of this frame's surface planes has been enqueued: the set is free for the frame after the next one
     if (!rs_sync_enabled()) { RS_HIP(hipEventRecord(r->surfFree[r->surfSet], rs_stream())); r->surfFreeValid[r->surfSet] = true; }
@@ -1340,6 +1632,7 @@ int copy_rows(rs_restir* r, int which, int y0, int rows, char* buf, bool pack, c
 }
 // the light-id plane of buffer `which`: one launch of the copy kernel (refusals: see rs_restir_light_rows_bytes below)
 int copy_light_rows(rs_restir* r, int which, int y0, int rows, char* buf, bool pack, const char* what) {
+    if (r && r->retarget) return rs_fail(RS_ERR_UNSUPPORTED, "rs_restir_light_rows_pack / _unpack: light retargeting is on, and 4 B/px do not carry its records");
     if (!r || !buf || ((size_t)buf & 3) || which < 0 || which > 2 || y0 < 0 || rows < 0 || y0 + rows > r->height || !r->track || !r->idCur) return rs_fail(RS_ERR_INVALID_ARGUMENT, what);
     rs_rows::SegList l(pack);
     rs_rows::add_rows(l, rs_rows::light_id_plane(r, which), y0, rows, buf);
@@ -1432,8 +1725,10 @@ int rs_restir_upload(rs_restir* r, int which, const rs_reservoir* host) {
         RS_HIP(hipMemcpy(p->w, w.data(), n * 4, hipMemcpyHostToDevice));
         RS_HIP(hipMemcpy(p->m, m.data(), n * 4, hipMemcpyHostToDevice));
         if (r->track) RS_HIP(hipMemset(which == 0 ? r->idCur : r->idLast, 0xff, n * sizeof(int)));     // uploaded samples: light unknown
+        if (r->retarget) RS_HIP(hipMemset(which == 0 ? r->recCur : r->recLast, 0xff, n * sizeof(float4)));
     }
     if (which == 2 && r->track) RS_HIP(hipMemset(r->idTemp, 0xff, n * sizeof(int)));
+    if (which == 2 && r->retarget) RS_HIP(hipMemset(r->recTemp, 0xff, n * sizeof(float4)));
     return 0;
 }
 

@@ -263,6 +263,7 @@ struct rs_scene {
         rs::LightRec* lights = nullptr;
         rs::AliasRec* alias = nullptr;
         rs::TexRec* textures = nullptr;          // the texture table: its records point at the texel arrays current when the slot was filled
+        uint32_t* moved = nullptr;               // hLightMoved (below), one word per sampler entry: every slot has its own array, slot 0 too
         char* staging = nullptr;                 // pinned host copy the slot is filled from
         hipEvent_t retired[kVersionStreams] = {};
         bool retiredValid[kVersionStreams] = {};
@@ -287,6 +288,12 @@ struct rs_scene {
     std::vector<float> hLightArea;               // per light primitive, Math::triangleArea (filled on the first edit)
     float envPower = 0.f;                        // the environment map's sampler entry (its pdf's sum)
     bool envPowerKnown = false;
+    // Moved lamps (rs_restir_set_light_retargeting): lightMoves counts the accepted geometry edits that named an emitter, hLightMoved[i]
+    // is lightMoves at the last edit that named light i's primitive (0: never).  The device copy travels in the ring of versions next to
+    // the light records, so that a launch reads the stamps of the light records it reads.  hLightOfPrim: sampler entry of a primitive, -1 = none.
+    unsigned long long lightMoves = 0;
+    std::vector<uint32_t> hLightMoved;
+    std::vector<int> hLightOfPrim;
 };
 
 // ---- G-buffer (src/gbuffer.h:41-58) ------------------------------------------------------------
@@ -634,6 +641,22 @@ struct rs_restir {
     int* idTemp = nullptr;           // of the published copy (TempPlanes) the spatial pass gathers from
     int* candId[kSurfSets] = {};
     unsigned long long trackSceneId = 0;   // the scene whose light indices idLast holds (rs_scene::id; 0 = none yet)
+    // rs_restir_set_light_retargeting, on top of tracking: a 16-byte record { light, u, v, pdf } beside every reservoir's sample (cur /
+    // last, swapped with them; the published copy) and every RIS winner (one plane per surface set), and the planes k_retarget leaves
+    // the re-evaluated temporal candidates in.  Allocated when retargeting is first switched on.
+    bool retarget = false;
+    float4* recCur = nullptr;
+    float4* recLast = nullptr;
+    float4* recTemp = nullptr;
+    float4* candRec[kSurfSets] = {};
+    float4* rtLi = nullptr;          // re-evaluated candidate: Li xyz, dist
+    float4* rtWi = nullptr;          // wi xyz, W
+    float4* rtRec = nullptr;         // its record
+    int* rtFlag = nullptr;           // 1: the pixel's temporal candidate is the one in the three planes above
+    unsigned long long seenMoves = 0;      // the scene's lightMoves at the previous frame (forgotten with trackSceneId)
+    unsigned long long frameMoves = 0;     // ... at this frame's phase-A calls: seenMoves of the next frame (rs_restir_end_frame)
+    unsigned long long* dRetarget = nullptr;   // { re-evaluated, segments, zeroed } of the last frame that launched k_retarget: cleared, added to and read in the library stream's order
+    bool rtLaunched = false, rtLaunchedLast = false;     // this frame / the frame that ended last launched k_retarget
 };
 
 static_assert(rs_context::kAux >= 1 + rs_restir::kChains, "one auxiliary stream for GBuffer::render and one per chain");

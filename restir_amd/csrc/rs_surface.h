@@ -244,6 +244,28 @@ __device__ __forceinline__ void light_sample_again(LightPtr lights, int id, floa
     dist = len;
 }
 
+// The whole sample of light `id` at the barycentric pair (u, v) seen from pos: sample_light_with's expressions from `sampled` on, in its
+// order, with operations that give the IEEE results for every operand -- so a pair that the sampler drew gives the sampler's bits, and a
+// pair kept from an earlier frame is evaluated on the light records of this one (restir.hip k_retarget).  A sample that fails the facing
+// test leaves as sample_light_with's early exit does: pdf = kInvalidPdf, Li = wi = 0, dist = 0.
+template <typename LightPtr>
+__device__ __forceinline__ void light_sample_at(LightPtr lights, int id, float u, float v, f3 pos, f3& Li, f3& wi, float& dist, float& pdf) {
+    float4 a, b, c, d;
+    load_light(lights, id, a, b, c, d);
+    const f3 v0 = mk3(a.x, a.y, a.z), v1 = mk3(b.x, b.y, b.z), v2 = mk3(c.x, c.y, c.z);
+    const f3 nrm = mk3(a.w, b.w, c.w);
+    const f3 sampled = v1 * u + v2 * v + v0 * (1.f - u - v);
+    const f3 toS = sampled - pos;
+    Li = splat(0.f); wi = splat(0.f); dist = 0.f; pdf = kInvalidPdf;
+    if (dot(nrm, toS) > -1e-6f) return;
+    const float dd = dot(toS, toS);
+    const float len = sqrt_exact(dd);
+    Li = mk3(d.x, d.y, d.z);
+    wi = toS * rcp_exact(len);
+    dist = len;
+    pdf = div_exact(d.w * dd, gabs(-dot(nrm, wi)));
+}
+
 #endif  // __HIPCC__
 
 }  // namespace rs

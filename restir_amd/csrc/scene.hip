@@ -360,6 +360,7 @@ extern "C" int rs_debug_scene_table(const rs_scene* s, int which, void* host, si
     case RS_TABLE_ORD_TRIS:  src = s->dOrdTris; size = np * 3 * sizeof(TriRec); break;
     case RS_TABLE_EMI_NODES: src = s->dEmiNodes; size = ((size_t)s->dev.emiCount + 1) * 16; break;
     case RS_TABLE_EMI_TRIS:  src = s->dEmiTris; size = emissive * sizeof(TriRec); break;
+    case RS_TABLE_LIGHT_MOVED: src = s->lightMoves ? s->ver[s->verCur].moved : nullptr; size = (size_t)s->numLights * sizeof(uint32_t); break;
     default: return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_scene_table: unknown table");
     }
     if (!src) size = 0;

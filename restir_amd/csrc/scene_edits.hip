@@ -26,7 +26,7 @@ int fail_named(int code, const char* name, const char* text) { return rs_fail(co
 int refused(int code, const std::string& why) { return why.empty() ? code : rs_fail(code, why.c_str()); }
 
 // Byte offsets of one version's tables in its staging buffer (each 64-byte aligned)
-struct VersionLayout { size_t mat, light, alias, tex, total; };
+struct VersionLayout { size_t mat, light, alias, tex, moved, total; };
 VersionLayout version_layout(const rs_scene* s) {
     auto up = [](size_t b) { return (b + 63) & ~(size_t)63; };
     VersionLayout l;
@@ -34,7 +34,8 @@ VersionLayout version_layout(const rs_scene* s) {
     l.light = up(s->hMaterials.size() * sizeof(rs_material));
     l.alias = l.light + up((size_t)s->numLights * sizeof(LightRec));
     l.tex = l.alias + up((size_t)s->numLights * sizeof(AliasRec));
-    l.total = l.tex + up(s->hTextures.size() * sizeof(TexRec));
+    l.moved = l.tex + up(s->hTextures.size() * sizeof(TexRec));
+    l.total = l.moved + up((size_t)s->numLights * sizeof(uint32_t));
     return l;
 }
 
@@ -61,6 +62,8 @@ int versions_prepare(rs_scene* s) {
             RS_TRY(rs_dev_alloc(&x.alias, nl));
             if (nt) RS_TRY(rs_dev_alloc(&x.textures, nt));
         }
+        RS_TRY(rs_dev_alloc(&x.moved, nl));
+        RS_HIP(hipMemset(x.moved, 0, (nl ? nl : 1) * sizeof(uint32_t)));
         RS_HIP(hipHostMalloc((void**)&x.staging, l.total, hipHostMallocDefault));
         for (hipEvent_t& e : x.retired) RS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
@@ -71,6 +74,9 @@ int versions_prepare(rs_scene* s) {
     RS_HIP(hipEventCreateWithFlags(&s->verFilled, hipEventDisableTiming));
     RS_HIP(hipStreamCreateWithFlags(&s->verStream, hipStreamNonBlocking));
     // Math::triangleArea of every light primitive, as rs_build_light_table computes it (scene_build.cpp)
+    s->hLightMoved.assign(nl, 0u);
+    s->hLightOfPrim.assign((size_t)s->numPrims, -1);
+    for (size_t i = 0; i < s->hLightPrimIds.size(); i++) s->hLightOfPrim[(size_t)s->hLightPrimIds[i]] = (int)i;
     s->hLightArea.resize(s->hLightPrimIds.size());
     for (size_t i = 0; i < s->hLightArea.size(); i++) s->hLightArea[i] = triangle_area(&s->hVertices[(size_t)s->hLightPrimIds[i] * 9]);
     // the environment map's sampler entry keeps its power: the sum of its pdf, as rs_scene_build_textured passes it on (a scene made by
@@ -99,6 +105,7 @@ void versions_free(rs_scene* s) {
     for (int v = 0; v < rs_scene::kVersions; v++) {
         rs_scene::Version& x = s->ver[v];
         if (v > 0) { rs_dev_free(x.materials); rs_dev_free(x.lights); rs_dev_free(x.alias); rs_dev_free(x.textures); }
+        rs_dev_free(x.moved);
         if (x.staging) { (void)hipHostFree(x.staging); x.staging = nullptr; }
         for (hipEvent_t& e : x.retired) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     }
@@ -179,6 +186,7 @@ int version_commit(rs_scene* s, const char* what) {
         const rs_scene::Edited& e = s->texEdited[i];
         recs[i] = TexRec{ static_cast<float*>(e.dev[e.cur]), s->hTextures[i].width, s->hTextures[i].height };
     }
+    if (nl) std::memcpy(nv.staging + l.moved, s->hLightMoved.data(), nl * sizeof(uint32_t));
 
     // the current slot is retired by what has been enqueued so far on the library stream and on every auxiliary stream
     rs_context* c = rs_ctx();
@@ -194,6 +202,7 @@ int version_commit(rs_scene* s, const char* what) {
     if (nl) {
         RS_HIP(hipMemcpyAsync(nv.lights, nv.staging + l.light, nl * sizeof(LightRec), hipMemcpyHostToDevice, s->verStream));
         RS_HIP(hipMemcpyAsync(nv.alias, nv.staging + l.alias, nl * sizeof(AliasRec), hipMemcpyHostToDevice, s->verStream));
+        RS_HIP(hipMemcpyAsync(nv.moved, nv.staging + l.moved, nl * sizeof(uint32_t), hipMemcpyHostToDevice, s->verStream));
     }
     if (nt) RS_HIP(hipMemcpyAsync(nv.textures, nv.staging + l.tex, nt * sizeof(TexRec), hipMemcpyHostToDevice, s->verStream));
     RS_HIP(hipEventRecord(s->verFilled, s->verStream));
@@ -513,6 +522,12 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
     s->hLightProb.swap(lights.prob);
     s->hLightFailId.swap(lights.fail);
     s->sumLightPower = lights.sumAll;
+    // moved lamps: this edit's number on every sampler entry it named (rs_restir_set_light_retargeting re-evaluates their samples)
+    s->lightMoves++;
+    for (int j = 0; j < plan.m; j++) {
+        const int light = s->hLightOfPrim[(size_t)rec.ids[j]];
+        if (light >= 0) s->hLightMoved[(size_t)light] = (uint32_t)s->lightMoves;
+    }
     return version_commit(s, name);
 }
 
@@ -619,6 +634,12 @@ extern "C" int rs_scene_set_part_transforms(rs_scene* s, int count, const int* p
     }
     const PartSource src{ (int)p->recs.size(), p->recs.data() };
     return set_geometry(s, (int)m, p->ids.data(), p->vertices.data(), p->normals.data(), true, name, &src);
+}
+
+extern "C" int rs_scene_light_moves(const rs_scene* s, unsigned long long* moves) {
+    if (!s || !moves) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_light_moves: null argument");
+    *moves = s->lightMoves;
+    return 0;
 }
 
 extern "C" int rs_scene_parts_info(const rs_scene* s, int* numParts, int* numListedPrims) {

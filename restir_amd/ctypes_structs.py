@@ -113,6 +113,9 @@ INDIRECT_RESERVOIR_DTYPE = np.dtype(
      ("numSamples", "<i4"), ("weight", "<f4")]
 )
 assert MATERIAL_DTYPE.itemsize == 44 and RESERVOIR_DTYPE.itemsize == 36 and INDIRECT_RESERVOIR_DTYPE.itemsize == 68
+# rs_light_sample (rs_restir_download_light_samples): the record beside a reservoir's sample while light retargeting is on, 16 bytes
+LIGHT_SAMPLE_DTYPE = np.dtype([("light", "<i4"), ("u", "<f4"), ("v", "<f4"), ("pdf", "<f4")])
+assert LIGHT_SAMPLE_DTYPE.itemsize == 16
 
 # Material::Type (src/material.h:114-120)
 LAMBERTIAN, METALLIC_WORKFLOW, DIELECTRIC, DISNEY, LIGHT = range(5)
