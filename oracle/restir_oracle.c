@@ -1344,7 +1344,7 @@ static resv_t find_spatial_neighbor_disk(const orc_reservoir* reservoir, int x, 
 
 /* Light tracking (rs_restir_set_light_tracking, include/restir_hip.h): a reused sample of light `id` re-evaluated under the scene's
  * current emission, W *= luminance(Le) / luminance(Li) (the division first) and Li = Le.  Not for an unknown light (-1), the
- * environment map's entry or W = 0, nor when luminance(Li) is not positive (restir.hip k_temporal, the TRACK blocks of the merge
+ * environment map's entry or W = 0, nor when luminance(Li) is not positive (restir.hip k_temporal, the LIGHTS >= 1 blocks of the merge
  * and of the `!shaded` branch). */
 static void rescale_to_emission(const orc_scene* s, int id, float* W, v3* Li) {
     const int envId = s->envMapSamplerLength != 0 ? s->numLights - 1 : -1;

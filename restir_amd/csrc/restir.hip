@@ -25,7 +25,7 @@
 #include <cstring>
 
 #include "rs_row_layouts.h"
-#include "rs_internal.h"
+#include "rs_light_history.h"
 #include "rs_cuts.h"
 
 using namespace rs;
@@ -35,28 +35,12 @@ namespace {
 constexpr int kReservoirSize = 32;   // restir.cu:3
 constexpr int kHalo = RS_SPATIAL_HALO_ROWS;
 
-// kind of a pixel after the primary hit
-constexpr int kKindMiss = 0, kKindLight = 1, kKindShaded = 2;
-// per-pixel tag: material id (24 bits) | kind << 24 (2 bits) | Material::Type << 26 (3 bits)
-__device__ __forceinline__ int mk_kind(int mk) { return (mk >> 24) & 3; }
-__device__ __forceinline__ int mk_type(int mk) { return (mk >> 26) & 7; }
 // Sobol sampler (src/sampler.h:9-36): the passes carry the scramble in rngMat.x and know the table position from the number of
 // draws made so far -- 4 by the primary ray (restir.cu:129), 5 per RIS candidate (:158,168), and the temporal merge's one draw if it
 // happened (bit 29 of the tag as k_temporal leaves it in rngMat.y).
 constexpr int kDrawsPrimary = 4, kDrawsRis = kDrawsPrimary + 5 * 32;
 constexpr unsigned kTemporalDrewBit = 1u << 29;
 constexpr int kRaySlots = 1024;   // ring of per-frame BVH-walk counters
-constexpr int kRaySub = 64, kRayStride = 8;   // per frame: 64 partial counters, 64 B apart (one hot address cost ~85 us/frame)
-
-struct SurfPlanes {
-    float4* posMat;     // pos.xyz (radiance of the environment map for a miss pixel of an env-mapped scene), bits(tag)
-    float4* norm;       // shading normal xyz (normal-mapped, flipped to the wo side), w = metallic (after its map)
-    float4* wo;         // wo.xyz, w = roughness (after its map); written and read only for the metallic BSDF
-    uint2*  rngMat;     // { RNG state carried from pass to pass, matId | kind << 24 }: all the spatial pass needs for a Lambertian pixel
-    float4* candLi;     // RIS winner Li.xyz, dist
-    float4* candWi;     // RIS winner wi.xyz, reservoir weight
-};
-
 // ---- phase A.1: primary hit ---------------------------------------------------------------------
 // what ReSTIRDirectKernel keeps of its primary hit (restir.cu:127-153) for the later passes; returns whether the pixel is shaded
 template <bool TEX>
@@ -214,7 +198,7 @@ __device__ __forceinline__ float ris_candidate(const DevScene& s, AliasPtr alias
     return weight;
 }
 
-// TRACK (rs_restir_set_light_tracking): the winner's light-sampler index goes to candId as well (-1: no winner)
+// LIGHTS (the light history's mode, rs_light_history.h) >= 1: the winner's light-sampler index goes to win.id as well (-1: no winner)
 // Two of a candidate's five draws are only compared -- the one that picks the sampler entry and the one that is held against the entry's
 // prob -- and a power-of-two scale commutes with both comparisons (sample_light_with): they are taken before the generator's multiply by
 // 2^-31 (Rng::raw).  The first meets numLights * 2^-31, a constant of the launch; the second needs prob * 2^31, which a kernel that
@@ -222,11 +206,11 @@ __device__ __forceinline__ float ris_candidate(const DevScene& s, AliasPtr alias
 // k_ris, reading the scene's table, would pay for per candidate what it saves: it scales its second draw as before.  The Sobol sampler's
 // draws come as they are (scale 1).
 template <bool SOBOL> constexpr float kRisRawScale = SOBOL ? 1.f : kRngRawScale;
-// REC (rs_restir_set_light_retargeting, with TRACK): the winner's record { light, u, v, pdf } goes to candRec -- the pair is the one the loop
-// carries already; the pdf is evaluated again after the loop with the pair (light_sample_at), or carried where the loop carries the sample (ENV)
-template <bool ENV, bool SOBOL, bool TRACK, bool SCALED_ALIAS, typename AliasPtr, typename LightPtr, bool REC = false>
-__device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& sp, AliasPtr alias, LightPtr lights, int index, int looper, int* candId,
-                                          float4* candRec = nullptr) {
+// LIGHTS = 2: the winner's record { light, u, v, pdf } goes to win.rec -- the pair is the one the loop carries already; the pdf is
+// evaluated again after the loop with the pair (light_sample_at), or carried where the loop carries the sample (ENV)
+template <bool ENV, bool SOBOL, int LIGHTS, bool SCALED_ALIAS, typename AliasPtr, typename LightPtr>
+__device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& sp, AliasPtr alias, LightPtr lights, int index, int looper, RisWinners<LIGHTS> win) {
+    constexpr bool TRACK = LIGHTS >= 1, REC = LIGHTS == 2;
     RS_SETPRIO(RS_PRIO_RIS);
     const float4 pm = sp.posMat[index];
     const int mk = __float_as_int(pm.w);
@@ -305,34 +289,25 @@ __device__ __forceinline__ void ris_pixel(const DevScene& s, const SurfPlanes& s
     sp.candLi[index] = make_float4(selLi.x, selLi.y, selLi.z, selDist);
     sp.candWi[index] = make_float4(selWi.x, selWi.y, selWi.z, wsum);
     reinterpret_cast<unsigned*>(sp.rngMat + index)[0] = rng.word();
-    if (TRACK) candId[index] = selId;
-    if (REC) candRec[index] = make_float4(__int_as_float(selId), selU, selV, selPdf);
+    if (TRACK) win.id[index] = selId;
+    if constexpr (REC) win.rec[index] = make_float4(__int_as_float(selId), selU, selV, selPdf);
 }
 
-template <bool ENV, bool SOBOL, bool TRACK, bool REC = false>
-__device__ __forceinline__ void ris_rows(const DevScene& s, const SurfPlanes& sp, int width, int y0, int y1, int looper, int* candId, float4* candRec = nullptr) {
+template <bool ENV, bool SOBOL, int LIGHTS>
+__global__ void __launch_bounds__(256) k_ris(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, RisWinners<LIGHTS> win) {
     const int n0 = y0 * width, n1 = y1 * width;
     const int index = n0 + blockIdx.x * blockDim.x + threadIdx.x;
     if (index >= n1) return;
-    ris_pixel<ENV, SOBOL, TRACK, false, const AliasRec*, const LightRec*, REC>(s, sp, s.alias, s.lights, index, looper, candId, candRec);
-}
-
-template <bool ENV, bool SOBOL, bool TRACK>
-__global__ void __launch_bounds__(256) k_ris(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
-    ris_rows<ENV, SOBOL, TRACK>(s, sp, width, y0, y1, looper, candId);
-}
-// ... with the winners' records (retargeting): a form of its own, so that the forms above keep their code
-template <bool ENV, bool SOBOL>
-__global__ void __launch_bounds__(256) k_ris_rec(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId, float4* candRec) {
-    ris_rows<ENV, SOBOL, true, true>(s, sp, width, y0, y1, looper, candId, candRec);
+    ris_pixel<ENV, SOBOL, LIGHTS, false, const AliasRec*, const LightRec*>(s, sp, s.alias, s.lights, index, looper, win);
 }
 
 // amdgpu_waves_per_eu(8): two 1 024-thread blocks per CU are 8 waves per SIMD, i.e. 64 registers at most, and nothing but this attribute
 // tells the register allocator so (the block size alone allows 128).  Left to itself the single-guard loop takes 67 and the kernel
 // loses half its waves.  The kernel now sits AT 64: a value added to the loop shows as scratch, not as a 65th register -- check the
 // scratch column of tools/kernel_resources.sh restir.hip after every change here (0 bytes today).
-template <bool SOBOL, bool TRACK, bool REC = false>
-__device__ __forceinline__ void ris_lds_block(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId, float4* candRec = nullptr) {
+// (LIGHTS = 2: the record's pdf lives only after the loop, the loop's registers are those of LIGHTS = 1)
+template <bool SOBOL, int LIGHTS>
+__device__ __forceinline__ void ris_lds_block(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, RisWinners<LIGHTS> win) {
     // The copy is laid out by quarter: the lanes of a wave read the same quarter of 64 random records, and in record order those
     // 16 bytes lie in 2 of the 8 four-bank groups whatever the light (a 4-fold bank conflict; SQ_LDS_BANK_CONFLICT was 80 % of the
     // LDS cycles); by quarter, light i's lies in group i mod 8.
@@ -364,40 +339,25 @@ __device__ __forceinline__ void ris_lds_block(DevScene s, SurfPlanes sp, int wid
     const int n0 = y0 * width, n1 = y1 * width;
     const int index = n0 + blockIdx.x * kRisThreads + threadIdx.x;
     if (index >= n1) return;
-    ris_pixel<false, SOBOL, TRACK, true, const AliasRec*, LightQuarters<kRisLdsLights>, REC>(s, sp, sAlias, LightQuarters<kRisLdsLights>{ sQuarters }, index, looper, candId, candRec);
+    ris_pixel<false, SOBOL, LIGHTS, true, const AliasRec*, LightQuarters<kRisLdsLights>>(s, sp, sAlias, LightQuarters<kRisLdsLights>{ sQuarters }, index, looper, win);
 }
-template <bool SOBOL, bool TRACK>
-__global__ void __launch_bounds__(kRisThreads) __attribute__((amdgpu_waves_per_eu(8))) k_ris_lds(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
-    ris_lds_block<SOBOL, TRACK>(s, sp, width, y0, y1, looper, candId);
-}
-// (the retargeting form: the record's pdf lives only after the loop, the loop's registers are those of the tracked form)
-template <bool SOBOL>
-__global__ void __launch_bounds__(kRisThreads) __attribute__((amdgpu_waves_per_eu(8))) k_ris_lds_rec(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId, float4* candRec) {
-    ris_lds_block<SOBOL, true, true>(s, sp, width, y0, y1, looper, candId, candRec);
+template <bool SOBOL, int LIGHTS>
+__global__ void __launch_bounds__(kRisThreads) __attribute__((amdgpu_waves_per_eu(8))) k_ris_lds(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, RisWinners<LIGHTS> win) {
+    ris_lds_block<SOBOL, LIGHTS>(s, sp, width, y0, y1, looper, win);
 }
 
 // More lights than the LDS copy of the whole table holds (config 5: 10 240): the alias records alone (8 B per light) still fit -- one
 // LDS read and four 16-byte gathers of the light record per candidate instead of five gathers; the light records stay in L2.
 // Dynamic LDS: numLights * 8 bytes.
-template <bool SOBOL, bool TRACK>
-__global__ void __launch_bounds__(kRisThreads) k_ris_alias_lds(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId) {
+template <bool SOBOL, int LIGHTS>
+__global__ void __launch_bounds__(kRisThreads) k_ris_alias_lds(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, RisWinners<LIGHTS> win) {
     extern __shared__ AliasRec sAliasDyn[];
     for (int i = threadIdx.x; i < s.numLights; i += kRisThreads) { AliasRec al = s.alias[i]; al.prob *= kRisRawScale<SOBOL>; sAliasDyn[i] = al; }     // ris_pixel<SCALED_ALIAS>
     __syncthreads();
     const int n0 = y0 * width, n1 = y1 * width;
     const int index = n0 + blockIdx.x * kRisThreads + threadIdx.x;
     if (index >= n1) return;
-    ris_pixel<false, SOBOL, TRACK, true, const AliasRec*, const LightRec*>(s, sp, sAliasDyn, s.lights, index, looper, candId);
-}
-template <bool SOBOL>
-__global__ void __launch_bounds__(kRisThreads) k_ris_alias_lds_rec(DevScene s, SurfPlanes sp, int width, int y0, int y1, int looper, int* candId, float4* candRec) {
-    extern __shared__ AliasRec sAliasDyn[];
-    for (int i = threadIdx.x; i < s.numLights; i += kRisThreads) { AliasRec al = s.alias[i]; al.prob *= kRisRawScale<SOBOL>; sAliasDyn[i] = al; }
-    __syncthreads();
-    const int n0 = y0 * width, n1 = y1 * width;
-    const int index = n0 + blockIdx.x * kRisThreads + threadIdx.x;
-    if (index >= n1) return;
-    ris_pixel<false, SOBOL, true, true, const AliasRec*, const LightRec*, true>(s, sp, sAliasDyn, s.lights, index, looper, candId, candRec);
+    ris_pixel<false, SOBOL, LIGHTS, true, const AliasRec*, const LightRec*>(s, sp, sAliasDyn, s.lights, index, looper, win);
 }
 
 // ---- phase A.3: shadow ray, temporal merge, publish -------------------------------------------------
@@ -452,32 +412,19 @@ __global__ void __launch_bounds__(256, RS_WALK_WAVES) k_shadow(DevScene s, SurfP
 // were built and measured in round 4: bit-exact and THREE TIMES slower, 0.475 -> 1.38 ms.  The 64 rays of an 8x8 tile start next to each
 // other and walk in lockstep through the same cache lines; replacement desynchronises them, and what the wave then fetches per step is 64
 // different lines.  EXPERIMENTS.md, commit 5febf79, profiles/r04_ab_shadow_streaming_replacement.log.)
-// Light tracking (rs_restir_set_light_tracking): the light-sampler index of the RIS winners (cand), of the reservoirs the merge reads
-// (last) and of those it publishes (cur), and the light records of the scene's current emission
-struct LightIds {
-    const int* cand; const int* last; int* cur;
-    int* temp;                       // of the published copy the spatial pass gathers from (TempPlanes)
-    const LightRec* lights;
-    int numLights, envId;            // envId: the environment map's sampler entry, -1 = none
-};
-
-// TRACK: the temporal candidate is re-evaluated under the current emission before the merge -- its target toScalar(Li * BSDF * cos) scales
-// with luminance(Li) (the DI path evaluates the BSDF with baseColor 1, restir.cu:141), so W takes the ratio of the luminances and Li the
-// light's current radiance.  Not for an unknown light (-1), the environment map's entry or W = 0.  The published copy of a pixel that shades
-// nothing this frame keeps an older frame's reservoir (Q1) and is still a spatial tap: it is re-evaluated in place the same way.
-// Retargeting (rs_restir_set_light_retargeting): the records { light, u, v, pdf } of the RIS winners (cand), of the reservoirs the merge
-// reads (last) and publishes (cur, temp), and what k_retarget left for this frame: flag[i] != 0 -- pixel i's temporal candidate is
-// { rtLi | rtWi (w = W) | rtRec }[i] instead of last[motion[i]]; M stays the slot's.  flag null: k_retarget was not launched.
-struct LightRecs {
-    const float4* cand; const float4* last; float4* cur; float4* temp;
-    const float4* rtLi; const float4* rtWi; const float4* rtRec; const int* flag;
-};
-
-// RETARGET (with TRACK): the merge carries the records, and takes the flagged candidates from k_retarget's planes
-template <bool SOBOL, bool TRACK, bool RETARGET>
+// LIGHTS >= 1 (MergeLights, rs_light_history.h): the temporal candidate is re-evaluated under the current emission before the merge -- its
+// target toScalar(Li * BSDF * cos) scales with luminance(Li) (the DI path evaluates the BSDF with baseColor 1, restir.cu:141), so W takes
+// the ratio of the luminances and Li the light's current radiance.  Not for an unknown light (-1), the environment map's entry or W = 0.
+// The published copy of a pixel that shades nothing this frame keeps an older frame's reservoir (Q1) and is still a spatial tap: it is
+// re-evaluated in place the same way -- written out twice: as one function of (light table, id, count, env id) that updates W and Li,
+// k_temporal<*, 1> and <*, 2> came out of the compiler four to five instructions shorter with a quarter of their lines changed (the
+// published copy's loads of W and Li no longer wait for the id test), and this form keeps the instructions of the measured kernels.
+// LIGHTS = 2: the merge carries the records, and takes the flagged candidates from k_retarget's planes
+template <bool SOBOL, int LIGHTS>
 __device__ __forceinline__ void temporal_body(const SurfPlanes& sp, const GBufView& g, const ResvPlanes& last, const ResvPlanes& cur, const TempPlanes& temp, const uint32_t* sampleSeq, int looper,
                                               int first, int reuse, int n0, int n1, unsigned long long* rayWork, unsigned long long* rayDone, const LightIds& ids,
                                               const LightRecs& recs) {
+    constexpr bool TRACK = LIGHTS >= 1, RETARGET = LIGHTS == 2;
     RS_SETPRIO(RS_PRIO_STREAM);
     // this call's BVH-walk counters are complete (the launch is ordered after the chain that counted): publish them and leave the
     // working slot zero for its next user, so that the chain itself needs no clearing launch
@@ -592,102 +539,11 @@ __device__ __forceinline__ void temporal_body(const SurfPlanes& sp, const GBufVi
     resv_store(cur, index, r);
 }
 
-template <bool SOBOL, bool TRACK>
+template <bool SOBOL, int LIGHTS>
 __global__ void __launch_bounds__(256) k_temporal(SurfPlanes sp, GBufView g, ResvPlanes last, ResvPlanes cur, TempPlanes temp, const uint32_t* sampleSeq, int looper,
-                                                  int first, int reuse, int n0, int n1, unsigned long long* rayWork, unsigned long long* rayDone, LightIds ids) {
-    temporal_body<SOBOL, TRACK, false>(sp, g, last, cur, temp, sampleSeq, looper, first, reuse, n0, n1, rayWork, rayDone, ids, LightRecs{});
-}
-template <bool SOBOL>
-__global__ void __launch_bounds__(256) k_temporal_retarget(SurfPlanes sp, GBufView g, ResvPlanes last, ResvPlanes cur, TempPlanes temp, const uint32_t* sampleSeq, int looper,
-                                                           int first, int reuse, int n0, int n1, unsigned long long* rayWork, unsigned long long* rayDone, LightIds ids, LightRecs recs) {
-    temporal_body<SOBOL, true, true>(sp, g, last, cur, temp, sampleSeq, looper, first, reuse, n0, n1, rayWork, rayDone, ids, recs);
-}
-
-// Retargeting: the temporal candidates whose lamp has moved since the previous frame, evaluated again on this frame's light records
-// before the merge.  One lane per pixel, tiles and walk as k_shadow.  For a shaded pixel whose history slot j = motion[i] passes
-// findTemporalNeighbor and holds a sample of a light with moved[light] > seenMoves (not the environment's entry, not W = 0):
-//   1  (Li', wi', dist', pdf') of the light at the sample's (u, v) seen from the pixel's position; a sample that now faces away, or a pdf'
-//      that is not finite and positive: W = 0
-//   2  pOld, pNew: luminance(Li * bsdf(wi) * sat_dot(n, wi)) of the old and the new sample on the pixel's surface (ris_candidate's g)
-//   3  W = (W * (pNew / pOld)) * (pdfOld / pdf') when pOld and pdfOld are positive and finite, else 0
-//   5  a sample left with W != 0 walks its shadow segment, pos -> pos + wi' * dist', and is cleared when occluded
-// The candidate goes to planes of this kernel's own; the history buffers are not written (with a moving camera two pixels read one slot).
-// Registers: everything but W and the index is stored before the walk, which then carries what k_shadow's carries.
-struct RetargetOut { float4* li; float4* wi; float4* rec; int* flag; };
-__global__ void __launch_bounds__(256, RS_WALK_WAVES) k_retarget(DevScene s, SurfPlanes sp, GBufView g, ResvPlanes last, const float4* recLast, const uint32_t* moved,
-                                                                 uint32_t seenMoves, int envId, RetargetOut out, int width, int y0, int y1, int tilesX,
-                                                                 unsigned long long* rayCount, unsigned long long* stats) {
-    RS_SETPRIO(RS_PRIO_WALK);
-    int x, y;
-    const int lane = pixel_of_lane(tilesX, y0, x, y);
-    const bool inside = x < width && y < y1;
-    const int index = inside ? y * width + x : 0;
-    const float4 pm = inside ? sp.posMat[index] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const int mk = __float_as_int(pm.w);
-    const bool shaded = inside && mk_kind(mk) == kKindShaded;
-    const f3 pos = mk3(pm.x, pm.y, pm.z);
-    bool take = false;
-    int lastIdx = 0;
-    if (shaded) {                                               // findTemporalNeighbor, as k_temporal
-        const int primId = g.primId[index];
-        lastIdx = g.motion[index];
-        bool diff = false;
-        if (lastIdx < 0) diff = true;
-        else if (primId <= kNullPrim) diff = true;
-        else if (g.lastPrimId[lastIdx] != primId) diff = true;
-        else {
-            const f3 n = ld3(g.normal + (size_t)index * 3), ln = ld3(g.lastNormal + (size_t)lastIdx * 3);
-            const float depth = g.depth[index], pdepth = g.lastDepth[lastIdx];
-            if (abs_dot(n, ln) < .9f || gabs(pdepth - depth) > depth * .1f) diff = true;
-        }
-        take = !diff;
-    }
-    float W = 0.f;
-    f3 wi = splat(0.f);
-    float dist = 0.f;
-    if (take) {
-        const float4 rc = recLast[lastIdx];
-        const int id = __float_as_int(rc.x);
-        W = last.w[lastIdx];
-        take = id >= 0 && id < s.numLights && id != envId && W != 0.f;
-        if (take) take = moved[id] > seenMoves;
-        if (take) {
-            const float4 a = last.li[lastIdx], b = last.wi[lastIdx], nr = sp.norm[index];
-            const f3 oldLi = mk3(a.x, a.y, a.z), oldWi = mk3(b.x, b.y, b.z), norm = mk3(nr.x, nr.y, nr.z);
-            const int type = mk_type(mk);
-            f3 wo = splat(0.f);
-            float roughness = 0.f;
-            if (type == 1) { const float4 w4 = sp.wo[index]; wo = mk3(w4.x, w4.y, w4.z); roughness = w4.w; }
-            f3 Li;
-            float pdf;
-            light_sample_at(s.lights, id, rc.y, rc.z, pos, Li, wi, dist, pdf);
-            if (!(pdf > 0.f) || is_nan_or_inf(pdf)) W = 0.f;                                  // step 1
-            else {
-                const f3 one = splat(1.f);
-                const float pOld = luminance(oldLi * eval_bsdf(type, one, nr.w, roughness, norm, wo, oldWi) * sat_dot(norm, oldWi));
-                const float pNew = luminance(Li * eval_bsdf(type, one, nr.w, roughness, norm, wo, wi) * sat_dot(norm, wi));
-                const float pdfOld = rc.w;
-                if (pOld > 0.f && pdfOld > 0.f && !is_nan_or_inf(pOld) && !is_nan_or_inf(pdfOld)) W = (W * (pNew / pOld)) * (pdfOld / pdf);
-                else W = 0.f;                                                                 // step 3
-            }
-            out.li[index] = make_float4(Li.x, Li.y, Li.z, dist);
-            out.wi[index] = make_float4(wi.x, wi.y, wi.z, W);
-            out.rec[index] = make_float4(rc.x, rc.y, rc.z, pdf);
-        }
-    }
-    if (inside) out.flag[index] = take ? 1 : 0;
-    const bool walk = take && W != 0.f;
-    const bool occluded = trace_occluded_wave(s, pos, pos + wi * dist, walk);                 // every lane of the wave takes part
-    if (walk && occluded) { reinterpret_cast<float*>(out.wi + index)[3] = 0.f; W = 0.f; }    // step 5
-    const unsigned long long bTake = __ballot(take), bWalk = __ballot(walk), bZero = __ballot(take && W == 0.f);
-    if (lane == 0 && bTake) {
-        atomicAdd(stats, (unsigned long long)__popcll(bTake));
-        atomicAdd(stats + 2, (unsigned long long)__popcll(bZero));
-        if (bWalk) {
-            atomicAdd(stats + 1, (unsigned long long)__popcll(bWalk));
-            atomicAdd(rayCount + (blockIdx.x % kRaySub) * kRayStride, (unsigned long long)__popcll(bWalk));
-        }
-    }
+                                                  int first, int reuse, int n0, int n1, unsigned long long* rayWork, unsigned long long* rayDone, MergeLights<LIGHTS> lights) {
+    if constexpr (LIGHTS == 2) temporal_body<SOBOL, 2>(sp, g, last, cur, temp, sampleSeq, looper, first, reuse, n0, n1, rayWork, rayDone, lights.ids, lights.recs);
+    else temporal_body<SOBOL, LIGHTS>(sp, g, last, cur, temp, sampleSeq, looper, first, reuse, n0, n1, rayWork, rayDone, lights.ids, LightRecs{});
 }
 
 // ---- phase B: spatial reuse + shade --------------------------------------------------------------
@@ -1048,11 +904,7 @@ int rs_restir_free(rs_restir* r) {
     rs_dev_free(r->dRayCount);
     for (auto& perStream : r->split) for (auto& t : perStream) rs_tile_split_free(&t);
     rs_dev_free(r->indResv[0]); rs_dev_free(r->indResv[1]);
-    rs_dev_free(r->idCur); rs_dev_free(r->idLast); rs_dev_free(r->idTemp);
-    for (int*& p : r->candId) rs_dev_free(p);
-    rs_dev_free(r->recCur); rs_dev_free(r->recLast); rs_dev_free(r->recTemp);
-    for (float4*& p : r->candRec) rs_dev_free(p);
-    rs_dev_free(r->rtLi); rs_dev_free(r->rtWi); rs_dev_free(r->rtRec); rs_dev_free(r->rtFlag); rs_dev_free(r->dRetarget);
+    rs_light_history_free(r->lights);
     rs_primary_cuts_destroy(r->cuts);
     for (auto& e : r->ev) if (e) (void)hipEventDestroy(e);
     for (auto& pair : r->spatialEv) for (hipEvent_t& e : pair) if (e) (void)hipEventDestroy(e);
@@ -1132,120 +984,6 @@ int rs_restir_set_probe(rs_restir* r, int enable) {
     return 0;
 }
 
-// Light tracking (include/restir_hip.h): the id planes are allocated on the first switch-on; the reservoirs published while tracking was
-// off carry no light index, so every switch-on starts from "unknown" (-1) -- ordered on the library stream like the frames around it.
-int rs_restir_set_light_tracking(rs_restir* r, int enable) {
-    RS_SCOPE(r);
-    if (!r) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_set_light_tracking: null");
-    const bool on = enable != 0;
-    if (on == r->track) return 0;
-    if (on) {
-        const size_t n = (size_t)r->width * r->height;
-        if (!r->idCur) {
-            RS_TRY(rs_dev_alloc(&r->idCur, n)); RS_TRY(rs_dev_alloc(&r->idLast, n)); RS_TRY(rs_dev_alloc(&r->idTemp, n));
-            for (int*& p : r->candId) RS_TRY(rs_dev_alloc(&p, n));
-        }
-        RS_HIP(hipMemsetAsync(r->idCur, 0xff, n * sizeof(int), rs_stream()));
-        RS_HIP(hipMemsetAsync(r->idLast, 0xff, n * sizeof(int), rs_stream()));
-        RS_HIP(hipMemsetAsync(r->idTemp, 0xff, n * sizeof(int), rs_stream()));
-        r->trackSceneId = 0;             // (the RIS winners' planes need no clearing: a frame writes its set before it reads it)
-    }
-    r->track = on;
-    if (!on) r->retarget = false;        // retargeting rides on tracking
-    return rs_after_launch("rs_restir_set_light_tracking");
-}
-
-// Light retargeting (include/restir_hip.h), on top of tracking.  The planes are allocated before anything of the object changes, and
-// `retarget` is set last: a failed allocation leaves it off with nothing changed, and so does a failure of the tracking switch (which
-// leaves tracking as that call leaves it).  A clear that fails to enqueue leaves retargeting off as well.  Every record AND every tracked
-// id starts unknown, in the order of the library stream -- ids that tracking carried so far have no record to go with -- and the next frame
-// takes the scene's count of moves as seen (trackSceneId = 0): nothing that happened before the switch is evaluated again.
-int rs_restir_set_light_retargeting(rs_restir* r, int enable) {
-    RS_SCOPE(r);
-    if (!r) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_set_light_retargeting: null");
-    const bool on = enable != 0;
-    if (on == r->retarget) return 0;
-    if (!on) { r->retarget = false; return 0; }
-    const size_t n = (size_t)r->width * r->height;
-    constexpr int kPlanes = 3 + rs_restir::kSurfSets + 3;
-    float4* f[kPlanes] = {};
-    int* flag = nullptr;
-    unsigned long long* counters = nullptr;
-    const bool fresh = !r->recCur;
-    auto drop = [&]() { for (float4*& p : f) rs_dev_free(p); rs_dev_free(flag); rs_dev_free(counters); };
-    if (fresh) {
-        int e = 0;
-        for (float4*& p : f) if (!e) e = rs_dev_alloc(&p, n);
-        if (!e) e = rs_dev_alloc(&flag, n);
-        if (!e) e = rs_dev_alloc(&counters, 3);
-        if (!e) e = rs_check_hip(hipMemset(counters, 0, 3 * sizeof(unsigned long long)), "memset");
-        if (e) { drop(); return e; }
-    }
-    const bool tracked = r->track;
-    if (!tracked) if (int e = rs_restir_set_light_tracking(r, 1)) { drop(); return e; }
-    if (fresh) {
-        r->recCur = f[0]; r->recLast = f[1]; r->recTemp = f[2];
-        for (int k = 0; k < rs_restir::kSurfSets; k++) r->candRec[k] = f[3 + k];
-        r->rtLi = f[3 + rs_restir::kSurfSets]; r->rtWi = f[4 + rs_restir::kSurfSets]; r->rtRec = f[5 + rs_restir::kSurfSets];
-        r->rtFlag = flag; r->dRetarget = counters;
-    }
-    if (tracked)                          // (a switch-on of tracking has just cleared them)
-        for (int* p : { r->idCur, r->idLast, r->idTemp }) RS_HIP(hipMemsetAsync(p, 0xff, n * sizeof(int), rs_stream()));
-    for (float4* p : { r->recCur, r->recLast, r->recTemp }) RS_HIP(hipMemsetAsync(p, 0xff, n * sizeof(float4), rs_stream()));      // light = -1
-    r->trackSceneId = 0;
-    r->retarget = true;
-    r->rtLaunched = r->rtLaunchedLast = false;
-    return rs_after_launch("rs_restir_set_light_retargeting");
-}
-
-int rs_restir_get_light_retargeting(const rs_restir* r, int* enabled) {
-    if (!r || !enabled) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_get_light_retargeting: null argument");
-    *enabled = r->retarget ? 1 : 0;
-    return 0;
-}
-
-int rs_restir_download_light_samples(const rs_restir* rc, int which, rs_light_sample* host) {
-    RS_SCOPE(rc);
-    rs_restir* r = const_cast<rs_restir*>(rc);
-    if (!r || !host || which < 0 || which > 2) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_download_light_samples: bad argument");
-    const size_t n = (size_t)r->width * r->height;
-    static_assert(sizeof(rs_light_sample) == sizeof(float4), "a record is one 16-byte element of the planes");
-    if (!r->retarget || !r->recCur) { for (size_t i = 0; i < n; i++) host[i] = rs_light_sample{ -1, 0.f, 0.f, 0.f }; return 0; }
-    RS_HIP(hipStreamSynchronize(rs_stream()));
-    RS_HIP(hipMemcpy(host, which == 0 ? r->recCur : which == 1 ? r->recLast : r->recTemp, n * sizeof(float4), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// test hook: what k_retarget did in the frame that rs_restir_end_frame ended last -- { samples re-evaluated, shadow segments walked,
-// samples left with W = 0 }; zeros when that frame did not launch it
-int rs_debug_restir_retarget(rs_restir* r, unsigned long long out[3]) {
-    RS_SCOPE(r);
-    if (!r || !out) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_restir_retarget: null argument");
-    out[0] = out[1] = out[2] = 0;
-    if (!r->retarget || !r->rtLaunchedLast) return 0;
-    RS_HIP(hipStreamSynchronize(rs_stream()));
-    RS_HIP(hipMemcpy(out, r->dRetarget, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// ... and whether that frame launched it at all (a launch that found nothing to evaluate reports zeros too)
-int rs_debug_restir_retarget_launched(rs_restir* r, int* launched) {
-    if (!r || !launched) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_restir_retarget_launched: null argument");
-    *launched = r->retarget && r->rtLaunchedLast ? 1 : 0;
-    return 0;
-}
-
-int rs_restir_download_light_ids(const rs_restir* rc, int which, int* host) {
-    RS_SCOPE(rc);
-    rs_restir* r = const_cast<rs_restir*>(rc);
-    if (!r || !host || which < 0 || which > 2) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_download_light_ids: bad argument");
-    const size_t n = (size_t)r->width * r->height;
-    if (!r->track || !r->idCur) { for (size_t i = 0; i < n; i++) host[i] = -1; return 0; }
-    RS_HIP(hipStreamSynchronize(rs_stream()));
-    RS_HIP(hipMemcpy(host, which == 0 ? r->idCur : which == 1 ? r->idLast : r->idTemp, n * sizeof(int), hipMemcpyDeviceToHost));
-    return 0;
-}
-
 // rs_restir_enable_timing(r, 2): the durations (ms) of the spatial pass in the last frames, oldest first, at most `capacity` and at most the
 // ring's 256; *count = how many.  Waits for the library stream.
 int rs_restir_spatial_times(rs_restir* r, float* ms, int capacity, int* count) {
@@ -1268,46 +1006,31 @@ int rs_restir_spatial_times(rs_restir* r, float* ms, int capacity, int* count) {
 
 namespace {
 // RIS over the light table for rows [y0, y1) on stream st in the form the plan names (RS_RIS_*, rs_frame_plan.h)
-// candId: the winners' light-sampler indices (light tracking), null = not tracked
-// candRec: the winners' records (retargeting, with candId), null = none
-int launch_ris(const rs_scene* scene, const SurfPlanes& sp, int W, int y0, int y1, int looper, bool sobol, hipStream_t st, int form, int* candId, float4* candRec) {
-    const bool track = candId != nullptr;
+// lights, set: the light history and the surface set whose winners' planes the launch writes in the history's mode
+int launch_ris(const rs_scene* scene, const SurfPlanes& sp, int W, int y0, int y1, int looper, bool sobol, hipStream_t st, int form, const rs_light_history& lights, int set) {
     const int npx = (y1 - y0) * W;
     const dim3 grid((npx + kRisThreads - 1) / kRisThreads);
-    if (candRec && form == RS_RIS_LDS)
-        rs_dispatch([&](auto SOBOL) { hipLaunchKernelGGL((k_ris_lds_rec<SOBOL()>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, candId, candRec); }, sobol);
-    else if (candRec && form == RS_RIS_ALIAS_LDS) {
-        static const bool ldsAllowed = []{      // more than 64 KB of dynamic LDS is opt-in
-            bool ok = true;
-            for (const void* k : { reinterpret_cast<const void*>(&k_ris_alias_lds_rec<true>), reinterpret_cast<const void*>(&k_ris_alias_lds_rec<false>) })
+    static const bool ldsAllowed = []{      // more than 64 KB of dynamic LDS is opt-in, for every instantiation of k_ris_alias_lds
+        bool ok = true;
+        for (int mode = 0; mode < 3; mode++) rs_dispatch_lights(mode, [&](auto LIGHTS) {
+            for (const void* k : { reinterpret_cast<const void*>(&k_ris_alias_lds<true, LIGHTS()>), reinterpret_cast<const void*>(&k_ris_alias_lds<false, LIGHTS()>) })
                 ok = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kRisAliasLdsLights * (int)sizeof(AliasRec)) == hipSuccess && ok;
-            (void)hipGetLastError();
-            return ok; }();
-        (void)ldsAllowed;
-        rs_dispatch([&](auto SOBOL) { hipLaunchKernelGGL((k_ris_alias_lds_rec<SOBOL()>), grid, dim3(kRisThreads), (size_t)scene->numLights * sizeof(AliasRec), st, scene->dev, sp, W, y0, y1, looper, candId, candRec); }, sobol);
-    }
-    else if (candRec)
-        rs_dispatch([&](auto ENV, auto SOBOL) { hipLaunchKernelGGL((k_ris_rec<ENV(), SOBOL()>), dim3((npx + 255) / 256), dim3(256), 0, st, scene->dev, sp, W, y0, y1, looper, candId, candRec); },
-                    scene->envMapTexId >= 0, sobol);
-    else if (form == RS_RIS_LDS)
-        // (one block per CU instead of two -- half of the wave slots left to the latency-bound kernels of the other streams -- measured
-        // slower: frame 1.088 -> 1.142 ms, profiles/r03_ab_ris_blocks_per_cu.log)
-        rs_dispatch([&](auto SOBOL, auto TRACK) { hipLaunchKernelGGL((k_ris_lds<SOBOL(), TRACK()>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, candId); }, sobol, track);
-    else if (form == RS_RIS_ALIAS_LDS) {
-        const size_t lds = (size_t)scene->numLights * sizeof(AliasRec);
-        static const bool ldsAllowed = []{      // more than 64 KB of dynamic LDS is opt-in
-            bool ok = true;
-            for (const void* k : { reinterpret_cast<const void*>(&k_ris_alias_lds<true, false>), reinterpret_cast<const void*>(&k_ris_alias_lds<false, false>),
-                                   reinterpret_cast<const void*>(&k_ris_alias_lds<true, true>), reinterpret_cast<const void*>(&k_ris_alias_lds<false, true>) })
-                ok = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kRisAliasLdsLights * (int)sizeof(AliasRec)) == hipSuccess && ok;
-            (void)hipGetLastError();
-            return ok; }();
-        (void)ldsAllowed;
-        rs_dispatch([&](auto SOBOL, auto TRACK) { hipLaunchKernelGGL((k_ris_alias_lds<SOBOL(), TRACK()>), grid, dim3(kRisThreads), lds, st, scene->dev, sp, W, y0, y1, looper, candId); }, sobol, track);
-    }
-    else                               // the environment map is one more light (scene.h:400-403)
-        rs_dispatch([&](auto ENV, auto SOBOL, auto TRACK) { hipLaunchKernelGGL((k_ris<ENV(), SOBOL(), TRACK()>), dim3((npx + 255) / 256), dim3(256), 0, st, scene->dev, sp, W, y0, y1, looper, candId); },
-                    scene->envMapTexId >= 0, sobol, track);
+        });
+        (void)hipGetLastError();
+        return ok; }();
+    (void)ldsAllowed;
+    rs_dispatch_lights(rs_light_mode(lights), [&](auto LIGHTS) {
+        const RisWinners<LIGHTS()> win = rs_light_history_winners<LIGHTS()>(lights, set);
+        if (form == RS_RIS_LDS)
+            // (one block per CU instead of two -- half of the wave slots left to the latency-bound kernels of the other streams -- measured
+            // slower: frame 1.088 -> 1.142 ms, profiles/r03_ab_ris_blocks_per_cu.log)
+            rs_dispatch([&](auto SOBOL) { hipLaunchKernelGGL((k_ris_lds<SOBOL(), LIGHTS()>), grid, dim3(kRisThreads), 0, st, scene->dev, sp, W, y0, y1, looper, win); }, sobol);
+        else if (form == RS_RIS_ALIAS_LDS)
+            rs_dispatch([&](auto SOBOL) { hipLaunchKernelGGL((k_ris_alias_lds<SOBOL(), LIGHTS()>), grid, dim3(kRisThreads), (size_t)scene->numLights * sizeof(AliasRec), st, scene->dev, sp, W, y0, y1, looper, win); }, sobol);
+        else                               // the environment map is one more light (scene.h:400-403)
+            rs_dispatch([&](auto ENV, auto SOBOL) { hipLaunchKernelGGL((k_ris<ENV(), SOBOL(), LIGHTS()>), dim3((npx + 255) / 256), dim3(256), 0, st, scene->dev, sp, W, y0, y1, looper, win); },
+                        scene->envMapTexId >= 0, sobol);
+    });
     return 0;
 }
 
@@ -1413,8 +1136,7 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     }
     mark(r, 1);
     const int npx = (y1 - y0) * W;
-    RS_TRY(launch_ris(scene, sp, W, y0, y1, looper, sobol, st, p.risForm, r->track ? r->candId[r->surfSet] : nullptr,
-                      r->retarget ? r->candRec[r->surfSet] : nullptr));
+    RS_TRY(launch_ris(scene, sp, W, y0, y1, looper, sobol, st, p.risForm, r->lights, r->surfSet));
     mark(r, 2);
     // (the shadow rays of a launch that fills the chip several times over go to the library stream: rs_frame_plan.h)
     if (!p.shadowOnLibrary) hipLaunchKernelGGL(k_shadow, dim3(tilesX * tilesY), dim3(256), 0, st, scene->dev, sp, W, y0, y1, tilesX);
@@ -1427,46 +1149,14 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     if (p.cut == 1) RS_TRY(rs_primary_cuts_build(r->cuts, scene, cp, y0, tilesX, tilesY, st));
     if (p.shadowOnLibrary) hipLaunchKernelGGL(k_shadow, dim3(tilesX * tilesY), dim3(256), 0, rs_stream(), scene->dev, sp, W, y0, y1, tilesX);
     RS_TRY(rs_gbuffer_join(g));                                 // first consumer of the G-buffer planes
-    LightIds ids{ nullptr, nullptr, nullptr, nullptr, nullptr, 0, -1 };
-    if (r->track) {
-        // the light indices of another scene's reservoirs name other lights: unknown from here on
-        if (r->trackSceneId != scene->id) {
-            RS_HIP(hipMemsetAsync(r->idLast, 0xff, (size_t)W * r->height * sizeof(int), rs_stream()));
-            RS_HIP(hipMemsetAsync(r->idTemp, 0xff, (size_t)W * r->height * sizeof(int), rs_stream()));
-            if (r->retarget) {
-                RS_HIP(hipMemsetAsync(r->recLast, 0xff, (size_t)W * r->height * sizeof(float4), rs_stream()));
-                RS_HIP(hipMemsetAsync(r->recTemp, 0xff, (size_t)W * r->height * sizeof(float4), rs_stream()));
-            }
-            r->trackSceneId = scene->id;
-            r->seenMoves = scene->lightMoves;                   // (no record names a light of this scene yet)
-        }
-        ids = LightIds{ r->candId[r->surfSet], r->idLast, r->idCur, r->idTemp, scene->dev.lights, scene->numLights, scene->envMapTexId >= 0 ? scene->numLights - 1 : -1 };
-    }
-    if (r->retarget) {
-        // Lamps moved since the previous frame: their samples are evaluated again before the merge, on the library stream behind the
-        // chain's join.  A frame after which none moved launches nothing extra (the merge's retargeting form carries the records).
-        r->frameMoves = scene->lightMoves;
-        const bool moved = !r->firstFrame && (reuse & 1) && scene->lightMoves != r->seenMoves;
-        LightRecs recs{ r->candRec[r->surfSet], r->recLast, r->recCur, r->recTemp, r->rtLi, r->rtWi, r->rtRec, moved ? r->rtFlag : nullptr };
-        if (moved) {
-            if (!r->rtLaunched) {
-                RS_HIP(hipMemsetAsync(r->dRetarget, 0, 3 * sizeof(unsigned long long), rs_stream()));
-                r->rtLaunched = true;
-            }
-            hipLaunchKernelGGL(k_retarget, dim3(tilesX * tilesY), dim3(256), 0, rs_stream(), scene->dev, sp, gbuf_view(g), r->last, r->recLast,
-                               scene->ver[scene->verCur].moved, (uint32_t)r->seenMoves, ids.envId, RetargetOut{ r->rtLi, r->rtWi, r->rtRec, r->rtFlag },
-                               W, y0, y1, tilesX, rayCounter, r->dRetarget);
-        }
+    LightIds ids; LightRecs recs;
+    RS_TRY(rs_light_history_phase_a(r->lights, scene, r->surfSet, !r->firstFrame && (reuse & 1), sp, gbuf_view(g), r->last, y0, y1, tilesX, tilesY, rayCounter, &ids, &recs));
+    rs_dispatch_lights(rs_light_mode(r->lights), [&](auto LIGHTS) {
         rs_dispatch([&](auto SOBOL) {
-            hipLaunchKernelGGL((k_temporal_retarget<SOBOL()>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g),
-                               r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, ids, recs);
+            hipLaunchKernelGGL((k_temporal<SOBOL(), LIGHTS()>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g), r->last, r->cur, r->temp,
+                               scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, merge_lights<LIGHTS()>(ids, recs));
         }, sobol);
-    }
-    else
-    rs_dispatch([&](auto SOBOL, auto TRACK) {
-        hipLaunchKernelGGL((k_temporal<SOBOL(), TRACK()>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g),
-                           r->last, r->cur, r->temp, scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, ids);
-    }, sobol, r->track);
+    });
     mark(r, 3);
     return last ? rs_after_launch("ReSTIR Direct (phase A)") : rs_check_hip(hipGetLastError(), "ReSTIR Direct (phase A)");
 }
@@ -1589,10 +1279,7 @@ int rs_restir_end_frame(rs_restir* r) {
     RS_SCOPE(r);
     if (!r) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_end_frame: null");
     ResvPlanes t = r->cur; r->cur = r->last; r->last = t;       // std::swap(devDirectReservoir, devLastDirectReservoir)
-    int* ti = r->idCur; r->idCur = r->idLast; r->idLast = ti;   // (light tracking: the reservoirs' light indices travel with them)
-    float4* tr = r->recCur; r->recCur = r->recLast; r->recLast = tr;      // (retargeting: so do their records)
-    if (r->retarget && r->phaseACalls > 0) r->seenMoves = r->frameMoves;
-    r->rtLaunchedLast = r->rtLaunched; r->rtLaunched = false;
+    rs_light_history_end_frame(r->lights, r->phaseACalls);
     r->firstFrame = false;
     // every reader of this frame's surface planes has been enqueued: the set is free for the frame after the next one
     if (!rs_sync_enabled()) { RS_HIP(hipEventRecord(r->surfFree[r->surfSet], rs_stream())); r->surfFreeValid[r->surfSet] = true; }
@@ -1632,8 +1319,8 @@ int copy_rows(rs_restir* r, int which, int y0, int rows, char* buf, bool pack, c
 }
 // the light-id plane of buffer `which`: one launch of the copy kernel (refusals: see rs_restir_light_rows_bytes below)
 int copy_light_rows(rs_restir* r, int which, int y0, int rows, char* buf, bool pack, const char* what) {
-    if (r && r->retarget) return rs_fail(RS_ERR_UNSUPPORTED, "rs_restir_light_rows_pack / _unpack: light retargeting is on, and 4 B/px do not carry its records");
-    if (!r || !buf || ((size_t)buf & 3) || which < 0 || which > 2 || y0 < 0 || rows < 0 || y0 + rows > r->height || !r->track || !r->idCur) return rs_fail(RS_ERR_INVALID_ARGUMENT, what);
+    if (r && rs_light_mode(r->lights) == RS_LIGHTS_RECORDS) return rs_fail(RS_ERR_UNSUPPORTED, "rs_restir_light_rows_pack / _unpack: light retargeting is on, and 4 B/px do not carry its records");
+    if (!r || !buf || ((size_t)buf & 3) || which < 0 || which > 2 || y0 < 0 || rows < 0 || y0 + rows > r->height || rs_light_mode(r->lights) == RS_LIGHTS_OFF || !rs_light_id_plane(r->lights, 0)) return rs_fail(RS_ERR_INVALID_ARGUMENT, what);
     rs_rows::SegList l(pack);
     rs_rows::add_rows(l, rs_rows::light_id_plane(r, which), y0, rows, buf);
     RS_TRY(rs_copy::copy_segments(l));
@@ -1724,12 +1411,8 @@ int rs_restir_upload(rs_restir* r, int which, const rs_reservoir* host) {
         RS_HIP(hipMemcpy(p->wi, wi.data(), n * 16, hipMemcpyHostToDevice));
         RS_HIP(hipMemcpy(p->w, w.data(), n * 4, hipMemcpyHostToDevice));
         RS_HIP(hipMemcpy(p->m, m.data(), n * 4, hipMemcpyHostToDevice));
-        if (r->track) RS_HIP(hipMemset(which == 0 ? r->idCur : r->idLast, 0xff, n * sizeof(int)));     // uploaded samples: light unknown
-        if (r->retarget) RS_HIP(hipMemset(which == 0 ? r->recCur : r->recLast, 0xff, n * sizeof(float4)));
     }
-    if (which == 2 && r->track) RS_HIP(hipMemset(r->idTemp, 0xff, n * sizeof(int)));
-    if (which == 2 && r->retarget) RS_HIP(hipMemset(r->recTemp, 0xff, n * sizeof(float4)));
-    return 0;
+    return rs_light_history_forget(r->lights, n, 1u << which, true);          // uploaded samples: light unknown
 }
 
 // test hook: sqrt_of_uniform (rs_surface.h) against the compiler's exactly rounded sqrtf on EVERY value Rng::uniform() can return

@@ -584,6 +584,32 @@ int  rs_primary_cuts_launched(rs_primary_cuts& c, int k, hipStream_t st);
 int  rs_primary_cuts_build(rs_primary_cuts& c, const rs_scene* scene, const rs::CamParams& cp, int y0, int tilesX, int tilesY, hipStream_t st);
 void rs_primary_cuts_destroy(rs_primary_cuts& c);
 
+// Light tracking and retargeting of one rs_restir (include/restir_hip.h); light_history.hip owns every field.  ids
+// (rs_restir_set_light_tracking): the light-sampler index of every reservoir's sample, -1 = not known, allocated when tracking is first
+// switched on.  records (rs_restir_set_light_retargeting, on top of the ids): a 16-byte record { light, u, v, pdf } beside each id, and
+// the planes k_retarget leaves the re-evaluated temporal candidates in; allocated when retargeting is first switched on.
+enum { RS_LIGHTS_OFF = 0, RS_LIGHTS_IDS = 1, RS_LIGHTS_RECORDS = 2 };
+struct rs_light_history {
+    int mode = RS_LIGHTS_OFF;
+    int* id[3] = {}; float4* rec[3] = {};      // by the public `which`: 0 cur, 1 last (swapped with the reservoirs), 2 the published copy (TempPlanes)
+    int* candId[RS_SURF_SETS] = {}; float4* candRec[RS_SURF_SETS] = {};      // of the RIS winners, one plane per surface set
+    unsigned long long sceneId = 0;        // the scene whose light indices id[1] holds (rs_scene::id; 0 = none yet)
+    float4 *rtLi = nullptr, *rtWi = nullptr, *rtRec = nullptr;      // re-evaluated candidate: { Li xyz, dist }, { wi xyz, W }, its record
+    int* rtFlag = nullptr;           // 1: the pixel's temporal candidate is the one in the three planes above
+    unsigned long long seenMoves = 0;      // the scene's lightMoves at the previous frame (forgotten with sceneId)
+    unsigned long long frameMoves = 0;     // ... at this frame's phase-A calls: seenMoves of the next frame (rs_light_history_end_frame)
+    unsigned long long* dRetarget = nullptr;   // { re-evaluated, segments, zeroed } of the last frame that launched k_retarget: cleared, added to and read in the library stream's order
+    bool rtLaunched = false, rtLaunchedLast = false;     // this frame / the frame that ended last launched k_retarget
+};
+// What restir.hip, rs_row_layouts.h and strips.hip ask of light_history.hip (phase_a_impl's call: rs_light_history.h).  forget: the
+// planes of the buffers in `which` (bit k: buffer k as above) become unknown -- `planes` bit 0 the ids, bit 1 the records, -1 what the
+// mode has -- with hipMemset (blocking: rs_restir_upload, behind its blocking copies) or in the library stream's order.
+inline int  rs_light_mode(const rs_light_history& h) { return h.mode; }
+inline int* rs_light_id_plane(const rs_light_history& h, int which) { return h.id[which]; }
+int  rs_light_history_forget(rs_light_history& h, size_t pixels, unsigned which, bool blocking, int planes = -1);
+void rs_light_history_end_frame(rs_light_history& h, int phaseACalls);      // cur and last change places, as the reservoirs'
+void rs_light_history_free(rs_light_history& h);
+
 struct rs_restir {
     rs_context* ctx = nullptr;
     rs_primary_cuts cuts;
@@ -633,30 +659,7 @@ struct rs_restir {
     hipEvent_t spatialEv[kSpatialRing][2] = {};     // timing 2: the spatial pass of the last frames between two events each (rs_restir_spatial_times)
     int spatialNext = 0;
     bool probe = false;              // the spatial pass goes out as k_spatial_shade_probe (rs_restir_set_probe)
-    // rs_restir_set_light_tracking: the light-sampler index of every reservoir's sample, carried with cur / last (swapped with them),
-    // and of every RIS winner (one plane per surface set).  Allocated when tracking is switched on; -1 = not known.
-    bool track = false;
-    int* idCur = nullptr;
-    int* idLast = nullptr;
-    int* idTemp = nullptr;           // of the published copy (TempPlanes) the spatial pass gathers from
-    int* candId[kSurfSets] = {};
-    unsigned long long trackSceneId = 0;   // the scene whose light indices idLast holds (rs_scene::id; 0 = none yet)
-    // rs_restir_set_light_retargeting, on top of tracking: a 16-byte record { light, u, v, pdf } beside every reservoir's sample (cur /
-    // last, swapped with them; the published copy) and every RIS winner (one plane per surface set), and the planes k_retarget leaves
-    // the re-evaluated temporal candidates in.  Allocated when retargeting is first switched on.
-    bool retarget = false;
-    float4* recCur = nullptr;
-    float4* recLast = nullptr;
-    float4* recTemp = nullptr;
-    float4* candRec[kSurfSets] = {};
-    float4* rtLi = nullptr;          // re-evaluated candidate: Li xyz, dist
-    float4* rtWi = nullptr;          // wi xyz, W
-    float4* rtRec = nullptr;         // its record
-    int* rtFlag = nullptr;           // 1: the pixel's temporal candidate is the one in the three planes above
-    unsigned long long seenMoves = 0;      // the scene's lightMoves at the previous frame (forgotten with trackSceneId)
-    unsigned long long frameMoves = 0;     // ... at this frame's phase-A calls: seenMoves of the next frame (rs_restir_end_frame)
-    unsigned long long* dRetarget = nullptr;   // { re-evaluated, segments, zeroed } of the last frame that launched k_retarget: cleared, added to and read in the library stream's order
-    bool rtLaunched = false, rtLaunchedLast = false;     // this frame / the frame that ended last launched k_retarget
+    rs_light_history lights;         // light tracking and retargeting (light_history.hip)
 };
 
 static_assert(rs_context::kAux >= 1 + rs_restir::kChains, "one auxiliary stream for GBuffer::render and one per chain");

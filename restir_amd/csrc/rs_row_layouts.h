@@ -39,7 +39,7 @@ inline Planes gbuffer_planes(rs_gbuffer* g, int set) {
 }
 // the light-id plane that goes with reservoir buffer `which` 0 / 1 / 2 (light tracking) -- 4 B/px
 inline Planes light_id_plane(rs_restir* r, int which) {
-    return { r ? r->width : 0, 1, { { !r ? nullptr : which == 0 ? r->idCur : which == 1 ? r->idLast : r->idTemp, 4 } } };
+    return { r ? r->width : 0, 1, { { r ? rs_light_id_plane(r->lights, which) : nullptr, 4 } } };
 }
 
 // Rows [y, y + rows) of every plane of `planes` against a packed buffer: plane after plane from `packed` on; returns the address after the

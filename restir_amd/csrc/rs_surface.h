@@ -246,7 +246,7 @@ __device__ __forceinline__ void light_sample_again(LightPtr lights, int id, floa
 
 // The whole sample of light `id` at the barycentric pair (u, v) seen from pos: sample_light_with's expressions from `sampled` on, in its
 // order, with operations that give the IEEE results for every operand -- so a pair that the sampler drew gives the sampler's bits, and a
-// pair kept from an earlier frame is evaluated on the light records of this one (restir.hip k_retarget).  A sample that fails the facing
+// pair kept from an earlier frame is evaluated on the light records of this one (light_history.hip k_retarget).  A sample that fails the facing
 // test leaves as sample_light_with's early exit does: pdf = kInvalidPdf, Li = wi = 0, dist = 0.
 template <typename LightPtr>
 __device__ __forceinline__ void light_sample_at(LightPtr lights, int id, float u, float v, f3 pos, f3& Li, f3& wi, float& dist, float& pdf) {

@@ -131,9 +131,10 @@ void history_segments(SegList& l, rs_restir* r, rs_gbuffer* g, bool track, int y
 // the driver's setting and the rs_restir it is handed must agree: the setting is the size of the history messages
 int check_tracking(const rs_strips* s, const rs_restir* r, const char* unsupported, const char* mismatch) {
     // (light retargeting: its 16-byte records do not fit the 4 B/px the messages carry for tracking)
-    if (r->retarget) return rs_fail(RS_ERR_UNSUPPORTED, "rs_strips_frame / rs_strips_exchange_history: light retargeting (rs_restir_set_light_retargeting) is not supported by the strip driver");
-    if (r->track && !s->track) return rs_fail(RS_ERR_UNSUPPORTED, unsupported);
-    if (!r->track && s->track) return rs_fail(RS_ERR_INVALID_ARGUMENT, mismatch);
+    const int lights = rs_light_mode(r->lights);
+    if (lights == RS_LIGHTS_RECORDS) return rs_fail(RS_ERR_UNSUPPORTED, "rs_strips_frame / rs_strips_exchange_history: light retargeting (rs_restir_set_light_retargeting) is not supported by the strip driver");
+    if (lights != RS_LIGHTS_OFF && !s->track) return rs_fail(RS_ERR_UNSUPPORTED, unsupported);
+    if (lights == RS_LIGHTS_OFF && s->track) return rs_fail(RS_ERR_INVALID_ARGUMENT, mismatch);
     return 0;
 }
 

@@ -141,7 +141,7 @@ def test_tracking_switched_off_and_on_mid_run(hip, sampler):
 
 def test_one_restir_two_scenes(hip):
     """An rs_restir that renders scene A, then scene B (the same geometry, other lamps): B's first frame must not take A's light indices
-    for its own (rs_restir::trackSceneId).  Then A again."""
+    for its own (rs_light_history::sceneId).  Then A again."""
     sd = scene_data("sponza:0.125")
     W, H = 160, 96
     p = Pair(hip, sd, W, H, track=True)

@@ -2,7 +2,7 @@
 """tools/ris_loop_isa.py [file.s ...] -- the instructions a wave executes per pass of every innermost loop of one kernel, counted in the
 compiler's assembly (no GPU needed): all of them, without s_nop / s_waitcnt, the vector ones, and the 64-bit multiply-adds.
 
-Default kernel: k_ris_lds<false,false>, whose three loops are, in the order printed, the candidate loop of a wave with metallic lanes, the
+Default kernel: k_ris_lds<false, 0> (minstd, the light history off), whose three loops are, in the order printed, the candidate loop of a wave with metallic lanes, the
 candidate loop of a wave of Lambertian pixels alone, and the draws-only loop of an empty light table (EXPERIMENTS.md, "One range guard per
 RIS candidate" and "The generator on its state minus one": 331 / 202 / 34 before the latter, 321 / 191 / 28 after it).  A loop's body is
 the lines from its header label to its last back-branch: the path on which no branch but the loop's own is taken, i.e. every guard
@@ -15,7 +15,7 @@ The assembly of a source, with the library's flags (restir_amd/csrc/Makefile):
 import re
 import sys
 
-DEFAULT = "_ZN12_GLOBAL__N_19k_ris_ldsILb0ELb0EEEvN2rs8DevSceneENS_10SurfPlanesEiiiiPi"
+DEFAULT = "_ZN12_GLOBAL__N_19k_ris_ldsILb0ELi0EEEvN2rs8DevSceneENS1_10SurfPlanesEiiiiNS1_10RisWinnersIXT0_EEE"     # k_ris_lds<false, 0>
 
 
 def kernel(path, name):
