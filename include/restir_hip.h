@@ -153,7 +153,7 @@ int  rs_set_stream(void* hipStream);
 /* The streams the library makes for itself in overlapped mode (three: the chains of consecutive frames and the render) are CHOSEN BY
  * MEASUREMENT when first needed, and again after rs_set_stream: whether four streams of a process run side by side depends on every
  * stream the process has made before (torch's pool, an ncclComm's own), so candidates of every priority level are timed next to the
- * caller's stream and the best three kept (about 25 ms, once, with the device idle; api_common.hip).  This call names the PREFERRED level
+ * caller's stream and the best three kept (about 25 ms, once, with the device idle; internal_streams.hip).  This call names the PREFERRED level
  * among those that measure equal: 2 (default) = automatic, above the caller's stream first; -1 high / 0 normal / 1 low first.  A caller
  * that runs a denoiser on the library stream every frame does 5 % better with 1 (config 5: 1.87 -> 1.78 ms).  Before the first frame. */
 int  rs_set_internal_stream_priority(int level);
@@ -728,6 +728,41 @@ typedef struct rs_primary_cut_sizes { int numCells; unsigned capacity; int numTi
  * cells, records, tiles (0: no lists), list records. */
 int  rs_debug_plan_primary_cut_slot(int on, int capturing, rs_primary_cut_slot* slot, const rs_primary_cut_key* key, int tilesX, int tilesY,
                                     int* cutState, rs_primary_cut_sizes* sizes);
+/* The choice of the internal streams as plain data (restir_amd/csrc/rs_stream_choice.h; rs_set_internal_stream_priority above says what
+ * is chosen).  Levels: 0 high, 1 normal, 2 low.  Stream handles are opaque here.  A choice is the internal streams made for one caller
+ * stream under one level key (the asked level -1 / 0 / 1, or 2 for automatic), the priority they were made at and, when they were chosen by
+ * measurement, the chosen streams' time and the fastest candidates' (zeros: plain streams).  The state is the current choice, what it
+ * holds, what the next use has to do first, and the choices kept for other callers and keys, oldest first. */
+#ifndef RS_AUX_STREAMS
+#define RS_AUX_STREAMS 3
+#endif
+#define RS_STREAM_CHOICES_KEPT 4
+#define RS_STREAMS_HELD_NONE     0   /* no stream made yet */
+#define RS_STREAMS_HELD_MEASURED 1   /* chosen by measurement */
+#define RS_STREAMS_HELD_PLAIN    2   /* nothing could be measured: made one by one at the level the rule names */
+#define RS_STREAMS_PENDING_NONE         0
+#define RS_STREAMS_PENDING_AGAIN        1   /* another caller stream or preference: choose again on next use, keep what was measured */
+#define RS_STREAMS_PENDING_AGAIN_FORGET 2   /* rs_choose_internal_streams_again: the kept choices go as well */
+typedef struct rs_stream_choice { void* caller; int levelKey; void* stream[RS_AUX_STREAMS]; int priority; double chosenUs, fastestUs; } rs_stream_choice;
+typedef struct rs_stream_choices { rs_stream_choice current; int held, pending, numKept; rs_stream_choice kept[RS_STREAM_CHOICES_KEPT]; } rs_stream_choices;
+typedef struct rs_stream_choice_inputs {
+    int least, greatest;        /* the device's stream priority range (hipDeviceGetStreamPriorityRange) */
+    int asked;                  /* -1 / 0 / 1, 2 = automatic */
+    int callerHasStream, callerPriority;   /* the library stream is not the default stream; its priority */
+    double timesUs[3][4];       /* per level: the time of the triple "all four candidates but this one"; levels not in the order are not read */
+} rs_stream_choice_inputs;
+typedef struct rs_stream_choice_plan {
+    int order[3], numLevels;    /* the levels that are measured, preferred first */
+    int level, skip;            /* the level chosen and the candidate left out; -1, -1: nothing chosen */
+    double fastestUs;
+    int plainPriority;          /* the priority of plain streams */
+} rs_stream_choice_plan;
+/* Test hooks, host only.  The first evaluates the level order, the pick among measured times and the priority of plain streams.  The
+ * second is what the first use after a change does to the state: the current choice is kept (measured) or released (plain, or forget:
+ * then every kept one too), the oldest kept choice is released when a fifth arrives, and a kept choice for (caller, levelKey) becomes
+ * current.  released[RS_STREAM_CHOICES_KEPT + 1]: the choices whose streams the caller has to destroy. */
+int  rs_debug_plan_stream_choice(const rs_stream_choice_inputs* in, rs_stream_choice_plan* out);
+int  rs_debug_plan_stream_switch(rs_stream_choices* state, int forget, void* caller, int levelKey, rs_stream_choice* released, int* numReleased);
 /* Test hook: the per-pixel state the primary rays of the last ended frame left for the later passes (host arrays of width * height
  * pixels): 4 floats { hit position, tag bits }, 4 floats { shading normal, metallic }, 2 words { sampler state, tag }.  Waits for the
  * device. */

@@ -11,6 +11,7 @@ import numpy as np
 
 from .ctypes_structs import Camera, Material, Reservoir, MATERIAL_DTYPE, RESERVOIR_DTYPE, INDIRECT_RESERVOIR_DTYPE, LIGHT_SAMPLE_DTYPE, copy_camera
 from .ctypes_structs import GeometryEditLights, GeometryEditPlan, GeometryEditView
+from .ctypes_structs import STREAM_CHOICES_KEPT, StreamChoice, StreamChoiceInputs, StreamChoicePlan, StreamChoices
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RESTIR_HIP_LIB") or os.path.join(_HERE, "librestir_hip.so")   # env override: A/B builds
@@ -142,6 +143,8 @@ class PrimaryCutSizes(C.Structure):
 
 
 CUT_ARENA_NOTHING, CUT_ARENA_NO_MEMORY, CUT_ARENA_BUILT = 0, 1, 2
+STREAMS_HELD_NONE, STREAMS_HELD_MEASURED, STREAMS_HELD_PLAIN = 0, 1, 2
+STREAMS_PENDING_NONE, STREAMS_PENDING_AGAIN, STREAMS_PENDING_AGAIN_FORGET = 0, 1, 2
 
 
 # every symbol include/restir_hip.h declares; tests check that the library exports all of them
@@ -153,7 +156,7 @@ EXPORTS = [
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
     "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_set_light_retargeting", "rs_restir_get_light_retargeting", "rs_restir_download_light_samples", "rs_debug_restir_retarget", "rs_debug_restir_retarget_launched", "rs_debug_restir_surface_wo", "rs_scene_light_moves", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
-    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_restir_set_primary_leaf_lists", "rs_debug_set_primary_leaf_list_cap", "rs_debug_primary_leaf_list_info", "rs_debug_primary_leaf_list_missing", "rs_debug_plan_primary_leaf_list", "rs_debug_plan_primary_cut", "rs_debug_plan_primary_cut_slot", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
+    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_restir_set_primary_leaf_lists", "rs_debug_set_primary_leaf_list_cap", "rs_debug_primary_leaf_list_info", "rs_debug_primary_leaf_list_missing", "rs_debug_plan_primary_leaf_list", "rs_debug_plan_primary_cut", "rs_debug_plan_primary_cut_slot", "rs_debug_plan_stream_choice", "rs_debug_plan_stream_switch", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
     "rs_path_trace", "rs_path_trace_indirect", "rs_restir_indirect", "rs_restir_download_indirect",
     "rs_svgf_create", "rs_svgf_destroy", "rs_svgf_filter", "rs_svgf_next_frame", "rs_svgf_get_view",
     "rs_copy_image_to_pbo", "rs_copy_image2_to_pbo", "rs_copy_imagef_to_pbo", "rs_copy_imagei_to_pbo", "rs_eaw_create", "rs_eaw_destroy", "rs_eaw_set_params", "rs_eaw_get_params", "rs_eaw_set_tiled", "rs_eaw_set_fused", "rs_svgf_set_params", "rs_svgf_get_params", "rs_svgf_set_tiled", "rs_svgf_set_fused", "rs_eaw_filter", "rs_eaw_positions_rows", "rs_eaw_level_rows", "rs_modulate_albedo",
@@ -284,6 +287,8 @@ def lib():
     L.rs_debug_plan_primary_leaf_list.argtypes = [vp, ci, ci, ci, vp, C.POINTER(vp * 6), ci, C.POINTER(ci), C.POINTER(ci), vp]
     L.rs_debug_plan_primary_cut.argtypes = [vp, ci, ci, ci, ci, ci, vp, C.POINTER(vp * 6), ci, C.POINTER(ci), C.POINTER(ci), vp, vp]
     L.rs_debug_plan_primary_cut_slot.argtypes = [ci, ci, C.POINTER(PrimaryCutSlot), C.POINTER(PrimaryCutKey), ci, ci, C.POINTER(ci), C.POINTER(PrimaryCutSizes)]
+    L.rs_debug_plan_stream_choice.argtypes = [C.POINTER(StreamChoiceInputs), C.POINTER(StreamChoicePlan)]
+    L.rs_debug_plan_stream_switch.argtypes = [C.POINTER(StreamChoices), ci, vp, ci, C.POINTER(StreamChoice), C.POINTER(ci)]
     L.rs_debug_restir_surface.argtypes = [vp, vp, vp, vp]
     L.rs_pbo_register.argtypes = [C.c_uint, C.POINTER(vp)]
     L.rs_pbo_map.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -585,6 +590,27 @@ def plan_primary_cut_slot(slot, key, on=True, capturing=False, tiles=(1, 1)):
     state, sizes = C.c_int(), PrimaryCutSizes()
     check(lib().rs_debug_plan_primary_cut_slot(int(on), int(capturing), C.byref(slot), C.byref(key), int(tiles[0]), int(tiles[1]), C.byref(state), C.byref(sizes)))
     return state.value, sizes
+
+
+def plan_stream_choice(priority_range, asked=2, caller_priority=None, times_us=None):
+    """rs_debug_plan_stream_choice (host only): priority_range = (least, greatest) of the device, asked -1 / 0 / 1 / 2 = automatic,
+    caller_priority None for the default stream, times_us[3][4] the measured triples (None: all 1.0).  Returns StreamChoicePlan."""
+    i, o = StreamChoiceInputs(), StreamChoicePlan()
+    i.least, i.greatest, i.asked = int(priority_range[0]), int(priority_range[1]), int(asked)
+    i.callerHasStream, i.callerPriority = int(caller_priority is not None), int(caller_priority or 0)
+    for lvl in range(3):
+        for k in range(4):
+            i.timesUs[lvl][k] = 1.0 if times_us is None else float(times_us[lvl][k])
+    check(lib().rs_debug_plan_stream_choice(C.byref(i), C.byref(o)))
+    return o
+
+
+def plan_stream_switch(state, caller, level_key=2, forget=False):
+    """rs_debug_plan_stream_switch (host only): the first use after a change under caller stream `caller` (an opaque integer) and
+    `level_key` meets StreamChoices `state`, which is updated in place.  Returns the list of StreamChoice released."""
+    released, n = (StreamChoice * (STREAM_CHOICES_KEPT + 1))(), C.c_int()
+    check(lib().rs_debug_plan_stream_switch(C.byref(state), int(forget), C.c_void_p(caller), int(level_key), released, C.byref(n)))
+    return [released[k] for k in range(n.value)]
 
 
 # ---- host builders (no GPU needed) ----------------------------------------------------------------

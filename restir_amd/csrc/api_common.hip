@@ -48,238 +48,6 @@ int rs_check_hip(hipError_t e, const char* what) {
 hipStream_t rs_stream() { rs_context* c = rs_ctx(); return c->streamOverride ? c->streamOverride : c->stream; }
 bool rs_sync_enabled() { return rs_ctx()->sync; }
 
-// ---- which streams the library makes for itself ------------------------------------------------------------------------------------
-// In overlapped mode four streams carry work at any time: the caller's (temporal / spatial passes, tone map, the strip driver's
-// transfers) and three of the library's own (the chains of consecutive frames).  Whether four streams of a process really run side by
-// side is decided below the API: the runtime maps streams onto four hardware queues PER PRIORITY LEVEL in the order they are made, the
-// legacy default stream holds one of the normal level's, and how hardware queues share the command processor's pipes depends on every
-// queue the process has made before -- torch's stream pool, an ncclComm's own streams.  Measured on 1/8 strips of 1080p
-// (profiles/r05_ab_stream_priority_pools.log, r05_ab_stream_levels_with_rccl.log): three normal-priority streams next to an ordinary caller
-// stream 0.29 ms per frame instead of 0.19 (five streams on four queues); the same three at high priority 0.19 -- until a one-rank RCCL
-// communicator exists in the process, then 0.39, and only the normal level gives 0.17.  No fixed rule survives all of that, so the
-// streams are CHOSEN BY MEASUREMENT when they are first needed (and again after rs_set_stream): four candidates per level, and for
-// every triple of a level eight rounds of [a 20-us spin on each of the four streams, an event hand-over to the neighbour] are timed
-// (tools/micro/queue_quads.hip is the same test stand-alone: 280-320 us when the four run side by side, 450-860 when two of them take
-// turns).  The best triple within 8 % of the fastest is kept, levels in the order of rs_set_internal_stream_priority's preference
-// (default: above the caller's stream -- the chains are the frame's critical path, config 3 1.071 -> 1.045 ms; with a denoiser on the
-// library stream below it, config 5 1.87 -> 1.78 ms); the other nine streams are destroyed.  About 25 ms, once, with the device idle:
-// the one place where the overlapped mode waits on the host.
-namespace {
-__global__ void k_calibration_spin(long long ticks) {
-    const long long t0 = wall_clock64();                                // 100 MHz
-    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-}
-struct Calibration {
-    static constexpr int kMax = 8;
-    hipEvent_t begin = nullptr, end[kMax] = {}, hand[8][kMax] = {};
-    bool ok = true;
-    Calibration() {
-        ok = hipEventCreate(&begin) == hipSuccess;
-        for (auto& e : end) ok = ok && hipEventCreate(&e) == hipSuccess;
-        for (auto& r : hand) for (auto& e : r) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-    }
-    ~Calibration() {
-        if (begin) (void)hipEventDestroy(begin);
-        for (auto& e : end) if (e) (void)hipEventDestroy(e);
-        for (auto& r : hand) for (auto& e : r) if (e) (void)hipEventDestroy(e);
-        (void)hipGetLastError();
-    }
-    // microseconds until all n streams have finished their eight rounds (best of three), or a negative value on error
-    double chained(const hipStream_t* s, int n = 4) {
-        double best = 1e30;
-        for (int rep = 0; rep < 3; rep++) {
-            for (int k = 0; k < n; k++) if (hipStreamSynchronize(s[k]) != hipSuccess) return -1;      // (these streams only: other contexts' work goes on)
-            (void)hipEventRecord(begin, s[0]);
-            for (int r = 0; r < 8; r++) {
-                for (int k = 0; k < n; k++) { hipLaunchKernelGGL(k_calibration_spin, dim3(1), dim3(64), 0, s[k], 2000); (void)hipEventRecord(hand[r][k], s[k]); }
-                for (int k = 0; k < n; k++) (void)hipStreamWaitEvent(s[k], hand[r][(k + 1) % n], 0);
-            }
-            for (int k = 0; k < n; k++) (void)hipEventRecord(end[k], s[k]);
-            for (int k = 0; k < n; k++) if (hipEventSynchronize(end[k]) != hipSuccess) return -1;
-            float worst = 0.f;
-            for (int k = 0; k < n; k++) { float t = 0.f; if (hipEventElapsedTime(&t, begin, end[k]) != hipSuccess) return -1; worst = t > worst ? t : worst; }
-            best = worst < best ? worst : best;
-        }
-        return best * 1e3;
-    }
-};
-}  // namespace
-
-// fills c->aux with the three streams chosen by measurement; false: nothing could be measured (the caller falls back to plain streams)
-static bool calibrate_internal_streams(rs_context* c) {
-    static_assert(rs_context::kAux >= 3 && rs_context::kAux < Calibration::kMax, "three auxiliary streams (measurement builds: up to seven)");
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (rs_context::kAux != 3) {
-        // measurement builds with more chains in flight (-DRS_AUX_STREAMS=4): twelve candidates, chosen greedily -- the stream that runs
-        // best next to the ones already chosen, one at a time
-        Calibration cal;
-        if (!cal.ok) { (void)hipGetLastError(); return false; }
-        std::vector<hipStream_t> cand;
-        for (int p : { greatest, 0, least }) for (int i = 0; i < 4; i++) { hipStream_t st = nullptr; if (hipStreamCreateWithPriority(&st, hipStreamNonBlocking, p) == hipSuccess) cand.push_back(st); }
-        (void)hipGetLastError();
-        hipStream_t chosen[Calibration::kMax] = { c->stream };
-        double last = 0;
-        for (int k = 1; k <= rs_context::kAux; k++) {
-            int best = -1; double bestT = 1e30;
-            for (size_t i = 0; i < cand.size(); i++) {
-                if (!cand[i]) continue;
-                chosen[k] = cand[i];
-                const double t = cal.chained(chosen, k + 1);
-                if (t >= 0 && t < bestT) { bestT = t; best = (int)i; }
-            }
-            if (best < 0) { for (hipStream_t st : cand) if (st) (void)hipStreamDestroy(st); return false; }
-            chosen[k] = cand[(size_t)best]; cand[(size_t)best] = nullptr; last = bestT;
-        }
-        for (hipStream_t st : cand) if (st) (void)hipStreamDestroy(st);
-        for (int k = 0; k < rs_context::kAux; k++) c->aux[k] = chosen[k + 1];
-        c->auxPriority = 0; c->auxCalibratedUs = last; c->auxFastestUs = last;
-        return true;
-    }
-    const int levels[3] = { greatest, 0, least };
-    const int nLevels = (greatest < 0 ? 1 : 0) + 1 + (least > 0 ? 1 : 0);
-    int order[3], n = 0;                                               // preference: high, normal, low -- or low first when asked for
-    if (c->auxLevelSet && c->auxLevel > 0) { if (least > 0) order[n++] = 2; order[n++] = 1; if (greatest < 0) order[n++] = 0; }
-    else if (c->auxLevelSet && c->auxLevel == 0) { order[n++] = 1; if (greatest < 0) order[n++] = 0; if (least > 0) order[n++] = 2; }
-    else { if (greatest < 0) order[n++] = 0; order[n++] = 1; if (least > 0) order[n++] = 2; }
-    (void)nLevels;
-    // not the caller's own level: there the library's streams share the level's four hardware queues with the caller's stream and whatever
-    // else the process keeps at it, and the eight-round test does not always see it (RCCL in the process, ordinary caller stream, normal
-    // level: a calibration time as good as any and a config 5 frame of 2.14 ms instead of 1.79).  The default stream is no such caller: it
-    // holds one queue of the normal level, and next to it the normal level measures as well as any.
-    if (c->stream) {
-        int own = 0;
-        if (hipStreamGetPriority(c->stream, &own) != hipSuccess) { (void)hipGetLastError(); own = 0; }
-        int m = 0;
-        for (int q = 0; q < n; q++) if (levels[order[q]] != own) order[m++] = order[q];
-        if (m > 0) n = m;
-    }
-    Calibration cal;
-    if (!cal.ok) { (void)hipGetLastError(); return false; }
-    hipStream_t cand[3][4] = {};
-    bool made = true;
-    for (int q = 0; q < n && made; q++)
-        for (int i = 0; i < 4 && made; i++) made = hipStreamCreateWithPriority(&cand[order[q]][i], hipStreamNonBlocking, levels[order[q]]) == hipSuccess;
-    double t[3][4];
-    double fastest = 1e30;
-    for (int q = 0; q < n && made; q++)
-        for (int skip = 0; skip < 4; skip++) {
-            hipStream_t s[4] = { c->stream };
-            int k = 1;
-            for (int i = 0; i < 4; i++) if (i != skip) s[k++] = cand[order[q]][i];
-            t[order[q]][skip] = cal.chained(s);
-            if (t[order[q]][skip] < 0) { made = false; break; }
-            fastest = t[order[q]][skip] < fastest ? t[order[q]][skip] : fastest;
-        }
-    int level = -1, skip = -1;
-    for (int q = 0; q < n && made && level < 0; q++) {
-        int bestSkip = 0;
-        for (int i = 1; i < 4; i++) if (t[order[q]][i] < t[order[q]][bestSkip]) bestSkip = i;
-        if (t[order[q]][bestSkip] <= fastest * 1.08) { level = order[q]; skip = bestSkip; }
-    }
-    int k = 0;
-    for (int p = 0; p < 3; p++)
-        for (int i = 0; i < 4; i++) {
-            if (!cand[p][i]) continue;
-            if (p == level && i != skip) c->aux[k++] = cand[p][i];
-            else (void)hipStreamDestroy(cand[p][i]);
-        }
-    (void)hipGetLastError();
-    if (level < 0) { for (hipStream_t& st : c->aux) st = nullptr; return false; }
-    c->auxPriority = levels[level];
-    c->auxCalibratedUs = t[level][skip];
-    c->auxFastestUs = fastest;
-    return true;
-}
-
-// (kept for the streams the strip driver makes for itself, and as the fallback when nothing can be measured)
-int rs_internal_stream_priority() {
-    rs_context* c = rs_ctx();
-    if (c->auxWant != -99) return c->auxWant;
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    int own = 0;
-    if (c->stream && hipStreamGetPriority(c->stream, &own) != hipSuccess) { (void)hipGetLastError(); own = 0; }
-    int want = (greatest < 0 && own > greatest) ? greatest : 0;        // the caller's stream is not in the high pool: ours are
-    if (c->auxLevelSet) {                                               // the caller's choice, unless it is the caller's own level
-        const int asked = c->auxLevel < 0 ? greatest : c->auxLevel > 0 ? least : 0;
-        if (asked != own || !c->stream) want = asked;
-    }
-    c->auxWant = want;
-    return want;
-}
-// Auxiliary streams (asynchronous mode only): 0 carries GBuffer::render, 1 + k the primary-ray + RIS + shadow-ray kernels of every
-// kChains-th frame (frames take the chains in turn, so that these chains of consecutive frames overlap each other
-// as well as the passes of the frames before); for small launches, whose render is part of the chain's first launch, stream 0 is
-// a third chain.
-// Neither reads what the temporal / spatial passes of the previous frame write, so with the per-frame surface planes
-// in four sets and the G-buffer planes in a ring of five they run next to those passes; the objects own the events
-// that order them (rs_gbuffer, rs_restir).
-// The auxiliary stream i of the current context, or nullptr when launches are synchronous (rs_set_sync(1): nothing to overlap)
-// or the feature is off (rs_set_side_stream(0) / RS_SIDE_STREAM=0).
-hipStream_t rs_aux_stream_any(int i) {
-    rs_context* c = rs_ctx();
-    const bool sync = c->sync;
-    c->sync = false;
-    const hipStream_t st = rs_aux_stream(i);
-    c->sync = sync;
-    return st;
-}
-hipStream_t rs_aux_stream(int i) {
-    rs_context* c = rs_ctx();
-    if (c->auxMode < 0) {
-        // RS_SIDE_STREAM=0 pre-sets rs_set_side_stream(0) for a process that cannot call it: the profiling scripts in tools/ time every
-        // kernel alone on one stream under rocprofv3
-        const char* e = std::getenv("RS_SIDE_STREAM");
-        c->auxMode = (e && e[0] == '0') ? 0 : 1;
-    }
-    if (c->sync || !c->auxMode || i < 0 || i >= rs_context::kAux) return nullptr;
-    const int levelKey = c->auxLevelSet ? c->auxLevel : 2;
-    if (c->auxStale) {
-        // rs_set_stream handed the library another stream (or rs_set_internal_stream_priority another preference) after the streams were
-        // made: they are chosen for the new stream.  The old ones are idle (rs_set_stream waited for them) and are KEPT under the stream and
-        // preference they were chosen for -- a caller that alternates between two streams measures each once, not at every switch (at most
-        // four choices are kept; rs_choose_internal_streams_again forgets them all).
-        bool any = false;
-        for (hipStream_t st : c->aux) any = any || st != nullptr;
-        if (any && !c->auxPlain && !c->auxForget) {
-            rs_context::AuxChoice keep{ c->auxForStream, c->auxForLevel, {}, c->auxPriority, c->auxCalibratedUs, c->auxFastestUs };
-            for (int k = 0; k < rs_context::kAux; k++) keep.aux[k] = c->aux[k];
-            if (c->auxKept.size() >= 4) { for (hipStream_t st : c->auxKept.front().aux) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } c->auxKept.erase(c->auxKept.begin()); }
-            c->auxKept.push_back(keep);
-        }
-        else {
-            for (hipStream_t& st : c->aux) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-            if (c->auxForget) { for (auto& k : c->auxKept) for (hipStream_t st : k.aux) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } c->auxKept.clear(); }
-        }
-        for (hipStream_t& st : c->aux) st = nullptr;
-        c->auxStale = false; c->auxForget = false; c->auxPlain = false;
-        for (size_t k = 0; k < c->auxKept.size(); k++)
-            if (c->auxKept[k].caller == c->stream && c->auxKept[k].level == levelKey) {
-                for (int j = 0; j < rs_context::kAux; j++) c->aux[j] = c->auxKept[k].aux[j];
-                c->auxPriority = c->auxKept[k].priority; c->auxCalibratedUs = c->auxKept[k].chosenUs; c->auxFastestUs = c->auxKept[k].fastestUs;
-                c->auxForStream = c->stream; c->auxForLevel = levelKey;
-                c->auxKept.erase(c->auxKept.begin() + (long)k);
-                break;
-            }
-    }
-    if (!c->aux[i]) {
-        bool any = false;
-        for (hipStream_t st : c->aux) any = any || st != nullptr;
-        // a stream that is being captured into a graph cannot be timed (the spins and the waits would end the capture): plain streams
-        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-        if (c->stream && hipStreamIsCapturing(c->stream, &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
-        if (!any && !c->auxPlain && capturing == hipStreamCaptureStatusNone && calibrate_internal_streams(c)) { c->auxForStream = c->stream; c->auxForLevel = levelKey; return c->aux[i]; }
-        c->auxPlain = true;                                 // nothing could be measured: plain streams at the level the rule names
-        c->auxPriority = rs_internal_stream_priority();
-        int prio = c->auxPriority;
-#ifdef RS_AUX_PRIORITY_ENV                              // measurement builds: RS_AUX_PRIORITIES=-1,-1,0,... per auxiliary stream
-        if (const char* e = std::getenv("RS_AUX_PRIORITIES")) { for (int k = 0; k < i && e; k++) { e = std::strchr(e, ','); if (e) e++; } if (e) prio = std::atoi(e); }
-#endif
-        if (hipStreamCreateWithPriority(&c->aux[i], hipStreamNonBlocking, prio) != hipSuccess) { (void)hipGetLastError(); c->aux[i] = nullptr; c->auxMode = 0; return nullptr; }
-    }
-    return c->aux[i];
-}
 // In asynchronous mode GBuffer::render can be deferred and launched by ReSTIRDirect together with its primary rays (the two rays
 // of a pixel in one packet walk).  That saves walk work on a full frame, but the slowest tile of the launch takes longer, which
 // costs on scenes whose closest-hit kernels are tails of a few long tiles: by default every rs_restir measures the
@@ -302,10 +70,6 @@ int rs_ris_global_below() {
     rs_context* c = rs_ctx();
     if (c->risGlobalBelow < 0) c->risGlobalBelow = 64 * 1024;
     return c->risGlobalBelow;
-}
-int rs_aux_synchronize() {
-    for (hipStream_t st : rs_ctx()->aux) if (st) RS_HIP(hipStreamSynchronize(st));
-    return 0;
 }
 
 // ---- the denoise stream ---------------------------------------------------------------------------------------------------------------
@@ -388,9 +152,11 @@ int rs_denoise_order(const void* p, bool write) {
 }
 int rs_denoise_join() {
     rs_context* c = rs_ctx();
-    if (c->streamOverride || !c->denoiseUsed || !c->aux[0]) return 0;    // (the streams are only ever replaced behind an rs_synchronize, which clears denoiseUsed)
+    hipStream_t aux[rs_context::kAux];
+    rs_aux_streams_made(aux);
+    if (c->streamOverride || !c->denoiseUsed || !aux[0]) return 0;    // (the streams are only ever replaced behind an rs_synchronize, which clears denoiseUsed)
     if (!c->denoiseFork) RS_HIP(hipEventCreateWithFlags(&c->denoiseFork, hipEventDisableTiming));
-    RS_HIP(hipEventRecord(c->denoiseFork, c->aux[0]));
+    RS_HIP(hipEventRecord(c->denoiseFork, aux[0]));
     RS_HIP(hipStreamWaitEvent(c->stream, c->denoiseFork, 0));
     for (auto& b : c->denoiseBufs) b.pending = false;
     return 0;
@@ -573,9 +339,7 @@ int rs_context_destroy(rs_context* c) {
     {
         rs_ctx_scope scope(c);
         (void)rs_synchronize();
-        for (hipStream_t& st : c->aux) if (st) { (void)hipStreamDestroy(st); st = nullptr; }
-        for (auto& k : c->auxKept) for (hipStream_t st : k.aux) if (st) (void)hipStreamDestroy(st);
-        c->auxKept.clear();
+        rs_internal_streams_destroy(c);
         rs_dev_free(c->walkCount);
         for (auto& b : c->denoiseBufs) if (b.ev) (void)hipEventDestroy(b.ev);
         c->denoiseBufs.clear();
@@ -596,49 +360,13 @@ int rs_set_stream(void* hipStream) {
     const bool changed = (hipStream_t)hipStream != c->stream;
     if (changed) RS_TRY(rs_synchronize());              // events recorded on the old stream order the auxiliary ones
     c->stream = (hipStream_t)hipStream;
-    c->auxWant = -99;
-    if (changed) c->auxStale = true;                    // the library's own streams were chosen next to the old stream: chosen again on next use
+    if (changed) rs_internal_streams_invalidate(c, false);      // the library's own streams were chosen next to the old stream: chosen again on next use
     return 0;
 }
 int rs_set_sync(int sync) { rs_ctx()->sync = sync != 0; return 0; }
-// what the choice by measurement came to (for logs): the level of the three streams (-1 high / 0 normal / 1 low), the chosen triple's
-// calibration time and the fastest time any candidate triple reached, in microseconds (0 / 0: not chosen by measurement -- none made yet,
-// or the measurement failed and plain streams are in use)
-int rs_internal_streams_info(int* priority, double* chosenUs, double* fastestUs) {
-    rs_context* c = rs_ctx();
-    if (priority) *priority = c->auxPriority;
-    if (chosenUs) *chosenUs = c->auxPlain ? 0.0 : c->auxCalibratedUs;
-    if (fastestUs) *fastestUs = c->auxPlain ? 0.0 : c->auxFastestUs;
-    return 0;
-}
-// Makes the choice again at the next overlapped launch: for a caller whose process has gained streams since the library chose (an
-// ncclComm created after the first frames, a torch stream pool touched for the first time).  Waits for the library's streams.
-int rs_choose_internal_streams_again(void) {
-    rs_context* c = rs_ctx();
-    RS_TRY(rs_synchronize());
-    c->auxStale = true; c->auxForget = true; c->auxPlain = false; c->auxWant = -99;
-    return 0;
-}
-// Makes the choice NOW (about 25 ms: spins on the caller's stream and on twelve candidate streams, waits for those streams only) instead of
-// at the first overlapped launch -- for a caller that wants no such pause inside its first frame.  No-op when launches are synchronous,
-// the side streams are off, or a choice for the current stream and preference is in force.
-int rs_prepare_streams(void) {
-    rs_ctx_scope scope(nullptr);
-    (void)rs_aux_stream(0);
-    return 0;
-}
-int rs_set_internal_stream_priority(int level) {
-    rs_context* c = rs_ctx();
-    if (level < -1 || level > 2) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_set_internal_stream_priority: -1 high, 0 normal, 1 low, 2 automatic");
-    const bool changed = c->auxLevelSet != (level != 2) || (level != 2 && c->auxLevel != level);
-    c->auxLevelSet = level != 2; c->auxLevel = level == 2 ? 0 : level;
-    c->auxWant = -99;
-    if (changed) { RS_TRY(rs_synchronize()); c->auxStale = true; }
-    return 0;
-}
 int rs_set_side_stream(int enable) {
     rs_context* c = rs_ctx();
-    c->auxMode = enable ? 1 : 0;                        // work already enqueued on the auxiliary streams is still joined by its consumers
+    rs_internal_streams_set_mode(c, enable != 0);       // work already enqueued on the auxiliary streams is still joined by its consumers
     c->fuseMode = enable == 2 ? 1 : enable == 3 ? 2 : enable == 4 ? 3 : 0;      // 2 always, 3 always and at any size (tests), 4 measured
     return 0;
 }

@@ -13,6 +13,7 @@
 #endif
 #include "rs_frame_plan.h"
 #include "rs_cut_plan.h"
+#include "rs_stream_choice.h"
 #ifndef RS_GBUF_SETS
 #define RS_GBUF_SETS (RS_AUX_STREAMS + 2)
 #endif
@@ -39,18 +40,7 @@ struct rs_context {
     int device = 0;
     hipStream_t stream = nullptr;
     bool sync = true;
-    hipStream_t aux[kAux] = {};
-    int auxPriority = 0;                  // the level the auxiliary streams were created at
-    int auxWant = -99;                    // cached rs_internal_stream_priority(); -99: recompute
-    bool auxLevelSet = false; int auxLevel = 0;   // rs_set_internal_stream_priority
-    bool auxStale = false;                // the auxiliary streams were chosen for another caller stream / preference: choose again on next use
-    bool auxPlain = false;                // the choice by measurement failed once: plain streams from then on
-    bool auxForget = false;               // rs_choose_internal_streams_again: the kept choices are dropped as well
-    hipStream_t auxForStream = nullptr; int auxForLevel = 2;     // the caller stream and the preference the current three were chosen for
-    struct AuxChoice { hipStream_t caller; int level; hipStream_t aux[RS_AUX_STREAMS]; int priority; double chosenUs, fastestUs; };
-    std::vector<AuxChoice> auxKept;       // choices made for other caller streams / preferences (rs_set_stream back to one of them takes its three again)
-    double auxCalibratedUs = 0, auxFastestUs = 0;   // the chosen triple's calibration time and the fastest of all candidates (rs_internal_streams_info)
-    int auxMode = -1;                     // -1: not decided yet (RS_SIDE_STREAM); 0 off; 1 on
+    rs_internal_streams streams;          // the library's own streams, which were chosen and which are kept (internal_streams.hip owns every field)
     int risGlobalBelow = -1;              // launches of fewer pixels read the RIS light table from global memory (rs_set_ris_table_pixels): -1 = the default, 64 Ki
     int fuseMode = -1;                    // deferred G-buffer render walked with the primary rays: -1 = not resolved yet (rs_set_side_stream; default: measured per rs_restir)
     int chainStreams = -1, smallChains = -1, shadowOnMain = -1;   // rs_set_stream_plan; -1: not resolved yet (environment or default)
@@ -86,12 +76,14 @@ hipStream_t rs_stream();
 bool rs_sync_enabled();
 // after a launch: hipGetLastError (+ stream sync when sync mode is on), like checkCUDAError
 int rs_after_launch(const char* what);
-// auxiliary streams of the asynchronous mode (api_common.hip): 0 = GBuffer::render, 1 + k = primary rays + RIS + shadow rays of every
-// kChains-th frame; nullptr = not in use
+// auxiliary streams of the asynchronous mode (internal_streams.hip): 0 = GBuffer::render, 1 + k = primary rays + RIS + shadow rays of every
+// kChains-th frame; nullptr = not in use.  The first call after a change chooses them (about 25 ms); a call that finds them chosen only reads.
 hipStream_t rs_aux_stream(int i);
-hipStream_t rs_aux_stream_any(int i);                  // the same stream whatever the launch mode (null only when the side streams are switched off)
+int rs_aux_streams_made(hipStream_t out[rs_context::kAux]);   // the streams that exist right now, by index (null: not made); returns how many.  Makes and measures nothing
 int rs_aux_synchronize();
-int rs_internal_stream_priority();                     // the priority level the library's own streams are created at: not the caller's stream's
+void rs_internal_streams_invalidate(rs_context* c, bool forget);   // the streams are chosen again on next use (another caller stream or preference); forget: the kept choices go as well
+void rs_internal_streams_set_mode(rs_context* c, bool on);   // rs_set_side_stream
+void rs_internal_streams_destroy(rs_context* c);        // rs_context_destroy, after an rs_synchronize: the current and the kept streams
 int rs_chains_in_flight();                             // how many auxiliary streams the frames' chains take in turn: 3, less one per other stream of the context with work in flight (a strip driver's transfer stream, the denoise stream)
 // ---- the denoise stream (api_common.hip) ----
 hipStream_t rs_denoise_stream();                       // auxiliary stream 0 when rs_set_denoise_stream(1) is in force and launches are asynchronous, else null

@@ -189,12 +189,13 @@ int version_commit(rs_scene* s, const char* what) {
     if (nl) std::memcpy(nv.staging + l.moved, s->hLightMoved.data(), nl * sizeof(uint32_t));
 
     // the current slot is retired by what has been enqueued so far on the library stream and on every auxiliary stream
-    rs_context* c = rs_ctx();
+    hipStream_t aux[rs_context::kAux];
+    rs_aux_streams_made(aux);
     const hipStream_t st = rs_stream();
     rs_scene::Version& ov = s->ver[s->verCur];
     RS_HIP(hipEventRecord(ov.retired[0], st)); ov.retiredValid[0] = true;
     for (int i = 0; i < rs_context::kAux; i++)
-        if (c->aux[i]) { RS_HIP(hipEventRecord(ov.retired[1 + i], c->aux[i])); ov.retiredValid[1 + i] = true; }
+        if (aux[i]) { RS_HIP(hipEventRecord(ov.retired[1 + i], aux[i])); ov.retiredValid[1 + i] = true; }
     // The slot is free (no launch reads it), so its fill waits for nothing: it goes to a stream of the scene's own and the library and
     // auxiliary streams wait for that copy alone.  (Filled on the library stream, the edit would order the auxiliary streams after the
     // frames in flight there and end the overlap of consecutive frames: config 5 with an edit per frame 1.69 -> 3.12 ms.)
@@ -208,7 +209,7 @@ int version_commit(rs_scene* s, const char* what) {
     RS_HIP(hipEventRecord(s->verFilled, s->verStream));
     RS_HIP(hipStreamWaitEvent(st, s->verFilled, 0));             // launches from now on see the new tables
     for (int i = 0; i < rs_context::kAux; i++)
-        if (c->aux[i]) RS_HIP(hipStreamWaitEvent(c->aux[i], s->verFilled, 0));
+        if (aux[i]) RS_HIP(hipStreamWaitEvent(aux[i], s->verFilled, 0));
     s->dev.materials = nv.materials;
     s->dev.lights = nv.lights;
     s->dev.alias = nv.alias;
@@ -361,16 +362,18 @@ namespace {
 // by events, for what those streams have been handed so far (fence_before), the edit's kernels run on the library stream, and the next
 // launch of every internal stream waits for them (fence_after).  Launches enqueued before the edit read the old arrays, launches after it the new.
 int fence_before(hipEvent_t* before) {
-    rs_context* c = rs_ctx();
+    hipStream_t aux[rs_context::kAux];
+    rs_aux_streams_made(aux);
     for (int i = 0; i < rs_context::kAux; i++)
-        if (c->aux[i]) { RS_HIP(hipEventRecord(before[i], c->aux[i])); RS_HIP(hipStreamWaitEvent(rs_stream(), before[i], 0)); }
+        if (aux[i]) { RS_HIP(hipEventRecord(before[i], aux[i])); RS_HIP(hipStreamWaitEvent(rs_stream(), before[i], 0)); }
     return 0;
 }
 int fence_after(hipEvent_t after) {
-    rs_context* c = rs_ctx();
+    hipStream_t aux[rs_context::kAux];
+    rs_aux_streams_made(aux);
     RS_HIP(hipEventRecord(after, rs_stream()));
     for (int i = 0; i < rs_context::kAux; i++)
-        if (c->aux[i]) RS_HIP(hipStreamWaitEvent(c->aux[i], after, 0));
+        if (aux[i]) RS_HIP(hipStreamWaitEvent(aux[i], after, 0));
     return 0;
 }
 

@@ -87,6 +87,34 @@ class GeometryEditLights(C.Structure):
                 ("emiBase", C.c_float * 3), ("emiScale", C.c_float * 3), ("emiMargin", C.c_double)]
 
 
+AUX_STREAMS, STREAM_CHOICES_KEPT = 3, 4
+
+
+class StreamChoice(C.Structure):
+    """rs_stream_choice: the internal streams made for one caller stream under one level key; handles are opaque."""
+    _fields_ = [("caller", C.c_void_p), ("levelKey", C.c_int), ("stream", C.c_void_p * AUX_STREAMS), ("priority", C.c_int),
+                ("chosenUs", C.c_double), ("fastestUs", C.c_double)]
+
+
+class StreamChoices(C.Structure):
+    """rs_stream_choices: the current choice, what it holds (STREAMS_HELD_*), what is pending (STREAMS_PENDING_*), the kept choices."""
+    _fields_ = [("current", StreamChoice), ("held", C.c_int), ("pending", C.c_int), ("numKept", C.c_int),
+                ("kept", StreamChoice * STREAM_CHOICES_KEPT)]
+
+
+class StreamChoiceInputs(C.Structure):
+    """rs_stream_choice_inputs: what the level order, the pick and the priority of plain streams are decided from."""
+    _fields_ = [("least", C.c_int), ("greatest", C.c_int), ("asked", C.c_int), ("callerHasStream", C.c_int), ("callerPriority", C.c_int),
+                ("timesUs", (C.c_double * 4) * 3)]
+
+
+class StreamChoicePlan(C.Structure):
+    """rs_stream_choice_plan: what they come to."""
+    _fields_ = [("order", C.c_int * 3), ("numLevels", C.c_int), ("level", C.c_int), ("skip", C.c_int), ("fastestUs", C.c_double),
+                ("plainPriority", C.c_int)]
+
+
+assert (C.sizeof(StreamChoice), C.sizeof(StreamChoices), C.sizeof(StreamChoiceInputs), C.sizeof(StreamChoicePlan)) == (64, 336, 120, 40)
 assert C.sizeof(Material) == 44
 assert C.sizeof(Camera) == 196
 assert C.sizeof(Reservoir) == 36

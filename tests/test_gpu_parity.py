@@ -912,8 +912,8 @@ def test_strip_tiling_equals_full_frame(hip):
 
 def test_internal_streams_are_chosen_by_measurement_and_change_no_result(hip):
     """The library chooses its three internal streams by measurement when an overlapped frame first needs them, again after
-    rs_choose_internal_streams_again / rs_set_internal_stream_priority / rs_set_stream with another stream (api_common.hip).  Which streams
-    carry the chains is scheduling only: overlapped frames under every preference, on the default stream and on an ordinary one, with the
+    rs_choose_internal_streams_again / rs_set_internal_stream_priority / rs_set_stream with another stream (internal_streams.hip; the rules of the choice
+    themselves: tests/test_stream_choice.py).  Which streams carry the chains is scheduling only: overlapped frames under every preference, on the default stream and on an ordinary one, with the
     choice repeated in the middle of the sequence, equal the synchronous frames bit for bit; rs_internal_streams_info reports a level and a
     calibration time."""
     import torch
@@ -1016,6 +1016,70 @@ def test_stream_choice_is_kept_per_caller_stream(hip):
     finally:
         hip.set_sync(True)
         hip.set_stream(torch.cuda.current_stream().cuda_stream)
+
+
+def test_recalled_stream_choice_reports_its_own_numbers(hip):
+    """A choice that is taken again is the choice that was kept: on the visits A, B, A, B, A of two caller streams, rs_internal_streams_info
+    at the third to fifth visit gives -- as exact floats -- the level and the two times it gave at the first visit of that stream, which a
+    second measurement would not.  (Where nothing could be measured the streams are plain, both times are 0.0, and nothing is kept.)"""
+    import torch
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    hip.set_sync(False)
+    try:
+        hip.choose_internal_streams_again()                         # (what earlier tests left: torch hands out its streams again)
+        first = {}
+        for visit, st in enumerate((a, b, a, b, a)):
+            hip.set_stream(st.cuda_stream)
+            hip.prepare_streams()
+            info = hip.internal_streams_info()
+            print("visit", visit, "stream", "ab"[st is b], info)
+            assert info[0] in (-1, 0, 1) and (info[1] == 0.0) == (info[2] == 0.0), info
+            if st not in first:
+                first[st] = info
+            elif first[st][1] > 0:
+                assert info == first[st], (visit, info, first[st])
+    finally:
+        hip.set_sync(True)
+        hip.set_stream(torch.cuda.current_stream().cuda_stream)
+
+
+def test_context_destroy_releases_current_and_kept_streams(hip):
+    """rs_context_destroy with internal streams in every place they can be: a choice kept for one caller stream, the current one for
+    another, both then forgotten and chosen again (rs_choose_internal_streams_again), a frame in flight on the new ones.  Every call returns
+    0, and the default context renders the synchronous frame bit for bit afterwards."""
+    import ctypes as C
+    import torch
+    sd = get_scene("sponza:0.1")
+    W, H = 320, 180
+    ref = HipRenderer(hip, sd, W, H).frame(3)
+    L = hip.lib()
+    ctx = hip.Context(0)
+    ctx.make_current()
+    try:
+        hip.set_sync(False)
+        a, b = torch.cuda.Stream(), torch.cuda.Stream()
+        for st in (a, b):                                           # a's choice is kept, b's is the current one
+            hip.set_stream(st.cuda_stream)
+            hip.prepare_streams()
+        hip.set_stream(a.cuda_stream)
+        hip.prepare_streams()                                       # ... and the other way round
+        hip.choose_internal_streams_again()
+        hip.prepare_streams()                                       # both released, a third made
+        with torch.cuda.stream(a):
+            h = HipRenderer(hip, sd, W, H)                          # scene, G-buffer, reservoirs of this context
+            got = h.frame(3)
+        assert bits_equal(got, ref), radiance_stats(ref, got)
+        hip.set_stream(b.cuda_stream)
+        hip.prepare_streams()                                       # one kept, one current at the end
+        for obj, free in ((h.restir, L.rs_restir_free), (h.gbuf, L.rs_gbuffer_destroy), (h.scene, L.rs_scene_destroy)):
+            assert free(obj.handle) == 0, L.rs_last_error()
+            obj.handle = C.c_void_p()
+    finally:
+        hip.Context.use_default()
+    assert L.rs_context_destroy(ctx.handle) == 0, L.rs_last_error()
+    ctx.handle = C.c_void_p()
+    torch.cuda.synchronize()
+    assert bits_equal(HipRenderer(hip, sd, W, H).frame(3), ref)
 
 
 @pytest.mark.parametrize("fused", [False, True])
