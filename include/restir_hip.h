@@ -709,6 +709,25 @@ int  rs_debug_plan_primary_leaf_list(const rs_camera* cam, int x0, int y0, int b
  * within the cut (*count: the cut's end).  The walk and the re-linking are the functions the device builder runs. */
 int  rs_debug_plan_primary_cut(const rs_camera* cam, int x0, int y0, int w, int h, int bvhSize, const float* boundingBoxes, const int* const bvhNodes[6], int cap,
                                int* order, int* count, int* positions, int* links);
+/* Shadow rays regrouped by length: in a scene with the shadow tree, a block of the shadow-ray kernel (32x8 pixels, four waves) hands its
+ * segments out to its waves by length before the walk -- 64 bins over the diagonal of the scene's root box, the longest bin first -- so
+ * that a wave's rays end together instead of waiting for the tile's longest (restir_amd/csrc/rs_shadow_regroup.h).  Occlusion does not
+ * depend on the lane that carries a ray: no result changes by a bit.  Full frames and strips.  on = 1 is the default;
+ * RS_SHADOW_REGROUP=0 makes 0 the default (A/B measurements). */
+int  rs_restir_set_shadow_regroup(rs_restir* r, int on);
+/* Test hooks.  Host only: bins[i] = shadow_bin(lengths[i], binsOverExtent) for n segments and, where first and count are given
+ * (n <= 256, the lanes of one block; active[i] == 0: the lane has no segment, active == NULL: all have), the block's slot plan:
+ * first[64] = the first slot of every bin, *count = the active rays, which take slots 0 .. *count - 1, longest bin first.  rootLo /
+ * rootHi non-null: binsOverExtent is computed from that root box as the launch does; *binsOverExtentOut (may be null) is the value used.
+ * On the device: the shadow-ray pass of a phase-A call alone, in the form the switch chooses (a scene without the shadow tree: the plain
+ * form), over the caller's planes of width * height pixels each -- posTag { position, bits(matId | kind << 24) }, candLi { Li, dist },
+ * candWi { wi, weight }, in and out: an occluded segment's weight comes back 0 -- on rows [y0, y1); slots (may be null): the slot every
+ * pixel's ray took in its 32x8 block, -1 where a pixel has no segment and everywhere under the plain form; *binsOverExtent (may be
+ * null): shadow_bin's scale for this scene, 0 without the shadow tree. */
+int  rs_debug_plan_shadow_regroup(int n, const float* lengths, const unsigned char* active, float binsOverExtent, const float* rootLo, const float* rootHi,
+                                  int* bins, int* first, int* count, float* binsOverExtentOut);
+int  rs_debug_shadow_pass(rs_restir* r, const rs_scene* scene, int y0, int y1, const float* posTag, const float* candLi, float* candWi, int* slots,
+                          float* binsOverExtent);
 /* What one phase-A call of a frame keeps about its cuts between frames, as plain data (restir_amd/csrc/rs_cut_plan.h).  The key is what
  * the cuts and lists were built from; listCap is 0 while the lists' switch is off.  `cuts` and `lists` say what became of each arena
  * under that key. */

@@ -156,7 +156,7 @@ EXPORTS = [
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
     "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_set_light_retargeting", "rs_restir_get_light_retargeting", "rs_restir_download_light_samples", "rs_debug_restir_retarget", "rs_debug_restir_retarget_launched", "rs_debug_restir_surface_wo", "rs_scene_light_moves", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
-    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_restir_set_primary_leaf_lists", "rs_debug_set_primary_leaf_list_cap", "rs_debug_primary_leaf_list_info", "rs_debug_primary_leaf_list_missing", "rs_debug_plan_primary_leaf_list", "rs_debug_plan_primary_cut", "rs_debug_plan_primary_cut_slot", "rs_debug_plan_stream_choice", "rs_debug_plan_stream_switch", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
+    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_restir_set_primary_leaf_lists", "rs_debug_set_primary_leaf_list_cap", "rs_debug_primary_leaf_list_info", "rs_debug_primary_leaf_list_missing", "rs_debug_plan_primary_leaf_list", "rs_debug_plan_primary_cut", "rs_debug_plan_primary_cut_slot", "rs_restir_set_shadow_regroup", "rs_debug_plan_shadow_regroup", "rs_debug_shadow_pass", "rs_debug_plan_stream_choice", "rs_debug_plan_stream_switch", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
     "rs_path_trace", "rs_path_trace_indirect", "rs_restir_indirect", "rs_restir_download_indirect",
     "rs_svgf_create", "rs_svgf_destroy", "rs_svgf_filter", "rs_svgf_next_frame", "rs_svgf_get_view",
     "rs_copy_image_to_pbo", "rs_copy_image2_to_pbo", "rs_copy_imagef_to_pbo", "rs_copy_imagei_to_pbo", "rs_eaw_create", "rs_eaw_destroy", "rs_eaw_set_params", "rs_eaw_get_params", "rs_eaw_set_tiled", "rs_eaw_set_fused", "rs_svgf_set_params", "rs_svgf_get_params", "rs_svgf_set_tiled", "rs_svgf_set_fused", "rs_eaw_filter", "rs_eaw_positions_rows", "rs_eaw_level_rows", "rs_modulate_albedo",
@@ -287,6 +287,10 @@ def lib():
     L.rs_debug_plan_primary_leaf_list.argtypes = [vp, ci, ci, ci, vp, C.POINTER(vp * 6), ci, C.POINTER(ci), C.POINTER(ci), vp]
     L.rs_debug_plan_primary_cut.argtypes = [vp, ci, ci, ci, ci, ci, vp, C.POINTER(vp * 6), ci, C.POINTER(ci), C.POINTER(ci), vp, vp]
     L.rs_debug_plan_primary_cut_slot.argtypes = [ci, ci, C.POINTER(PrimaryCutSlot), C.POINTER(PrimaryCutKey), ci, ci, C.POINTER(ci), C.POINTER(PrimaryCutSizes)]
+    if hasattr(L, "rs_restir_set_shadow_regroup"):        # (an A/B build from before the regrouped shadow rays, RESTIR_HIP_LIB: tools/ab.sh)
+        L.rs_restir_set_shadow_regroup.argtypes = [vp, ci]
+        L.rs_debug_plan_shadow_regroup.argtypes = [ci, vp, vp, C.c_float, vp, vp, vp, vp, C.POINTER(ci), C.POINTER(C.c_float)]
+        L.rs_debug_shadow_pass.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, C.POINTER(C.c_float)]
     L.rs_debug_plan_stream_choice.argtypes = [C.POINTER(StreamChoiceInputs), C.POINTER(StreamChoicePlan)]
     L.rs_debug_plan_stream_switch.argtypes = [C.POINTER(StreamChoices), ci, vp, ci, C.POINTER(StreamChoice), C.POINTER(ci)]
     L.rs_debug_restir_surface.argtypes = [vp, vp, vp, vp]
@@ -590,6 +594,20 @@ def plan_primary_cut_slot(slot, key, on=True, capturing=False, tiles=(1, 1)):
     state, sizes = C.c_int(), PrimaryCutSizes()
     check(lib().rs_debug_plan_primary_cut_slot(int(on), int(capturing), C.byref(slot), C.byref(key), int(tiles[0]), int(tiles[1]), C.byref(state), C.byref(sizes)))
     return state.value, sizes
+
+
+def plan_shadow_regroup(lengths, bins_over_extent=None, root=None, active=None, plan=False):
+    """rs_debug_plan_shadow_regroup (host only): the length bins of the segments `lengths` under bins_over_extent, or under the value the
+    launch computes from the root box root = (lo, hi).  Returns (bins, bins_over_extent), and with plan=True (at most 256 segments: the
+    lanes of one block; active[i] false: no segment) (bins, bins_over_extent, first[64], count)."""
+    lengths = np.ascontiguousarray(lengths, np.float32).reshape(-1)
+    n = len(lengths)
+    bins, first, count, used = np.zeros(max(n, 1), np.int32), np.zeros(64, np.int32), C.c_int(), C.c_float()
+    act = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
+    lo, hi = (None, None) if root is None else (np.ascontiguousarray(root[0], np.float32), np.ascontiguousarray(root[1], np.float32))
+    check(lib().rs_debug_plan_shadow_regroup(n, _p(lengths), None if act is None else _p(act), float(bins_over_extent or 0.0), None if lo is None else _p(lo),
+                                             None if hi is None else _p(hi), _p(bins), _p(first) if plan else None, C.byref(count) if plan else None, C.byref(used)))
+    return (bins[:n], used.value, first, count.value) if plan else (bins[:n], used.value)
 
 
 def plan_stream_choice(priority_range, asked=2, caller_priority=None, times_us=None):
@@ -1223,6 +1241,21 @@ class ReSTIR:
     def set_primary_leaf_lists(self, on=True):
         """rs_restir_set_primary_leaf_lists: whole tiles of such a launch walk the leaf lists of their own 8x8 pixels (on by default)."""
         check(lib().rs_restir_set_primary_leaf_lists(self.handle, 1 if on else 0))
+
+    def set_shadow_regroup(self, on=True):
+        """rs_restir_set_shadow_regroup: the shadow-ray kernel hands a block's segments out to its waves by length (on by default)."""
+        check(lib().rs_restir_set_shadow_regroup(self.handle, 1 if on else 0))
+
+    def shadow_pass(self, scene, pos_tag, cand_li, cand_wi, rows=None):
+        """rs_debug_shadow_pass: the shadow-ray pass alone, in the form the switch chooses, over (n, 4) f32 planes { position, tag bits },
+        { Li, dist }, { wi, weight }.  Returns (cand_wi after the pass, slots (n,) i32: -1 without a segment or under the plain form, shadow_bin's scale
+        for the scene: 0 without the shadow tree)."""
+        n = self.width * self.height
+        y0, y1 = rows or (0, self.height)
+        a, b = np.ascontiguousarray(pos_tag, np.float32).reshape(n, 4), np.ascontiguousarray(cand_li, np.float32).reshape(n, 4)
+        w, slots, k = np.array(cand_wi, np.float32).reshape(n, 4).copy(), np.zeros(n, np.int32), C.c_float()
+        check(lib().rs_debug_shadow_pass(self.handle, scene.handle, y0, y1, _p(a), _p(b), _p(w), _p(slots), C.byref(k)))
+        return w, slots, k.value
 
     def set_primary_leaf_list_cap(self, records):
         """rs_debug_set_primary_leaf_list_cap: the most records one tile's leaf list may have (0: no tile takes a list)."""

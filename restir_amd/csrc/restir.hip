@@ -7,7 +7,9 @@
 //   phase A  k_primary          jittered primary ray, wave-cooperative packet walk of
 //                               the MTBVH, material after its texture maps            restir.cu:127-153
 //            k_ris / k_ris_lds  32-candidate RIS over the light table (no rays)       restir.cu:155-170
-//            k_shadow           shadow ray on the RIS winner (shadow tree)            restir.cu:172-176
+//            k_shadow_regroup   shadow ray on the RIS winner (shadow tree), a block's
+//                               rays handed out to its waves by length (k_shadow: a
+//                               scene without that tree, or the switch off)           restir.cu:172-176
 //            k_temporal         temporal merge, publish reservoirs                    restir.cu:178-194,211-212
 //   phase B  k_spatial_shade    5-tap spatial reuse from an LDS-staged tile+halo,
 //                               shade, accumulate                                     restir.cu:196-230
@@ -27,6 +29,7 @@
 #include "rs_row_layouts.h"
 #include "rs_light_history.h"
 #include "rs_cuts.h"
+#include "rs_shadow_regroup.h"
 
 using namespace rs;
 
@@ -401,11 +404,63 @@ __global__ void __launch_bounds__(256, RS_WALK_WAVES) k_shadow(DevScene s, SurfP
     float4 cl = make_float4(0.f, 0.f, 0.f, 0.f), cw = cl;
     if (shaded) { cl = sp.candLi[index]; cw = sp.candWi[index]; }
     const f3 pos = mk3(pm.x, pm.y, pm.z), wi = mk3(cw.x, cw.y, cw.z);
+    // A weight with exactly the bits of +0 (no RIS winner: a NaN direction, a special-case ray that sends its whole wave through the
+    // reference's tree as well) has nothing to clear: no segment.  -0 and NaN have a bit that the store would change, and walk.
+    const bool walks = shaded && __float_as_uint(cw.w) != 0u;
     // every lane of the wave takes part in the cooperative any-hit walk
     // (the tree's top levels as an LDS-resident table -- 54 % of a ray's node steps -- were built and measured in round 4: bit-exact and
     // slower, 0.478 -> 0.528 ms; EXPERIMENTS.md, commit 6f00700)
-    const bool occluded = trace_occluded_wave(s, pos, pos + wi * cl.w, shaded);
-    if (shaded && occluded) reinterpret_cast<float*>(sp.candWi + index)[3] = 0.f;      // `if (testOcclusion(...)) reservoir.weight = 0`
+    const bool occluded = trace_occluded_wave(s, pos, pos + wi * cl.w, walks);
+    if (walks && occluded) reinterpret_cast<float*>(sp.candWi + index)[3] = 0.f;      // `if (testOcclusion(...)) reservoir.weight = 0`
+}
+
+// The same rays, handed out to the block's four waves by segment length before the walk (rs_shadow_regroup.h): a wave walks until its
+// longest segment is done, and the 64 segments of a tile go to independently drawn lamps.  A lane loads its own pixel's segment, the block
+// counts the segments per length bin (the return value of the LDS atomic is the ray's rank within its bin: arrival order), every wave scans
+// the histogram from the top bin down for itself (no barrier for a shared prefix), each lane writes its ray to slot first[bin] + rank, and
+// lane t walks the ray of slot t.  Every ray still starts at the root together with its wave-mates, and the block's set of rays -- the
+// lines its CU's L1 sees -- is unchanged.  The occlusion of a ray does not depend on the lane that carries it, so results are the plain
+// kernel's bit for bit.  LDS: 2 x 256 float4 + the histogram = 8 448 B, eight blocks per CU.
+// (Blocks of 512 threads over 32x16 pixels -- more balance in tools/models/shadow_regroup.cpp -- were built and measured: bit-exact, and a
+// slower frame than this form, 0.742 against 0.727 ms; EXPERIMENTS.md, profiles/shadow_regroup_ab.log.)
+__global__ void __launch_bounds__(kShadowRegroupRays, RS_WALK_WAVES) k_shadow_regroup(DevScene s, SurfPlanes sp, int width, int y0, int y1, int tilesX, float binsOverExtent, int* slotsOut) {
+    __shared__ float4 sRay[2 * kShadowRegroupRays];
+    __shared__ int sHist[kShadowBins];
+    RS_SETPRIO(RS_PRIO_WALK);
+    int x, y;
+    const int lane = pixel_of_lane(tilesX, y0, x, y);                // (the plain kernel's pixels)
+    if (threadIdx.x < kShadowBins) sHist[threadIdx.x] = 0;
+    const bool inside = x < width && y < y1;
+    const int index = inside ? y * width + x : 0;
+    const float4 pm = inside ? sp.posMat[index] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool shaded = inside && mk_kind(__float_as_int(pm.w)) == kKindShaded;
+    float4 cl = make_float4(0.f, 0.f, 0.f, 0.f), cw = cl;
+    if (shaded) { cl = sp.candLi[index]; cw = sp.candWi[index]; }
+    const bool walks = shaded && __float_as_uint(cw.w) != 0u;        // (as in k_shadow)
+    const int bin = shadow_bin(cl.w, binsOverExtent);
+    __syncthreads();
+    int rank = 0;
+    if (walks) rank = atomicAdd(&sHist[bin], 1);
+    __syncthreads();
+    // lane l holds bin 63 - l: an inclusive scan over the lanes is the number of rays in that bin and above
+    int above = sHist[kShadowBins - 1 - lane];
+    for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(above, off); above += lane >= off ? v : 0; }
+    const int count = __shfl(above, 63);
+    const int first = __shfl(above, bin < kShadowBins - 1 ? kShadowBins - 2 - bin : 0);     // the rays above bin b: the scan at bin b + 1
+    const int slot = (bin < kShadowBins - 1 ? first : 0) + rank;
+    if (walks) {
+        sRay[slot] = make_float4(pm.x, pm.y, pm.z, __int_as_float(index));
+        sRay[kShadowRegroupRays + slot] = make_float4(cw.x, cw.y, cw.z, cl.w);
+    }
+    if (slotsOut && inside) slotsOut[index] = walks ? slot : -1;     // test hook (rs_debug_shadow_pass)
+    __syncthreads();
+    if ((int)(threadIdx.x & ~63u) >= count) return;                  // a wave without a ray (wave-uniform)
+    const bool mine = (int)threadIdx.x < count;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+    if (mine) { a = sRay[threadIdx.x]; b = sRay[kShadowRegroupRays + threadIdx.x]; }
+    const f3 pos = mk3(a.x, a.y, a.z), wi = mk3(b.x, b.y, b.z);
+    const bool occluded = trace_occluded_wave(s, pos, pos + wi * b.w, mine);
+    if (mine && occluded) reinterpret_cast<float*>(sp.candWi + __float_as_int(a.w))[3] = 0.f;
 }
 
 // (The shadow rays as a resident grid of waves that replace finished rays from a run of tiles -- 87 % of the lanes walking instead of 54 % --
@@ -924,6 +979,7 @@ int rs_restir_init(int width, int height, rs_restir** out) {
     rs_ctx_scope scope(r->ctx);
     r->width = width; r->height = height;
     rs_primary_cuts_init(r->cuts);
+    if (const char* env = std::getenv("RS_SHADOW_REGROUP")) r->shadowRegroup = std::atoi(env) != 0;     // A/B switch for measurements: the default of rs_restir_set_shadow_regroup
     const size_t n = (size_t)width * height;
     int e = 0;
     if (!e) e = alloc_planes(r->cur, n);
@@ -984,6 +1040,30 @@ int rs_restir_set_probe(rs_restir* r, int enable) {
     return 0;
 }
 
+// Shadow rays regrouped by length (k_shadow_regroup): 1 on (the default; RS_SHADOW_REGROUP=0 makes 0 the default), 0 the plain kernel.
+int rs_restir_set_shadow_regroup(rs_restir* r, int on) {
+    RS_SCOPE(r);
+    if (!r) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_set_shadow_regroup: null");
+    r->shadowRegroup = on != 0;
+    return 0;
+}
+
+// test hook, host only: rs_shadow_regroup.h's two functions
+int rs_debug_plan_shadow_regroup(int n, const float* lengths, const unsigned char* active, float binsOverExtent, const float* rootLo, const float* rootHi,
+                                 int* bins, int* first, int* count, float* binsOverExtentOut) {
+    if (n < 0 || (n > 0 && (!lengths || !bins)) || (!rootLo != !rootHi) || (!first != !count) || (first && n > kShadowRegroupRays))
+        return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_plan_shadow_regroup: bad argument");
+    if (rootLo) binsOverExtent = shadow_bins_over_extent(rootLo, rootHi);
+    if (binsOverExtentOut) *binsOverExtentOut = binsOverExtent;
+    for (int i = 0; i < n; i++) bins[i] = shadow_bin(lengths[i], binsOverExtent);
+    if (first) {
+        int lanes[kShadowRegroupRays];
+        for (int i = 0; i < n; i++) lanes[i] = (!active || active[i]) ? bins[i] : -1;
+        *count = rs_plan_shadow_slots(lanes, n, first);
+    }
+    return 0;
+}
+
 // rs_restir_enable_timing(r, 2): the durations (ms) of the spatial pass in the last frames, oldest first, at most `capacity` and at most the
 // ring's 256; *count = how many.  Waits for the library stream.
 int rs_restir_spatial_times(rs_restir* r, float* ms, int capacity, int* count) {
@@ -1032,6 +1112,20 @@ int launch_ris(const rs_scene* scene, const SurfPlanes& sp, int W, int y0, int y
                         scene->envMapTexId >= 0, sobol);
     });
     return 0;
+}
+
+// shadow_bin's scale for a scene with the shadow tree: the bins over the diagonal of the reference's root box
+float shadow_scale(const rs_scene* scene) {
+    const float lo[3] = { scene->dev.occRootLo.x, scene->dev.occRootLo.y, scene->dev.occRootLo.z }, hi[3] = { scene->dev.occRootHi.x, scene->dev.occRootHi.y, scene->dev.occRootHi.z };
+    return shadow_bins_over_extent(lo, hi);
+}
+
+// the shadow rays of a phase-A call, in the chosen form: regrouped by length (rs_restir_set_shadow_regroup) where the scene has the shadow tree
+void launch_shadow(const rs_restir* r, const rs_scene* scene, const SurfPlanes& sp, int W, int y0, int y1, int tilesX, int tilesY, hipStream_t st, int* slotsOut = nullptr) {
+    if (r->shadowRegroup && scene->dev.occNodes) {
+        hipLaunchKernelGGL(k_shadow_regroup, dim3(tilesX * tilesY), dim3(kShadowRegroupRays), 0, st, scene->dev, sp, W, y0, y1, tilesX, shadow_scale(scene), slotsOut);
+    }
+    else hipLaunchKernelGGL(k_shadow, dim3(tilesX * tilesY), dim3(256), 0, st, scene->dev, sp, W, y0, y1, tilesX);
 }
 
 // `last`: the call ends with rs_after_launch (which synchronises in synchronous mode); ReSTIRDirect passes false for its two
@@ -1139,7 +1233,7 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     RS_TRY(launch_ris(scene, sp, W, y0, y1, looper, sobol, st, p.risForm, r->lights, r->surfSet));
     mark(r, 2);
     // (the shadow rays of a launch that fills the chip several times over go to the library stream: rs_frame_plan.h)
-    if (!p.shadowOnLibrary) hipLaunchKernelGGL(k_shadow, dim3(tilesX * tilesY), dim3(256), 0, st, scene->dev, sp, W, y0, y1, tilesX);
+    if (!p.shadowOnLibrary) launch_shadow(r, scene, sp, W, y0, y1, tilesX, tilesY, st);
     if (aux) {
         RS_TRY(rs_check_hip(hipGetLastError(), "ReSTIR Direct (primary / RIS / shadow rays)"));
         RS_HIP(hipEventRecord(r->auxDone, aux));
@@ -1147,7 +1241,7 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     }
     // (behind the chain's end event: this frame's temporal pass does not wait for the build, the chain's next frame does)
     if (p.cut == 1) RS_TRY(rs_primary_cuts_build(r->cuts, scene, cp, y0, tilesX, tilesY, st));
-    if (p.shadowOnLibrary) hipLaunchKernelGGL(k_shadow, dim3(tilesX * tilesY), dim3(256), 0, rs_stream(), scene->dev, sp, W, y0, y1, tilesX);
+    if (p.shadowOnLibrary) launch_shadow(r, scene, sp, W, y0, y1, tilesX, tilesY, rs_stream());
     RS_TRY(rs_gbuffer_join(g));                                 // first consumer of the G-buffer planes
     LightIds ids; LightRecs recs;
     RS_TRY(rs_light_history_phase_a(r->lights, scene, r->surfSet, !r->firstFrame && (reuse & 1), sp, gbuf_view(g), r->last, y0, y1, tilesX, tilesY, rayCounter, &ids, &recs));
@@ -1247,6 +1341,39 @@ int rs_debug_restir_surface(rs_restir* r, float* posTag, float* normal, unsigned
     RS_HIP(hipMemcpy(normal, f.norm, n * 16, hipMemcpyDeviceToHost));
     RS_HIP(hipMemcpy(rngTag, f.rngMat, n * 8, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// test hook: the shadow-ray pass of a phase-A call alone, in the form the switch chooses (a scene without the shadow tree: the plain one),
+// over hand-made planes of width * height pixels: posTag { position, bits(matId | kind << 24) }, candLi { Li, dist }, candWi { wi, weight }
+// (in and out: an occluded segment's weight comes back 0).  slots (may be null): the slot every pixel's ray took in its block, -1 where a
+// pixel has no segment and everywhere when the plain form ran; binsOverExtent (may be null): shadow_bin's scale for this scene (0 without
+// the shadow tree).  Rows [y0, y1).
+int rs_debug_shadow_pass(rs_restir* r, const rs_scene* scene, int y0, int y1, const float* posTag, const float* candLi, float* candWi, int* slots, float* binsOverExtent) {
+    RS_SCOPE(r);
+    if (!r || !scene || !posTag || !candLi || !candWi || y0 < 0 || y1 > r->height || y1 <= y0) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_shadow_pass: bad argument");
+    if (scene->ctx != r->ctx) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_shadow_pass: the scene belongs to another context");
+    RS_TRY(rs_synchronize());
+    if (binsOverExtent) *binsOverExtent = scene->dev.occNodes ? shadow_scale(scene) : 0.f;
+    const size_t n = (size_t)r->width * r->height;
+    SurfPlanes sp{};
+    int* dSlots = nullptr;
+    int e = rs_dev_alloc(&sp.posMat, n);
+    if (!e) e = rs_dev_alloc(&sp.candLi, n);
+    if (!e) e = rs_dev_alloc(&sp.candWi, n);
+    if (!e) e = rs_dev_alloc(&dSlots, n);
+    if (!e) e = rs_check_hip(hipMemcpy(sp.posMat, posTag, n * 16, hipMemcpyHostToDevice), "rs_debug_shadow_pass");
+    if (!e) e = rs_check_hip(hipMemcpy(sp.candLi, candLi, n * 16, hipMemcpyHostToDevice), "rs_debug_shadow_pass");
+    if (!e) e = rs_check_hip(hipMemcpy(sp.candWi, candWi, n * 16, hipMemcpyHostToDevice), "rs_debug_shadow_pass");
+    if (!e) e = rs_check_hip(hipMemset(dSlots, 0xff, n * sizeof(int)), "rs_debug_shadow_pass");
+    if (!e) {
+        launch_shadow(r, scene, sp, r->width, y0, y1, (r->width + 31) / 32, (y1 - y0 + 7) / 8, rs_stream(), dSlots);
+        e = rs_after_launch("rs_debug_shadow_pass");
+    }
+    if (!e) e = rs_synchronize();
+    if (!e) e = rs_check_hip(hipMemcpy(candWi, sp.candWi, n * 16, hipMemcpyDeviceToHost), "rs_debug_shadow_pass");
+    if (!e && slots) e = rs_check_hip(hipMemcpy(slots, dSlots, n * sizeof(int), hipMemcpyDeviceToHost), "rs_debug_shadow_pass");
+    rs_dev_free(sp.posMat); rs_dev_free(sp.candLi); rs_dev_free(sp.candWi); rs_dev_free(dSlots);
+    return e;
 }
 
 // ... and its { wo, roughness } plane, which only the pixels of a MetallicWorkflow material wrote

@@ -652,6 +652,7 @@ struct rs_restir {
     int spatialNext = 0;
     bool probe = false;              // the spatial pass goes out as k_spatial_shade_probe (rs_restir_set_probe)
     rs_light_history lights;         // light tracking and retargeting (light_history.hip)
+    bool shadowRegroup = true;       // rs_restir_set_shadow_regroup (RS_SHADOW_REGROUP=0: off from the start); a scene without occNodes keeps the plain kernel
 };
 
 static_assert(rs_context::kAux >= 1 + rs_restir::kChains, "one auxiliary stream for GBuffer::render and one per chain");
