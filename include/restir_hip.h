@@ -837,7 +837,7 @@ int  rs_restir_light_rows_unpack(rs_restir* r, int which, int y0, int rows, cons
  *   segment (one ray in rs_restir_ray_count) and is cleared when occluded.
  * Every other candidate takes today's path, the emission rescale of tracking included.  The history buffers are not written.  Slots of
  * pixels that shade nothing this frame, and the published copies they keep, have no surface to evaluate from: they are treated as
- * tracking treats them (emission rescale only).  Moved occluders do not trigger anything.
+ * tracking treats them (emission rescale only).  Moved occluders are rs_restir_set_shadow_revalidation's (below).
  * With no emitter moved since the previous frame nothing extra is launched, and the results equal tracking's bit for bit.
  * Stream-ordered like tracking; a failed allocation leaves it off with nothing changed.  Switching on marks every record AND every tracked light id
  * unknown (ids that tracking carried so far have no record to go with), and edits made before the switch are taken as seen;
@@ -854,6 +854,48 @@ int  rs_restir_download_light_samples(const rs_restir* r, int which, rs_light_sa
 int  rs_debug_restir_retarget(rs_restir* r, unsigned long long out[3]);
 /* ... and whether that frame launched the kernel at all: 1 or 0.  Host only. */
 int  rs_debug_restir_retarget_launched(rs_restir* r, int* launched);
+/* Shadow revalidation: temporal reuse notices occluders that rs_scene_set_triangles / rs_scene_set_geometry / rs_scene_set_part_transforms
+ * moved.  The reference tests visibility once, on the RIS winner, so a temporal reservoir keeps the weight it had when its
+ * shadow segment was free, and a floor behind a door that has just closed stays lit from history for up to the M clamp's 20 frames.
+ * Off by default; independent of light tracking and retargeting (all three light modes).  While it is on, a phase-A call that merges
+ * temporally (reuse & 1, not the first frame) launches one extra pass before the merge when the scene's count of accepted geometry edits
+ * (rs_scene_geometry_edits) differs from what this rs_restir saw at its previous frame, or the scene is another one.  The pass examines
+ * the temporal candidate of every shaded pixel of the call's rows whose history slot j = motion[i] passes the reference's neighbour test
+ * and holds W != 0 -- except, with retargeting on, a candidate that pass has just evaluated again.  Its segment runs from the pixel's own
+ * position of this frame to pos + wi * dist (wi, dist of slot j).  The segment is walked when its bounding box overlaps the box of one of
+ * the edits made since the previous frame (closed intervals: touching counts; a NaN coordinate never does) -- the scene keeps the boxes
+ * of its last RS_DIRTY_BOXES_KEPT edits, each the exact bounds of the old and the new corners of the triangles the edit named -- or,
+ * when an edit of that interval has left the ring or the scene changed, always.  A walked segment counts as one ray in
+ * rs_restir_ray_count / _total.  A candidate found occluded is merged as if its slot held W = 0: its M is added and it is never selected
+ * (the reference's own convention for a blocked shadow ray).  The history buffers are not written (with a moving camera two pixels read
+ * one slot), published copies of pixels that shade nothing this frame and ReSTIR-GI's reservoirs are not touched.
+ * A frame without an edit since the previous one launches exactly the kernels it launches with the switch off.  Stream-ordered, no host
+ * wait; the boxes are chosen on the host when the frame is enqueued.  Switching on takes the edits made so far as seen; a failed
+ * allocation leaves it off with nothing changed.  Memory: 4 B/px from the first switch-on.  Row bands and the strip driver's ranks
+ * revalidate their own rows; every rank applies the same edits. */
+#define RS_DIRTY_BOXES_KEPT 8
+int  rs_restir_set_shadow_revalidation(rs_restir* r, int enable);
+int  rs_restir_get_shadow_revalidation(const rs_restir* r, int* enabled);
+/* Accepted geometry edits of the scene so far (host only), and what a frame whose previous frame saw sinceEdit of them would take now:
+ * *count boxes -- the first min(*count, capacity) in boxes6, { lo xyz, hi xyz } each, oldest edit first -- or *everything = 1 (then
+ * *count = 0) when one of those edits has left the ring.  Host only. */
+int  rs_scene_geometry_edits(const rs_scene* scene, unsigned long long* count);
+int  rs_scene_dirty_boxes(const rs_scene* scene, unsigned long long sinceEdit, int capacity, float* boxes6, int* count, int* everything);
+/* Test hooks.  What the revalidation pass did in the last ended frame: out[0] candidates examined, out[1] segments walked, out[2]
+ * candidates found occluded; all 0 when the frame launched no such pass.  Waits for the library stream. */
+int  rs_debug_restir_revalidate(rs_restir* r, unsigned long long out[3]);
+/* ... and whether that frame launched the pass at all: 1 or 0.  Host only. */
+int  rs_debug_restir_revalidate_launched(rs_restir* r, int* launched);
+/* Host only (restir_amd/csrc/rs_revalidate_plan.h).  The dirty box of an edit of `count` records over a table of numPrims triangles: old
+ * corners from oldVertices (9 floats per primitive), new ones from newVertices (9 per record); an id named twice takes its last record. */
+int  rs_debug_plan_dirty_box(int numPrims, const float* oldVertices, int count, const int* primIds, const float* newVertices, float lo[3], float hi[3]);
+/* numEdits edits numbered firstEdit, firstEdit + 1, ... with the boxes boxes6 enter an empty ring one after the other; then a frame whose
+ * previous frame saw `seen` edits chooses at `now`: *launch, *everything, *n boxes (outBoxes6, room for RS_DIRTY_BOXES_KEPT, may be null). */
+int  rs_debug_plan_revalidation(int numEdits, unsigned long long firstEdit, const float* boxes6, unsigned long long seen, unsigned long long now, int sameScene,
+                                int* launch, int* everything, int* n, float* outBoxes6);
+/* n segments { a xyz, b xyz } against m <= RS_DIRTY_BOXES_KEPT boxes { lo xyz, hi xyz }, or against "everything": flags[i] = 1 where the
+ * segment is walked -- the function the kernel evaluates per lane. */
+int  rs_debug_segment_in_boxes(int n, const float* segments6, int m, const float* boxes6, int everything, unsigned char* flags);
 /* BVH walks (intersect + testOcclusion calls) performed by the last rs_restir_direct / phase_a,
  * for the Mrays/s metric. Synchronises. */
 int  rs_restir_ray_count(rs_restir* r, unsigned long long* rays);

@@ -10,6 +10,7 @@ import os
 import numpy as np
 
 from .ctypes_structs import Camera, Material, Reservoir, MATERIAL_DTYPE, RESERVOIR_DTYPE, INDIRECT_RESERVOIR_DTYPE, LIGHT_SAMPLE_DTYPE, copy_camera
+from .ctypes_structs import DIRTY_BOXES_KEPT, DIRTY_BOX_DTYPE  # noqa: F401
 from .ctypes_structs import GeometryEditLights, GeometryEditPlan, GeometryEditView
 from .ctypes_structs import STREAM_CHOICES_KEPT, StreamChoice, StreamChoiceInputs, StreamChoicePlan, StreamChoices
 
@@ -155,7 +156,7 @@ EXPORTS = [
     "rs_gbuffer_create", "rs_gbuffer_destroy", "rs_gbuffer_render", "rs_gbuffer_render_rows", "rs_gbuffer_update",
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
-    "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_set_light_retargeting", "rs_restir_get_light_retargeting", "rs_restir_download_light_samples", "rs_debug_restir_retarget", "rs_debug_restir_retarget_launched", "rs_debug_restir_surface_wo", "rs_scene_light_moves", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
+    "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_set_light_retargeting", "rs_restir_get_light_retargeting", "rs_restir_download_light_samples", "rs_debug_restir_retarget", "rs_debug_restir_retarget_launched", "rs_debug_restir_surface_wo", "rs_scene_light_moves", "rs_restir_set_shadow_revalidation", "rs_restir_get_shadow_revalidation", "rs_scene_geometry_edits", "rs_scene_dirty_boxes", "rs_debug_restir_revalidate", "rs_debug_restir_revalidate_launched", "rs_debug_plan_dirty_box", "rs_debug_plan_revalidation", "rs_debug_segment_in_boxes", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
     "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_restir_set_primary_leaf_lists", "rs_debug_set_primary_leaf_list_cap", "rs_debug_primary_leaf_list_info", "rs_debug_primary_leaf_list_missing", "rs_debug_plan_primary_leaf_list", "rs_debug_plan_primary_cut", "rs_debug_plan_primary_cut_slot", "rs_restir_set_shadow_regroup", "rs_debug_plan_shadow_regroup", "rs_debug_shadow_pass", "rs_debug_plan_stream_choice", "rs_debug_plan_stream_switch", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
     "rs_path_trace", "rs_path_trace_indirect", "rs_restir_indirect", "rs_restir_download_indirect",
     "rs_svgf_create", "rs_svgf_destroy", "rs_svgf_filter", "rs_svgf_next_frame", "rs_svgf_get_view",
@@ -239,6 +240,17 @@ def lib():
         L.rs_debug_restir_retarget_launched.argtypes = [vp, C.POINTER(ci)]
         L.rs_debug_restir_surface_wo.argtypes = [vp, vp]
         L.rs_scene_light_moves.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+    if hasattr(L, "rs_restir_set_shadow_revalidation"):   # (an A/B build from before shadow revalidation, RESTIR_HIP_LIB: tools/bench_shadow_revalidate.py)
+        ull = C.c_ulonglong
+        L.rs_restir_set_shadow_revalidation.argtypes = [vp, ci]
+        L.rs_restir_get_shadow_revalidation.argtypes = [vp, C.POINTER(ci)]
+        L.rs_scene_geometry_edits.argtypes = [vp, C.POINTER(ull)]
+        L.rs_scene_dirty_boxes.argtypes = [vp, ull, ci, vp, C.POINTER(ci), C.POINTER(ci)]
+        L.rs_debug_restir_revalidate.argtypes = [vp, C.POINTER(ull * 3)]
+        L.rs_debug_restir_revalidate_launched.argtypes = [vp, C.POINTER(ci)]
+        L.rs_debug_plan_dirty_box.argtypes = [ci, vp, ci, vp, vp, vp, vp]
+        L.rs_debug_plan_revalidation.argtypes = [ci, ull, vp, ull, ull, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
+        L.rs_debug_segment_in_boxes.argtypes = [ci, vp, ci, vp, ci, vp]
     L.rs_restir_light_rows_bytes.argtypes = [vp, ci]
     L.rs_restir_light_rows_bytes.restype = C.c_size_t
     L.rs_restir_light_rows_pack.argtypes = [vp, ci, ci, ci, vp]
@@ -610,6 +622,39 @@ def plan_shadow_regroup(lengths, bins_over_extent=None, root=None, active=None, 
     return (bins[:n], used.value, first, count.value) if plan else (bins[:n], used.value)
 
 
+def plan_dirty_box(old_vertices, prim_ids, new_vertices):
+    """rs_debug_plan_dirty_box (host only): (lo, hi) of the edit that gives the primitives prim_ids of the table old_vertices (n, 3, 3) the
+    corners new_vertices (len(prim_ids), 3, 3); an id named twice takes its last record."""
+    old = np.ascontiguousarray(old_vertices, np.float32).reshape(-1, 9)
+    ids = np.ascontiguousarray(prim_ids, np.int32).reshape(-1)
+    new = np.ascontiguousarray(new_vertices, np.float32).reshape(-1, 9)
+    if len(new) != len(ids):
+        raise ValueError("plan_dirty_box: three new vertices per id")
+    lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    check(lib().rs_debug_plan_dirty_box(len(old), _p(old), len(ids), _p(ids), _p(new), _p(lo), _p(hi)))
+    return lo, hi
+
+
+def plan_revalidation(boxes, seen, now, same_scene=True, first_edit=1):
+    """rs_debug_plan_revalidation (host only): the edits first_edit, first_edit + 1, ... with the boxes `boxes` (k, 6: lo, hi) go through
+    the scene's ring; a frame whose previous frame saw `seen` edits then chooses at `now`.  Returns (launch, everything, boxes (n, 6))."""
+    b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
+    launch, everything, n = C.c_int(), C.c_int(), C.c_int()
+    out = np.zeros((DIRTY_BOXES_KEPT, 6), np.float32)
+    check(lib().rs_debug_plan_revalidation(len(b), int(first_edit), _p(b) if len(b) else None, int(seen), int(now), 1 if same_scene else 0,
+                                           C.byref(launch), C.byref(everything), C.byref(n), _p(out)))
+    return bool(launch.value), bool(everything.value), out[:n.value].copy()
+
+
+def segment_in_boxes(segments, boxes, everything=False):
+    """rs_debug_segment_in_boxes (host only): which of the segments (n, 6: a, b) are walked against the boxes (m <= 8, 6: lo, hi)."""
+    seg = np.ascontiguousarray(segments, np.float32).reshape(-1, 6)
+    b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
+    flags = np.zeros(max(len(seg), 1), np.uint8)
+    check(lib().rs_debug_segment_in_boxes(len(seg), _p(seg) if len(seg) else None, len(b), _p(b) if len(b) else None, 1 if everything else 0, _p(flags)))
+    return flags[:len(seg)] != 0
+
+
 def plan_stream_choice(priority_range, asked=2, caller_priority=None, times_us=None):
     """rs_debug_plan_stream_choice (host only): priority_range = (least, greatest) of the device, asked -1 / 0 / 1 / 2 = automatic,
     caller_priority None for the default stream, times_us[3][4] the measured triples (None: all 1.0).  Returns StreamChoicePlan."""
@@ -924,6 +969,19 @@ class Scene:
         n = C.c_ulonglong(0)
         check(lib().rs_scene_light_moves(self.handle, C.byref(n)))
         return int(n.value)
+
+    def geometry_edits(self):
+        """rs_scene_geometry_edits: accepted geometry edits so far (host only)."""
+        n = C.c_ulonglong(0)
+        check(lib().rs_scene_geometry_edits(self.handle, C.byref(n)))
+        return int(n.value)
+
+    def dirty_boxes(self, since_edit):
+        """rs_scene_dirty_boxes: (boxes (n, 6: lo, hi), everything) a frame whose previous frame saw since_edit edits would take now."""
+        out = np.zeros((DIRTY_BOXES_KEPT, 6), np.float32)
+        n, everything = C.c_int(), C.c_int()
+        check(lib().rs_scene_dirty_boxes(self.handle, int(since_edit), DIRTY_BOXES_KEPT, _p(out), C.byref(n), C.byref(everything)))
+        return out[:n.value].copy(), bool(everything.value)
 
     def set_part_transforms(self, part_ids, matrices):
         """rs_scene_set_part_transforms: one (4, 4) float32 matrix, [column][row], per entry of `part_ids`; does what set_geometry does
@@ -1358,6 +1416,28 @@ class ReSTIR:
         """rs_debug_restir_retarget_launched: did the last ended frame launch the retargeting kernel?"""
         on = C.c_int(0)
         check(lib().rs_debug_restir_retarget_launched(self.handle, C.byref(on)))
+        return bool(on.value)
+
+    def set_shadow_revalidation(self, on=True):
+        """rs_restir_set_shadow_revalidation: after a geometry edit, temporal candidates whose shadow segment crosses the edit's box are
+        walked again before the merge; an occluded one merges as W = 0."""
+        check(lib().rs_restir_set_shadow_revalidation(self.handle, 1 if on else 0))
+
+    def get_shadow_revalidation(self):
+        on = C.c_int(0)
+        check(lib().rs_restir_get_shadow_revalidation(self.handle, C.byref(on)))
+        return bool(on.value)
+
+    def revalidate_stats(self):
+        """rs_debug_restir_revalidate: (candidates examined, segments walked, candidates found occluded) of the last ended frame."""
+        out = (C.c_ulonglong * 3)()
+        check(lib().rs_debug_restir_revalidate(self.handle, C.byref(out)))
+        return tuple(int(x) for x in out)
+
+    def revalidate_launched(self):
+        """rs_debug_restir_revalidate_launched: did the last ended frame launch the revalidation kernel?"""
+        on = C.c_int(0)
+        check(lib().rs_debug_restir_revalidate_launched(self.handle, C.byref(on)))
         return bool(on.value)
 
     def light_rows_bytes(self, rows):

@@ -30,6 +30,7 @@
 #include "rs_light_history.h"
 #include "rs_cuts.h"
 #include "rs_shadow_regroup.h"
+#include "rs_revalidate.h"
 
 using namespace rs;
 
@@ -475,10 +476,13 @@ __global__ void __launch_bounds__(kShadowRegroupRays, RS_WALK_WAVES) k_shadow_re
 // k_temporal<*, 1> and <*, 2> came out of the compiler four to five instructions shorter with a quarter of their lines changed (the
 // published copy's loads of W and Li no longer wait for the id test), and this form keeps the instructions of the measured kernels.
 // LIGHTS = 2: the merge carries the records, and takes the flagged candidates from k_retarget's planes
-template <bool SOBOL, int LIGHTS>
+// MARKED (shadow revalidation, rs_revalidate.h): a candidate read from its history slot whose pixel k_revalidate marked in this call merges
+// as if the slot held W = 0 -- its M is added, it is never selected, and tracking does not rescale it.  A compile-time form: the
+// unmarked kernels keep their code, and only a call that launched k_revalidate takes the marked one.
+template <bool SOBOL, int LIGHTS, bool MARKED = false>
 __device__ __forceinline__ void temporal_body(const SurfPlanes& sp, const GBufView& g, const ResvPlanes& last, const ResvPlanes& cur, const TempPlanes& temp, const uint32_t* sampleSeq, int looper,
                                               int first, int reuse, int n0, int n1, unsigned long long* rayWork, unsigned long long* rayDone, const LightIds& ids,
-                                              const LightRecs& recs) {
+                                              const LightRecs& recs, const RevalMarks marks = RevalMarks{ nullptr, 0u }) {
     constexpr bool TRACK = LIGHTS >= 1, RETARGET = LIGHTS == 2;
     RS_SETPRIO(RS_PRIO_STREAM);
     // this call's BVH-walk counters are complete (the launch is ordered after the chain that counted): publish them and leave the
@@ -555,6 +559,7 @@ __device__ __forceinline__ void temporal_body(const SurfPlanes& sp, const GBufVi
             const float4 a = ld_stream(last.li + lastIdx), b = ld_stream(last.wi + lastIdx);
             t.Li = mk3(a.x, a.y, a.z); t.dist = a.w; t.wi = mk3(b.x, b.y, b.z);
             t.W = ld_stream(last.w + lastIdx); t.M = ld_stream(last.m + lastIdx);
+            if (MARKED) { if (__builtin_nontemporal_load(marks.flag + index) == marks.epoch) t.W = 0.f; }
             if (TRACK) {
                 tid = ld_stream(ids.last + lastIdx);
                 if (tid >= 0 && tid < ids.numLights && tid != ids.envId && t.W != 0.f) {
@@ -599,6 +604,15 @@ __global__ void __launch_bounds__(256) k_temporal(SurfPlanes sp, GBufView g, Res
                                                   int first, int reuse, int n0, int n1, unsigned long long* rayWork, unsigned long long* rayDone, MergeLights<LIGHTS> lights) {
     if constexpr (LIGHTS == 2) temporal_body<SOBOL, 2>(sp, g, last, cur, temp, sampleSeq, looper, first, reuse, n0, n1, rayWork, rayDone, lights.ids, lights.recs);
     else temporal_body<SOBOL, LIGHTS>(sp, g, last, cur, temp, sampleSeq, looper, first, reuse, n0, n1, rayWork, rayDone, lights.ids, LightRecs{});
+}
+
+// the merge of a call that launched k_revalidate
+template <bool SOBOL, int LIGHTS>
+__global__ void __launch_bounds__(256) k_temporal_marked(SurfPlanes sp, GBufView g, ResvPlanes last, ResvPlanes cur, TempPlanes temp, const uint32_t* sampleSeq, int looper,
+                                                         int first, int reuse, int n0, int n1, unsigned long long* rayWork, unsigned long long* rayDone, MergeLights<LIGHTS> lights,
+                                                         RevalMarks marks) {
+    if constexpr (LIGHTS == 2) temporal_body<SOBOL, 2, true>(sp, g, last, cur, temp, sampleSeq, looper, first, reuse, n0, n1, rayWork, rayDone, lights.ids, lights.recs, marks);
+    else temporal_body<SOBOL, LIGHTS, true>(sp, g, last, cur, temp, sampleSeq, looper, first, reuse, n0, n1, rayWork, rayDone, lights.ids, LightRecs{}, marks);
 }
 
 // ---- phase B: spatial reuse + shade --------------------------------------------------------------
@@ -960,6 +974,7 @@ int rs_restir_free(rs_restir* r) {
     for (auto& perStream : r->split) for (auto& t : perStream) rs_tile_split_free(&t);
     rs_dev_free(r->indResv[0]); rs_dev_free(r->indResv[1]);
     rs_light_history_free(r->lights);
+    rs_revalidate_free(r->reval);
     rs_primary_cuts_destroy(r->cuts);
     for (auto& e : r->ev) if (e) (void)hipEventDestroy(e);
     for (auto& pair : r->spatialEv) for (hipEvent_t& e : pair) if (e) (void)hipEventDestroy(e);
@@ -1245,9 +1260,14 @@ int phase_a_impl(rs_restir* r, const rs_scene* scene, const rs_camera* cam, cons
     RS_TRY(rs_gbuffer_join(g));                                 // first consumer of the G-buffer planes
     LightIds ids; LightRecs recs;
     RS_TRY(rs_light_history_phase_a(r->lights, scene, r->surfSet, !r->firstFrame && (reuse & 1), sp, gbuf_view(g), r->last, y0, y1, tilesX, tilesY, rayCounter, &ids, &recs));
+    // geometry edited since the previous frame: the temporal candidates whose shadow segment crosses an edit's box are walked again
+    RevalMarks marks;
+    RS_TRY(rs_revalidate_phase_a(r, scene, !r->firstFrame && (reuse & 1), sp, gbuf_view(g), y0, y1, tilesX, tilesY, rayCounter, recs.flag, &marks));
     rs_dispatch_lights(rs_light_mode(r->lights), [&](auto LIGHTS) {
         rs_dispatch([&](auto SOBOL) {
-            hipLaunchKernelGGL((k_temporal<SOBOL(), LIGHTS()>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g), r->last, r->cur, r->temp,
+            if (marks.flag) hipLaunchKernelGGL((k_temporal_marked<SOBOL(), LIGHTS()>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g), r->last, r->cur, r->temp,
+                               scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, merge_lights<LIGHTS()>(ids, recs), marks);
+            else hipLaunchKernelGGL((k_temporal<SOBOL(), LIGHTS()>), dim3((npx + 255) / 256), dim3(256), 0, rs_stream(), sp, gbuf_view(g), r->last, r->cur, r->temp,
                                scene->dev.sampleSeq, looper, r->firstFrame ? 1 : 0, reuse, y0 * W, y1 * W, rayCounter, rayDone, merge_lights<LIGHTS()>(ids, recs));
         }, sobol);
     });
@@ -1407,6 +1427,7 @@ int rs_restir_end_frame(rs_restir* r) {
     if (!r) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_restir_end_frame: null");
     ResvPlanes t = r->cur; r->cur = r->last; r->last = t;       // std::swap(devDirectReservoir, devLastDirectReservoir)
     rs_light_history_end_frame(r->lights, r->phaseACalls);
+    rs_revalidate_end_frame(r->reval, r->phaseACalls);
     r->firstFrame = false;
     // every reader of this frame's surface planes has been enqueued: the set is free for the frame after the next one
     if (!rs_sync_enabled()) { RS_HIP(hipEventRecord(r->surfFree[r->surfSet], rs_stream())); r->surfFreeValid[r->surfSet] = true; }

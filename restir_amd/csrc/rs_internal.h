@@ -24,6 +24,7 @@
 
 #include "rs_scene.h"
 #include "rs_geometry_plan.h"
+#include "rs_revalidate_plan.h"
 #include "rs_walk.h"
 #include "rs_bsdf.h"
 #include "rs_tilesplit.h"
@@ -286,6 +287,9 @@ struct rs_scene {
     unsigned long long lightMoves = 0;
     std::vector<uint32_t> hLightMoved;
     std::vector<int> hLightOfPrim;
+    // Dirty boxes (rs_restir_set_shadow_revalidation; rs_revalidate_plan.h): the box of each of the last RS_DIRTY_BOXES_KEPT accepted
+    // geometry edits with its number, geomEdits once the edit was counted.  Host only, written where the edit is enqueued.
+    rs_dirty_ring dirty;
 };
 
 // ---- G-buffer (src/gbuffer.h:41-58) ------------------------------------------------------------
@@ -602,6 +606,23 @@ int  rs_light_history_forget(rs_light_history& h, size_t pixels, unsigned which,
 void rs_light_history_end_frame(rs_light_history& h, int phaseACalls);      // cur and last change places, as the reservoirs'
 void rs_light_history_free(rs_light_history& h);
 
+// Shadow revalidation of one rs_restir (include/restir_hip.h); shadow_revalidate.hip owns every field.  sceneId / seen: the scene of the
+// previous frame and its count of accepted geometry edits then -- kept whether the switch is on or not; frameScene / frameEdits: of this
+// frame's phase-A calls, which rs_revalidate_end_frame makes the previous frame's.  flag: one word per pixel, equal to the epoch of the
+// phase-A call whose k_revalidate found the pixel's temporal candidate occluded -- every launch takes a new epoch, so the plane is never
+// cleared, and a block without a walker does not touch it.
+struct rs_shadow_revalidation {
+    bool on = false;
+    bool fresh = false;                    // switched on since the previous frame: the edits made so far count as seen
+    unsigned* flag = nullptr;              // 4 B/px, allocated at the first switch-on
+    unsigned long long* dStats = nullptr;  // { examined, walked, occluded } of the last frame that launched, each in partial counters: cleared, added to and read in the library stream's order
+    unsigned epoch = 0;                    // of the last launch (0: none; the plane starts as zeros)
+    unsigned long long sceneId = 0, seen = 0, frameScene = 0, frameEdits = 0;
+    bool launched = false, launchedLast = false;      // this frame / the frame that ended last launched k_revalidate
+};
+void rs_revalidate_end_frame(rs_shadow_revalidation& v, int phaseACalls);
+void rs_revalidate_free(rs_shadow_revalidation& v);
+
 struct rs_restir {
     rs_context* ctx = nullptr;
     rs_primary_cuts cuts;
@@ -653,6 +674,7 @@ struct rs_restir {
     bool probe = false;              // the spatial pass goes out as k_spatial_shade_probe (rs_restir_set_probe)
     rs_light_history lights;         // light tracking and retargeting (light_history.hip)
     bool shadowRegroup = true;       // rs_restir_set_shadow_regroup (RS_SHADOW_REGROUP=0: off from the start); a scene without occNodes keeps the plain kernel
+    rs_shadow_revalidation reval;    // rs_restir_set_shadow_revalidation (shadow_revalidate.hip)
 };
 
 static_assert(rs_context::kAux >= 1 + rs_restir::kChains, "one auxiliary stream for GBuffer::render and one per chain");

@@ -448,6 +448,9 @@ void make_boxes_exact(rs_scene* s) {
 // `dev` follows from them
 void update_host_tables(rs_scene* s, int m, const Records& rec, bool normals) {
     rs_refit* r = s->refit;
+    // the edit's dirty box (rs_revalidate_plan.h), while hVertices still holds the old corners
+    float dirtyLo[3], dirtyHi[3];
+    rs_plan_dirty_box(s->hVertices.data(), m, rec.ids, rec.vertices, true, dirtyLo, dirtyHi);
     for (int j = 0; j < m; j++) {
         std::memcpy(&s->hVertices[(size_t)rec.ids[j] * 9], rec.vertices + (size_t)j * 9, 9 * sizeof(float));
         if (normals) std::memcpy(&s->hNormals[(size_t)rec.ids[j] * 9], rec.normals + (size_t)j * 9, 9 * sizeof(float));
@@ -463,6 +466,7 @@ void update_host_tables(rs_scene* s, int m, const Records& rec, bool normals) {
     }
     s->edits++;                                                  // retained G-buffer planes are not this scene's any more
     s->geomEdits++;                                              // ... and cuts of the tree carry boxes the refit has just changed
+    rs_dirty_ring_push(s->dirty, s->geomEdits, dirtyLo, dirtyHi);   // ... and shadow segments through this box may have changed their answer
     if (s->dev.prevVertices) s->motionDirty = true;              // rs_scene_advance_motion has something to copy
 }
 
@@ -642,6 +646,23 @@ extern "C" int rs_scene_set_part_transforms(rs_scene* s, int count, const int* p
 extern "C" int rs_scene_light_moves(const rs_scene* s, unsigned long long* moves) {
     if (!s || !moves) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_light_moves: null argument");
     *moves = s->lightMoves;
+    return 0;
+}
+
+extern "C" int rs_scene_geometry_edits(const rs_scene* s, unsigned long long* count) {
+    if (!s || !count) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_geometry_edits: null argument");
+    *count = s->geomEdits;
+    return 0;
+}
+
+// what a frame whose previous frame saw `sinceEdit` edits would take from the ring now (rs_plan_revalidation)
+extern "C" int rs_scene_dirty_boxes(const rs_scene* s, unsigned long long sinceEdit, int capacity, float* boxes6, int* count, int* everything) {
+    if (!s || !count || !everything || capacity < 0 || (capacity > 0 && !boxes6)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_dirty_boxes: bad argument");
+    rs_revalidate_choice c;
+    rs_plan_revalidation(s->dirty.e, s->dirty.count, sinceEdit, s->geomEdits, true, c);
+    *count = c.boxes.n; *everything = c.boxes.everything;
+    for (int i = 0; i < c.boxes.n && i < capacity; i++)
+        for (int k = 0; k < 3; k++) { boxes6[i * 6 + k] = c.boxes.box[i].lo[k]; boxes6[i * 6 + 3 + k] = c.boxes.box[i].hi[k]; }
     return 0;
 }
 

@@ -144,6 +144,11 @@ assert MATERIAL_DTYPE.itemsize == 44 and RESERVOIR_DTYPE.itemsize == 36 and INDI
 # rs_light_sample (rs_restir_download_light_samples): the record beside a reservoir's sample while light retargeting is on, 16 bytes
 LIGHT_SAMPLE_DTYPE = np.dtype([("light", "<i4"), ("u", "<f4"), ("v", "<f4"), ("pdf", "<f4")])
 assert LIGHT_SAMPLE_DTYPE.itemsize == 16
+# a dirty box of shadow revalidation (rs_scene_dirty_boxes, rs_debug_plan_revalidation): { lo xyz, hi xyz }, 24 bytes; a scene keeps the
+# boxes of its last DIRTY_BOXES_KEPT geometry edits (RS_DIRTY_BOXES_KEPT)
+DIRTY_BOX_DTYPE = np.dtype([("lo", "<f4", (3,)), ("hi", "<f4", (3,))])
+DIRTY_BOXES_KEPT = 8
+assert DIRTY_BOX_DTYPE.itemsize == 24
 
 # Material::Type (src/material.h:114-120)
 LAMBERTIAN, METALLIC_WORKFLOW, DIELECTRIC, DISNEY, LIGHT = range(5)
