@@ -304,7 +304,8 @@ int  rs_scene_set_materials(rs_scene* scene, int count, const int* materialIds, 
  * stream waits, by events, for what the library's internal streams have been handed so far, the refit runs on the library stream, and
  * the next launch of every internal stream waits for it -- launches enqueued before the call read the old geometry, launches after
  * it the new.  The first edit of a scene builds and uploads the refit's tables and waits for the device once.  Every edit refits the
- * whole scene, O(numPrims) on the device and on the host, however few triangles it names (DESIGN.md section 3 has the cost).  An
+ * whole scene, O(numPrims) on the device, however few triangles it names, unless rs_scene_set_partial_refit (below) has been switched
+ * on (DESIGN.md section 3 has the cost of both).  An
  * accepted edit invalidates retained G-buffer planes.  A repeated id takes its last record; count == 0 succeeds and changes nothing.
  * Refused with RS_ERR_INVALID_ARGUMENT, the scene unchanged: count < 0 or null arrays with count > 0; an id out of range; a vertex or
  * normal that is not finite; a triangle whose material is a Light (this is the call that guarantees that the light sampler, the light
@@ -367,7 +368,8 @@ int  rs_scene_light_moves(const rs_scene* scene, unsigned long long* moves);
  * any number of frames.  rs_scene_set_triangles / rs_scene_set_geometry on a part's triangle is allowed and moves it until the next
  * transform of that part puts it back on the baked rest pose.  count == 0, or only empty parts, succeeds and changes nothing.
  * Additionally refused with RS_ERR_INVALID_ARGUMENT: no parts defined, a part id out of range, null arrays with count > 0.
- * INTEGRATION.md section 3f has the frame loop; DESIGN.md section 3 the cost (every edit still refits the whole scene). */
+ * INTEGRATION.md section 3f has the frame loop; DESIGN.md section 3 the cost (the refit is the whole scene's unless
+ * rs_scene_set_partial_refit is on). */
 int  rs_scene_define_parts(rs_scene* scene, int numParts, const int* partFirst, const int* primIds, const float* restVertices, const float* restNormals);
 int  rs_scene_set_part_transforms(rs_scene* scene, int count, const int* partIds, const float* matrices16);
 /* Host only: the number of parts and of primitives listed in them (0, 0: none defined).  Either pointer may be NULL. */
@@ -417,6 +419,45 @@ typedef struct rs_geometry_edit_lights {
 int  rs_debug_plan_geometry_edit(const rs_geometry_edit_view* view, const char* name, int emitters, int count, const int* primIds,
                                  const float* vertices, const float* normals, int numPartRecs, rs_geometry_edit_plan* plan, int* slots,
                                  rs_geometry_edit_lights* lights, float* area, float* prob, int* failId);
+/* Partial refit: an edit that names few triangles recomputes, in every tree, only the boxes on the paths from those triangles' leaves to
+ * the roots, and leaves every device table bit for bit what the whole-scene refit leaves.  (The reference has no moving geometry: there is
+ * no reference line to cite.)  on = 0 is the default: every edit refits the whole scene, through exactly the launches it made before this
+ * switch existed, and nothing more is allocated.  on = 1: an accepted edit of any of the three kinds (rs_scene_set_triangles,
+ * rs_scene_set_geometry, rs_scene_set_part_transforms) is partial when it names at most maxTriangles distinct triangles, when the bound
+ * on the nodes it can dirty -- that number times the sum over the scene's trees of (depth + 1) -- is at most what the path's work words
+ * can name (2^32 - 2), and when a whole refit of this scene has run before; otherwise it refits the whole scene.  The first edit of a
+ * scene is therefore always whole: it builds the tables and replaces caller-supplied inexact boxes.  maxTriangles < 0 selects the
+ * library's default, 4096: the largest m of the sweep 1, 16, 256, 4096, 1 % of the triangles at which the partial refit's stream time
+ * was at most 0.8 x the whole refit's on both benchmark scenes.  Stream time of one edit, partial / whole refit of the commit before
+ * the switch (DESIGN.md section 3 has the full table and the frame periods):
+ *       m        262 144 triangles (Sponza-class)     2 830 336 triangles (Bistro-class)
+ *       1        0.298 / 6.10 ms   0.05 x             0.340 / 74.5 ms   0.005 x
+ *       16       0.524 / 6.04      0.09               0.544 / 74.4      0.007
+ *       256      0.778 / 6.09      0.13               0.910 / 74.6      0.012
+ *       4 096    1.828 / 6.19      0.30               2.725 / 74.7      0.037
+ *       1 %      1.212 / 6.16      0.20  (2 611)      50.90 / 76.1      0.67  (28 200: host-bound, and a different m per scene)
+ * Everything else about the three
+ * entry points is unchanged: arguments, refusals, staging ring, fences, "a repeated id takes its last record", count == 0,
+ * rs_scene_host_desc afterwards, RS_ERR_UNSUPPORTED during capture, invalidation of retained planes, dirty boxes for shadow
+ * revalidation, RS_TABLE_LIGHT_MOVED and the previous pose of a tracked scene.  An edit that names an emitter still re-quantises every
+ * record of the emissive tree, whose grid moves with the lamps.  The switch itself is host only, waits for nothing and may be flipped
+ * between any two edits; the first edit made with it on builds the path's tables (12 bytes per tree node, 24 per reference node, 4 per
+ * triangle and grid-box tree: INTEGRATION.md section 3c) and waits for the device once, as the first edit of a scene does.
+ * rs_scene_get_partial_refit returns the switch and the threshold in force (the default's value, not -1); either pointer may be NULL.
+ * rs_scene_refit_counts: how many accepted edits of this scene refitted the whole scene and how many were partial (host only; either
+ * pointer may be NULL).  Refused with RS_ERR_INVALID_ARGUMENT: a null scene, on other than 0 / 1, maxTriangles == 0. */
+int  rs_scene_set_partial_refit(rs_scene* scene, int on, int maxTriangles);
+int  rs_scene_get_partial_refit(const rs_scene* scene, int* on, int* maxTriangles);
+int  rs_scene_refit_counts(const rs_scene* scene, unsigned long long* whole, unsigned long long* partial);
+/* Test hooks.  rs_debug_scene_refit_dirty waits as rs_synchronize does and returns how many distinct nodes the most recent accepted edit
+ * recomputed on the partial path, 0 when that edit refitted the whole scene or there was none: nodes of the reference tree, records of
+ * the shadow tree and of the six ordered trees; the emissive tree's are not counted.  RS_ERR_UNSUPPORTED while the library stream is being
+ * captured.  rs_debug_plan_refit is the decision itself (restir_amd/csrc/rs_geometry_plan.h rs_plan_refit), device-free: m distinct
+ * triangles, treeDepth[numTrees] the deepest leaf of each tree with the root at 0; *bound = m x sum (treeDepth + 1), *partial = 1 iff on,
+ * keysValid, m <= maxTriangles (< 0: the default) and bound <= capacity.  numNodes does not enter the decision. */
+int  rs_debug_scene_refit_dirty(const rs_scene* scene, unsigned long long* nodes);
+int  rs_debug_plan_refit(int on, int maxTriangles, int keysValid, int m, int numTrees, const int* treeDepth,
+                         unsigned long long numNodes, unsigned long long capacity, int* partial, unsigned long long* bound);
 /* Motion tracking: the previous pose of the scene, for the G-buffer's motion plane.  (The reference has no moving geometry: there is no
  * reference line to cite.  Its renderGBuffer, src/gbuffer.cu:49-54, asks where the hit's world point was on last frame's screen.)
  * A tracked scene keeps a second vertex array on the device, 36 bytes per triangle: the vertices as they stood at the last

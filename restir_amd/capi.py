@@ -164,6 +164,7 @@ EXPORTS = [
     "rs_add_image", "rs_add_image3", "rs_comm_create_rccl", "rs_comm_create_rccl_lib", "rs_comm_create", "rs_comm_destroy", "rs_comm_self_exchange", "rs_strips_create", "rs_strips_destroy", "rs_strips_rows", "rs_strips_set_comm_stream", "rs_strips_set_gbuffer_halo", "rs_strips_set_light_tracking", "rs_strips_frame", "rs_strips_eaw_filter", "rs_strips_svgf_filter", "rs_strips_exchange_svgf_history", "rs_strips_exchange_history", "rs_strips_gather", "rs_strips_gather_begin", "rs_strips_gather_end", "rs_strips_enable_timing", "rs_strips_halo_wait_ms",
     "rs_scene_file_load", "rs_scene_file_get", "rs_scene_file_free", "rs_build_transformation_matrix", "rs_bake_instance",
     "rs_bake_matrix", "rs_scene_file_objects", "rs_scene_define_parts", "rs_scene_set_part_transforms", "rs_scene_parts_info", "rs_scene_download_part_rest", "rs_debug_scene_staged_bytes", "rs_debug_plan_geometry_edit",
+    "rs_scene_set_partial_refit", "rs_scene_get_partial_refit", "rs_scene_refit_counts", "rs_debug_scene_refit_dirty", "rs_debug_plan_refit",
 ]
 
 _lib = None
@@ -288,6 +289,13 @@ def lib():
     L.rs_debug_phase_a_plan.argtypes = [C.POINTER(PhaseAInputs), C.POINTER(PhaseAPlan)]
     L.rs_debug_plan_geometry_edit.argtypes = [C.POINTER(GeometryEditView), C.c_char_p, ci, ci, vp, vp, vp, ci, C.POINTER(GeometryEditPlan), vp,
                                               C.POINTER(GeometryEditLights), vp, vp, vp]
+    if hasattr(L, "rs_scene_set_partial_refit"):          # (an A/B build from before the partial refit, RESTIR_HIP_LIB: tools/bench_partial_refit.py)
+        ull = C.c_ulonglong
+        L.rs_scene_set_partial_refit.argtypes = [vp, ci, ci]
+        L.rs_scene_get_partial_refit.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+        L.rs_scene_refit_counts.argtypes = [vp, C.POINTER(ull), C.POINTER(ull)]
+        L.rs_debug_scene_refit_dirty.argtypes = [vp, C.POINTER(ull)]
+        L.rs_debug_plan_refit.argtypes = [ci, ci, ci, ci, ci, vp, ull, ull, C.POINTER(ci), C.POINTER(ull)]
     L.rs_restir_set_primary_cuts.argtypes = [vp, ci]
     L.rs_debug_set_primary_cut_cap.argtypes = [vp, ci]
     L.rs_debug_primary_cut_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(ci), C.POINTER(C.c_ulonglong)]
@@ -506,6 +514,16 @@ def plan_geometry_edit(view, name, emitters, prim_ids, vertices, normals=None, n
     for k in ("emiLo", "emiHi", "emiBase", "emiScale"):
         out[k] = np.array(getattr(lights, k)[:], np.float32)
     return plan, slots, out
+
+
+def plan_refit(on, max_triangles, keys_valid, m, tree_depths, num_nodes=0, capacity=0xfffffffe):
+    """rs_debug_plan_refit: whether an edit of m distinct triangles is partial, and its bound on dirty nodes; needs no device.
+    tree_depths: the deepest leaf of every tree (the root at 0).  Returns (partial, bound)."""
+    d = np.ascontiguousarray(tree_depths, np.int32).reshape(-1)
+    partial, bound = C.c_int(-1), C.c_ulonglong(0)
+    check(lib().rs_debug_plan_refit(int(on), int(max_triangles), int(keys_valid), int(m), int(d.size), _p(d), int(num_nodes), int(capacity),
+                                    C.byref(partial), C.byref(bound)))
+    return bool(partial.value), int(bound.value)
 
 
 def prepare_streams():
@@ -1004,6 +1022,29 @@ class Scene:
         ids, v, nn = np.zeros(n, np.int32), np.zeros((n, 3, 3), np.float32), np.zeros((n, 3, 3), np.float32)
         check(lib().rs_scene_download_part_rest(self.handle, _p(ids), _p(v), _p(nn)))
         return ids, v, nn
+
+    def set_partial_refit(self, on=True, max_triangles=-1):
+        """rs_scene_set_partial_refit: an edit of at most max_triangles triangles (< 0: the library's default) recomputes only the boxes
+        above those triangles' leaves; host only."""
+        check(lib().rs_scene_set_partial_refit(self.handle, 1 if on else 0, int(max_triangles)))
+
+    def partial_refit(self):
+        """rs_scene_get_partial_refit: (on, the threshold in force)."""
+        on, m = C.c_int(-1), C.c_int(0)
+        check(lib().rs_scene_get_partial_refit(self.handle, C.byref(on), C.byref(m)))
+        return bool(on.value), m.value
+
+    def refit_counts(self):
+        """rs_scene_refit_counts: (whole, partial) refits of the accepted edits so far (host only)."""
+        w, p = C.c_ulonglong(0), C.c_ulonglong(0)
+        check(lib().rs_scene_refit_counts(self.handle, C.byref(w), C.byref(p)))
+        return int(w.value), int(p.value)
+
+    def refit_dirty(self):
+        """rs_debug_scene_refit_dirty (test hook): distinct nodes the most recent edit recomputed on the partial path (0: it was whole)."""
+        n = C.c_ulonglong(0)
+        check(lib().rs_debug_scene_refit_dirty(self.handle, C.byref(n)))
+        return int(n.value)
 
     def staged_bytes(self):
         """rs_debug_scene_staged_bytes (test hook): bytes the last accepted geometry edit copied from the host to the device."""

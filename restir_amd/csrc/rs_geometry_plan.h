@@ -1,7 +1,7 @@
 // rs_geometry_plan.h -- the device-free half of a geometry edit (rs_scene_set_triangles, rs_scene_set_geometry, rs_scene_set_part_transforms):
 // every check of the caller's arrays, the compaction of repeated ids, the layout of the staged records, and -- when an emitter moves --
 // the new light sampler and the emissive tree's new grid, as functions of plain arrays and integers (rs_geometry_edit_view ->
-// rs_geometry_edit_plan, include/restir_hip.h).  Nothing here touches the device, a context or a global: scene_edits.hip set_geometry
+// rs_geometry_edit_plan, include/restir_hip.h); and whether the edit refits the whole scene or only above its triangles (rs_plan_refit).  Nothing here touches the device, a context or a global: scene_edits.hip set_geometry
 // fills the view from the scene, asks for the plans and acts on their fields, and rs_debug_plan_geometry_edit hands the same functions to
 // a test that has no device.  A refusal is the error code returned and, in `why`, the text as the entry point reports it.
 #pragma once
@@ -99,6 +99,28 @@ inline void rs_fill_edit_records(const rs_geometry_edit_plan& plan, const rs_edi
         std::memcpy(hv + j * 9, vertices + (size_t)i * 9, 9 * sizeof(float));
         if (normals) std::memcpy(hn + j * 9, normals + (size_t)i * 9, 9 * sizeof(float));
     }
+}
+
+// Whole refit or partial (rs_scene_set_partial_refit): a function of these integers alone.  m: the distinct triangles the edit names;
+// treeDepth[numTrees]: the deepest leaf of every tree the partial path climbs (the reference tree, and the grid-box trees the scene has),
+// the root at depth 0.  An edited triangle dirties one leaf and that leaf's ancestors in every tree, so
+//     bound = m * sum over the trees of (depth + 1)
+// is the most nodes the edit can dirty and, being at least m * numTrees, also bounds the lanes of a launch of the partial path (one per
+// edited triangle and tree).  capacity is what the path's owner words can name (kRefitPartialCapacity below).  maxTriangles < 0: the
+// library's default.  Partial iff on, keysValid (a whole refit of this scene has left its key boxes), m <= maxTriangles, bound <= capacity.
+// numNodes is carried for the record (the whole refit's launches are sized by it); the decision does not read it.
+// DESIGN.md section 3 has the measurement the default threshold is set from.
+constexpr int kRefitPartialDefaultMaxTriangles = 4096;
+// a leaf's owner word holds 1 + the index of a lane of the mark launch in 32 bits: so many lanes can be told apart
+constexpr unsigned long long kRefitPartialCapacity = 0xfffffffeull;
+inline void rs_plan_refit(bool on, int maxTriangles, bool keysValid, int m, int numTrees, const int* treeDepth, unsigned long long numNodes,
+                          unsigned long long capacity, bool* partial, unsigned long long* bound) {
+    (void)numNodes;
+    unsigned long long perTriangle = 0;
+    for (int t = 0; t < numTrees; t++) perTriangle += (unsigned long long)treeDepth[t] + 1ull;
+    *bound = (unsigned long long)m * perTriangle;
+    const int limit = maxTriangles < 0 ? kRefitPartialDefaultMaxTriangles : maxTriangles;
+    *partial = on && keysValid && m <= limit && *bound <= capacity;
 }
 
 // The light sampler of numLightPrims light primitives with radiance `rad` (3 floats each), areas `area` and, when numLights is one more, the

@@ -229,7 +229,11 @@ struct rs_scene {
     std::vector<int> hEmiLeafPrims;
     double emiMargin = 0.0;
     struct rs_refit* refit = nullptr;
-    struct rs_parts* parts = nullptr;    // rigid parts and their rest pose (rs_scene_define_parts; rs_refit.h); null: none defined
+    // rs_scene_set_partial_refit: the switch and its threshold as the caller set them (< 0: the library's default).  The scene's own, because
+    // the switch may be set before the first edit has made `refit`; the tables of the partial path belong to `refit` (rs_refit.h)
+    bool partialRefit = false;
+    int partialMaxTriangles = -1;
+    struct rs_parts* parts = nullptr;   // rigid parts and their rest pose (rs_scene_define_parts; rs_refit.h); null: none defined
     // Motion tracking (rs_scene_set_motion_tracking, rs_scene_advance_motion): dev.prevVertices is dPrevVertices while tracking is on, null
     // otherwise; the array stays allocated until rs_scene_destroy.  motionDirty: a geometry edit has been accepted since prevVertices was
     // last made equal to the vertices, i.e. the two may differ.  The fences are the geometry edits' (rs_refit::before / after), the scene's own

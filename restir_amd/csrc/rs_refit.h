@@ -1,7 +1,8 @@
 // rs_refit.h -- what rs_scene_set_triangles / rs_scene_set_geometry keep per scene (scene_edits.hip: the entry points; rs_geometry_plan.h: their host decisions; scene_refit.hip: tables,
 // kernels, rs_refit_boxes).
 //
-// A refit keeps every tree's topology and recomputes every box from the vertices: the reference tree (nodesAll's six orders, occChain)
+// A refit keeps every tree's topology and recomputes every box from the vertices (the partial refit of rs_scene_set_partial_refit: every
+// box above an edited triangle, which leaves the same tables): the reference tree (nodesAll's six orders, occChain)
 // and the grid-box trees over the reference's leaf boxes (occNodes, the six orders of ordNodes and, when the edit names an emitter,
 // emiNodes on the emissive tree's own grid).  A box is a min / max of floats, taken
 // on order-preserving integer keys (-0 below +0), so the result does not depend on the order in which threads arrive and the host
@@ -41,9 +42,24 @@ struct rs_refit {
     size_t numNodes = 0, gridFirst = 0, occRecords = 0, ordRecords = 0;      // ordRecords: per order (ordStride / 16)
     size_t emiRecords = 0;           // last in the index space, so that an edit that names no emitter simply stops short of them
     bool emiSticky = false;          // the emissive tree was switched off for good (caller-supplied boxes that were not exact unions)
-    // ---- scratch of one refit ----
-    unsigned* dKeys = nullptr;       // [numNodes][6] the boxes as keys
+    // ---- the boxes as keys: scratch of a whole refit, and what it leaves is the state a partial refit starts from ----
+    unsigned* dKeys = nullptr;       // [numNodes][6] after any refit: the exact key box of every node (the emissive range: only after a refit that reached it)
     unsigned* dArrived = nullptr;    // [numNodes] children that have merged their box into the node
+    bool keysValid = false;          // a whole refit has run: dKeys holds every box outside the emissive range, and every later refit keeps it so
+    // ---- the partial refit (rs_scene_set_partial_refit; scene_refit.hip).  Trees: the reference tree, then occNodes, then the six orders of
+    //      ordNodes, as far as the scene has them; the emissive tree is none of them.  Depths from rs_refit_prepare; the device tables from
+    //      the first edit made with the switch on (rs_refit_prepare_partial) ----
+    int numTrees = 0;
+    int treeDepth[8] = {};           // the deepest leaf of each tree, the root at 0: an edited triangle dirties at most treeDepth + 1 nodes of it
+    bool partialReady = false;
+    int* dOther = nullptr;           // [numNodes - emiRecords] the node's sibling (-1 at a root, and at a record that is no node)
+    int* dLeafNode = nullptr;        // [numTrees - 1][numPrims] primitive -> the leaf record, in the index space, that holds it in each grid-box tree
+    int* dNodeRecs = nullptr;        // [bvhSize][6] the inverse of dBoxId: the record of each order of nodesAll that carries the node's box
+    unsigned* dExpected = nullptr;   // [numNodes - emiRecords] children of the node that are dirty in the edit under way; 0 between edits
+    unsigned* dOwner = nullptr;      // [numNodes - emiRecords] at a leaf: 1 + the lane (edited triangle, tree) that owns it in the edit under way; 0 between edits
+    unsigned* dDirty = nullptr;      // [1] nodes the most recent partial refit recomputed (rs_debug_scene_refit_dirty)
+    bool lastPartial = false;        // the most recent accepted edit took the partial path
+    unsigned long long wholeRefits = 0, partialRefits = 0;      // rs_scene_refit_counts
     // ---- the edited triangles on their way to the device ----
     static constexpr int kStaging = 4;
     struct Stage { char* host = nullptr; size_t capacity = 0; hipEvent_t copied = nullptr; bool pending = false; } stage[kStaging];
@@ -85,10 +101,14 @@ int rs_bake_parts_enqueue(const rs_parts* parts, int numRecs, const rs::PartRec*
 void rs_parts_free(rs_parts* parts);                    // (null: nothing to do) rs_scene_destroy, rs_scene_define_parts
 // first edit: builds and uploads the tables, allocates the scratch (waits for the device once: it reads the grid-box trees back)
 int rs_refit_prepare(rs_scene* s);
+// the first edit made with the switch of rs_scene_set_partial_refit on: builds and uploads the tables of the partial path and allocates
+// its counters (waits for the device once, as rs_refit_prepare does: it reads the grid-box trees back again)
+int rs_refit_prepare_partial(rs_scene* s);
 // one edit, on stream st: scatters the m staged triangles (ids, 9 floats of vertices each, 9 of normals or null: all device pointers) and refits.
 // emiTris: the edit names emitters, whose records in emiTris are written too; emiNodes: the emissive tree's boxes are refitted as well, on
-// the grid dev.emiBase / emiScale / emiMargin hold at the call
-int rs_refit_enqueue(rs_scene* s, int m, const int* dIds, const float* dVertices, const float* dNormals, bool emiTris, bool emiNodes, hipStream_t st);
+// the grid dev.emiBase / emiScale / emiMargin hold at the call.  partial (rs_plan_refit said so; rs_refit_prepare_partial has run): only the
+// boxes on the paths from the m triangles' leaves to the roots are recomputed; the emissive range, when asked for, as a whole either way
+int rs_refit_enqueue(rs_scene* s, int m, const int* dIds, const float* dVertices, const float* dNormals, bool emiTris, bool emiNodes, bool partial, hipStream_t st);
 // rs_scene_set_motion_tracking / rs_scene_advance_motion: prevVertices = vertices (9 floats per triangle, both device arrays), on stream st
 int rs_motion_copy_enqueue(const float* vertices, float* prevVertices, size_t numPrims, hipStream_t st);
 // the host's side of rs_refit_boxes once the arguments have been checked: `parent` from rs_reference_chain_tables

@@ -479,6 +479,7 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
     RS_TRY(refuse_while_capturing(name));
     if (count == 0) return 0;
     RS_TRY(rs_refit_prepare(s));
+    if (s->partialRefit) RS_TRY(rs_refit_prepare_partial(s));       // (the first edit with the switch on: the path's tables)
     const bool lamps = plan.lamps != 0;
     if (lamps) RS_TRY(versions_prepare(s));             // (the ring's slots, hLightArea, the environment entry's power)
     rs_refit* r = s->refit;
@@ -518,8 +519,12 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
     r->stagedBytes = staged;
     if (parts) RS_TRY(rs_bake_parts_enqueue(s->parts, parts->numRecs, reinterpret_cast<const PartRec*>(d + stagedAt), (size_t)plan.m, reinterpret_cast<int*>(d),
                                             reinterpret_cast<float*>(d + plan.offV), reinterpret_cast<float*>(d + plan.offN), st));
+    // whole or partial (rs_geometry_plan.h): the first edit of a scene is whole, since no whole refit has left its key boxes yet
+    bool partial = false;
+    unsigned long long bound = 0;
+    rs_plan_refit(s->partialRefit, s->partialMaxTriangles, r->keysValid, plan.m, r->numTrees, r->treeDepth, r->numNodes, kRefitPartialCapacity, &partial, &bound);
     RS_TRY(rs_refit_enqueue(s, plan.m, reinterpret_cast<const int*>(d), reinterpret_cast<const float*>(d + plan.offV),
-                            normals ? reinterpret_cast<const float*>(d + plan.offN) : nullptr, lamps, emiNodes, st));
+                            normals ? reinterpret_cast<const float*>(d + plan.offN) : nullptr, lamps, emiNodes, partial, st));
     RS_TRY(fence_after(r->after));
 
     update_host_tables(s, plan.m, rec, normals != nullptr);
@@ -690,6 +695,51 @@ extern "C" int rs_scene_download_part_rest(const rs_scene* s, int* primIds, floa
 extern "C" int rs_debug_scene_staged_bytes(const rs_scene* s, size_t* bytes) {
     if (!s || !bytes) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_scene_staged_bytes: null argument");
     *bytes = s->refit ? s->refit->stagedBytes : 0;
+    return 0;
+}
+
+// ---- the partial refit's switch (include/restir_hip.h; rs_geometry_plan.h rs_plan_refit decides per edit) ----
+extern "C" int rs_scene_set_partial_refit(rs_scene* s, int on, int maxTriangles) {
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_partial_refit: null scene");
+    if ((on != 0 && on != 1) || maxTriangles == 0) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_set_partial_refit: on is neither 0 nor 1, or maxTriangles is 0");
+    s->partialRefit = on != 0;
+    s->partialMaxTriangles = maxTriangles < 0 ? -1 : maxTriangles;
+    return 0;
+}
+
+extern "C" int rs_scene_get_partial_refit(const rs_scene* s, int* on, int* maxTriangles) {
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_get_partial_refit: null scene");
+    if (on) *on = s->partialRefit ? 1 : 0;
+    if (maxTriangles) *maxTriangles = s->partialMaxTriangles < 0 ? kRefitPartialDefaultMaxTriangles : s->partialMaxTriangles;
+    return 0;
+}
+
+extern "C" int rs_scene_refit_counts(const rs_scene* s, unsigned long long* whole, unsigned long long* partial) {
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_refit_counts: null scene");
+    if (whole) *whole = s->refit ? s->refit->wholeRefits : 0;
+    if (partial) *partial = s->refit ? s->refit->partialRefits : 0;
+    return 0;
+}
+
+extern "C" int rs_debug_scene_refit_dirty(const rs_scene* s, unsigned long long* nodes) {
+    RS_SCOPE(s);
+    if (!s || !nodes) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_scene_refit_dirty: null argument");
+    RS_TRY(refuse_while_capturing("rs_debug_scene_refit_dirty"));
+    RS_TRY(rs_synchronize());
+    *nodes = 0;
+    if (!s->refit || !s->refit->lastPartial) return 0;
+    unsigned dirty = 0;
+    RS_HIP(hipMemcpy(&dirty, s->refit->dDirty, sizeof(unsigned), hipMemcpyDeviceToHost));
+    *nodes = dirty;
+    return 0;
+}
+
+extern "C" int rs_debug_plan_refit(int on, int maxTriangles, int keysValid, int m, int numTrees, const int* treeDepth, unsigned long long numNodes,
+                                   unsigned long long capacity, int* partial, unsigned long long* bound) {
+    if (m < 0 || numTrees < 0 || (numTrees > 0 && !treeDepth) || !partial || !bound) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_debug_plan_refit: null or negative argument");
+    bool p = false;
+    rs_plan_refit(on != 0, maxTriangles, keysValid != 0, m, numTrees, treeDepth, numNodes, capacity, &p, bound);
+    *partial = p ? 1 : 0;
     return 0;
 }
 
