@@ -36,8 +36,11 @@
 //     roundings of terms below |D|), and normalisation and the reciprocal scale all three components alike up to 2^-22: the lane's
 //     direction is a positive multiple of some D + e, |e.c| < 2^-20 |D|.  The intervals are widened by 2^-16 M, M = the largest
 //     |component| of the corner directions (>= |D| / sqrt 3).  (The rounding of the screen coordinate, 2^-23, enters X scaled by aspect *
-//     tanFovY * focalDist while |D| >= focalDist: the bound holds while aspect * tanFovY and tanFovY stay below 16, and a camera beyond
-//     that -- a half angle above 86 degrees -- takes no cut at all.)  A cell whose widened interval reaches within 2^-10 M of zero takes no
+//     tanFovY * focalDist while |D| >= |focalDist|: the bound holds while |aspect * tanFovY| and |tanFovY| stay below 16, and a camera
+//     beyond that takes no cut at all.  The MAGNITUDES: rs_make_cam_params takes the tangent of the whole angle fov.y, which is
+//     negative past 90 degrees -- -2.29e7 at the float right angle, -57.3 at 91 -- and the argument is about the size of X, not its
+//     sign.  An angle whose tangent is negative and small, such as 120 or -60 degrees, mirrors the image and keeps its cuts; so does a
+//     negative focalDist, which scales all of D.)  A cell whose widened interval reaches within 2^-10 M of zero takes no
 //     cut: that covers the sign change, AABB::intersect's near-zero and axis-aligned cases (the wave checks ray_is_special itself
 //     and ignores the cut), and keeps the widening below 2^-6 of the interval's ends.
 //   * its slab distances.  (p - o) * dinv is a rounded difference times a rounded reciprocal, rounded: relative error below 2^-22.  A
@@ -96,7 +99,7 @@ RS_HD CutCell cut_cell(const CamParams& c, int x0, int y0, int w, int h) {
     cell.order = -1; cell.margin = 0.0;
     double lo[3], hi[3], M = 0.0;
     int order = -1;
-    bool ok = c.aspect * c.tanFovY <= 16.f && c.tanFovY <= 16.f;       // (the widening's bound, above; false for NaN)
+    bool ok = gabs(c.aspect * c.tanFovY) <= 16.f && gabs(c.tanFovY) <= 16.f;       // (the widening's bound, above, on the magnitudes; false for NaN)
     for (int k = 0; k < 4; k++) {
         double D[3];
         cut_corner_dir(c, (double)(x0 + ((k & 1) ? w : 0)), (double)(y0 + ((k & 2) ? h : 0)), D);

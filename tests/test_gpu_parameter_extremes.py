@@ -56,10 +56,11 @@ def scenes():
 
 
 class HipBackend:
-    """The library behind the interface extreme_cases.run drives (its OracleBackend is the other one)."""
+    """The library behind the interface extreme_cases.run drives (its OracleBackend is the other one).  sd: the SceneData to render instead
+    of the table's scene of that name (tests/test_gpu_camera_extremes.py: one rs_scene under `name`, a camera per row)."""
 
-    def __init__(self, hip, scenes, name, size):
-        self.hip, self.sd, self.size, self.n = hip, xc.scene(name), size, size[0] * size[1]
+    def __init__(self, hip, scenes, name, size, sd=None):
+        self.hip, self.sd, self.size, self.n = hip, sd or xc.scene(name), size, size[0] * size[1]
         if name not in scenes:
             scenes[name] = hip_scene(hip, self.sd)
             scenes[name].set_sample_sequence(None)
