@@ -380,6 +380,57 @@ int  rs_scene_parts_info(const rs_scene* scene, int* numParts, int* numListedPri
  * geometry edit of either kind copied from the host to the device (0 before the first); host only. */
 int  rs_scene_download_part_rest(const rs_scene* scene, int* primIds, float* restVertices, float* restNormals);
 int  rs_debug_scene_staged_bytes(const rs_scene* scene, size_t* bytes);
+/* Skinned meshes: triangles whose corners follow a blend of bone matrices (a character, a flag, a cable), with a rest pose, four bone ids
+ * and four weights per corner that the scene keeps on the host and on the device, and a palette of bone matrices the caller poses.  (The
+ * reference has no moving geometry: there is no reference line to cite.)
+ * rs_skin_corners is the skinning counterpart of rs_bake_matrix, host only, no GPU call: n corners (3 floats each in and out), 4 bone ids
+ * and 4 weights per corner, numBones column-major 4x4 matrices.  With p_k and q_k the position and the not yet normalised normal that
+ * rs_bake_matrix computes for the matrix of the corner's k-th bone,
+ *     position = (w0 * p0 + w1 * p1) + (w2 * p2 + w3 * p3)  per component,  normal = normalize((w0 * q0 + w1 * q1) + (w2 * q2 + w3 * q3)),
+ * one rounding per operation; the normal matrix is computed once per matrix with GLM's inverse.  All four influences are always evaluated
+ * (a slot of weight 0 still names a valid bone) and the weights are used as given, not renormalised.  Non-finite results are returned, not
+ * refused.  RS_ERR_INVALID_ARGUMENT: numBones < 1, null matrices, a null array with n > 0, a bone id outside [0, numBones). */
+#define RS_SKIN_MAX_BONES 256   /* 28 KB of palette */
+int  rs_skin_corners(int numBones, const float* matrices16, size_t n, const float* vertsIn, const float* normalsIn,
+                     const int* boneIds4, const float* weights4, float* vertsOut, float* normalsOut);
+/* rs_scene_define_skin: primIds[numListed] are the skinned primitives, emitters among them if wanted, no primitive twice; restVertices /
+ * restNormals hold 9 floats per listed primitive in the order of primIds, or are both NULL: the rest pose is then the scene's pose as
+ * rs_scene_host_desc returns it at the call; boneIds / weights hold 12 values per listed primitive, corner-major, 4 per corner.  (The
+ * reference has no moving geometry: there is no reference line to cite.)  Everything is copied, to the host and to the device (4 + 72 + 96
+ * bytes per listed triangle); the device copy is read by the skinning kernel alone and never written afterwards.  The call renders
+ * nothing and changes no geometry.  The host palette starts as numBones identities.  Calling it again replaces the definition and the
+ * palette; numBones == 0 with numListed == 0 drops it and frees the arrays.  Ordering is rs_scene_define_parts': a definition that
+ * replaces or drops an earlier one waits for the device.  A skin and parts may coexist and may name the same primitive: as with
+ * rs_scene_set_geometry on a part's triangle, the last edit wins.
+ * Refused with RS_ERR_INVALID_ARGUMENT, the definition unchanged: a null scene, numBones < 0 or above RS_SKIN_MAX_BONES, numListed < 0 or
+ * triangles without a bone, null ids, bone ids or weights with numListed > 0, a primitive id out of range or listed twice, exactly one of
+ * the two rest arrays NULL, a rest value or a weight that is not finite, a negative weight, a corner whose four weights are all 0, a bone
+ * id outside [0, numBones); with RS_ERR_UNSUPPORTED while the library stream is being captured into a graph. */
+int  rs_scene_define_skin(rs_scene* scene, int numBones, int numListed, const int* primIds,
+                          const float* restVertices, const float* restNormals, const int* boneIds, const float* weights);
+/* rs_scene_set_bone_transforms: matrices16 holds one column-major 4x4 per entry of boneIds.  The named bones take their new matrix (a bone
+ * named twice takes its last, bones not named keep the matrix they had), and the call then does exactly what
+ * rs_scene_set_geometry(scene, numListed, primIds, v, n) does with v, n = rs_skin_corners of the whole palette over the rest arrays: the
+ * same refusals with the scene AND THE PALETTE unchanged (a skinned vertex or normal that is not finite, a vertex outside the
+ * creation-time root box, a light sampler left without finite positive power, RS_ERR_UNSUPPORTED while captured), the same
+ * rs_scene_host_desc and device tables afterwards, lights moved and rs_scene_light_moves counted the same way, the same dirty box, the
+ * partial or whole refit rs_scene_set_partial_refit decides, retained G-buffer planes invalidated, the previous pose of a tracked scene
+ * left alone, the same fences at the same point of the library stream.  (The reference has no moving geometry: there is no reference line
+ * to cite.)  Only the source of the records differs: the host stages the palette, numBones 112-byte records (the matrix and its normal
+ * matrix), through the ring of pinned buffers, and a kernel writes the ids | vertices | normals the refit reads from the device's rest
+ * arrays, with the arithmetic of rs_skin_corners, bit for bit.  As for parts, the host still skins the listed triangles once itself: for
+ * the checks above, the light areas, and the tables rs_scene_host_desc returns.  The rest arrays are never written and poses do not
+ * accumulate.  count == 0 succeeds and changes nothing.  Additionally refused with RS_ERR_INVALID_ARGUMENT: no skin defined, a bone id
+ * out of range, null arrays with count > 0.  INTEGRATION.md section 3i has the frame loop; DESIGN.md section 3 the cost. */
+int  rs_scene_set_bone_transforms(rs_scene* scene, int count, const int* boneIds, const float* matrices16);
+/* Host only: the number of bones and of primitives the skin lists (0, 0: none defined).  Either pointer may be NULL.  (The reference has
+ * no moving geometry: there is no reference line to cite.) */
+int  rs_scene_skin_info(const rs_scene* scene, int* numBones, int* numListedPrims);
+/* Test hook.  Waits as rs_synchronize does, then copies the DEVICE copies of the skin's primitive ids, rest pose, bone ids and weights
+ * out (sizes: rs_scene_skin_info; any array may be NULL).  RS_ERR_INVALID_ARGUMENT: a null scene, or no skin defined;
+ * RS_ERR_UNSUPPORTED while the library stream is being captured.  (The reference has no moving geometry: there is no reference line to
+ * cite.) */
+int  rs_scene_download_skin(const rs_scene* scene, int* primIds, float* restVertices, float* restNormals, int* boneIds, float* weights);
 /* What a geometry edit of any of the three kinds decides on the host before it touches the device, as functions of plain arrays and
  * integers (restir_amd/csrc/rs_geometry_plan.h).  The view is what they read of a scene; flags are 0 / 1. */
 typedef struct rs_geometry_edit_view {

@@ -165,6 +165,7 @@ EXPORTS = [
     "rs_scene_file_load", "rs_scene_file_get", "rs_scene_file_free", "rs_build_transformation_matrix", "rs_bake_instance",
     "rs_bake_matrix", "rs_scene_file_objects", "rs_scene_define_parts", "rs_scene_set_part_transforms", "rs_scene_parts_info", "rs_scene_download_part_rest", "rs_debug_scene_staged_bytes", "rs_debug_plan_geometry_edit",
     "rs_scene_set_partial_refit", "rs_scene_get_partial_refit", "rs_scene_refit_counts", "rs_debug_scene_refit_dirty", "rs_debug_plan_refit",
+    "rs_skin_corners", "rs_scene_define_skin", "rs_scene_set_bone_transforms", "rs_scene_skin_info", "rs_scene_download_skin",
 ]
 
 _lib = None
@@ -216,6 +217,12 @@ def lib():
     L.rs_scene_parts_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
     L.rs_scene_download_part_rest.argtypes = [vp, vp, vp, vp]
     L.rs_debug_scene_staged_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
+    if hasattr(L, "rs_skin_corners"):                     # (an A/B build from before skinned meshes, RESTIR_HIP_LIB)
+        L.rs_skin_corners.argtypes = [ci, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+        L.rs_scene_define_skin.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp]
+        L.rs_scene_set_bone_transforms.argtypes = [vp, ci, vp, vp]
+        L.rs_scene_skin_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+        L.rs_scene_download_skin.argtypes = [vp, vp, vp, vp, vp, vp]
     L.rs_scene_host_desc.argtypes = [vp, C.POINTER(SceneDesc)]
     L.rs_scene_destroy.argtypes = [vp]
     L.rs_scene_set_emission.argtypes = [vp, ci, vp, vp]
@@ -808,6 +815,21 @@ def bake_matrix(matrix, vertices, normals):
     return vo, no
 
 
+def skin_corners(matrices, vertices, normals, bone_ids, weights):
+    """rs_skin_corners (host only): (k, 3) corners blended by 4 bone ids and 4 weights each over a palette of (4, 4) float32 matrices,
+    [column][row]; the weights are used as given."""
+    m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 16)
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    b = np.ascontiguousarray(bone_ids, np.int32).reshape(-1, 4)
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1, 4)
+    if not (len(v) == len(n) == len(b) == len(w)):
+        raise ValueError("skin_corners: one normal, four bone ids and four weights per corner")
+    vo, no = np.zeros_like(v), np.zeros_like(n)
+    check(lib().rs_skin_corners(len(m), _p(m), len(v), _p(v), _p(n), _p(b), _p(w), _p(vo), _p(no)))
+    return vo, no
+
+
 class SceneFile:
     """Scene::Scene(filename) (src/scene.cpp:96-131): the parsed scene as flat host arrays (copies)."""
 
@@ -1022,6 +1044,44 @@ class Scene:
         ids, v, nn = np.zeros(n, np.int32), np.zeros((n, 3, 3), np.float32), np.zeros((n, 3, 3), np.float32)
         check(lib().rs_scene_download_part_rest(self.handle, _p(ids), _p(v), _p(nn)))
         return ids, v, nn
+
+    def define_skin(self, num_bones, prim_ids, bone_ids, weights, rest_vertices=None, rest_normals=None):
+        """rs_scene_define_skin: the listed primitives follow a blend of `num_bones` bone matrices; bone_ids / weights are (listed, 3, 4),
+        4 per corner; the rest pose is (listed, 3, 3) float32 vertices and normals, or None: the scene's current pose.  num_bones == 0 with
+        no primitive drops the definition."""
+        ids = np.ascontiguousarray(prim_ids, np.int32).reshape(-1)
+        b = np.ascontiguousarray(bone_ids, np.int32).reshape(-1, 12)
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1, 12)
+        v = None if rest_vertices is None else np.ascontiguousarray(rest_vertices, np.float32).reshape(-1, 9)
+        n = None if rest_normals is None else np.ascontiguousarray(rest_normals, np.float32).reshape(-1, 9)
+        for a in (b, w, v, n):
+            if a is not None and a.shape[0] != ids.size:
+                raise ValueError("define_skin: per listed primitive three rest vertices and normals, and four bone ids and weights per corner")
+        check(lib().rs_scene_define_skin(self.handle, int(num_bones), int(ids.size), _p(ids), None if v is None else _p(v), None if n is None else _p(n),
+                                         _p(b), _p(w)))
+
+    def set_bone_transforms(self, bone_ids, matrices):
+        """rs_scene_set_bone_transforms: one (4, 4) float32 matrix, [column][row], per entry of `bone_ids`; does what set_geometry does with
+        the skin's rest pose blended by the whole palette, the skinning done on the device (one small record per bone crosses the bus)."""
+        ids = np.ascontiguousarray(bone_ids, np.int32).reshape(-1)
+        m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 16)
+        if m.shape[0] != ids.size:
+            raise ValueError("set_bone_transforms: one matrix per bone id")
+        check(lib().rs_scene_set_bone_transforms(self.handle, int(ids.size), _p(ids), _p(m)))
+
+    def skin_info(self):
+        """rs_scene_skin_info: (number of bones, number of primitives the skin lists); (0, 0) when none is defined."""
+        a, b = C.c_int(0), C.c_int(0)
+        check(lib().rs_scene_skin_info(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def download_skin(self):
+        """rs_scene_download_skin (test hook): the device copies of (primitive ids, rest vertices, rest normals, bone ids, weights)."""
+        n = self.skin_info()[1]
+        ids, v, nn = np.zeros(n, np.int32), np.zeros((n, 3, 3), np.float32), np.zeros((n, 3, 3), np.float32)
+        b, w = np.zeros((n, 3, 4), np.int32), np.zeros((n, 3, 4), np.float32)
+        check(lib().rs_scene_download_skin(self.handle, _p(ids), _p(v), _p(nn), _p(b), _p(w)))
+        return ids, v, nn, b, w
 
     def set_partial_refit(self, on=True, max_triangles=-1):
         """rs_scene_set_partial_refit: an edit of at most max_triangles triangles (< 0: the library's default) recomputes only the boxes

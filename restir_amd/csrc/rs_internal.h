@@ -294,6 +294,9 @@ struct rs_scene {
     // Dirty boxes (rs_restir_set_shadow_revalidation; rs_revalidate_plan.h): the box of each of the last RS_DIRTY_BOXES_KEPT accepted
     // geometry edits with its number, geomEdits once the edit was counted.  Host only, written where the edit is enqueued.
     rs_dirty_ring dirty;
+    // Skinned triangles, their rest pose and the bone palette (rs_scene_define_skin; rs_refit.h); null: none defined.  Last, so that every
+    // field a frame reads lies where it lay before there were skins.
+    struct rs_skin* skin = nullptr;
 };
 
 // ---- G-buffer (src/gbuffer.h:41-58) ------------------------------------------------------------

@@ -65,7 +65,7 @@ struct rs_refit {
     struct Stage { char* host = nullptr; size_t capacity = 0; hipEvent_t copied = nullptr; bool pending = false; } stage[kStaging];
     int stageNext = 0;
     char* dStage = nullptr;          // read by the scatter kernel, in the order of the library stream: ids | vertices | normals, copied from a
-    size_t dStageCapacity = 0;       // staging buffer or written by k_bake_parts from the part records, which then follow them in this buffer
+    size_t dStageCapacity = 0;       // staging buffer or written by k_bake_parts / k_skin from the part / bone records, which then follow them in this buffer
     size_t stagedBytes = 0;          // what the last accepted edit copied from the host (rs_debug_scene_staged_bytes)
     // ---- fences ----
     hipEvent_t before[rs_context::kAux] = {};      // what an internal stream has been handed so far
@@ -94,11 +94,35 @@ struct rs_parts {
     std::vector<float> vertices, normals;
 };
 
+// The skin of a scene (rs_scene_define_skin): which primitives deform by a blend of bone matrices, their rest pose and, per corner, four
+// bone ids and four weights.  The device copies are read by k_skin alone and never written after the definition (72 + 96 bytes per listed
+// triangle, and its id).  The palette stays on the host; a pose stages all of it (rs::BoneRec, 112 bytes a bone).
+struct rs_skin {
+    int numBones = 0;
+    std::vector<int> primIds;        // [numListed] no primitive twice
+    std::vector<float> restVertices, restNormals;       // 9 floats per listed primitive
+    std::vector<int> boneIds;        // 12 per listed primitive: corner-major, 4 per corner
+    std::vector<float> weights;      // the same shape
+    int* dPrimIds = nullptr;
+    float* dRestVertices = nullptr;
+    float* dRestNormals = nullptr;
+    int* dBoneIds = nullptr;         // (16 bytes per corner at a 16-byte aligned base: k_skin reads an int4 and a float4)
+    float* dWeights = nullptr;
+    std::vector<rs::BoneRec> palette;                   // [numBones] as the last accepted pose left it; identities after the definition
+    // scratch of one rs_scene_set_bone_transforms: the palette it asks for, and the host's own skinning (checks, light areas, mirror)
+    std::vector<rs::BoneRec> recs;
+    std::vector<float> vertices, normals;
+};
+
 // scene_refit.hip
 // one rs_scene_set_part_transforms, on stream st, before rs_refit_enqueue: the triangles of the numRecs parts dRecs baked from the rest
 // arrays into dIds | dVertices | dNormals, m triangles in all, in the layout a staged edit has
 int rs_bake_parts_enqueue(const rs_parts* parts, int numRecs, const rs::PartRec* dRecs, size_t m, int* dIds, float* dVertices, float* dNormals, hipStream_t st);
 void rs_parts_free(rs_parts* parts);                    // (null: nothing to do) rs_scene_destroy, rs_scene_define_parts
+// one rs_scene_set_bone_transforms, on stream st, before rs_refit_enqueue: the skin's listed triangles skinned by the palette dBones (all
+// skin->numBones records) from the rest arrays into dIds | dVertices | dNormals, in the layout a staged edit has
+int rs_skin_enqueue(const rs_skin* skin, const rs::BoneRec* dBones, int* dIds, float* dVertices, float* dNormals, hipStream_t st);
+void rs_skin_free(rs_skin* skin);                       // (null: nothing to do) rs_scene_destroy, rs_scene_define_skin
 // first edit: builds and uploads the tables, allocates the scratch (waits for the device once: it reads the grid-box trees back)
 int rs_refit_prepare(rs_scene* s);
 // the first edit made with the switch of rs_scene_set_partial_refit on: builds and uploads the tables of the partial path and allocates

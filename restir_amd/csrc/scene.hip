@@ -310,6 +310,7 @@ extern "C" int rs_scene_destroy(rs_scene* s) {
     versions_free(s);
     rs_refit_free(s);
     rs_parts_free(s->parts);
+    rs_skin_free(s->skin);
     motion_free(s);
     delete s;
     return 0;

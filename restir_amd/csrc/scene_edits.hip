@@ -1,7 +1,8 @@
 // scene_edits.hip -- edits of a live scene (include/restir_hip.h), all stream-ordered: the ring of versions behind rs_scene_set_emission /
 // rs_scene_set_materials / rs_scene_set_texture; geometry edits in place behind fences (set_geometry, the one implementation of
-// rs_scene_set_triangles, rs_scene_set_geometry and rs_scene_set_part_transforms: its host decisions are rs_geometry_plan.h's, its
-// kernels scene_refit.hip's); rigid parts; motion tracking.  The scene itself, its trees and its debug tables: scene.hip.
+// rs_scene_set_triangles, rs_scene_set_geometry, rs_scene_set_part_transforms and rs_scene_set_bone_transforms: its host decisions are
+// rs_geometry_plan.h's, its kernels scene_refit.hip's); rigid parts; skinned meshes; motion tracking.  The scene itself, its trees and
+// its debug tables: scene.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -380,7 +381,16 @@ int fence_after(hipEvent_t after) {
 // parts (rs_scene_set_part_transforms): the edit's records are not copied from the host but written on the device, by k_bake_parts from the
 // numRecs part records `recs` (which alone are staged) and the scene's rest pose; primIds / vertices / normals are then the host's own baking
 // of the same triangles, every id once, in the order the kernel writes them -- for the checks, the light areas and the host's tables.
-struct PartSource { int numRecs; const PartRec* recs; };
+// A skin (rs_scene_set_bone_transforms) is the same kind of source, and `skin` says so: the staged records are then skin->recs, the whole
+// palette the pose asks for (numRecs = skin->numBones records of rs::BoneRec, a part record's size), k_skin writes the edit's records from
+// them and the skin's rest arrays, and the palette becomes the scene's where the host's tables take the pose.  Exactly one of `recs` and
+// `skin` is set.
+struct PartSource {
+    int numRecs;
+    const PartRec* recs;
+    rs_skin* skin;
+    const void* staged() const { return skin ? static_cast<const void*>(skin->recs.data()) : static_cast<const void*>(recs); }
+};
 
 // What rs_geometry_plan.h reads of the scene.  (hLightArea and envPower are versions_prepare's, emiRecords rs_refit_prepare's: the plan
 // of the lights asks for the view again after them.)
@@ -425,7 +435,7 @@ int stage_reserve(rs_refit* r, size_t staged, size_t onDevice, rs_refit::Stage**
 struct Records { const int* ids; const float* vertices; const float* normals; };
 Records fill_stage(char* host, const rs_geometry_edit_plan& plan, const rs_edit_stamps& stamps, int count, const int* primIds, const float* vertices,
                    const float* normals, const PartSource* parts) {
-    if (parts) { std::memcpy(host, parts->recs, plan.partStaged); return Records{ primIds, vertices, normals }; }
+    if (parts) { std::memcpy(host, parts->staged(), plan.partStaged); return Records{ primIds, vertices, normals }; }
     rs_fill_edit_records(plan, stamps, count, primIds, vertices, normals, host);
     return Records{ reinterpret_cast<const int*>(host), reinterpret_cast<const float*>(host + plan.offV), reinterpret_cast<const float*>(host + plan.offN) };
 }
@@ -517,8 +527,10 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
     g->pending = true;
     r->stageNext = (r->stageNext + 1) % rs_refit::kStaging;
     r->stagedBytes = staged;
-    if (parts) RS_TRY(rs_bake_parts_enqueue(s->parts, parts->numRecs, reinterpret_cast<const PartRec*>(d + stagedAt), (size_t)plan.m, reinterpret_cast<int*>(d),
-                                            reinterpret_cast<float*>(d + plan.offV), reinterpret_cast<float*>(d + plan.offN), st));
+    if (parts && parts->skin) RS_TRY(rs_skin_enqueue(parts->skin, reinterpret_cast<const BoneRec*>(d + stagedAt), reinterpret_cast<int*>(d),
+                                                     reinterpret_cast<float*>(d + plan.offV), reinterpret_cast<float*>(d + plan.offN), st));
+    else if (parts) RS_TRY(rs_bake_parts_enqueue(s->parts, parts->numRecs, reinterpret_cast<const PartRec*>(d + stagedAt), (size_t)plan.m, reinterpret_cast<int*>(d),
+                                                 reinterpret_cast<float*>(d + plan.offV), reinterpret_cast<float*>(d + plan.offN), st));
     // whole or partial (rs_geometry_plan.h): the first edit of a scene is whole, since no whole refit has left its key boxes yet
     bool partial = false;
     unsigned long long bound = 0;
@@ -528,6 +540,8 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
     RS_TRY(fence_after(r->after));
 
     update_host_tables(s, plan.m, rec, normals != nullptr);
+    // ... and the palette with them: geometry and palette stay one pose whatever the calls below return
+    if (parts && parts->skin) parts->skin->palette.swap(parts->skin->recs);
     if (!lamps) return rs_after_launch(name);
     // the lights' version: light_records reads the vertices just written; launches from here on see new geometry and new lights alike
     s->hLightArea.swap(lights.area);
@@ -644,8 +658,143 @@ extern "C" int rs_scene_set_part_transforms(rs_scene* s, int count, const int* p
         std::memcpy(&p->ids[out], &p->primIds[in], (size_t)rec.count * sizeof(int));
         rs_bake_corners(rec.m, rec.nm, (size_t)rec.count * 3, &p->restVertices[in * 9], &p->restNormals[in * 9], &p->vertices[out * 9], &p->normals[out * 9]);
     }
-    const PartSource src{ (int)p->recs.size(), p->recs.data() };
+    const PartSource src{ (int)p->recs.size(), p->recs.data(), nullptr };
     return set_geometry(s, (int)m, p->ids.data(), p->vertices.data(), p->normals.data(), true, name, &src);
+}
+
+// ---- skinned meshes (include/restir_hip.h) ----
+// rs_skin_corners' and rs_scene_set_bone_transforms' palette: one record per matrix, the normal matrix computed once per matrix
+static void bone_record(const float* matrix16, BoneRec& rec) {
+    std::memcpy(rec.m, matrix16, 16 * sizeof(float));
+    rs_bake_normal_matrix(rec.m, rec.nm);
+    rec.pad[0] = rec.pad[1] = rec.pad[2] = 0;
+}
+
+extern "C" int rs_skin_corners(int numBones, const float* matrices16, size_t n, const float* vertsIn, const float* normalsIn, const int* boneIds4,
+                               const float* weights4, float* vertsOut, float* normalsOut) {
+    if (numBones < 1 || !matrices16) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_skin_corners: numBones < 1 or null matrices");
+    if (n > 0 && (!vertsIn || !normalsIn || !boneIds4 || !weights4 || !vertsOut || !normalsOut)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_skin_corners: a null array with n > 0");
+    for (size_t i = 0; i < n * 4; i++)
+        if (boneIds4[i] < 0 || boneIds4[i] >= numBones) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_skin_corners: a bone id out of range");
+    std::vector<BoneRec> palette((size_t)numBones);
+    for (int b = 0; b < numBones; b++) bone_record(matrices16 + (size_t)b * 16, palette[(size_t)b]);
+    rs_skin_corners_host(palette.data(), n, vertsIn, normalsIn, boneIds4, weights4, vertsOut, normalsOut);
+    return 0;
+}
+
+// The definition is replaced behind a wait for the device, as rs_scene_define_parts replaces its own.  Nothing of the scene's geometry changes.
+extern "C" int rs_scene_define_skin(rs_scene* s, int numBones, int numListed, const int* primIds, const float* restVertices, const float* restNormals,
+                                    const int* boneIds, const float* weights) {
+    RS_SCOPE(s);
+    const char* name = "rs_scene_define_skin";
+    if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
+    if (numBones < 0 || numBones > RS_SKIN_MAX_BONES) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "numBones < 0 or above RS_SKIN_MAX_BONES");
+    if (numListed < 0 || (numBones == 0 && numListed > 0)) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "numListed < 0, or triangles without a bone");
+    if ((restVertices == nullptr) != (restNormals == nullptr)) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "rest vertices without rest normals, or the reverse");
+    if (numListed > 0 && (!primIds || !boneIds || !weights)) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null primitive ids, bone ids or weights");
+    const size_t listed = (size_t)numListed;
+    {
+        std::vector<char> seen((size_t)s->numPrims, 0);
+        for (size_t i = 0; i < listed; i++) {
+            const int p = primIds[i];
+            if (p < 0 || p >= s->numPrims) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a primitive id out of range");
+            if (seen[(size_t)p]) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a primitive listed twice");
+            seen[(size_t)p] = 1;
+        }
+    }
+    if (restVertices)
+        for (size_t i = 0; i < listed * 9; i++)
+            if (!std::isfinite(restVertices[i]) || !std::isfinite(restNormals[i])) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a rest value that is not finite");
+    for (size_t c = 0; c < listed * 3; c++) {
+        bool any = false;
+        for (size_t k = c * 4; k < c * 4 + 4; k++) {
+            if (boneIds[k] < 0 || boneIds[k] >= numBones) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a bone id out of range");
+            if (!std::isfinite(weights[k])) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a weight that is not finite");
+            if (weights[k] < 0.f) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a negative weight");
+            any = any || weights[k] != 0.f;
+        }
+        if (!any) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a corner whose four weights are all 0");
+    }
+    RS_TRY(refuse_while_capturing(name));
+    if (numBones == 0) {
+        if (s->skin) { RS_TRY(rs_synchronize()); rs_skin_free(s->skin); s->skin = nullptr; }
+        return 0;
+    }
+
+    rs_skin* k = new rs_skin();
+    k->numBones = numBones;
+    k->primIds.assign(primIds, primIds + listed);
+    k->restVertices.resize(listed * 9); k->restNormals.resize(listed * 9);
+    for (size_t i = 0; i < listed; i++) {
+        // the scene's own pose, or the caller's arrays
+        std::memcpy(&k->restVertices[i * 9], restVertices ? restVertices + i * 9 : &s->hVertices[(size_t)primIds[i] * 9], 9 * sizeof(float));
+        std::memcpy(&k->restNormals[i * 9], restNormals ? restNormals + i * 9 : &s->hNormals[(size_t)primIds[i] * 9], 9 * sizeof(float));
+    }
+    k->boneIds.assign(boneIds, boneIds + listed * 12);
+    k->weights.assign(weights, weights + listed * 12);
+    const float identity[16] = { 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f };
+    k->palette.resize((size_t)numBones);
+    for (BoneRec& rec : k->palette) bone_record(identity, rec);
+    int e = upload(&k->dPrimIds, k->primIds);
+    if (!e) e = upload(&k->dRestVertices, k->restVertices);
+    if (!e) e = upload(&k->dRestNormals, k->restNormals);
+    if (!e) e = upload(&k->dBoneIds, k->boneIds);
+    if (!e) e = upload(&k->dWeights, k->weights);
+    if (!e && s->skin) e = rs_synchronize();            // a pose in flight reads the tables that are about to be freed
+    if (e) { rs_skin_free(k); return e; }               // (the definition stays what it was)
+    rs_skin_free(s->skin);
+    s->skin = k;
+    return 0;
+}
+
+// The palette the call asks for (a bone named twice takes its last matrix, a bone not named keeps its own), the host's own skinning of every
+// listed triangle by it, and then rs_scene_set_geometry's implementation with the records written on the device.  The palette becomes
+// the scene's inside set_geometry, past its last refusal, where the host's tables take the pose; a skin that lists no triangle has no
+// edit to make and takes the palette here.
+extern "C" int rs_scene_set_bone_transforms(rs_scene* s, int count, const int* boneIds, const float* matrices16) {
+    RS_SCOPE(s);
+    const char* name = "rs_scene_set_bone_transforms";
+    if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
+    if (count < 0 || (count > 0 && (!boneIds || !matrices16))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "count < 0 or null arrays");
+    rs_skin* k = s->skin;
+    if (!k) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "the scene has no skin (rs_scene_define_skin)");
+    for (int i = 0; i < count; i++)
+        if (boneIds[i] < 0 || boneIds[i] >= k->numBones) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a bone id out of range");
+    if (count == 0) return 0;
+
+    k->recs = k->palette;
+    for (int i = 0; i < count; i++) bone_record(matrices16 + (size_t)i * 16, k->recs[(size_t)boneIds[i]]);
+    const size_t listed = k->primIds.size();
+    k->vertices.resize(listed * 9); k->normals.resize(listed * 9);
+    rs_skin_corners_host(k->recs.data(), listed * 3, k->restVertices.data(), k->restNormals.data(), k->boneIds.data(), k->weights.data(),
+                         k->vertices.data(), k->normals.data());
+    const PartSource src{ k->numBones, nullptr, k };
+    RS_TRY(set_geometry(s, (int)listed, k->primIds.data(), k->vertices.data(), k->normals.data(), true, name, &src));
+    if (listed == 0) k->palette.swap(k->recs);
+    return 0;
+}
+
+extern "C" int rs_scene_skin_info(const rs_scene* s, int* numBones, int* numListedPrims) {
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_skin_info: null scene");
+    if (numBones) *numBones = s->skin ? s->skin->numBones : 0;
+    if (numListedPrims) *numListedPrims = s->skin ? (int)s->skin->primIds.size() : 0;
+    return 0;
+}
+
+extern "C" int rs_scene_download_skin(const rs_scene* s, int* primIds, float* restVertices, float* restNormals, int* boneIds, float* weights) {
+    RS_SCOPE(s);
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_skin: null scene");
+    const rs_skin* k = s->skin;
+    if (!k) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_skin: the scene has no skin (rs_scene_define_skin)");
+    RS_TRY(refuse_while_capturing("rs_scene_download_skin"));
+    RS_TRY(rs_synchronize());
+    const size_t n = k->primIds.size();
+    if (n && primIds) RS_HIP(hipMemcpy(primIds, k->dPrimIds, n * sizeof(int), hipMemcpyDeviceToHost));
+    if (n && restVertices) RS_HIP(hipMemcpy(restVertices, k->dRestVertices, n * 9 * sizeof(float), hipMemcpyDeviceToHost));
+    if (n && restNormals) RS_HIP(hipMemcpy(restNormals, k->dRestNormals, n * 9 * sizeof(float), hipMemcpyDeviceToHost));
+    if (n && boneIds) RS_HIP(hipMemcpy(boneIds, k->dBoneIds, n * 12 * sizeof(int), hipMemcpyDeviceToHost));
+    if (n && weights) RS_HIP(hipMemcpy(weights, k->dWeights, n * 12 * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 extern "C" int rs_scene_light_moves(const rs_scene* s, unsigned long long* moves) {

@@ -21,7 +21,8 @@
 // lays it over the new emissive root box before the launches (scene_edits.hip), so base, scale and margin are per record range (GridArgs).
 //
 // In front of the refit, for rs_scene_set_part_transforms alone: k_bake_parts writes the records k_scatter reads -- the staged edit -- from the
-// scene's rest pose and one matrix per part, instead of a copy from the host bringing them.
+// scene's rest pose and one matrix per part, instead of a copy from the host bringing them.  For rs_scene_set_bone_transforms k_skin does the
+// same from the skin's rest pose and a palette of bone matrices blended per corner.
 //
 // Next to the refit: k_copy_pose, the copy rs_scene_advance_motion makes of the vertices into the scene's previous pose (scene_edits.hip).
 //
@@ -397,6 +398,39 @@ __global__ void __launch_bounds__(256) k_bake_parts(int numRecs, const PartRec* 
     if (corner == 0) ids[tri] = partPrimIds[slot];
 }
 
+// rs_scene_set_bone_transforms: the same staged edit, written from the skin's rest pose and a palette of bone matrices.  One lane per output
+// corner.  The block first copies the whole palette -- numBones records of 112 bytes = 7 x 16, staged 16-byte aligned behind the records
+// this kernel writes -- into LDS, 16 bytes a lane and step, and meets at one barrier: lanes past numCorners take part in both, nothing
+// returns before the barrier.  A lane then reads its four bone ids and four weights as one int4 and one float4 (16 bytes per corner at a
+// hipMalloc'ed base), its 12 + 12 bytes of rest corner, evaluates rs_bake.h's skin_corner against the LDS palette -- the bits are
+// rs_skin_corners' -- and writes 12 + 12 bytes; the lane of corner 0 also writes the primitive id.  Bone ids differ from lane to lane, so the
+// palette reads conflict on LDS banks: accepted.  The ids were checked against numBones by rs_scene_define_skin and
+// the device copy is never written again, so no read leaves the staged palette.  28 KB of LDS: five blocks a CU.
+__global__ void __launch_bounds__(256) k_skin(int numBones, const BoneRec* __restrict__ bones, const int* __restrict__ skinPrimIds,
+                                              const float* __restrict__ restVertices, const float* __restrict__ restNormals,
+                                              const int4* __restrict__ boneIds, const float4* __restrict__ weights,
+                                              size_t numCorners, int* __restrict__ ids, float* __restrict__ vertices, float* __restrict__ normals) {
+    __shared__ BoneRec palette[RS_SKIN_MAX_BONES];
+    {
+        const uint4* src = reinterpret_cast<const uint4*>(bones);
+        uint4* dst = reinterpret_cast<uint4*>(palette);
+        const int n16 = numBones * (int)(sizeof(BoneRec) / 16);
+        for (int i = (int)threadIdx.x; i < n16; i += 256) dst[i] = src[i];
+    }
+    __syncthreads();
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= numCorners) return;
+    const int4 b4 = boneIds[c];
+    const float4 w4 = weights[c];
+    const int b[4] = { b4.x, b4.y, b4.z, b4.w };
+    const float w[4] = { w4.x, w4.y, w4.z, w4.w };
+    const BakedCorner o = skin_corner(palette, b, w, ld3(restVertices + c * 3), ld3(restNormals + c * 3));
+    st3(vertices + c * 3, o.position);
+    st3(normals + c * 3, o.normal);
+    const size_t tri = c / 3;
+    if (c == tri * 3) ids[tri] = skinPrimIds[tri];
+}
+
 inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -493,6 +527,22 @@ void rs_parts_free(rs_parts* p) {
     if (!p) return;
     rs_dev_free(p->dPrimIds); rs_dev_free(p->dRestVertices); rs_dev_free(p->dRestNormals);
     delete p;
+}
+
+int rs_skin_enqueue(const rs_skin* skin, const BoneRec* dBones, int* dIds, float* dVertices, float* dNormals, hipStream_t st) {
+    const size_t corners = skin->primIds.size() * 3;
+    if (corners == 0) return 0;
+    if (skin->numBones < 1 || skin->numBones > RS_SKIN_MAX_BONES) return rs_fail(RS_ERR_INTERNAL, "rs_scene_set_bone_transforms: a palette the kernel has no room for");
+    hipLaunchKernelGGL(k_skin, dim3(blocks_for(corners)), dim3(256), 0, st, skin->numBones, dBones, (const int*)skin->dPrimIds,
+                       (const float*)skin->dRestVertices, (const float*)skin->dRestNormals, reinterpret_cast<const int4*>(skin->dBoneIds),
+                       reinterpret_cast<const float4*>(skin->dWeights), corners, dIds, dVertices, dNormals);
+    return rs_check_hip(hipGetLastError(), "rs_scene_set_bone_transforms: skin kernel");
+}
+
+void rs_skin_free(rs_skin* k) {
+    if (!k) return;
+    rs_dev_free(k->dPrimIds); rs_dev_free(k->dRestVertices); rs_dev_free(k->dRestNormals); rs_dev_free(k->dBoneIds); rs_dev_free(k->dWeights);
+    delete k;
 }
 
 void rs_refit_free(rs_scene* s) {
