@@ -2,9 +2,9 @@
 //     position = vec3(transform * vec4(v, 1))                       mat4 * vec4 (type_mat4x4.inl:612-628)
 //     normal   = normalize(normalMat * n)                           normalMat = transpose(mat3(inverse(transform))), mat3 * vec3
 // in GLM's grouping of every sum.  The scene-file loader, rs_bake_instance, rs_bake_matrix (scene_file.cpp) and the kernel behind
-// rs_scene_set_part_transforms (scene_refit.hip k_bake_parts) all evaluate this function and nothing else, so with -ffp-contract=off and
+// rs_scene_set_part_transforms (scene_deform.hip k_bake_parts) all evaluate this function and nothing else, so with -ffp-contract=off and
 // the correctly rounded divide and square root of rs_math.h they return the same bits.  skin_corner blends four such corners by weight
-// out of the same pieces: rs_skin_corners and the kernel behind rs_scene_set_bone_transforms (scene_refit.hip k_skin) evaluate it alone.
+// out of the same pieces: rs_skin_corners and the kernel behind rs_scene_set_bone_transforms (scene_deform.hip k_skin) evaluate it alone.
 // The inverse is a host matter: the normal matrix is computed once per matrix (scene_file.cpp bake_normal_matrix) and travels next to it.
 #pragma once
 
@@ -50,7 +50,7 @@ RS_HD BakedCorner bake_corner(const float* m, const float* nm, f3 v, f3 n) {
     return o;
 }
 
-// Linear blend skinning of one corner (rs_skin_corners, rs_scene_set_bone_transforms; scene_refit.hip k_skin): four influences, bone b[k]
+// Linear blend skinning of one corner (rs_skin_corners, rs_scene_set_bone_transforms; scene_deform.hip k_skin): four influences, bone b[k]
 // with weight w[k].  With p_k = bake_position of bone b[k] and q_k = bake_direction of bone b[k]:
 //     position = (w0 * p0 + w1 * p1) + (w2 * p2 + w3 * p3)             per component
 //     normal   = normalize((w0 * q0 + w1 * q1) + (w2 * q2 + w3 * q3))

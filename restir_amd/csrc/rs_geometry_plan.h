@@ -1,7 +1,7 @@
 // rs_geometry_plan.h -- the device-free half of a geometry edit (rs_scene_set_triangles, rs_scene_set_geometry, rs_scene_set_part_transforms):
 // every check of the caller's arrays, the compaction of repeated ids, the layout of the staged records, and -- when an emitter moves --
 // the new light sampler and the emissive tree's new grid, as functions of plain arrays and integers (rs_geometry_edit_view ->
-// rs_geometry_edit_plan, include/restir_hip.h); and whether the edit refits the whole scene or only above its triangles (rs_plan_refit).  Nothing here touches the device, a context or a global: scene_edits.hip set_geometry
+// rs_geometry_edit_plan, include/restir_hip.h); and whether the edit refits the whole scene or only above its triangles (rs_plan_refit).  Nothing here touches the device, a context or a global: scene_edits.hip rs_set_geometry
 // fills the view from the scene, asks for the plans and acts on their fields, and rs_debug_plan_geometry_edit hands the same functions to
 // a test that has no device.  A refusal is the error code returned and, in `why`, the text as the entry point reports it.
 #pragma once

@@ -233,7 +233,7 @@ struct rs_scene {
     // the switch may be set before the first edit has made `refit`; the tables of the partial path belong to `refit` (rs_refit.h)
     bool partialRefit = false;
     int partialMaxTriangles = -1;
-    struct rs_parts* parts = nullptr;   // rigid parts and their rest pose (rs_scene_define_parts; rs_refit.h); null: none defined
+    struct rs_parts* parts = nullptr;   // rigid parts and their rest pose (rs_scene_define_parts; rs_deform.h); null: none defined
     // Motion tracking (rs_scene_set_motion_tracking, rs_scene_advance_motion): dev.prevVertices is dPrevVertices while tracking is on, null
     // otherwise; the array stays allocated until rs_scene_destroy.  motionDirty: a geometry edit has been accepted since prevVertices was
     // last made equal to the vertices, i.e. the two may differ.  The fences are the geometry edits' (rs_refit::before / after), the scene's own
@@ -246,7 +246,7 @@ struct rs_scene {
     float sumLightPower = 0.f;
     int numPrims = 0, bvhSize = 0, numLights = 0;
     unsigned long long id = 0;       // unique per rs_scene_create (a freed scene's address can come back; its id cannot)
-    unsigned long long geomEdits = 0;   // counts the edits that refit the box tables (set_geometry, scene_edits.hip): part of a primary cut's key (rs_primary_cut_key, rs_cut_plan.h)
+    unsigned long long geomEdits = 0;   // counts the edits that refit the box tables (rs_set_geometry, scene_edits.hip): part of a primary cut's key (rs_primary_cut_key, rs_cut_plan.h)
     unsigned long long edits = 0;    // counts the edits that change what GBuffer::render writes (rs_scene_set_emission: baseColor, hence the albedo plane); part of a G-buffer set's content key
     // Edits (rs_scene_set_emission, rs_scene_set_materials, rs_scene_set_texture): a ring of versions of { materials, light records,
     // alias table, texture table }.  Kernels capture
@@ -294,7 +294,7 @@ struct rs_scene {
     // Dirty boxes (rs_restir_set_shadow_revalidation; rs_revalidate_plan.h): the box of each of the last RS_DIRTY_BOXES_KEPT accepted
     // geometry edits with its number, geomEdits once the edit was counted.  Host only, written where the edit is enqueued.
     rs_dirty_ring dirty;
-    // Skinned triangles, their rest pose and the bone palette (rs_scene_define_skin; rs_refit.h); null: none defined.  Last, so that every
+    // Skinned triangles, their rest pose and the bone palette (rs_scene_define_skin; rs_deform.h); null: none defined.  Last, so that every
     // field a frame reads lies where it lay before there were skins.
     struct rs_skin* skin = nullptr;
 };
@@ -734,6 +734,9 @@ int rs_build_ordered_bvh(int numPrims, const float* primBoxes, const int* seq, s
 int rs_reference_chain_tables(int bvhSize, const int* order0, std::vector<int>& parent, std::vector<int>& leafOfPrim, int numPrims);
 // scene_refit.hip
 void rs_refit_free(rs_scene* s);                        // rs_scene_destroy: what the first geometry edit allocated (nothing without one)
+// scene_deform.hip (rs_deform.h); null: nothing to do
+void rs_parts_free(struct rs_parts* parts);             // rs_scene_destroy, rs_scene_define_parts
+void rs_skin_free(struct rs_skin* skin);                // rs_scene_destroy, rs_scene_define_skin
 // scene.hip, for scene_edits.hip as well
 // map ids of n materials against a table of numTextures; the two refusal texts carry the entry point's name
 int check_materials(int n, const rs_material* m, int numTextures, bool* anyMap,
@@ -743,7 +746,7 @@ int check_materials(int n, const rs_material* m, int numTextures, bool* anyMap,
 void light_records(const rs_scene* s, float sumInv, rs::LightRec* rec, rs::AliasRec* al);
 std::vector<rs::AliasRec> alias_records(const std::vector<float>& prob, const std::vector<int>& fail);
 bool far_skip_allowed(const float* vertices, size_t count);   // may skip_far_on_axis (rs_intersect.h) run on a scene with these triangles?
-// scene_edits.hip, for rs_scene_destroy as well
+// scene_edits.hip, for rs_scene_destroy and scene_deform.hip as well
 int refuse_while_capturing(const char* name);           // edits are not recorded into graphs: RS_ERR_UNSUPPORTED while the library stream is captured
 void versions_free(rs_scene* s);                        // what the first edit of materials, lights or textures allocated
 void motion_free(rs_scene* s);                          // what rs_scene_set_motion_tracking allocated

@@ -1,5 +1,5 @@
 // rs_refit.h -- what rs_scene_set_triangles / rs_scene_set_geometry keep per scene (scene_edits.hip: the entry points; rs_geometry_plan.h: their host decisions; scene_refit.hip: tables,
-// kernels, rs_refit_boxes).
+// kernels, rs_refit_boxes), and what an edit whose records a kernel writes hands to them (rs_record_source; the deformers: rs_deform.h).
 //
 // A refit keeps every tree's topology and recomputes every box from the vertices (the partial refit of rs_scene_set_partial_refit: every
 // box above an edited triangle, which leaves the same tables): the reference tree (nodesAll's six orders, occChain)
@@ -10,7 +10,6 @@
 #pragma once
 
 #include "rs_internal.h"
-#include "rs_bake.h"
 
 namespace rs {
 
@@ -65,7 +64,7 @@ struct rs_refit {
     struct Stage { char* host = nullptr; size_t capacity = 0; hipEvent_t copied = nullptr; bool pending = false; } stage[kStaging];
     int stageNext = 0;
     char* dStage = nullptr;          // read by the scatter kernel, in the order of the library stream: ids | vertices | normals, copied from a
-    size_t dStageCapacity = 0;       // staging buffer or written by k_bake_parts / k_skin from the part / bone records, which then follow them in this buffer
+    size_t dStageCapacity = 0;       // staging buffer or written by an rs_record_source's kernel from its staged records, which then follow them in this buffer
     size_t stagedBytes = 0;          // what the last accepted edit copied from the host (rs_debug_scene_staged_bytes)
     // ---- fences ----
     hipEvent_t before[rs_context::kAux] = {};      // what an internal stream has been handed so far
@@ -76,53 +75,23 @@ struct rs_refit {
     size_t root = 0;
 };
 
-// The rigid parts of a scene (rs_scene_define_parts): which primitives move by one matrix, and their rest pose.  The device copies are
-// read by k_bake_parts alone and never written after the definition; the part offsets stay on the host, whose records (rs::PartRec) carry
-// each named part's range to the device.
-struct rs_parts {
-    std::vector<int> first;          // [numParts + 1] offsets into primIds
-    std::vector<int> primIds;        // the parts' primitives, concatenated; no primitive twice
-    std::vector<float> restVertices, restNormals;       // 9 floats per listed primitive
-    int* dPrimIds = nullptr;
-    float* dRestVertices = nullptr;
-    float* dRestNormals = nullptr;
-    // scratch of one rs_scene_set_part_transforms: the records, and the host's own baking of the named parts (checks, light areas, mirror)
-    std::vector<rs::PartRec> recs;
-    std::vector<int> recOf, ids;     // recOf: [numParts] the record of a part named by the call, by stamp
-    std::vector<unsigned> recStamp;
-    unsigned stamp = 0;
-    std::vector<float> vertices, normals;
+// An edit whose records a kernel writes on the device (rs_deform.h), as rs_set_geometry knows it.  In the edit's records' place numRecs
+// records of 112 bytes are staged (rs_geometry_plan.h partStaged / partOnDevice); `enqueue` has a kernel expand them, on stream st before
+// the refit: dRecs is the staged block's device address, dIds | dVertices | dNormals the m triangles in the layout a staged edit has.
+struct rs_record_source {
+    const void* recs;
+    int numRecs;
+    const void* owner;               // what else `enqueue` reads: its maker's business
+    int (*enqueue)(const rs_record_source& src, const void* dRecs, size_t m, int* dIds, float* dVertices, float* dNormals, hipStream_t st);
 };
 
-// The skin of a scene (rs_scene_define_skin): which primitives deform by a blend of bone matrices, their rest pose and, per corner, four
-// bone ids and four weights.  The device copies are read by k_skin alone and never written after the definition (72 + 96 bytes per listed
-// triangle, and its id).  The palette stays on the host; a pose stages all of it (rs::BoneRec, 112 bytes a bone).
-struct rs_skin {
-    int numBones = 0;
-    std::vector<int> primIds;        // [numListed] no primitive twice
-    std::vector<float> restVertices, restNormals;       // 9 floats per listed primitive
-    std::vector<int> boneIds;        // 12 per listed primitive: corner-major, 4 per corner
-    std::vector<float> weights;      // the same shape
-    int* dPrimIds = nullptr;
-    float* dRestVertices = nullptr;
-    float* dRestNormals = nullptr;
-    int* dBoneIds = nullptr;         // (16 bytes per corner at a 16-byte aligned base: k_skin reads an int4 and a float4)
-    float* dWeights = nullptr;
-    std::vector<rs::BoneRec> palette;                   // [numBones] as the last accepted pose left it; identities after the definition
-    // scratch of one rs_scene_set_bone_transforms: the palette it asks for, and the host's own skinning (checks, light areas, mirror)
-    std::vector<rs::BoneRec> recs;
-    std::vector<float> vertices, normals;
-};
+static inline int fail_named(int code, const char* name, const char* text) { return rs_fail(code, (std::string(name) + ": " + text).c_str()); }      // a refusal under an entry point's name
 
+// scene_edits.hip: rs_scene_set_triangles, rs_scene_set_geometry (emitters) and, with a source, the deformers' edits -- the arrays are then the host's
+// own evaluation of the triangles the kernel writes, every id once and in its order.  *taken: the scene took the edit, whatever the call returns.
+__attribute__((visibility("hidden"))) int rs_set_geometry(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals, bool emitters,
+                                                          const char* name, const rs_record_source* source = nullptr, bool* taken = nullptr);
 // scene_refit.hip
-// one rs_scene_set_part_transforms, on stream st, before rs_refit_enqueue: the triangles of the numRecs parts dRecs baked from the rest
-// arrays into dIds | dVertices | dNormals, m triangles in all, in the layout a staged edit has
-int rs_bake_parts_enqueue(const rs_parts* parts, int numRecs, const rs::PartRec* dRecs, size_t m, int* dIds, float* dVertices, float* dNormals, hipStream_t st);
-void rs_parts_free(rs_parts* parts);                    // (null: nothing to do) rs_scene_destroy, rs_scene_define_parts
-// one rs_scene_set_bone_transforms, on stream st, before rs_refit_enqueue: the skin's listed triangles skinned by the palette dBones (all
-// skin->numBones records) from the rest arrays into dIds | dVertices | dNormals, in the layout a staged edit has
-int rs_skin_enqueue(const rs_skin* skin, const rs::BoneRec* dBones, int* dIds, float* dVertices, float* dNormals, hipStream_t st);
-void rs_skin_free(rs_skin* skin);                       // (null: nothing to do) rs_scene_destroy, rs_scene_define_skin
 // first edit: builds and uploads the tables, allocates the scratch (waits for the device once: it reads the grid-box trees back)
 int rs_refit_prepare(rs_scene* s);
 // the first edit made with the switch of rs_scene_set_partial_refit on: builds and uploads the tables of the partial path and allocates

@@ -27,7 +27,7 @@ struct rs_revalidate_choice { int launch; rs_revalidate_boxes boxes; };
 // The box of one edit: the exact AABB of the old and the new corners of the primitives it names -- min and max alone, no arithmetic.
 // oldVertices is the scene's whole table (9 floats per primitive) as it was before the edit, newVertices the edit's records (9 floats per
 // record).  An id named twice takes its last record's new corners (the edit calls' rule) and its old corners once; `distinct`: the
-// caller knows that no id occurs twice (set_geometry's records) and the set below is not built.  count = 0: lo = +inf, hi = -inf.
+// caller knows that no id occurs twice (rs_set_geometry's records) and the set below is not built.  count = 0: lo = +inf, hi = -inf.
 inline void rs_plan_dirty_box(const float* oldVertices, int count, const int* ids, const float* newVertices, bool distinct, float lo[3], float hi[3]) {
     for (int k = 0; k < 3; k++) { lo[k] = __builtin_inff(); hi[k] = -__builtin_inff(); }
     auto take = [&](const float* v9) {

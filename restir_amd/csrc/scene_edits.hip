@@ -1,8 +1,8 @@
 // scene_edits.hip -- edits of a live scene (include/restir_hip.h), all stream-ordered: the ring of versions behind rs_scene_set_emission /
-// rs_scene_set_materials / rs_scene_set_texture; geometry edits in place behind fences (set_geometry, the one implementation of
-// rs_scene_set_triangles, rs_scene_set_geometry, rs_scene_set_part_transforms and rs_scene_set_bone_transforms: its host decisions are
-// rs_geometry_plan.h's, its kernels scene_refit.hip's); rigid parts; skinned meshes; motion tracking.  The scene itself, its trees and
-// its debug tables: scene.hip.
+// rs_scene_set_materials / rs_scene_set_texture; geometry edits in place behind fences (rs_set_geometry, the one implementation of
+// rs_scene_set_triangles and rs_scene_set_geometry here and of the deformers' edits in scene_deform.hip: its host decisions are
+// rs_geometry_plan.h's, its kernels scene_refit.hip's); motion tracking; the refit's and the plans' debug hooks.  The scene itself, its
+// trees and its debug tables: scene.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -22,7 +22,6 @@ int refuse_while_capturing(const char* name) {
 
 namespace {
 
-int fail_named(int code, const char* name, const char* text) { return rs_fail(code, (std::string(name) + ": " + text).c_str()); }
 // a refusal of rs_geometry_plan.h: its text is in `why` (empty: a library call inside the plan failed and has reported it)
 int refused(int code, const std::string& why) { return why.empty() ? code : rs_fail(code, why.c_str()); }
 
@@ -378,20 +377,6 @@ int fence_after(hipEvent_t after) {
     return 0;
 }
 
-// parts (rs_scene_set_part_transforms): the edit's records are not copied from the host but written on the device, by k_bake_parts from the
-// numRecs part records `recs` (which alone are staged) and the scene's rest pose; primIds / vertices / normals are then the host's own baking
-// of the same triangles, every id once, in the order the kernel writes them -- for the checks, the light areas and the host's tables.
-// A skin (rs_scene_set_bone_transforms) is the same kind of source, and `skin` says so: the staged records are then skin->recs, the whole
-// palette the pose asks for (numRecs = skin->numBones records of rs::BoneRec, a part record's size), k_skin writes the edit's records from
-// them and the skin's rest arrays, and the palette becomes the scene's where the host's tables take the pose.  Exactly one of `recs` and
-// `skin` is set.
-struct PartSource {
-    int numRecs;
-    const PartRec* recs;
-    rs_skin* skin;
-    const void* staged() const { return skin ? static_cast<const void*>(skin->recs.data()) : static_cast<const void*>(recs); }
-};
-
 // What rs_geometry_plan.h reads of the scene.  (hLightArea and envPower are versions_prepare's, emiRecords rs_refit_prepare's: the plan
 // of the lights asks for the view again after them.)
 rs_geometry_edit_view edit_view(const rs_scene* s) {
@@ -431,11 +416,11 @@ int stage_reserve(rs_refit* r, size_t staged, size_t onDevice, rs_refit::Stage**
     return 0;
 }
 
-// the edit's m records, every id once, on the host: the staged ones, or -- parts -- the caller's own arrays, which name no id twice
+// the edit's m records, every id once, on the host: the staged ones, or -- a source's are staged in their place -- the caller's own arrays
 struct Records { const int* ids; const float* vertices; const float* normals; };
 Records fill_stage(char* host, const rs_geometry_edit_plan& plan, const rs_edit_stamps& stamps, int count, const int* primIds, const float* vertices,
-                   const float* normals, const PartSource* parts) {
-    if (parts) { std::memcpy(host, parts->staged(), plan.partStaged); return Records{ primIds, vertices, normals }; }
+                   const float* normals, const rs_record_source* source) {
+    if (source) { std::memcpy(host, source->recs, plan.partStaged); return Records{ primIds, vertices, normals }; }
     rs_fill_edit_records(plan, stamps, count, primIds, vertices, normals, host);
     return Records{ reinterpret_cast<const int*>(host), reinterpret_cast<const float*>(host + plan.offV), reinterpret_cast<const float*>(host + plan.offN) };
 }
@@ -480,12 +465,15 @@ void update_host_tables(rs_scene* s, int m, const Records& rec, bool normals) {
     if (s->dev.prevVertices) s->motionDirty = true;              // rs_scene_advance_motion has something to copy
 }
 
-int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals, bool emitters, const char* name,
-                 const PartSource* parts = nullptr) {
+}  // namespace
+
+int rs_set_geometry(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals, bool emitters, const char* name,
+                    const rs_record_source* source, bool* taken) {
+    if (taken) *taken = false;
     if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
     rs_geometry_edit_plan plan;
     std::string why;
-    if (int e = rs_plan_edit_records(edit_view(s), count, primIds, vertices, normals, emitters, parts ? parts->numRecs : 0, name, s->editStamps, plan, why)) return refused(e, why);
+    if (int e = rs_plan_edit_records(edit_view(s), count, primIds, vertices, normals, emitters, source ? source->numRecs : 0, name, s->editStamps, plan, why)) return refused(e, why);
     RS_TRY(refuse_while_capturing(name));
     if (count == 0) return 0;
     RS_TRY(rs_refit_prepare(s));
@@ -497,11 +485,12 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
     rs_edit_lights_plan lights;
     if (lamps) if (int e = rs_plan_edit_lights(edit_view(s), s->editStamps, vertices, name, lights, why)) return refused(e, why);
 
-    // what crosses the bus: the records themselves, or the part records, which follow the records they expand to in the device buffer
-    const size_t staged = parts ? plan.partStaged : plan.staged, onDevice = parts ? plan.partOnDevice : plan.onDevice, stagedAt = parts ? plan.bytes : 0;
+    // what crosses the bus: the records themselves, or a source's records, which follow the records they expand to in the device buffer
+    size_t staged = plan.staged, onDevice = plan.onDevice, stagedAt = 0;
+    if (source) { staged = plan.partStaged; onDevice = plan.partOnDevice; stagedAt = plan.bytes; }
     rs_refit::Stage* g = nullptr;
     RS_TRY(stage_reserve(r, staged, onDevice, &g));
-    const Records rec = fill_stage(g->host, plan, s->editStamps, count, primIds, vertices, normals, parts);
+    const Records rec = fill_stage(g->host, plan, s->editStamps, count, primIds, vertices, normals, source);
 
     // frames in flight: a render that has only been recorded is launched now, with the old geometry (and the old lights)
     if (lamps) RS_TRY(version_begin(s));
@@ -527,10 +516,8 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
     g->pending = true;
     r->stageNext = (r->stageNext + 1) % rs_refit::kStaging;
     r->stagedBytes = staged;
-    if (parts && parts->skin) RS_TRY(rs_skin_enqueue(parts->skin, reinterpret_cast<const BoneRec*>(d + stagedAt), reinterpret_cast<int*>(d),
-                                                     reinterpret_cast<float*>(d + plan.offV), reinterpret_cast<float*>(d + plan.offN), st));
-    else if (parts) RS_TRY(rs_bake_parts_enqueue(s->parts, parts->numRecs, reinterpret_cast<const PartRec*>(d + stagedAt), (size_t)plan.m, reinterpret_cast<int*>(d),
-                                                 reinterpret_cast<float*>(d + plan.offV), reinterpret_cast<float*>(d + plan.offN), st));
+    if (source) RS_TRY(source->enqueue(*source, d + stagedAt, (size_t)plan.m, reinterpret_cast<int*>(d), reinterpret_cast<float*>(d + plan.offV),
+                                       reinterpret_cast<float*>(d + plan.offN), st));
     // whole or partial (rs_geometry_plan.h): the first edit of a scene is whole, since no whole refit has left its key boxes yet
     bool partial = false;
     unsigned long long bound = 0;
@@ -540,8 +527,7 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
     RS_TRY(fence_after(r->after));
 
     update_host_tables(s, plan.m, rec, normals != nullptr);
-    // ... and the palette with them: geometry and palette stay one pose whatever the calls below return
-    if (parts && parts->skin) parts->skin->palette.swap(parts->skin->recs);
+    if (taken) *taken = true;                           // past the last refusal: the scene holds the new pose whatever the calls below return
     if (!lamps) return rs_after_launch(name);
     // the lights' version: light_records reads the vertices just written; launches from here on see new geometry and new lights alike
     s->hLightArea.swap(lights.area);
@@ -557,244 +543,14 @@ int set_geometry(rs_scene* s, int count, const int* primIds, const float* vertic
     return version_commit(s, name);
 }
 
-}  // namespace
-
 extern "C" int rs_scene_set_triangles(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals) {
     RS_SCOPE(s);
-    return set_geometry(s, count, primIds, vertices, normals, false, "rs_scene_set_triangles");
+    return rs_set_geometry(s, count, primIds, vertices, normals, false, "rs_scene_set_triangles");
 }
 
 extern "C" int rs_scene_set_geometry(rs_scene* s, int count, const int* primIds, const float* vertices, const float* normals) {
     RS_SCOPE(s);
-    return set_geometry(s, count, primIds, vertices, normals, true, "rs_scene_set_geometry");
-}
-
-// ---- rigid parts (include/restir_hip.h) ----
-// The definition is replaced behind a wait for the device (rs_synchronize, as the first edit of a scene waits once): a transform enqueued
-// earlier has finished with the old tables, a later one finds the new.  Nothing of the scene's geometry changes.
-extern "C" int rs_scene_define_parts(rs_scene* s, int numParts, const int* partFirst, const int* primIds, const float* restVertices, const float* restNormals) {
-    RS_SCOPE(s);
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: null scene");
-    if (numParts < 0 || (numParts > 0 && !partFirst)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: numParts < 0 or null offsets");
-    if ((restVertices == nullptr) != (restNormals == nullptr)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: rest vertices without rest normals, or the reverse");
-    if (numParts > 0 && partFirst[0] != 0) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: the first offset is not 0");
-    for (int i = 0; i < numParts; i++)
-        if (partFirst[i + 1] < partFirst[i]) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: offsets that decrease");
-    const size_t listed = numParts > 0 ? (size_t)partFirst[numParts] : 0;
-    if (listed > 0 && !primIds) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: null primitive ids");
-    {
-        std::vector<char> seen((size_t)s->numPrims, 0);
-        for (size_t i = 0; i < listed; i++) {
-            const int p = primIds[i];
-            if (p < 0 || p >= s->numPrims) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: a primitive id out of range");
-            if (seen[(size_t)p]) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: a primitive listed twice");
-            seen[(size_t)p] = 1;
-        }
-    }
-    if (restVertices)
-        for (size_t i = 0; i < listed * 9; i++)
-            if (!std::isfinite(restVertices[i]) || !std::isfinite(restNormals[i])) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_define_parts: a rest value that is not finite");
-    RS_TRY(refuse_while_capturing("rs_scene_define_parts"));
-    if (numParts == 0) {
-        if (s->parts) { RS_TRY(rs_synchronize()); rs_parts_free(s->parts); s->parts = nullptr; }
-        return 0;
-    }
-
-    rs_parts* p = new rs_parts();
-    p->first.assign(partFirst, partFirst + numParts + 1);
-    p->primIds.assign(primIds, primIds + listed);
-    p->restVertices.resize(listed * 9); p->restNormals.resize(listed * 9);
-    for (size_t i = 0; i < listed; i++) {
-        // the scene's own pose, or the caller's arrays
-        std::memcpy(&p->restVertices[i * 9], restVertices ? restVertices + i * 9 : &s->hVertices[(size_t)primIds[i] * 9], 9 * sizeof(float));
-        std::memcpy(&p->restNormals[i * 9], restNormals ? restNormals + i * 9 : &s->hNormals[(size_t)primIds[i] * 9], 9 * sizeof(float));
-    }
-    p->recOf.assign((size_t)numParts, 0);
-    p->recStamp.assign((size_t)numParts, 0u);
-    int e = upload(&p->dPrimIds, p->primIds);
-    if (!e) e = upload(&p->dRestVertices, p->restVertices);
-    if (!e) e = upload(&p->dRestNormals, p->restNormals);
-    if (!e && s->parts) e = rs_synchronize();           // a transform in flight reads the tables that are about to be freed
-    if (e) { rs_parts_free(p); return e; }              // (the definition stays what it was)
-    rs_parts_free(s->parts);
-    s->parts = p;
-    return 0;
-}
-
-// The named parts' records (a part named twice keeps its place and takes its last matrix; an empty part has none), the host's own baking of
-// their triangles, and then rs_scene_set_geometry's implementation with the records written on the device.
-extern "C" int rs_scene_set_part_transforms(rs_scene* s, int count, const int* partIds, const float* matrices16) {
-    RS_SCOPE(s);
-    const char* name = "rs_scene_set_part_transforms";
-    if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
-    if (count < 0 || (count > 0 && (!partIds || !matrices16))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "count < 0 or null arrays");
-    rs_parts* p = s->parts;
-    if (!p) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "the scene has no parts (rs_scene_define_parts)");
-    const int numParts = (int)p->first.size() - 1;
-    for (int i = 0; i < count; i++)
-        if (partIds[i] < 0 || partIds[i] >= numParts) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a part id out of range");
-
-    if (++p->stamp == 0u) { std::fill(p->recStamp.begin(), p->recStamp.end(), 0u); p->stamp = 1u; }
-    p->recs.clear();
-    for (int i = 0; i < count; i++) {
-        const size_t part = (size_t)partIds[i];
-        const int first = p->first[part], n = p->first[part + 1] - first;
-        if (n == 0) continue;
-        if (p->recStamp[part] != p->stamp) {
-            p->recStamp[part] = p->stamp;
-            p->recOf[part] = (int)p->recs.size();
-            PartRec rec{};
-            rec.restFirst = first; rec.count = n;
-            p->recs.push_back(rec);
-        }
-        std::memcpy(p->recs[(size_t)p->recOf[part]].m, matrices16 + (size_t)i * 16, 16 * sizeof(float));
-    }
-    size_t m = 0;
-    for (PartRec& rec : p->recs) { rec.outFirst = (int)m; m += (size_t)rec.count; }
-    p->ids.resize(m); p->vertices.resize(m * 9); p->normals.resize(m * 9);
-    for (PartRec& rec : p->recs) {
-        rs_bake_normal_matrix(rec.m, rec.nm);
-        const size_t in = (size_t)rec.restFirst, out = (size_t)rec.outFirst;
-        std::memcpy(&p->ids[out], &p->primIds[in], (size_t)rec.count * sizeof(int));
-        rs_bake_corners(rec.m, rec.nm, (size_t)rec.count * 3, &p->restVertices[in * 9], &p->restNormals[in * 9], &p->vertices[out * 9], &p->normals[out * 9]);
-    }
-    const PartSource src{ (int)p->recs.size(), p->recs.data(), nullptr };
-    return set_geometry(s, (int)m, p->ids.data(), p->vertices.data(), p->normals.data(), true, name, &src);
-}
-
-// ---- skinned meshes (include/restir_hip.h) ----
-// rs_skin_corners' and rs_scene_set_bone_transforms' palette: one record per matrix, the normal matrix computed once per matrix
-static void bone_record(const float* matrix16, BoneRec& rec) {
-    std::memcpy(rec.m, matrix16, 16 * sizeof(float));
-    rs_bake_normal_matrix(rec.m, rec.nm);
-    rec.pad[0] = rec.pad[1] = rec.pad[2] = 0;
-}
-
-extern "C" int rs_skin_corners(int numBones, const float* matrices16, size_t n, const float* vertsIn, const float* normalsIn, const int* boneIds4,
-                               const float* weights4, float* vertsOut, float* normalsOut) {
-    if (numBones < 1 || !matrices16) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_skin_corners: numBones < 1 or null matrices");
-    if (n > 0 && (!vertsIn || !normalsIn || !boneIds4 || !weights4 || !vertsOut || !normalsOut)) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_skin_corners: a null array with n > 0");
-    for (size_t i = 0; i < n * 4; i++)
-        if (boneIds4[i] < 0 || boneIds4[i] >= numBones) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_skin_corners: a bone id out of range");
-    std::vector<BoneRec> palette((size_t)numBones);
-    for (int b = 0; b < numBones; b++) bone_record(matrices16 + (size_t)b * 16, palette[(size_t)b]);
-    rs_skin_corners_host(palette.data(), n, vertsIn, normalsIn, boneIds4, weights4, vertsOut, normalsOut);
-    return 0;
-}
-
-// The definition is replaced behind a wait for the device, as rs_scene_define_parts replaces its own.  Nothing of the scene's geometry changes.
-extern "C" int rs_scene_define_skin(rs_scene* s, int numBones, int numListed, const int* primIds, const float* restVertices, const float* restNormals,
-                                    const int* boneIds, const float* weights) {
-    RS_SCOPE(s);
-    const char* name = "rs_scene_define_skin";
-    if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
-    if (numBones < 0 || numBones > RS_SKIN_MAX_BONES) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "numBones < 0 or above RS_SKIN_MAX_BONES");
-    if (numListed < 0 || (numBones == 0 && numListed > 0)) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "numListed < 0, or triangles without a bone");
-    if ((restVertices == nullptr) != (restNormals == nullptr)) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "rest vertices without rest normals, or the reverse");
-    if (numListed > 0 && (!primIds || !boneIds || !weights)) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null primitive ids, bone ids or weights");
-    const size_t listed = (size_t)numListed;
-    {
-        std::vector<char> seen((size_t)s->numPrims, 0);
-        for (size_t i = 0; i < listed; i++) {
-            const int p = primIds[i];
-            if (p < 0 || p >= s->numPrims) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a primitive id out of range");
-            if (seen[(size_t)p]) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a primitive listed twice");
-            seen[(size_t)p] = 1;
-        }
-    }
-    if (restVertices)
-        for (size_t i = 0; i < listed * 9; i++)
-            if (!std::isfinite(restVertices[i]) || !std::isfinite(restNormals[i])) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a rest value that is not finite");
-    for (size_t c = 0; c < listed * 3; c++) {
-        bool any = false;
-        for (size_t k = c * 4; k < c * 4 + 4; k++) {
-            if (boneIds[k] < 0 || boneIds[k] >= numBones) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a bone id out of range");
-            if (!std::isfinite(weights[k])) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a weight that is not finite");
-            if (weights[k] < 0.f) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a negative weight");
-            any = any || weights[k] != 0.f;
-        }
-        if (!any) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a corner whose four weights are all 0");
-    }
-    RS_TRY(refuse_while_capturing(name));
-    if (numBones == 0) {
-        if (s->skin) { RS_TRY(rs_synchronize()); rs_skin_free(s->skin); s->skin = nullptr; }
-        return 0;
-    }
-
-    rs_skin* k = new rs_skin();
-    k->numBones = numBones;
-    k->primIds.assign(primIds, primIds + listed);
-    k->restVertices.resize(listed * 9); k->restNormals.resize(listed * 9);
-    for (size_t i = 0; i < listed; i++) {
-        // the scene's own pose, or the caller's arrays
-        std::memcpy(&k->restVertices[i * 9], restVertices ? restVertices + i * 9 : &s->hVertices[(size_t)primIds[i] * 9], 9 * sizeof(float));
-        std::memcpy(&k->restNormals[i * 9], restNormals ? restNormals + i * 9 : &s->hNormals[(size_t)primIds[i] * 9], 9 * sizeof(float));
-    }
-    k->boneIds.assign(boneIds, boneIds + listed * 12);
-    k->weights.assign(weights, weights + listed * 12);
-    const float identity[16] = { 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f };
-    k->palette.resize((size_t)numBones);
-    for (BoneRec& rec : k->palette) bone_record(identity, rec);
-    int e = upload(&k->dPrimIds, k->primIds);
-    if (!e) e = upload(&k->dRestVertices, k->restVertices);
-    if (!e) e = upload(&k->dRestNormals, k->restNormals);
-    if (!e) e = upload(&k->dBoneIds, k->boneIds);
-    if (!e) e = upload(&k->dWeights, k->weights);
-    if (!e && s->skin) e = rs_synchronize();            // a pose in flight reads the tables that are about to be freed
-    if (e) { rs_skin_free(k); return e; }               // (the definition stays what it was)
-    rs_skin_free(s->skin);
-    s->skin = k;
-    return 0;
-}
-
-// The palette the call asks for (a bone named twice takes its last matrix, a bone not named keeps its own), the host's own skinning of every
-// listed triangle by it, and then rs_scene_set_geometry's implementation with the records written on the device.  The palette becomes
-// the scene's inside set_geometry, past its last refusal, where the host's tables take the pose; a skin that lists no triangle has no
-// edit to make and takes the palette here.
-extern "C" int rs_scene_set_bone_transforms(rs_scene* s, int count, const int* boneIds, const float* matrices16) {
-    RS_SCOPE(s);
-    const char* name = "rs_scene_set_bone_transforms";
-    if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
-    if (count < 0 || (count > 0 && (!boneIds || !matrices16))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "count < 0 or null arrays");
-    rs_skin* k = s->skin;
-    if (!k) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "the scene has no skin (rs_scene_define_skin)");
-    for (int i = 0; i < count; i++)
-        if (boneIds[i] < 0 || boneIds[i] >= k->numBones) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a bone id out of range");
-    if (count == 0) return 0;
-
-    k->recs = k->palette;
-    for (int i = 0; i < count; i++) bone_record(matrices16 + (size_t)i * 16, k->recs[(size_t)boneIds[i]]);
-    const size_t listed = k->primIds.size();
-    k->vertices.resize(listed * 9); k->normals.resize(listed * 9);
-    rs_skin_corners_host(k->recs.data(), listed * 3, k->restVertices.data(), k->restNormals.data(), k->boneIds.data(), k->weights.data(),
-                         k->vertices.data(), k->normals.data());
-    const PartSource src{ k->numBones, nullptr, k };
-    RS_TRY(set_geometry(s, (int)listed, k->primIds.data(), k->vertices.data(), k->normals.data(), true, name, &src));
-    if (listed == 0) k->palette.swap(k->recs);
-    return 0;
-}
-
-extern "C" int rs_scene_skin_info(const rs_scene* s, int* numBones, int* numListedPrims) {
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_skin_info: null scene");
-    if (numBones) *numBones = s->skin ? s->skin->numBones : 0;
-    if (numListedPrims) *numListedPrims = s->skin ? (int)s->skin->primIds.size() : 0;
-    return 0;
-}
-
-extern "C" int rs_scene_download_skin(const rs_scene* s, int* primIds, float* restVertices, float* restNormals, int* boneIds, float* weights) {
-    RS_SCOPE(s);
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_skin: null scene");
-    const rs_skin* k = s->skin;
-    if (!k) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_skin: the scene has no skin (rs_scene_define_skin)");
-    RS_TRY(refuse_while_capturing("rs_scene_download_skin"));
-    RS_TRY(rs_synchronize());
-    const size_t n = k->primIds.size();
-    if (n && primIds) RS_HIP(hipMemcpy(primIds, k->dPrimIds, n * sizeof(int), hipMemcpyDeviceToHost));
-    if (n && restVertices) RS_HIP(hipMemcpy(restVertices, k->dRestVertices, n * 9 * sizeof(float), hipMemcpyDeviceToHost));
-    if (n && restNormals) RS_HIP(hipMemcpy(restNormals, k->dRestNormals, n * 9 * sizeof(float), hipMemcpyDeviceToHost));
-    if (n && boneIds) RS_HIP(hipMemcpy(boneIds, k->dBoneIds, n * 12 * sizeof(int), hipMemcpyDeviceToHost));
-    if (n && weights) RS_HIP(hipMemcpy(weights, k->dWeights, n * 12 * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    return rs_set_geometry(s, count, primIds, vertices, normals, true, "rs_scene_set_geometry");
 }
 
 extern "C" int rs_scene_light_moves(const rs_scene* s, unsigned long long* moves) {
@@ -817,27 +573,6 @@ extern "C" int rs_scene_dirty_boxes(const rs_scene* s, unsigned long long sinceE
     *count = c.boxes.n; *everything = c.boxes.everything;
     for (int i = 0; i < c.boxes.n && i < capacity; i++)
         for (int k = 0; k < 3; k++) { boxes6[i * 6 + k] = c.boxes.box[i].lo[k]; boxes6[i * 6 + 3 + k] = c.boxes.box[i].hi[k]; }
-    return 0;
-}
-
-extern "C" int rs_scene_parts_info(const rs_scene* s, int* numParts, int* numListedPrims) {
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_parts_info: null scene");
-    if (numParts) *numParts = s->parts ? (int)s->parts->first.size() - 1 : 0;
-    if (numListedPrims) *numListedPrims = s->parts ? (int)s->parts->primIds.size() : 0;
-    return 0;
-}
-
-extern "C" int rs_scene_download_part_rest(const rs_scene* s, int* primIds, float* restVertices, float* restNormals) {
-    RS_SCOPE(s);
-    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_part_rest: null scene");
-    const rs_parts* p = s->parts;
-    if (!p) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_download_part_rest: the scene has no parts (rs_scene_define_parts)");
-    RS_TRY(refuse_while_capturing("rs_scene_download_part_rest"));
-    RS_TRY(rs_synchronize());
-    const size_t n = p->primIds.size();
-    if (n && primIds) RS_HIP(hipMemcpy(primIds, p->dPrimIds, n * sizeof(int), hipMemcpyDeviceToHost));
-    if (n && restVertices) RS_HIP(hipMemcpy(restVertices, p->dRestVertices, n * 9 * sizeof(float), hipMemcpyDeviceToHost));
-    if (n && restNormals) RS_HIP(hipMemcpy(restNormals, p->dRestNormals, n * 9 * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -892,7 +627,7 @@ extern "C" int rs_debug_plan_refit(int on, int maxTriangles, int keysValid, int 
     return 0;
 }
 
-// Test hook of rs_geometry_plan.h (include/restir_hip.h): the two plans set_geometry asks for, of a view the caller made up
+// Test hook of rs_geometry_plan.h (include/restir_hip.h): the two plans rs_set_geometry asks for, of a view the caller made up
 static_assert(sizeof(rs_geometry_edit_view) == 120 && sizeof(rs_geometry_edit_plan) == 64 && sizeof(rs_geometry_edit_lights) == 64, "the sizes restir_amd/ctypes_structs.py mirrors");
 extern "C" int rs_debug_plan_geometry_edit(const rs_geometry_edit_view* view, const char* name, int emitters, int count, const int* primIds,
                                            const float* vertices, const float* normals, int numPartRecs, rs_geometry_edit_plan* plan, int* slots,

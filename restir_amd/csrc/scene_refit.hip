@@ -20,9 +20,8 @@
 // of other triangles stops short of them and writes no byte of emiNodes / emiTris.  Its grid is its own and moves with the lamps: the host
 // lays it over the new emissive root box before the launches (scene_edits.hip), so base, scale and margin are per record range (GridArgs).
 //
-// In front of the refit, for rs_scene_set_part_transforms alone: k_bake_parts writes the records k_scatter reads -- the staged edit -- from the
-// scene's rest pose and one matrix per part, instead of a copy from the host bringing them.  For rs_scene_set_bone_transforms k_skin does the
-// same from the skin's rest pose and a palette of bone matrices blended per corner.
+// In front of the refit, for the deformers alone (rs_scene_set_part_transforms, rs_scene_set_bone_transforms): a kernel of scene_deform.hip
+// writes the records k_scatter reads -- the staged edit -- from a rest pose, instead of a copy from the host bringing them.
 //
 // Next to the refit: k_copy_pose, the copy rs_scene_advance_motion makes of the vertices into the scene's previous pose (scene_edits.hip).
 //
@@ -368,69 +367,6 @@ __global__ void __launch_bounds__(256) k_copy_pose(const float* __restrict__ ver
     if (i < count) prevVertices[i] = vertices[i];
 }
 
-// rs_scene_set_part_transforms: the staged edit of rs_scene_set_geometry -- ids | vertices | normals of m triangles -- written on the device
-// from the parts' rest pose instead of copied from the host.  One lane per output corner: consecutive lanes read consecutive 12-byte rest
-// vertices and normals of their part and write consecutive 12-byte results; the lane of corner 0 also writes the primitive id.  A lane finds
-// its part by binary search for the last record whose outFirst is not beyond its triangle (outFirst is non-decreasing, recs[0].outFirst = 0,
-// no record is empty).  A wave that lies inside one part reads the two matrices through the scalar cache.  The arithmetic is rs_bake.h's
-// bake_corner and nothing else: the bits are rs_bake_matrix's.  No hand-off between lanes, nothing shared.
-__device__ __forceinline__ void bake_store(const PartRec* rec, const float* __restrict__ v, const float* __restrict__ n, float* outV, float* outN) {
-    const BakedCorner o = bake_corner(rec->m, rec->nm, ld3(v), ld3(n));
-    st3(outV, o.position);
-    st3(outN, o.normal);
-}
-__global__ void __launch_bounds__(256) k_bake_parts(int numRecs, const PartRec* __restrict__ recs, const int* __restrict__ partPrimIds,
-                                                    const float* __restrict__ restVertices, const float* __restrict__ restNormals,
-                                                    size_t numCorners, int* __restrict__ ids, float* __restrict__ vertices, float* __restrict__ normals) {
-    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= numCorners) return;
-    const size_t tri = c / 3, corner = c - tri * 3;
-    int lo = 0, hi = numRecs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((size_t)recs[mid].outFirst <= tri) lo = mid; else hi = mid - 1;
-    }
-    const size_t slot = (size_t)recs[lo].restFirst + (tri - (size_t)recs[lo].outFirst);
-    const size_t src = (slot * 3 + corner) * 3;
-    const int first = __builtin_amdgcn_readfirstlane(lo);
-    if (__all(lo == first)) bake_store(recs + first, restVertices + src, restNormals + src, vertices + c * 3, normals + c * 3);
-    else bake_store(recs + lo, restVertices + src, restNormals + src, vertices + c * 3, normals + c * 3);
-    if (corner == 0) ids[tri] = partPrimIds[slot];
-}
-
-// rs_scene_set_bone_transforms: the same staged edit, written from the skin's rest pose and a palette of bone matrices.  One lane per output
-// corner.  The block first copies the whole palette -- numBones records of 112 bytes = 7 x 16, staged 16-byte aligned behind the records
-// this kernel writes -- into LDS, 16 bytes a lane and step, and meets at one barrier: lanes past numCorners take part in both, nothing
-// returns before the barrier.  A lane then reads its four bone ids and four weights as one int4 and one float4 (16 bytes per corner at a
-// hipMalloc'ed base), its 12 + 12 bytes of rest corner, evaluates rs_bake.h's skin_corner against the LDS palette -- the bits are
-// rs_skin_corners' -- and writes 12 + 12 bytes; the lane of corner 0 also writes the primitive id.  Bone ids differ from lane to lane, so the
-// palette reads conflict on LDS banks: accepted.  The ids were checked against numBones by rs_scene_define_skin and
-// the device copy is never written again, so no read leaves the staged palette.  28 KB of LDS: five blocks a CU.
-__global__ void __launch_bounds__(256) k_skin(int numBones, const BoneRec* __restrict__ bones, const int* __restrict__ skinPrimIds,
-                                              const float* __restrict__ restVertices, const float* __restrict__ restNormals,
-                                              const int4* __restrict__ boneIds, const float4* __restrict__ weights,
-                                              size_t numCorners, int* __restrict__ ids, float* __restrict__ vertices, float* __restrict__ normals) {
-    __shared__ BoneRec palette[RS_SKIN_MAX_BONES];
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(bones);
-        uint4* dst = reinterpret_cast<uint4*>(palette);
-        const int n16 = numBones * (int)(sizeof(BoneRec) / 16);
-        for (int i = (int)threadIdx.x; i < n16; i += 256) dst[i] = src[i];
-    }
-    __syncthreads();
-    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= numCorners) return;
-    const int4 b4 = boneIds[c];
-    const float4 w4 = weights[c];
-    const int b[4] = { b4.x, b4.y, b4.z, b4.w };
-    const float w[4] = { w4.x, w4.y, w4.z, w4.w };
-    const BakedCorner o = skin_corner(palette, b, w, ld3(restVertices + c * 3), ld3(restNormals + c * 3));
-    st3(vertices + c * 3, o.position);
-    st3(normals + c * 3, o.normal);
-    const size_t tri = c / 3;
-    if (c == tri * 3) ids[tri] = skinPrimIds[tri];
-}
-
 inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -513,36 +449,6 @@ int rs_motion_copy_enqueue(const float* vertices, float* prevVertices, size_t nu
     if (count == 0) return 0;
     hipLaunchKernelGGL(k_copy_pose, dim3(blocks_for(count)), dim3(256), 0, st, vertices, prevVertices, count);
     return rs_check_hip(hipGetLastError(), "rs_scene_advance_motion: copy kernel");
-}
-
-int rs_bake_parts_enqueue(const rs_parts* parts, int numRecs, const PartRec* dRecs, size_t m, int* dIds, float* dVertices, float* dNormals, hipStream_t st) {
-    const size_t corners = m * 3;
-    if (corners == 0) return 0;
-    hipLaunchKernelGGL(k_bake_parts, dim3(blocks_for(corners)), dim3(256), 0, st, numRecs, dRecs, (const int*)parts->dPrimIds,
-                       (const float*)parts->dRestVertices, (const float*)parts->dRestNormals, corners, dIds, dVertices, dNormals);
-    return rs_check_hip(hipGetLastError(), "rs_scene_set_part_transforms: bake kernel");
-}
-
-void rs_parts_free(rs_parts* p) {
-    if (!p) return;
-    rs_dev_free(p->dPrimIds); rs_dev_free(p->dRestVertices); rs_dev_free(p->dRestNormals);
-    delete p;
-}
-
-int rs_skin_enqueue(const rs_skin* skin, const BoneRec* dBones, int* dIds, float* dVertices, float* dNormals, hipStream_t st) {
-    const size_t corners = skin->primIds.size() * 3;
-    if (corners == 0) return 0;
-    if (skin->numBones < 1 || skin->numBones > RS_SKIN_MAX_BONES) return rs_fail(RS_ERR_INTERNAL, "rs_scene_set_bone_transforms: a palette the kernel has no room for");
-    hipLaunchKernelGGL(k_skin, dim3(blocks_for(corners)), dim3(256), 0, st, skin->numBones, dBones, (const int*)skin->dPrimIds,
-                       (const float*)skin->dRestVertices, (const float*)skin->dRestNormals, reinterpret_cast<const int4*>(skin->dBoneIds),
-                       reinterpret_cast<const float4*>(skin->dWeights), corners, dIds, dVertices, dNormals);
-    return rs_check_hip(hipGetLastError(), "rs_scene_set_bone_transforms: skin kernel");
-}
-
-void rs_skin_free(rs_skin* k) {
-    if (!k) return;
-    rs_dev_free(k->dPrimIds); rs_dev_free(k->dRestVertices); rs_dev_free(k->dRestNormals); rs_dev_free(k->dBoneIds); rs_dev_free(k->dWeights);
-    delete k;
 }
 
 void rs_refit_free(rs_scene* s) {
