@@ -583,7 +583,12 @@ int  rs_debug_grid_box(const float lo[3], const float hi[3], const float base[3]
  * record -- and all of it reaches the device with the same version switch; rs_scene_host_desc then returns texels, envMapProb,
  * envMapFailId, lightProb, lightFailId and sumLightPower equal, bit for bit, to those of a scene built afresh, and a later
  * rs_scene_set_emission uses the new environment power.  An environment map whose pdf sum, or the resulting total light power, is not
- * finite and positive is refused with RS_ERR_INVALID_ARGUMENT, the scene unchanged.  The environment entry stays outside light
+ * finite and positive is refused with RS_ERR_INVALID_ARGUMENT, the scene unchanged.  (Creation is laxer: rs_scene_build_textured and
+ * rs_scene_create take a black environment map and one with an infinite or NaN texel as the reference does -- a black map's entry has power 0
+ * and yields no live sample; with an infinite or NaN texel the total light power is infinite or NaN, every pdf of every light 0 or NaN
+ * and no reservoir live; the map is still shown where a ray misses -- and such a scene
+ * renders bit for bit like the oracle's; the same map handed to this call is refused and the scene keeps the map it had:
+ * tests/test_gpu_texture_extremes.py.)  The environment entry stays outside light
  * tracking (rs_restir_set_light_tracking), as before. */
 int  rs_scene_set_texture(rs_scene* scene, int texId, int width, int height, const float* data);
 /* Scene::clear / DevScene::destroy (src/scene.cpp:217-220,511-532). */
@@ -1036,6 +1041,14 @@ int  rs_debug_exact_ops_mismatches(int op, unsigned firstSig, unsigned countSig,
 int  rs_debug_rng_step_mismatches(unsigned long long* out2);
 /* The same comparison of the same shared code on the host, for the `count` states from `first` on (all in [1, 2^31 - 2]): needs no device. */
 int  rs_debug_rng_step_host_mismatches(unsigned first, unsigned count, unsigned long long* out2);
+/* Test hook for restir_amd/csrc/rs_surface.h: the functions under the textured and environment-map kernel variants, unchanged, one
+ * lane per element of a batch of n, on host arrays.  op 0: linear_sample of (u, v) on the texture texWidth x texHeight of packed RGB
+ * `texels` (n x 2 -> n x 3); op 1: procedural_texture of (u, v) (n x 2 -> n x 3); op 2: to_sphere of (u, v) (n x 2 -> n x 3);
+ * op 3: to_plane of a direction (n x 3 -> n x 2); op 4: local_to_world of (normal, vector) (n x 6 -> n x 3).  The texture arguments
+ * are read by op 0 only.  Refused with RS_ERR_INVALID_ARGUMENT: an op outside 0..4, null in / out, n < 0 or above 2^26, and for op 0
+ * null texels, a width or height that is not positive, more than 2^26 texels.  Waits for the library stream.
+ * tests/test_gpu_surface_ops.py holds every op to the oracle's function bit for bit. */
+int  rs_debug_surface_ops(int op, int n, const float* in, float* out, int texWidth, int texHeight, const float* texels);
 
 /* ---- framebuffer tiling across the GPUs of one node: the row-strip frame of one rank ------------------------------------------
  * One process per GPU, the scene replicated, the framebuffer of runCuda (src/main.cpp:146-185) cut into `world` row strips.  A rank

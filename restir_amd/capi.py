@@ -157,7 +157,7 @@ EXPORTS = [
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
     "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_set_light_retargeting", "rs_restir_get_light_retargeting", "rs_restir_download_light_samples", "rs_debug_restir_retarget", "rs_debug_restir_retarget_launched", "rs_debug_restir_surface_wo", "rs_scene_light_moves", "rs_restir_set_shadow_revalidation", "rs_restir_get_shadow_revalidation", "rs_scene_geometry_edits", "rs_scene_dirty_boxes", "rs_debug_restir_revalidate", "rs_debug_restir_revalidate_launched", "rs_debug_plan_dirty_box", "rs_debug_plan_revalidation", "rs_debug_segment_in_boxes", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
-    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_restir_set_primary_leaf_lists", "rs_debug_set_primary_leaf_list_cap", "rs_debug_primary_leaf_list_info", "rs_debug_primary_leaf_list_missing", "rs_debug_plan_primary_leaf_list", "rs_debug_plan_primary_cut", "rs_debug_plan_primary_cut_slot", "rs_restir_set_shadow_regroup", "rs_debug_plan_shadow_regroup", "rs_debug_shadow_pass", "rs_debug_plan_stream_choice", "rs_debug_plan_stream_switch", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
+    "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_restir_set_primary_leaf_lists", "rs_debug_set_primary_leaf_list_cap", "rs_debug_primary_leaf_list_info", "rs_debug_primary_leaf_list_missing", "rs_debug_plan_primary_leaf_list", "rs_debug_plan_primary_cut", "rs_debug_plan_primary_cut_slot", "rs_restir_set_shadow_regroup", "rs_debug_plan_shadow_regroup", "rs_debug_shadow_pass", "rs_debug_plan_stream_choice", "rs_debug_plan_stream_switch", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_surface_ops", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
     "rs_path_trace", "rs_path_trace_indirect", "rs_restir_indirect", "rs_restir_download_indirect",
     "rs_svgf_create", "rs_svgf_destroy", "rs_svgf_filter", "rs_svgf_next_frame", "rs_svgf_get_view",
     "rs_copy_image_to_pbo", "rs_copy_image2_to_pbo", "rs_copy_imagef_to_pbo", "rs_copy_imagei_to_pbo", "rs_eaw_create", "rs_eaw_destroy", "rs_eaw_set_params", "rs_eaw_get_params", "rs_eaw_set_tiled", "rs_eaw_set_fused", "rs_svgf_set_params", "rs_svgf_get_params", "rs_svgf_set_tiled", "rs_svgf_set_fused", "rs_eaw_filter", "rs_eaw_positions_rows", "rs_eaw_level_rows", "rs_modulate_albedo",
@@ -337,6 +337,7 @@ def lib():
     L.rs_debug_div_sigma_mismatches.argtypes = [C.c_float, C.POINTER(C.c_ulonglong)]
     L.rs_debug_rng_step_mismatches.argtypes = [C.POINTER(C.c_ulonglong * 2)]
     L.rs_debug_rng_step_host_mismatches.argtypes = [C.c_uint, C.c_uint, C.POINTER(C.c_ulonglong * 2)]
+    L.rs_debug_surface_ops.argtypes = [ci, ci, vp, vp, ci, ci, vp]
     L.rs_scene_set_sample_sequence.argtypes = [vp, vp, ci, ci]
     L.rs_set_stream_plan.argtypes = [ci, ci, ci]
     L.rs_set_denoise_stream.argtypes = [ci]
@@ -733,6 +734,24 @@ def grid_box(lo, hi, base, scale, margin):
     fits = C.c_int(-1)
     check(lib().rs_debug_grid_box(_p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), float(margin), _p(out), C.byref(fits)))
     return (out if fits.value else None), out
+
+
+SURFACE_OPS = {"linear_sample": (0, 2, 3), "procedural_texture": (1, 2, 3), "to_sphere": (2, 2, 3), "to_plane": (3, 3, 2), "local_to_world": (4, 6, 3)}
+
+
+def surface_op(name, rows, texture=None):
+    """rs_debug_surface_ops (test hook): the device's rs_surface.h function `name` on every row of `rows` ((n, 2): (u, v); to_plane
+    (n, 3): a direction; local_to_world (n, 6): normal, vector); texture: the (H, W, 3) float32 map linear_sample reads."""
+    op, win, wout = SURFACE_OPS[name]
+    a = np.ascontiguousarray(rows, np.float32).reshape(-1, win)
+    out = np.zeros((len(a), wout), np.float32)
+    if texture is None:
+        check(lib().rs_debug_surface_ops(op, len(a), _p(a), _p(out), 0, 0, None))
+    else:
+        t = np.ascontiguousarray(texture, np.float32)
+        assert t.ndim == 3 and t.shape[2] == 3, "textures are (H, W, 3) float32"
+        check(lib().rs_debug_surface_ops(op, len(a), _p(a), _p(out), t.shape[1], t.shape[0], _p(t)))
+    return out
 
 
 # rs_debug_scene_table: name -> (RS_TABLE_*, record dtype)

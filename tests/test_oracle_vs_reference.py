@@ -130,6 +130,42 @@ def test_texture_and_environment_helpers(ref):
     ref.same((ob.local_to_world(n, v),), lambda: (R.ref_local_to_world(len(n), n.reshape(-1), v.reshape(-1), b.reshape(-1)), b)[1:])
 
 
+def test_texture_and_environment_helpers_at_their_edges(ref):
+    """The same four helpers on the edge lists of tests/surface_cases.py, which tests/test_gpu_surface_ops.py holds the device to: maps of
+    1 x 1, 1 x 7, 7 x 1, 2 x 2 and 3 x 8192 texels, coordinates at exact texel borders and centres with the float on either side, at
+    fract = 0 and fract = 1, at 2^23 and 1e30; texel centres of small environment maps; poles, seam, zero vector, subnormal components and
+    1e30 in toPlane; |n.y| around 0.9999f in localToWorld.  Only the FINITE rows: compiled for x86 the reference converts a NaN coordinate
+    to INT_MIN and indexes the map with it, while f2i's NaN -> 0 is the device's conversion, which the oracle and the library both
+    restate and tests/test_gpu_surface_ops.py compares.  (proceduralTexture stays unpinned: DESIGN.md section 2.)"""
+    from tests import surface_cases as sc
+    for shape in sc.TEXTURE_SHAPES:
+        if shape == (37, 53):
+            continue                                     # (the map of the test above)
+        tex = sc.texture(shape)
+        uv = sc.finite_rows(sc.linear_sample_rows(shape, random_rows=20000))
+        assert len(uv) > 20000 + 4 * sum(shape)
+        b = np.zeros((len(uv), 3), np.float32)
+        ref.same((ob.linear_sample(tex, uv),), lambda: (R.ref_linear_sample(shape[1], shape[0], tex.reshape(-1), len(uv), uv.reshape(-1), b.reshape(-1)), b)[1:])
+    u2 = sc.finite_rows(sc.to_sphere_rows(random_rows=0))
+    b = np.zeros((len(u2), 3), np.float32)
+    ref.same((ob.to_sphere(u2),), lambda: (R.ref_to_sphere(len(u2), u2.reshape(-1), b.reshape(-1)), b)[1:])
+    d = sc.finite_rows(sc.to_plane_rows(random_rows=0))
+    assert len(d) == 4 ** 3 + 9 ** 3 + 3 ** 3
+    b = np.zeros((len(d), 2), np.float32)
+    ref.same((ob.to_plane(d),), lambda: (R.ref_to_plane(len(d), d.reshape(-1), b.reshape(-1)), b)[1:])
+    nv = sc.finite_rows(sc.local_to_world_rows(random_rows=0))
+    n, v = np.ascontiguousarray(nv[:, :3]), np.ascontiguousarray(nv[:, 3:])
+    b = np.zeros((len(n), 3), np.float32)
+    ours = ob.local_to_world(n, v)
+    theirs = lambda: (R.ref_local_to_world(len(n), n.reshape(-1), v.reshape(-1), b.reshape(-1)), b)[1:]
+    # normalize(0) is NaN on both sides (a zero vector, a zero normal): of the unit's own sign and payload, so those rows are compared as NaN rows
+    gone = np.isnan(ours).any(axis=1)
+    assert 0 < gone.sum() < len(n) // 2               # (3 of the 9 vectors have length 0 in float, and so have 5 of the 32 normals or their tangents)
+    if ref.live:
+        assert np.array_equal(np.isnan(theirs()[0]).any(axis=1), gone)
+    ref.same((ours[~gone],), lambda: (theirs()[0][~gone],))
+
+
 def test_material_sample_and_pdf(ref):
     """Material::sample / pdf against the reference's material.h on 3e5 random inputs of every type."""
     rng = np.random.default_rng(3)
