@@ -965,7 +965,7 @@ int  rs_debug_restir_retarget_launched(rs_restir* r, int* launched);
  * when an edit of that interval has left the ring or the scene changed, always.  A walked segment counts as one ray in
  * rs_restir_ray_count / _total.  A candidate found occluded is merged as if its slot held W = 0: its M is added and it is never selected
  * (the reference's own convention for a blocked shadow ray).  The history buffers are not written (with a moving camera two pixels read
- * one slot), published copies of pixels that shade nothing this frame and ReSTIR-GI's reservoirs are not touched.
+ * one slot), published copies of pixels that shade nothing this frame and ReSTIR-GI's reservoirs are not touched (those are rs_restir_set_indirect_revalidation's, below).
  * A frame without an edit since the previous one launches exactly the kernels it launches with the switch off.  Stream-ordered, no host
  * wait; the boxes are chosen on the host when the frame is enqueued.  Switching on takes the edits made so far as seen; a failed
  * allocation leaves it off with nothing changed.  Memory: 4 B/px from the first switch-on.  Row bands and the strip driver's ranks
@@ -993,6 +993,41 @@ int  rs_debug_plan_revalidation(int numEdits, unsigned long long firstEdit, cons
 /* n segments { a xyz, b xyz } against m <= RS_DIRTY_BOXES_KEPT boxes { lo xyz, hi xyz }, or against "everything": flags[i] = 1 where the
  * segment is walked -- the function the kernel evaluates per lane. */
 int  rs_debug_segment_in_boxes(int n, const float* segments6, int m, const float* boxes6, int everything, unsigned char* flags);
+/* Indirect revalidation: ReSTIR-GI's temporal reuse drops the history samples that a geometry edit made stale.  A
+ * Reservoir<IndirectLiSample> holds a visible point xv, a sample point xs and the radiance Lo that once arrived from xs; after a door
+ * closes or a prop is carried away a slot may keep an xs that hangs in the air or lies behind the door, and with M clamped at 20 it keeps
+ * winning merges for tens of frames.  Off by default; independent of light tracking, retargeting and shadow revalidation.
+ * When the pass runs: an rs_restir_indirect call runs one extra pass before its path kernel when the call merges temporally (reuse & 1,
+ * not the first frame, reservoirs not allocated by this very call) and the scene's count of accepted geometry edits differs from what this
+ * rs_restir saw at its previous rs_restir_indirect call, or the scene is another one (the choice shadow revalidation makes, from the same
+ * ring of RS_DIRTY_BOXES_KEPT boxes).  The previous call's scene and count are noted on every accepted rs_restir_indirect call, with the
+ * switch on or off, apart from what rs_restir_direct notes.
+ * The pass has one lane per slot j of the width x height history buffer the call is about to merge from; the verdict depends on the slot
+ * alone -- both ends of the segment are stored in it -- so two pixels that read one slot cannot disagree, and the history is edited in place.
+ * A slot is examined iff its weight is neither NaN nor infinite, weight > 0, and xv == xs does not hold on all three components (IEEE ==).
+ * When an edit of the interval has left the ring or the scene is another one ("everything"), every examined slot is stale and nothing
+ * walks.  Otherwise, in this order: the slot is stale iff xs lies in one of the frame's dirty boxes (closed: lo <= xs <= hi on every axis;
+ * a NaN coordinate never lies in one); else its segment xv -> xs is walked iff its bounding box overlaps a dirty box (the test of
+ * rs_debug_segment_in_boxes); a walked segment is the reference's testOcclusion(xv, xs) on the current geometry and counts as one ray
+ * in the `rays` the call returns.  A stale slot and an occluded walker are dropped: numSamples = 0 and weight = 0, the sample fields stay.
+ * The path kernel then merges an empty candidate, draws its random number and never selects it, exactly as for a neighbour that fails
+ * the reference's neighbour test.  Dropped, not kept with W = 0 and its M: an occluded GI sample is not a sample of zero radiance, and
+ * its M would darken the pixel for 20 frames.
+ * A call without an accepted geometry edit since the previous rs_restir_indirect call launches exactly what it launches with the switch
+ * off and leaves every buffer bit for bit the same.  Stream-ordered, no host wait but the one `rays` asks for; a failed allocation leaves
+ * it off with nothing changed.  Memory: 16 KB of counters from the first switch-on, no per-pixel plane.
+ * Deliberately left as it is: emission, material and texture edits dirty no box, so a stale Lo stays stale; and there is no spatial side
+ * -- ReSTIR-GI has none here. */
+int  rs_restir_set_indirect_revalidation(rs_restir* r, int enable);
+int  rs_restir_get_indirect_revalidation(const rs_restir* r, int* enabled);
+/* Test hooks.  What the pass did in the last rs_restir_indirect call: out[0] slots examined, out[1] found stale, out[2] segments walked,
+ * out[3] walkers found occluded; all 0 when the call launched no such pass.  Waits for the library stream. */
+int  rs_debug_restir_indirect_revalidate(rs_restir* r, unsigned long long out[4]);
+/* ... and whether that call launched the pass at all: 1 or 0.  Host only. */
+int  rs_debug_restir_indirect_revalidate_launched(rs_restir* r, int* launched);
+/* Host only (restir_amd/csrc/rs_indirect_revalidate.h).  n reservoirs against m <= RS_DIRTY_BOXES_KEPT boxes { lo xyz, hi xyz }, or
+ * against "everything": classes[i] = 0 not examined, 1 stale, 2 walk, 3 examined and kept -- the function the kernel evaluates per lane. */
+int  rs_debug_indirect_candidate_classes(int n, const rs_indirect_reservoir* reservoirs, int m, const float* boxes6, int everything, unsigned char* classes);
 /* BVH walks (intersect + testOcclusion calls) performed by the last rs_restir_direct / phase_a,
  * for the Mrays/s metric. Synchronises. */
 int  rs_restir_ray_count(rs_restir* r, unsigned long long* rays);
@@ -1160,7 +1195,9 @@ int  rs_path_trace(const rs_scene* scene, const rs_camera* cam, float* devDirect
 int  rs_path_trace_indirect(const rs_scene* scene, const rs_camera* cam, float* devIndirectIllum,
                             int iter, int looper, int maxDepth, unsigned long long* rays);
 /* ReSTIRIndirect(devIndirectIllum, iter, gBuffer) (src/restir.cu:233-416,448-476): one path per pixel into a
- * Reservoir<IndirectLiSample>, temporal reuse (reuse bit 0), clamp<20>; shares the first-frame flag with rs_restir_direct. */
+ * Reservoir<IndirectLiSample>, temporal reuse (reuse bit 0), clamp<20>; shares the first-frame flag with rs_restir_direct.
+ * With rs_restir_set_indirect_revalidation on, a call after a geometry edit first drops the history's stale slots; the segments that
+ * pass walks are part of *rays. */
 int  rs_restir_indirect(rs_restir* r, const rs_scene* scene, const rs_camera* cam, const rs_gbuffer* g, float* devIndirectIllum,
                         int iter, int looper, int reuse, int maxDepth, unsigned long long* rays);
 /* which: 0 = the buffer the next call writes, 1 = the one the last call wrote (devIndLastTemporalReservoir) */

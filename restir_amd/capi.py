@@ -156,7 +156,7 @@ EXPORTS = [
     "rs_gbuffer_create", "rs_gbuffer_destroy", "rs_gbuffer_render", "rs_gbuffer_render_rows", "rs_gbuffer_update",
     "rs_gbuffer_get_view", "rs_gbuffer_set_reuse", "rs_gbuffer_reuse_stats", "rs_gbuffer_invalidate", "rs_gbuffer_rows_bytes", "rs_gbuffer_rows_pack", "rs_gbuffer_rows_unpack", "rs_restir_init", "rs_restir_free", "rs_restir_reset", "rs_restir_direct",
     "rs_restir_phase_a", "rs_restir_phase_b", "rs_restir_end_frame", "rs_restir_launch_choice", "rs_restir_halo_bytes", "rs_restir_halo_pack",
-    "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_set_light_retargeting", "rs_restir_get_light_retargeting", "rs_restir_download_light_samples", "rs_debug_restir_retarget", "rs_debug_restir_retarget_launched", "rs_debug_restir_surface_wo", "rs_scene_light_moves", "rs_restir_set_shadow_revalidation", "rs_restir_get_shadow_revalidation", "rs_scene_geometry_edits", "rs_scene_dirty_boxes", "rs_debug_restir_revalidate", "rs_debug_restir_revalidate_launched", "rs_debug_plan_dirty_box", "rs_debug_plan_revalidation", "rs_debug_segment_in_boxes", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
+    "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_set_light_retargeting", "rs_restir_get_light_retargeting", "rs_restir_download_light_samples", "rs_debug_restir_retarget", "rs_debug_restir_retarget_launched", "rs_debug_restir_surface_wo", "rs_scene_light_moves", "rs_restir_set_shadow_revalidation", "rs_restir_get_shadow_revalidation", "rs_scene_geometry_edits", "rs_scene_dirty_boxes", "rs_debug_restir_revalidate", "rs_debug_restir_revalidate_launched", "rs_debug_plan_dirty_box", "rs_debug_plan_revalidation", "rs_debug_segment_in_boxes", "rs_restir_set_indirect_revalidation", "rs_restir_get_indirect_revalidation", "rs_debug_restir_indirect_revalidate", "rs_debug_restir_indirect_revalidate_launched", "rs_debug_indirect_candidate_classes", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
     "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_restir_set_primary_leaf_lists", "rs_debug_set_primary_leaf_list_cap", "rs_debug_primary_leaf_list_info", "rs_debug_primary_leaf_list_missing", "rs_debug_plan_primary_leaf_list", "rs_debug_plan_primary_cut", "rs_debug_plan_primary_cut_slot", "rs_restir_set_shadow_regroup", "rs_debug_plan_shadow_regroup", "rs_debug_shadow_pass", "rs_debug_plan_stream_choice", "rs_debug_plan_stream_switch", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_surface_ops", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
     "rs_path_trace", "rs_path_trace_indirect", "rs_restir_indirect", "rs_restir_download_indirect",
     "rs_svgf_create", "rs_svgf_destroy", "rs_svgf_filter", "rs_svgf_next_frame", "rs_svgf_get_view",
@@ -259,6 +259,12 @@ def lib():
         L.rs_debug_plan_dirty_box.argtypes = [ci, vp, ci, vp, vp, vp, vp]
         L.rs_debug_plan_revalidation.argtypes = [ci, ull, vp, ull, ull, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
         L.rs_debug_segment_in_boxes.argtypes = [ci, vp, ci, vp, ci, vp]
+    if hasattr(L, "rs_restir_set_indirect_revalidation"):   # (an A/B build from before indirect revalidation, RESTIR_HIP_LIB: tools/bench_indirect_revalidate.py)
+        L.rs_restir_set_indirect_revalidation.argtypes = [vp, ci]
+        L.rs_restir_get_indirect_revalidation.argtypes = [vp, C.POINTER(ci)]
+        L.rs_debug_restir_indirect_revalidate.argtypes = [vp, C.POINTER(C.c_ulonglong * 4)]
+        L.rs_debug_restir_indirect_revalidate_launched.argtypes = [vp, C.POINTER(ci)]
+        L.rs_debug_indirect_candidate_classes.argtypes = [ci, vp, ci, vp, ci, vp]
     L.rs_restir_light_rows_bytes.argtypes = [vp, ci]
     L.rs_restir_light_rows_bytes.restype = C.c_size_t
     L.rs_restir_light_rows_pack.argtypes = [vp, ci, ci, ci, vp]
@@ -679,6 +685,17 @@ def segment_in_boxes(segments, boxes, everything=False):
     flags = np.zeros(max(len(seg), 1), np.uint8)
     check(lib().rs_debug_segment_in_boxes(len(seg), _p(seg) if len(seg) else None, len(b), _p(b) if len(b) else None, 1 if everything else 0, _p(flags)))
     return flags[:len(seg)] != 0
+
+
+def indirect_candidate_classes(reservoirs, boxes, everything=False):
+    """rs_debug_indirect_candidate_classes (host only): the class of every reservoir (INDIRECT_RESERVOIR_DTYPE) against the boxes (m <= 8,
+    6: lo, hi) -- 0 not examined, 1 stale, 2 walk, 3 examined and kept."""
+    resv = np.ascontiguousarray(reservoirs, INDIRECT_RESERVOIR_DTYPE).reshape(-1)
+    b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
+    classes = np.zeros(max(len(resv), 1), np.uint8)
+    check(lib().rs_debug_indirect_candidate_classes(len(resv), _p(resv) if len(resv) else None, len(b), _p(b) if len(b) else None, 1 if everything else 0,
+                                                    _p(classes)))
+    return classes[:len(resv)].copy()
 
 
 def plan_stream_choice(priority_range, asked=2, caller_priority=None, times_us=None):
@@ -1558,6 +1575,29 @@ class ReSTIR:
         """rs_debug_restir_revalidate_launched: did the last ended frame launch the revalidation kernel?"""
         on = C.c_int(0)
         check(lib().rs_debug_restir_revalidate_launched(self.handle, C.byref(on)))
+        return bool(on.value)
+
+    def set_indirect_revalidation(self, on=True):
+        """rs_restir_set_indirect_revalidation: after a geometry edit, the ReSTIR-GI history slots whose sample point lies in the edit's
+        box, or whose segment xv -> xs crosses it and is blocked now, are emptied before rs_restir_indirect merges them."""
+        check(lib().rs_restir_set_indirect_revalidation(self.handle, 1 if on else 0))
+
+    def get_indirect_revalidation(self):
+        on = C.c_int(0)
+        check(lib().rs_restir_get_indirect_revalidation(self.handle, C.byref(on)))
+        return bool(on.value)
+
+    def indirect_revalidate_stats(self):
+        """rs_debug_restir_indirect_revalidate: (slots examined, found stale, segments walked, walkers found occluded) of the last
+        rs_restir_indirect call."""
+        out = (C.c_ulonglong * 4)()
+        check(lib().rs_debug_restir_indirect_revalidate(self.handle, C.byref(out)))
+        return tuple(int(x) for x in out)
+
+    def indirect_revalidate_launched(self):
+        """rs_debug_restir_indirect_revalidate_launched: did the last rs_restir_indirect call launch the revalidation kernel?"""
+        on = C.c_int(0)
+        check(lib().rs_debug_restir_indirect_revalidate_launched(self.handle, C.byref(on)))
         return bool(on.value)
 
     def light_rows_bytes(self, rows):

@@ -426,18 +426,24 @@ int rs_restir_indirect(rs_restir* r, const rs_scene* scene, const rs_camera* cam
     if (cam->resolution[0] != r->width || cam->resolution[1] != r->height || g->width != r->width || g->height != r->height)
         return rs_fail(RS_ERR_INVALID_ARGUMENT, "ReSTIRIndirect: size mismatch");
     const size_t n = (size_t)r->width * r->height;
+    bool history = true;                                        // the buffers hold what an earlier call left
     for (int i = 0; i < 2; i++)
         if (!r->indResv[i]) {                                   // devIndTemporalReservoir / devIndLastTemporalReservoir (restir.cu:13-14,491-494)
             RS_TRY(rs_dev_alloc(&r->indResv[i], n));
             RS_HIP(hipMemsetAsync(r->indResv[i], 0, n * sizeof(rs_indirect_reservoir), rs_stream()));
+            history = false;
         }
     RS_TRY(rs_denoise_order(devIndirectIllum));
+    // rs_restir_set_indirect_revalidation: geometry moved since the previous call -- the stale slots of the history leave before the merge
+    RS_TRY(rs_indirect_revalidate_before_path(r, scene, history && !r->firstFrame && (reuse & 1), r->indResv[1], n));
     RS_TRY(launch_path<kModeReSTIR>(scene, cam, nullptr, devIndirectIllum, r->indResv[0], r->indResv[1], gbuf_view(g), looper, iter, maxDepth,
                                     r->firstFrame ? 1 : 0, reuse));
     { rs_indirect_reservoir* t = r->indResv[0]; r->indResv[0] = r->indResv[1]; r->indResv[1] = t; }      // std::swap (:463)
     r->firstFrame = false;                                                                                    // ReSTIRFirstFrame (:465-467)
+    rs_indirect_revalidate_note(r, scene);
     RS_TRY(rs_after_launch("ReSTIR Indirect"));
-    return rs_walk_counters_sum(rays);
+    RS_TRY(rs_walk_counters_sum(rays));
+    return rs_indirect_revalidate_add_rays(r, rays);
 }
 
 int rs_restir_download_indirect(rs_restir* r, int which, rs_indirect_reservoir* host) {

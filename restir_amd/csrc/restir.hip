@@ -975,6 +975,7 @@ int rs_restir_free(rs_restir* r) {
     rs_dev_free(r->indResv[0]); rs_dev_free(r->indResv[1]);
     rs_light_history_free(r->lights);
     rs_revalidate_free(r->reval);
+    rs_indirect_revalidate_free(r->indReval);
     rs_primary_cuts_destroy(r->cuts);
     for (auto& e : r->ev) if (e) (void)hipEventDestroy(e);
     for (auto& pair : r->spatialEv) for (hipEvent_t& e : pair) if (e) (void)hipEventDestroy(e);

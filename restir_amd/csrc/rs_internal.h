@@ -630,6 +630,24 @@ struct rs_shadow_revalidation {
 void rs_revalidate_end_frame(rs_shadow_revalidation& v, int phaseACalls);
 void rs_revalidate_free(rs_shadow_revalidation& v);
 
+// Revalidation of ReSTIR-GI's history of one rs_restir (include/restir_hip.h); indirect_revalidate.hip owns every field.  sceneId / seen:
+// the scene of the previous accepted rs_restir_indirect call and its count of accepted geometry edits then -- kept whether the switch is
+// on or not, and apart from rs_shadow_revalidation's: rs_restir_direct and rs_restir_indirect are separate calls.  No per-pixel plane: the
+// pass edits the history slots themselves.
+struct rs_indirect_revalidation {
+    bool on = false;
+    unsigned long long sceneId = 0, seen = 0;      // sceneId 0: no call yet
+    unsigned long long* dStats = nullptr;  // { examined, stale, walked, occluded } of the last call that launched, each in partial counters: cleared, added to and read in the library stream's order
+    bool launchedLast = false;             // the last rs_restir_indirect call launched k_revalidate_indirect
+};
+// What rs_restir_indirect (gi.hip) asks, in this order: before launch_path, the pass over the n slots of `history` (the buffer k_path is
+// about to read) when the call merges and the plan says so; after an accepted call, the scene and its edits noted; and, once the stream
+// has been waited for, the walked segments of this call's pass added to *rays.
+int  rs_indirect_revalidate_before_path(rs_restir* r, const rs_scene* scene, bool merges, rs_indirect_reservoir* history, size_t n);
+void rs_indirect_revalidate_note(rs_restir* r, const rs_scene* scene);
+int  rs_indirect_revalidate_add_rays(rs_restir* r, unsigned long long* rays);
+void rs_indirect_revalidate_free(rs_indirect_revalidation& v);
+
 struct rs_restir {
     rs_context* ctx = nullptr;
     rs_primary_cuts cuts;
@@ -682,6 +700,7 @@ struct rs_restir {
     rs_light_history lights;         // light tracking and retargeting (light_history.hip)
     bool shadowRegroup = true;       // rs_restir_set_shadow_regroup (RS_SHADOW_REGROUP=0: off from the start); a scene without occNodes keeps the plain kernel
     rs_shadow_revalidation reval;    // rs_restir_set_shadow_revalidation (shadow_revalidate.hip)
+    rs_indirect_revalidation indReval;   // rs_restir_set_indirect_revalidation (indirect_revalidate.hip)
 };
 
 static_assert(rs_context::kAux >= 1 + rs_restir::kChains, "one auxiliary stream for GBuffer::render and one per chain");
