@@ -431,6 +431,67 @@ int  rs_scene_skin_info(const rs_scene* scene, int* numBones, int* numListedPrim
  * RS_ERR_UNSUPPORTED while the library stream is being captured.  (The reference has no moving geometry: there is no reference line to
  * cite.) */
 int  rs_scene_download_skin(const rs_scene* scene, int* primIds, float* restVertices, float* restNormals, int* boneIds, float* weights);
+/* Morph targets (blend shapes): per-corner position and normal deltas on a rest pose, summed by weight -- a face, a muscle, a wrinkle --
+ * alone or, on a skinned mesh, in front of the bones.  The deltas stay on the device; an edit carries weights.  (The reference has no
+ * moving geometry: there is no reference line to cite.)
+ * The caller's table is by target, glTF's sparse form: targetFirst[numTargets + 1] are offsets (0 first, non-decreasing) into
+ * entryCorner[] -- the index of a listed corner, listedIndex * 3 + corner --, deltaPositions[3 per entry] and deltaNormals[3 per entry]
+ * (or NULL: zeros).  The library keeps it by corner, each corner's entries in ascending target id (32 bytes an entry and 4 per corner on
+ * the device), which fixes the order of every corner's sum.
+ * rs_morph_corners is the host function, no GPU call: n corners (3 floats each in and out), the table over those n corners, numTargets
+ * weights.  Per corner, with its entries in ascending target id:
+ *     p = v; q = n;  for each entry whose weight w[target] != 0 (-0 and +0 both skip):  p = p + w * dp,  q = q + w * dn  per component,
+ *     position = p;  normal = normalize(q) if any entry was applied, else n
+ * one multiply and one add per component and entry.  A corner without an applied entry returns its rest bits: all weights 0 is the rest
+ * pose exactly.  Weights and deltas are used as given (negative, above 1, denormal); non-finite results are returned, not refused.
+ * RS_ERR_INVALID_ARGUMENT: numTargets < 0 or above RS_MORPH_MAX_TARGETS, a null array that is needed, offsets that do not start at 0 or
+ * that decrease, a corner index outside [0, n), a (target, corner) pair listed twice. */
+#define RS_MORPH_MAX_TARGETS 256   /* 1 KB of weights */
+int  rs_morph_corners(int numTargets, const int* targetFirst, const int* entryCorner, const float* deltaPositions, const float* deltaNormals,
+                      const float* weights, size_t n, const float* vertsIn, const float* normalsIn, float* vertsOut, float* normalsOut);
+/* rs_scene_define_morph: a morph with a rest pose of its own.  primIds[numListed], restVertices / restNormals are rs_scene_define_skin's
+ * (both NULL: the scene's pose at the call); the table is over the numListed * 3 listed corners.  Everything is copied, to the host and
+ * to the device; the device copies are read by the morph kernel alone and never written afterwards.  The call renders nothing and changes
+ * no geometry.  Weights start at 0.  Calling it again replaces the definition and the weights; numTargets == 0 with numListed == 0 drops
+ * it.  A definition that replaces or drops an earlier one waits for the device.  The scene's morph, parts and a skin may name the same
+ * primitive: the last edit wins.
+ * rs_scene_define_skin_morph: a morph on the corners the skin lists, held by the skin and evaluated BEFORE its bones.  It needs a skin;
+ * rs_scene_define_skin called again, or dropping the skin, drops it as well; numTargets == 0 drops it alone.
+ * Both refuse with RS_ERR_INVALID_ARGUMENT, the definition unchanged: a null scene, numTargets < 0 or above RS_MORPH_MAX_TARGETS, null or
+ * bad offsets, a corner index out of range, a (target, corner) pair listed twice, a delta that is not finite; rs_scene_define_morph also
+ * what rs_scene_define_skin refuses of the listed primitives and the rest arrays, and triangles without a target; rs_scene_define_skin_morph
+ * a scene without a skin.  RS_ERR_UNSUPPORTED while the library stream is being captured into a graph. */
+int  rs_scene_define_morph(rs_scene* scene, int numTargets, int numListed, const int* primIds, const float* restVertices, const float* restNormals,
+                           const int* targetFirst, const int* entryCorner, const float* deltaPositions, const float* deltaNormals);
+int  rs_scene_define_skin_morph(rs_scene* scene, int numTargets, const int* targetFirst, const int* entryCorner, const float* deltaPositions,
+                                const float* deltaNormals);
+/* rs_scene_set_morph_weights: the named targets of the scene's own morph take their new weight (a target named twice takes its last, one
+ * not named keeps its weight), and the call then does exactly what rs_scene_set_geometry(scene, numListed, primIds, v, n) does with v, n =
+ * rs_morph_corners of all weights over the rest arrays: the same refusals with the scene AND THE WEIGHTS unchanged, the same
+ * rs_scene_host_desc and device tables afterwards, lights moved the same way, the same dirty box, the partial or whole refit, retained
+ * G-buffer planes invalidated, the same fences.  Only the source of the records differs: the host stages the weights as whole 112-byte
+ * records, 28 floats each, zero-padded -- ceil(numTargets / 28) of them -- and a kernel writes the ids | vertices | normals the refit
+ * reads from the device's rest arrays and table, with the arithmetic of rs_morph_corners, bit for bit.  The host still morphs the listed
+ * triangles once itself (checks, light areas, rs_scene_host_desc).  Every call evaluates every listed triangle.  Weights must be finite;
+ * count == 0 succeeds and changes nothing.  Additionally refused with RS_ERR_INVALID_ARGUMENT: no morph defined, a target id out of
+ * range, null arrays with count > 0.
+ * rs_scene_set_skin_pose names bones and targets of the skin and its morph and makes ONE edit of them: v, n = rs_skin_corners of the whole
+ * palette over rs_morph_corners of all weights over the rest arrays, evaluated per corner by one kernel.  It stages the numBones bone
+ * records, then the weight records.  Palette and weights become the scene's together, or neither does.  On a skin with a morph
+ * rs_scene_set_bone_transforms is this call with targetCount = 0 (the weights stay); on a skin without one, rs_scene_set_bone_transforms
+ * stages and launches what it always did and this call with targetCount > 0 is refused.  boneCount == 0 with targetCount == 0 changes
+ * nothing.  INTEGRATION.md section 3k has the frame loop; DESIGN.md section 3 the cost. */
+int  rs_scene_set_morph_weights(rs_scene* scene, int count, const int* targetIds, const float* weights);
+int  rs_scene_set_skin_pose(rs_scene* scene, int boneCount, const int* boneIds, const float* matrices16,
+                            int targetCount, const int* targetIds, const float* weights);
+/* Host only.  which: 0 the scene's own morph, 1 the skin's: targets, listed primitives and entries (0, 0, 0: none defined; any pointer
+ * may be NULL).  RS_ERR_INVALID_ARGUMENT: a null scene, which neither 0 nor 1. */
+int  rs_scene_morph_info(const rs_scene* scene, int which, int* numTargets, int* numListedPrims, int* numEntries);
+/* Test hook.  Waits as rs_synchronize does, then copies the DEVICE copies out: cornerFirst[numListedPrims * 3 + 1], the numEntries 32-byte
+ * entry records { int target; float dp[3]; float dn[3]; int pad; } and, for which = 0, the morph's primitive ids and rest pose (for
+ * which = 1 those three must be NULL: rs_scene_download_skin has the skin's).  Any array may be NULL.  RS_ERR_INVALID_ARGUMENT: a null
+ * scene, no such morph defined; RS_ERR_UNSUPPORTED while the library stream is being captured. */
+int  rs_scene_download_morph(const rs_scene* scene, int which, int* primIds, float* restVertices, float* restNormals, int* cornerFirst, void* entries);
 /* What a geometry edit of any of the three kinds decides on the host before it touches the device, as functions of plain arrays and
  * integers (restir_amd/csrc/rs_geometry_plan.h).  The view is what they read of a scene; flags are 0 / 1. */
 typedef struct rs_geometry_edit_view {

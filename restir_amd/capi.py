@@ -166,6 +166,7 @@ EXPORTS = [
     "rs_bake_matrix", "rs_scene_file_objects", "rs_scene_define_parts", "rs_scene_set_part_transforms", "rs_scene_parts_info", "rs_scene_download_part_rest", "rs_debug_scene_staged_bytes", "rs_debug_plan_geometry_edit",
     "rs_scene_set_partial_refit", "rs_scene_get_partial_refit", "rs_scene_refit_counts", "rs_debug_scene_refit_dirty", "rs_debug_plan_refit",
     "rs_skin_corners", "rs_scene_define_skin", "rs_scene_set_bone_transforms", "rs_scene_skin_info", "rs_scene_download_skin",
+    "rs_morph_corners", "rs_scene_define_morph", "rs_scene_define_skin_morph", "rs_scene_set_morph_weights", "rs_scene_set_skin_pose", "rs_scene_morph_info", "rs_scene_download_morph",
 ]
 
 _lib = None
@@ -223,6 +224,14 @@ def lib():
         L.rs_scene_set_bone_transforms.argtypes = [vp, ci, vp, vp]
         L.rs_scene_skin_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
         L.rs_scene_download_skin.argtypes = [vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "rs_morph_corners"):                    # (an A/B build from before morph targets, RESTIR_HIP_LIB)
+        L.rs_morph_corners.argtypes = [ci, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp]
+        L.rs_scene_define_morph.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+        L.rs_scene_define_skin_morph.argtypes = [vp, ci, vp, vp, vp, vp]
+        L.rs_scene_set_morph_weights.argtypes = [vp, ci, vp, vp]
+        L.rs_scene_set_skin_pose.argtypes = [vp, ci, vp, vp, ci, vp, vp]
+        L.rs_scene_morph_info.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+        L.rs_scene_download_morph.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.rs_scene_host_desc.argtypes = [vp, C.POINTER(SceneDesc)]
     L.rs_scene_destroy.argtypes = [vp]
     L.rs_scene_set_emission.argtypes = [vp, ci, vp, vp]
@@ -866,6 +875,35 @@ def skin_corners(matrices, vertices, normals, bone_ids, weights):
     return vo, no
 
 
+# rs::MorphEntry, the 32-byte record of a morph's by-corner table (rs_scene_download_morph)
+MORPH_ENTRY = np.dtype([("target", np.int32), ("dp", np.float32, 3), ("dn", np.float32, 3), ("pad", np.int32)])
+
+
+def _morph_table(target_first, entry_corner, delta_positions, delta_normals):
+    """The by-target table as contiguous arrays: (numTargets, offsets, corners, position deltas, normal deltas or None)."""
+    first = np.ascontiguousarray(target_first, np.int32).reshape(-1)
+    ec = np.ascontiguousarray(entry_corner, np.int32).reshape(-1)
+    dp = np.ascontiguousarray(delta_positions, np.float32).reshape(-1, 3)
+    dn = None if delta_normals is None else np.ascontiguousarray(delta_normals, np.float32).reshape(-1, 3)
+    if first.size < 1 or len(dp) != ec.size or (dn is not None and len(dn) != ec.size):
+        raise ValueError("a morph table: numTargets + 1 offsets, and one corner, position delta and normal delta per entry")
+    return first.size - 1, first, ec, dp, dn
+
+
+def morph_corners(target_first, entry_corner, delta_positions, delta_normals, weights, vertices, normals):
+    """rs_morph_corners (host only): (k, 3) corners with the weighted deltas of a by-target table over those k corners added, in ascending
+    target order; delta_normals may be None (zeros); weights are used as given and a weight of 0 skips its entries."""
+    t, first, ec, dp, dn = _morph_table(target_first, entry_corner, delta_positions, delta_normals)
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if len(v) != len(n) or w.size != t:
+        raise ValueError("morph_corners: one normal per corner and one weight per target")
+    vo, no = np.zeros_like(v), np.zeros_like(n)
+    check(lib().rs_morph_corners(t, _p(first), _p(ec), _p(dp), None if dn is None else _p(dn), _p(w), len(v), _p(v), _p(n), _p(vo), _p(no)))
+    return vo, no
+
+
 class SceneFile:
     """Scene::Scene(filename) (src/scene.cpp:96-131): the parsed scene as flat host arrays (copies)."""
 
@@ -1118,6 +1156,62 @@ class Scene:
         b, w = np.zeros((n, 3, 4), np.int32), np.zeros((n, 3, 4), np.float32)
         check(lib().rs_scene_download_skin(self.handle, _p(ids), _p(v), _p(nn), _p(b), _p(w)))
         return ids, v, nn, b, w
+
+    def define_morph(self, prim_ids, target_first, entry_corner, delta_positions, delta_normals=None, rest_vertices=None, rest_normals=None):
+        """rs_scene_define_morph: morph targets over the corners of the listed primitives (entry_corner: listed index * 3 + corner), as a
+        by-target table; the rest pose is (listed, 3, 3) vertices and normals, or None: the scene's current pose.  No target and no
+        primitive drops the definition."""
+        ids = np.ascontiguousarray(prim_ids, np.int32).reshape(-1)
+        t, first, ec, dp, dn = _morph_table(target_first, entry_corner, delta_positions, delta_normals)
+        v = None if rest_vertices is None else np.ascontiguousarray(rest_vertices, np.float32).reshape(-1, 9)
+        n = None if rest_normals is None else np.ascontiguousarray(rest_normals, np.float32).reshape(-1, 9)
+        for a in (v, n):
+            if a is not None and a.shape[0] != ids.size:
+                raise ValueError("define_morph: three rest vertices and three rest normals per listed primitive")
+        check(lib().rs_scene_define_morph(self.handle, t, int(ids.size), _p(ids), None if v is None else _p(v), None if n is None else _p(n),
+                                          _p(first), _p(ec), _p(dp), None if dn is None else _p(dn)))
+
+    def define_skin_morph(self, target_first, entry_corner, delta_positions, delta_normals=None):
+        """rs_scene_define_skin_morph: morph targets over the corners the skin lists, evaluated before its bones; no target drops it."""
+        t, first, ec, dp, dn = _morph_table(target_first, entry_corner, delta_positions, delta_normals)
+        check(lib().rs_scene_define_skin_morph(self.handle, t, _p(first), _p(ec), _p(dp), None if dn is None else _p(dn)))
+
+    def set_morph_weights(self, target_ids, weights):
+        """rs_scene_set_morph_weights: one weight per entry of `target_ids`; does what set_geometry does with the morph's rest pose and
+        all its weighted deltas, the sum taken on the device (only the weights cross the bus)."""
+        ids = np.ascontiguousarray(target_ids, np.int32).reshape(-1)
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        if w.size != ids.size:
+            raise ValueError("set_morph_weights: one weight per target id")
+        check(lib().rs_scene_set_morph_weights(self.handle, int(ids.size), _p(ids), _p(w)))
+
+    def set_skin_pose(self, bone_ids, matrices, target_ids, weights):
+        """rs_scene_set_skin_pose: bones and morph targets of the skin in one edit -- the targets first, then the bones, in one kernel."""
+        b = np.ascontiguousarray(bone_ids, np.int32).reshape(-1)
+        m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 16)
+        t = np.ascontiguousarray(target_ids, np.int32).reshape(-1)
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        if m.shape[0] != b.size or w.size != t.size:
+            raise ValueError("set_skin_pose: one matrix per bone id and one weight per target id")
+        check(lib().rs_scene_set_skin_pose(self.handle, int(b.size), _p(b), _p(m), int(t.size), _p(t), _p(w)))
+
+    def morph_info(self, which=0):
+        """rs_scene_morph_info: (targets, listed primitives, entries) of the scene's morph (which = 0) or the skin's (1); zeros: none."""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(lib().rs_scene_morph_info(self.handle, int(which), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def download_morph(self, which=0):
+        """rs_scene_download_morph (test hook): the device copies of (cornerFirst, entries as MORPH_ENTRY records) and, for the scene's
+        own morph, (primitive ids, rest vertices, rest normals) after them."""
+        _, listed, entries = self.morph_info(which)
+        first, recs = np.zeros(listed * 3 + 1, np.int32), np.zeros(entries, MORPH_ENTRY)
+        if which:
+            check(lib().rs_scene_download_morph(self.handle, 1, None, None, None, _p(first), _p(recs)))
+            return first, recs
+        ids, v, nn = np.zeros(listed, np.int32), np.zeros((listed, 3, 3), np.float32), np.zeros((listed, 3, 3), np.float32)
+        check(lib().rs_scene_download_morph(self.handle, 0, _p(ids), _p(v), _p(nn), _p(first), _p(recs)))
+        return first, recs, ids, v, nn
 
     def set_partial_refit(self, on=True, max_triangles=-1):
         """rs_scene_set_partial_refit: an edit of at most max_triangles triangles (< 0: the library's default) recomputes only the boxes

@@ -5,6 +5,8 @@
 // rs_scene_set_part_transforms (scene_deform.hip k_bake_parts) all evaluate this function and nothing else, so with -ffp-contract=off and
 // the correctly rounded divide and square root of rs_math.h they return the same bits.  skin_corner blends four such corners by weight
 // out of the same pieces: rs_skin_corners and the kernel behind rs_scene_set_bone_transforms (scene_deform.hip k_skin) evaluate it alone.
+// morph_corner adds weighted per-corner deltas to a rest corner, before the bones where there is a skin: rs_morph_corners and the kernels
+// behind rs_scene_set_morph_weights and rs_scene_set_skin_pose (k_morph, k_morph_skin) evaluate it alone.
 // The inverse is a host matter: the normal matrix is computed once per matrix (scene_file.cpp bake_normal_matrix) and travels next to it.
 #pragma once
 
@@ -69,6 +71,45 @@ RS_HD BakedCorner skin_corner(const BoneRec* bones, const int* b, const float* w
     BakedCorner o;
     o.position = skin_blend(w, bake_position(b0->m, v), bake_position(b1->m, v), bake_position(b2->m, v), bake_position(b3->m, v));
     o.normal = normalize(skin_blend(w, bake_direction(b0->nm, n), bake_direction(b1->nm, n), bake_direction(b2->nm, n), bake_direction(b3->nm, n)));
+    return o;
+}
+
+// One entry of a morph's by-corner table (rs_scene_define_morph, rs_scene_define_skin_morph; rs_deform.h): 32 bytes in two 16-byte halves,
+// the target id with the position delta, then the normal delta.  The halves are types of their own so that a reader takes each with one
+// 16-byte load, and the second only where it needs it.
+struct __attribute__((aligned(16))) MorphHead { int target; float dp[3]; };
+struct __attribute__((aligned(16))) MorphTail { float dn[3]; int pad; };
+struct __attribute__((aligned(16))) MorphEntry { MorphHead head; MorphTail tail; };
+static_assert(sizeof(MorphEntry) == 32 && sizeof(MorphHead) == 16, "a morph entry is two 16-byte loads");
+
+// Weights cross the bus as whole 112-byte records, zero-padded: rs_plan_edit_records lays them out as it lays out part records
+constexpr int kMorphWeightsPerRec = (int)(sizeof(BoneRec) / sizeof(float));
+static_assert(kMorphWeightsPerRec == 28, "28 weights a record");
+
+// Morph targets of one corner (rs_morph_corners, rs_scene_set_morph_weights, rs_scene_set_skin_pose; scene_deform.hip k_morph, k_morph_skin):
+// the corner's entries [first, last) of `entries`, in ascending target id, against the weights w[target]:
+//     p = v; q = n
+//     for each entry e whose weight w[e.target] != 0 (-0 and +0 both skip):   p = p + w * e.dp,  q = q + w * e.dn     per component
+//     position = p;  normal = normalize(q) if any entry was applied, else n
+// one multiply and one add per component and entry, in the entries' order.  A corner without an applied entry returns its rest bits, so
+// all weights 0 is the rest pose exactly; an entry of weight 0 is read as far as its first half.  Under a skin the result is what
+// skin_corner takes in the rest corner's place.  (The reference has no moving geometry: there is no reference line to cite.)
+RS_HD BakedCorner morph_corner(const MorphEntry* entries, int first, int last, const float* w, f3 v, f3 n) {
+    f3 p = v, q = n;
+    bool applied = false;
+    for (int e = first; e < last; e++) {
+        const MorphHead h = entries[e].head;
+        const float wt = w[h.target];
+        if (wt != 0.f) {
+            const MorphTail t = entries[e].tail;
+            p = mk3(p.x + wt * h.dp[0], p.y + wt * h.dp[1], p.z + wt * h.dp[2]);
+            q = mk3(q.x + wt * t.dn[0], q.y + wt * t.dn[1], q.z + wt * t.dn[2]);
+            applied = true;
+        }
+    }
+    BakedCorner o;
+    o.position = p;
+    o.normal = applied ? normalize(q) : n;
     return o;
 }
 

@@ -297,6 +297,8 @@ struct rs_scene {
     // Skinned triangles, their rest pose and the bone palette (rs_scene_define_skin; rs_deform.h); null: none defined.  Last, so that every
     // field a frame reads lies where it lay before there were skins.
     struct rs_skin* skin = nullptr;
+    // Morph targets with a rest pose of their own (rs_scene_define_morph; rs_deform.h); null: none defined.  (A skin's morph is the skin's.)
+    struct rs_morph* morph = nullptr;
 };
 
 // ---- G-buffer (src/gbuffer.h:41-58) ------------------------------------------------------------
@@ -756,6 +758,7 @@ void rs_refit_free(rs_scene* s);                        // rs_scene_destroy: wha
 // scene_deform.hip (rs_deform.h); null: nothing to do
 void rs_parts_free(struct rs_parts* parts);             // rs_scene_destroy, rs_scene_define_parts
 void rs_skin_free(struct rs_skin* skin);                // rs_scene_destroy, rs_scene_define_skin
+void rs_morph_free(struct rs_morph* morph);             // rs_scene_destroy, rs_scene_define_morph
 // scene.hip, for scene_edits.hip as well
 // map ids of n materials against a table of numTextures; the two refusal texts carry the entry point's name
 int check_materials(int n, const rs_material* m, int numTextures, bool* anyMap,

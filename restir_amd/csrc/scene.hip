@@ -311,6 +311,7 @@ extern "C" int rs_scene_destroy(rs_scene* s) {
     rs_refit_free(s);
     rs_parts_free(s->parts);
     rs_skin_free(s->skin);
+    rs_morph_free(s->morph);
     motion_free(s);
     delete s;
     return 0;

@@ -1,5 +1,5 @@
-// scene_deform.hip -- rigid parts and skinned meshes (include/restir_hip.h; rs_deform.h), all of them: the rest pose,
-// the kernels that write an edit's records from it (k_bake_parts, k_skin), the definitions, the edits, the queries.  An edit is
+// scene_deform.hip -- rigid parts, skinned meshes and morph targets (include/restir_hip.h; rs_deform.h), all of them: the rest pose,
+// the kernels that write an edit's records from it (k_bake_parts, k_skin, k_morph, k_morph_skin), the definitions, the edits, the queries.  An edit is
 // rs_set_geometry's (scene_edits.hip) with an rs_record_source (rs_refit.h): the entry point stages its 112-byte records, names the kernel that
 // expands them in front of the refit (scene_refit.hip) and hands over the host's own evaluation of the same triangles, by rs_bake.h like the kernel's.
 #include <algorithm>
@@ -75,6 +75,63 @@ __global__ void __launch_bounds__(256) k_skin(int numBones, const BoneRec* __res
     if (c == tri * 3) ids[tri] = skinPrimIds[tri];
 }
 
+// 16-byte pieces of a staged block into LDS, 16 bytes a lane and step; the caller's barrier follows
+__device__ __forceinline__ void stage16(const void* from, void* to, int n16) {
+    const uint4* src = reinterpret_cast<const uint4*>(from);
+    uint4* dst = reinterpret_cast<uint4*>(to);
+    for (int i = (int)threadIdx.x; i < n16; i += 256) dst[i] = src[i];
+}
+
+// rs_scene_set_morph_weights: the same staged edit, written from the morph's rest pose, its by-corner table and the weights.  One lane per
+// output corner.  The block first copies the weights -- staged as whole 112-byte records, zero-padded, so that ceil(numTargets / 4) 16-byte
+// pieces are there to read; at most 1 KB -- into LDS and meets at one barrier, which lanes past numCorners reach too: nothing returns
+// before it.  A lane then reads its two offsets and its 12 + 12 bytes of rest corner and walks its entries with rs_bake.h's morph_corner
+// -- the bits are rs_morph_corners' --: 16 bytes of target id and position delta, the weight from LDS, and the other 16 bytes only where
+// the weight is not 0.  It writes 12 + 12 bytes; the lane of corner 0 also writes the primitive id.  Entry counts differ from lane to lane:
+// a wave walks as long as its longest corner (accepted: DESIGN.md section 3).  The target ids were checked against numTargets by the
+// definition and the device copy is never written again, so no read leaves the staged weights.  No hand-off between lanes.
+__global__ void __launch_bounds__(256) k_morph(int numTargets, const float* __restrict__ staged, const int* __restrict__ morphPrimIds,
+                                               const float* __restrict__ restVertices, const float* __restrict__ restNormals,
+                                               const int* __restrict__ cornerFirst, const MorphEntry* __restrict__ entries,
+                                               size_t numCorners, int* __restrict__ ids, float* __restrict__ vertices, float* __restrict__ normals) {
+    __shared__ __attribute__((aligned(16))) float w[RS_MORPH_MAX_TARGETS];
+    stage16(staged, w, (numTargets + 3) >> 2);
+    __syncthreads();
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= numCorners) return;
+    const BakedCorner o = morph_corner(entries, cornerFirst[c], cornerFirst[c + 1], w, ld3(restVertices + c * 3), ld3(restNormals + c * 3));
+    st3(vertices + c * 3, o.position);
+    st3(normals + c * 3, o.normal);
+    const size_t tri = c / 3;
+    if (c == tri * 3) ids[tri] = morphPrimIds[tri];
+}
+
+// rs_scene_set_skin_pose on a skin that has a morph: k_skin with morph_corner in front -- skin_corner(morph_corner(rest)) per corner, and
+// nothing else.  The staged block is the numBones bone records, then the weight records; both go to LDS (28 KB + 1 KB) behind the one barrier.
+__global__ void __launch_bounds__(256) k_morph_skin(int numBones, int numTargets, const BoneRec* __restrict__ bones, const int* __restrict__ skinPrimIds,
+                                                    const float* __restrict__ restVertices, const float* __restrict__ restNormals,
+                                                    const int4* __restrict__ boneIds, const float4* __restrict__ weights,
+                                                    const int* __restrict__ cornerFirst, const MorphEntry* __restrict__ entries,
+                                                    size_t numCorners, int* __restrict__ ids, float* __restrict__ vertices, float* __restrict__ normals) {
+    __shared__ BoneRec palette[RS_SKIN_MAX_BONES];
+    __shared__ __attribute__((aligned(16))) float mw[RS_MORPH_MAX_TARGETS];
+    stage16(bones, palette, numBones * (int)(sizeof(BoneRec) / 16));
+    stage16(bones + numBones, mw, (numTargets + 3) >> 2);
+    __syncthreads();
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= numCorners) return;
+    const BakedCorner r = morph_corner(entries, cornerFirst[c], cornerFirst[c + 1], mw, ld3(restVertices + c * 3), ld3(restNormals + c * 3));
+    const int4 b4 = boneIds[c];
+    const float4 w4 = weights[c];
+    const int b[4] = { b4.x, b4.y, b4.z, b4.w };
+    const float w[4] = { w4.x, w4.y, w4.z, w4.w };
+    const BakedCorner o = skin_corner(palette, b, w, r.position, r.normal);
+    st3(vertices + c * 3, o.position);
+    st3(normals + c * 3, o.normal);
+    const size_t tri = c / 3;
+    if (c == tri * 3) ids[tri] = skinPrimIds[tri];
+}
+
 // rs_record_source::enqueue of a transform (owner: the rs_parts) and of a pose (owner: the rs_skin; dRecs: all numBones records); m > 0
 int enqueue_bake(const rs_record_source& src, const void* dRecs, size_t m, int* dIds, float* dVertices, float* dNormals, hipStream_t st) {
     const rs_rest_pose& rest = static_cast<const rs_parts*>(src.owner)->rest;
@@ -91,6 +148,31 @@ int enqueue_skin(const rs_record_source& src, const void* dRecs, size_t m, int* 
                        (const float*)skin->rest.dVertices, (const float*)skin->rest.dNormals, reinterpret_cast<const int4*>(skin->dBoneIds),
                        reinterpret_cast<const float4*>(skin->dWeights), corners, dIds, dVertices, dNormals);
     return rs_check_hip(hipGetLastError(), "rs_scene_set_bone_transforms: skin kernel");
+}
+
+// ... of morph weights (owner: the rs_morph; dRecs: the weight records) and of a pose of a skin with a morph (owner: the rs_skin; dRecs: all
+// numBones bone records, then the weight records)
+int enqueue_morph(const rs_record_source& src, const void* dRecs, size_t m, int* dIds, float* dVertices, float* dNormals, hipStream_t st) {
+    const rs_morph* mo = static_cast<const rs_morph*>(src.owner);
+    const size_t corners = m * 3;
+    if (mo->table.numTargets < 1 || mo->table.numTargets > RS_MORPH_MAX_TARGETS || mo->table.cornerFirst.size() != corners + 1)
+        return rs_fail(RS_ERR_INTERNAL, "rs_scene_set_morph_weights: a table the kernel has no room for");
+    hipLaunchKernelGGL(k_morph, dim3((unsigned)((corners + 255) / 256)), dim3(256), 0, st, mo->table.numTargets, static_cast<const float*>(dRecs), (const int*)mo->rest.dPrimIds,
+                       (const float*)mo->rest.dVertices, (const float*)mo->rest.dNormals, (const int*)mo->table.dCornerFirst, (const MorphEntry*)mo->table.dEntries,
+                       corners, dIds, dVertices, dNormals);
+    return rs_check_hip(hipGetLastError(), "rs_scene_set_morph_weights: morph kernel");
+}
+int enqueue_morph_skin(const rs_record_source& src, const void* dRecs, size_t m, int* dIds, float* dVertices, float* dNormals, hipStream_t st) {
+    const rs_skin* skin = static_cast<const rs_skin*>(src.owner);
+    const rs_morph_table* t = skin->morph;
+    const size_t corners = m * 3;
+    if (skin->numBones < 1 || skin->numBones > RS_SKIN_MAX_BONES || !t || t->numTargets < 1 || t->numTargets > RS_MORPH_MAX_TARGETS || t->cornerFirst.size() != corners + 1)
+        return rs_fail(RS_ERR_INTERNAL, "rs_scene_set_skin_pose: a palette or a table the kernel has no room for");
+    hipLaunchKernelGGL(k_morph_skin, dim3((unsigned)((corners + 255) / 256)), dim3(256), 0, st, skin->numBones, t->numTargets, static_cast<const BoneRec*>(dRecs),
+                       (const int*)skin->rest.dPrimIds, (const float*)skin->rest.dVertices, (const float*)skin->rest.dNormals,
+                       reinterpret_cast<const int4*>(skin->dBoneIds), reinterpret_cast<const float4*>(skin->dWeights), (const int*)t->dCornerFirst,
+                       (const MorphEntry*)t->dEntries, corners, dIds, dVertices, dNormals);
+    return rs_check_hip(hipGetLastError(), "rs_scene_set_skin_pose: morph and skin kernel");
 }
 
 // A definition is replaced (fresh), or removed (fresh null), behind a wait for the device -- rs_synchronize, as the first edit of a scene
@@ -282,32 +364,59 @@ extern "C" int rs_scene_define_skin(rs_scene* s, int numBones, int numListed, co
     return replace_definition(s->skin, k, e);
 }
 
-// The palette the call asks for (a bone named twice takes its last matrix, a bone not named keeps its own), the host's own skinning of every
-// listed triangle by it, and then rs_scene_set_geometry's implementation with the records written on the device.
-extern "C" int rs_scene_set_bone_transforms(rs_scene* s, int count, const int* boneIds, const float* matrices16) {
-    RS_SCOPE(s);
-    const char* name = "rs_scene_set_bone_transforms";
+// The palette and the weights the call asks for (a bone or target named twice takes its last value, one not named keeps its own), the
+// host's own evaluation of every listed triangle by them -- the targets, where the skin has a morph, and then the bones -- and then
+// rs_scene_set_geometry's implementation with the records written on the device: by k_skin from the staged palette, or, where the skin has
+// a morph, by k_morph_skin from the staged palette and weight records.
+static int set_skin_pose(rs_scene* s, const char* name, int boneCount, const int* boneIds, const float* matrices16, int targetCount, const int* targetIds,
+                         const float* weights) {
     if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
-    if (count < 0 || (count > 0 && (!boneIds || !matrices16))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "count < 0 or null arrays");
+    if (boneCount < 0 || (boneCount > 0 && (!boneIds || !matrices16))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "count < 0 or null arrays");
     rs_skin* k = s->skin;
     if (!k) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "the scene has no skin (rs_scene_define_skin)");
-    for (int i = 0; i < count; i++)
+    for (int i = 0; i < boneCount; i++)
         if (boneIds[i] < 0 || boneIds[i] >= k->numBones) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a bone id out of range");
-    if (count == 0) return 0;
+    rs_morph_table* t = k->morph;
+    if (targetCount < 0 || (targetCount > 0 && (!targetIds || !weights))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "targetCount < 0 or null arrays");
+    if (targetCount > 0 && !t) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "the skin has no morph (rs_scene_define_skin_morph)");
+    if (t) RS_TRY(t->ask(name, targetCount, targetIds, weights));
+    if (boneCount == 0 && targetCount == 0) return 0;
 
-    k->recs = k->palette;
-    for (int i = 0; i < count; i++) bone_record(matrices16 + (size_t)i * 16, k->recs[(size_t)boneIds[i]]);
-    const size_t listed = k->rest.primIds.size();
+    const size_t listed = k->rest.primIds.size(), bones = (size_t)k->numBones;
+    k->recs.assign(k->palette.begin(), k->palette.end());
+    for (int i = 0; i < boneCount; i++) bone_record(matrices16 + (size_t)i * 16, k->recs[(size_t)boneIds[i]]);
     k->vertices.resize(listed * 9); k->normals.resize(listed * 9);
-    rs_skin_corners_host(k->recs.data(), listed * 3, k->rest.vertices.data(), k->rest.normals.data(), k->boneIds.data(), k->weights.data(),
-                         k->vertices.data(), k->normals.data());
-    const rs_record_source src{ k->recs.data(), k->numBones, k, enqueue_skin };
+    const float *restV = k->rest.vertices.data(), *restN = k->rest.normals.data();
+    if (t) {
+        k->recs.resize(bones + t->records());
+        t->fill_records(k->recs.data() + bones);
+        k->morphedVertices.resize(listed * 9); k->morphedNormals.resize(listed * 9);
+        t->evaluate(t->asked.data(), restV, restN, k->morphedVertices.data(), k->morphedNormals.data());
+        restV = k->morphedVertices.data(); restN = k->morphedNormals.data();
+    }
+    rs_skin_corners_host(k->recs.data(), listed * 3, restV, restN, k->boneIds.data(), k->weights.data(), k->vertices.data(), k->normals.data());
+    const rs_record_source src{ k->recs.data(), (int)k->recs.size(), k, t ? enqueue_morph_skin : enqueue_skin };
     bool taken = false;
     const int e = rs_set_geometry(s, (int)listed, k->rest.primIds.data(), k->vertices.data(), k->normals.data(), true, name, &src, &taken);
-    // Geometry and palette stay one pose: the palette becomes the scene's where the scene took the edit, whatever the call returned after
-    // that, and where a skin that lists no triangle had no edit to make and nothing was refused.
-    if (taken || (listed == 0 && e == 0)) k->palette.swap(k->recs);
+    // Geometry, palette and weights stay one pose: they become the scene's where the scene took the edit, whatever the call returned
+    // after that, and where a skin that lists no triangle had no edit to make and nothing was refused.
+    if (taken || (listed == 0 && e == 0)) {
+        k->recs.resize(bones);
+        k->palette.swap(k->recs);
+        if (t) t->weights.swap(t->asked);
+    }
     return e;
+}
+
+extern "C" int rs_scene_set_bone_transforms(rs_scene* s, int count, const int* boneIds, const float* matrices16) {
+    RS_SCOPE(s);
+    return set_skin_pose(s, "rs_scene_set_bone_transforms", count, boneIds, matrices16, 0, nullptr, nullptr);
+}
+
+extern "C" int rs_scene_set_skin_pose(rs_scene* s, int boneCount, const int* boneIds, const float* matrices16, int targetCount, const int* targetIds,
+                                      const float* weights) {
+    RS_SCOPE(s);
+    return set_skin_pose(s, "rs_scene_set_skin_pose", boneCount, boneIds, matrices16, targetCount, targetIds, weights);
 }
 
 extern "C" int rs_scene_skin_info(const rs_scene* s, int* numBones, int* numListedPrims) {
@@ -326,5 +435,186 @@ extern "C" int rs_scene_download_skin(const rs_scene* s, int* primIds, float* re
     const size_t n = k->rest.primIds.size();
     if (n && boneIds) RS_HIP(hipMemcpy(boneIds, k->dBoneIds, n * 12 * sizeof(int), hipMemcpyDeviceToHost));
     if (n && weights) RS_HIP(hipMemcpy(weights, k->dWeights, n * 12 * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- morph targets ----
+void rs_morph_free(rs_morph* m) { delete m; }
+
+int rs_morph_table::check(const char* name, int targets, size_t numCorners, const int* targetFirst, const int* entryCorner, const float* deltaPositions,
+                          const float* deltaNormals, bool finite) {
+    if (targets < 0 || targets > RS_MORPH_MAX_TARGETS) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "numTargets < 0 or above RS_MORPH_MAX_TARGETS");
+    if (targets == 0) return 0;
+    if (!targetFirst) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null target offsets");
+    if (targetFirst[0] != 0) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "the first offset is not 0");
+    for (int t = 0; t < targets; t++)
+        if (targetFirst[t + 1] < targetFirst[t]) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "offsets that decrease");
+    const size_t n = (size_t)targetFirst[targets];
+    if (n > 0 && (!entryCorner || !deltaPositions)) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null entry corners or position deltas");
+    std::vector<int> lastTarget(numCorners, -1);
+    for (int t = 0; t < targets; t++)
+        for (size_t e = (size_t)targetFirst[t]; e < (size_t)targetFirst[t + 1]; e++) {
+            const int c = entryCorner[e];
+            if (c < 0 || (size_t)c >= numCorners) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a corner index out of range");
+            if (lastTarget[(size_t)c] == t) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a (target, corner) pair listed twice");
+            lastTarget[(size_t)c] = t;
+        }
+    if (finite)
+        for (size_t i = 0; i < n * 3; i++)
+            if (!std::isfinite(deltaPositions[i]) || (deltaNormals && !std::isfinite(deltaNormals[i]))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a delta that is not finite");
+    return 0;
+}
+
+// A counting sort by corner that visits the targets in ascending order: every corner's entries come out sorted by target id
+void rs_morph_table::build(int targets, size_t numCorners, const int* targetFirst, const int* entryCorner, const float* deltaPositions, const float* deltaNormals) {
+    numTargets = targets;
+    const size_t n = targets > 0 ? (size_t)targetFirst[targets] : 0;
+    cornerFirst.assign(numCorners + 1, 0);
+    for (size_t e = 0; e < n; e++) cornerFirst[(size_t)entryCorner[e] + 1]++;
+    for (size_t c = 0; c < numCorners; c++) cornerFirst[c + 1] += cornerFirst[c];
+    std::vector<int> next(cornerFirst.begin(), cornerFirst.end() - 1);
+    entries.assign(n, MorphEntry{});
+    for (int t = 0; t < targets; t++)
+        for (size_t e = (size_t)targetFirst[t]; e < (size_t)targetFirst[t + 1]; e++) {
+            MorphEntry& o = entries[(size_t)next[(size_t)entryCorner[e]]++];
+            o.head.target = t;
+            for (int k = 0; k < 3; k++) {
+                o.head.dp[k] = deltaPositions[e * 3 + k];
+                o.tail.dn[k] = deltaNormals ? deltaNormals[e * 3 + k] : 0.f;
+            }
+            o.tail.pad = 0;
+        }
+    weights.assign((size_t)targets, 0.f);
+}
+
+int rs_morph_table::upload_tables() {
+    RS_TRY(upload(&dCornerFirst, cornerFirst));
+    return upload(&dEntries, entries);
+}
+
+int rs_morph_table::ask(const char* name, int count, const int* targetIds, const float* w) {
+    for (int i = 0; i < count; i++) {
+        if (targetIds[i] < 0 || targetIds[i] >= numTargets) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a target id out of range");
+        if (!std::isfinite(w[i])) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a weight that is not finite");
+    }
+    asked = weights;
+    for (int i = 0; i < count; i++) asked[(size_t)targetIds[i]] = w[i];
+    return 0;
+}
+
+void rs_morph_table::fill_records(BoneRec* recs) const {
+    std::memset(recs, 0, records() * sizeof(BoneRec));
+    std::memcpy(recs, asked.data(), asked.size() * sizeof(float));
+}
+
+void rs_morph_table::evaluate(const float* w, const float* vertsIn, const float* normalsIn, float* vertsOut, float* normalsOut) const {
+    for (size_t c = 0; c + 1 < cornerFirst.size(); c++) {
+        const BakedCorner o = morph_corner(entries.data(), cornerFirst[c], cornerFirst[c + 1], w, ld3(vertsIn + c * 3), ld3(normalsIn + c * 3));
+        st3(vertsOut + c * 3, o.position);
+        st3(normalsOut + c * 3, o.normal);
+    }
+}
+
+extern "C" int rs_morph_corners(int numTargets, const int* targetFirst, const int* entryCorner, const float* deltaPositions, const float* deltaNormals,
+                                const float* weights, size_t n, const float* vertsIn, const float* normalsIn, float* vertsOut, float* normalsOut) {
+    const char* name = "rs_morph_corners";
+    if (n > 0 && (!vertsIn || !normalsIn || !vertsOut || !normalsOut)) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a null array with n > 0");
+    if (numTargets > 0 && !weights) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null weights");
+    RS_TRY(rs_morph_table::check(name, numTargets, n, targetFirst, entryCorner, deltaPositions, deltaNormals, false));
+    rs_morph_table t;
+    t.build(numTargets, n, targetFirst, entryCorner, deltaPositions, deltaNormals);
+    t.evaluate(weights, vertsIn, normalsIn, vertsOut, normalsOut);
+    return 0;
+}
+
+extern "C" int rs_scene_define_morph(rs_scene* s, int numTargets, int numListed, const int* primIds, const float* restVertices, const float* restNormals,
+                                     const int* targetFirst, const int* entryCorner, const float* deltaPositions, const float* deltaNormals) {
+    RS_SCOPE(s);
+    const char* name = "rs_scene_define_morph";
+    if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
+    if (numTargets < 0 || numTargets > RS_MORPH_MAX_TARGETS) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "numTargets < 0 or above RS_MORPH_MAX_TARGETS");
+    if (numListed < 0 || (numTargets == 0 && numListed > 0)) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "numListed < 0, or triangles without a target");
+    RS_TRY(rs_rest_pose::check_pair(name, restVertices, restNormals));
+    if (numListed > 0 && !primIds) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null primitive ids");
+    const size_t listed = (size_t)numListed;
+    RS_TRY(rs_rest_pose::check_listed(s, name, listed, primIds, restVertices, restNormals));
+    RS_TRY(rs_morph_table::check(name, numTargets, listed * 3, targetFirst, entryCorner, deltaPositions, deltaNormals, true));
+    RS_TRY(refuse_while_capturing(name));
+    if (numTargets == 0) return replace_definition<rs_morph>(s->morph, nullptr, 0);
+
+    rs_morph* m = new rs_morph();
+    m->table.build(numTargets, listed * 3, targetFirst, entryCorner, deltaPositions, deltaNormals);
+    int e = m->rest.build(s, listed, primIds, restVertices, restNormals);
+    if (!e) e = m->table.upload_tables();
+    return replace_definition(s->morph, m, e);
+}
+
+extern "C" int rs_scene_define_skin_morph(rs_scene* s, int numTargets, const int* targetFirst, const int* entryCorner, const float* deltaPositions,
+                                          const float* deltaNormals) {
+    RS_SCOPE(s);
+    const char* name = "rs_scene_define_skin_morph";
+    if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
+    rs_skin* k = s->skin;
+    if (!k) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "the scene has no skin (rs_scene_define_skin)");
+    const size_t corners = k->rest.primIds.size() * 3;
+    RS_TRY(rs_morph_table::check(name, numTargets, corners, targetFirst, entryCorner, deltaPositions, deltaNormals, true));
+    RS_TRY(refuse_while_capturing(name));
+    if (numTargets == 0) return replace_definition<rs_morph_table>(k->morph, nullptr, 0);
+
+    rs_morph_table* t = new rs_morph_table();
+    t->build(numTargets, corners, targetFirst, entryCorner, deltaPositions, deltaNormals);
+    return replace_definition(k->morph, t, t->upload_tables());
+}
+
+// The weights the call asks for, the host's own morphing of every listed triangle by them, and then rs_scene_set_geometry's implementation
+// with the records written on the device by k_morph from the staged weight records.
+extern "C" int rs_scene_set_morph_weights(rs_scene* s, int count, const int* targetIds, const float* weights) {
+    RS_SCOPE(s);
+    const char* name = "rs_scene_set_morph_weights";
+    if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
+    if (count < 0 || (count > 0 && (!targetIds || !weights))) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "count < 0 or null arrays");
+    rs_morph* m = s->morph;
+    if (!m) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "the scene has no morph (rs_scene_define_morph)");
+    rs_morph_table& t = m->table;
+    RS_TRY(t.ask(name, count, targetIds, weights));
+    if (count == 0) return 0;
+
+    const size_t listed = m->rest.primIds.size();
+    m->recs.resize(t.records());
+    t.fill_records(m->recs.data());
+    m->vertices.resize(listed * 9); m->normals.resize(listed * 9);
+    t.evaluate(t.asked.data(), m->rest.vertices.data(), m->rest.normals.data(), m->vertices.data(), m->normals.data());
+    const rs_record_source src{ m->recs.data(), (int)m->recs.size(), m, enqueue_morph };
+    bool taken = false;
+    const int e = rs_set_geometry(s, (int)listed, m->rest.primIds.data(), m->vertices.data(), m->normals.data(), true, name, &src, &taken);
+    // geometry and weights stay one pose, as a skin's palette does
+    if (taken || (listed == 0 && e == 0)) t.weights.swap(t.asked);
+    return e;
+}
+
+static const rs_morph_table* morph_table_of(const rs_scene* s, int which) { return which == 0 ? (s->morph ? &s->morph->table : nullptr) : (s->skin ? s->skin->morph : nullptr); }
+
+extern "C" int rs_scene_morph_info(const rs_scene* s, int which, int* numTargets, int* numListedPrims, int* numEntries) {
+    if (!s) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_morph_info: null scene");
+    if (which != 0 && which != 1) return rs_fail(RS_ERR_INVALID_ARGUMENT, "rs_scene_morph_info: which is neither 0 (the scene's morph) nor 1 (the skin's)");
+    const rs_morph_table* t = morph_table_of(s, which);
+    if (numTargets) *numTargets = t ? t->numTargets : 0;
+    if (numListedPrims) *numListedPrims = t ? (int)((t->cornerFirst.size() - 1) / 3) : 0;
+    if (numEntries) *numEntries = t ? (int)t->entries.size() : 0;
+    return 0;
+}
+
+extern "C" int rs_scene_download_morph(const rs_scene* s, int which, int* primIds, float* restVertices, float* restNormals, int* cornerFirst, void* entries) {
+    RS_SCOPE(s);
+    const char* name = "rs_scene_download_morph";
+    if (!s) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "null scene");
+    if (which != 0 && which != 1) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "which is neither 0 (the scene's morph) nor 1 (the skin's)");
+    const rs_morph_table* t = morph_table_of(s, which);
+    if (!t) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "no such morph defined (rs_scene_define_morph, rs_scene_define_skin_morph)");
+    if (which == 1 && (primIds || restVertices || restNormals)) return fail_named(RS_ERR_INVALID_ARGUMENT, name, "a skin's morph has no rest pose of its own (rs_scene_download_skin)");
+    if (which == 0) RS_TRY(s->morph->rest.download(name, primIds, restVertices, restNormals));
+    else { RS_TRY(refuse_while_capturing(name)); RS_TRY(rs_synchronize()); }
+    if (cornerFirst) RS_HIP(hipMemcpy(cornerFirst, t->dCornerFirst, t->cornerFirst.size() * sizeof(int), hipMemcpyDeviceToHost));
+    if (entries && !t->entries.empty()) RS_HIP(hipMemcpy(entries, t->dEntries, t->entries.size() * sizeof(MorphEntry), hipMemcpyDeviceToHost));
     return 0;
 }
