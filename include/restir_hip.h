@@ -1077,8 +1077,9 @@ int  rs_debug_segment_in_boxes(int n, const float* segments6, int m, const float
  * A call without an accepted geometry edit since the previous rs_restir_indirect call launches exactly what it launches with the switch
  * off and leaves every buffer bit for bit the same.  Stream-ordered, no host wait but the one `rays` asks for; a failed allocation leaves
  * it off with nothing changed.  Memory: 16 KB of counters from the first switch-on, no per-pixel plane.
- * Deliberately left as it is: emission, material and texture edits dirty no box, so a stale Lo stays stale; and there is no spatial side
- * -- ReSTIR-GI has none here. */
+ * Deliberately left as it is: emission, material and texture edits dirty no box, so a stale Lo stays stale.  The spatial pass
+ * (rs_restir_set_indirect_spatial, below) reads the temporal buffer after the path kernel and writes a buffer nothing merges from, so
+ * it has nothing to revalidate: its winners are tested on the current geometry. */
 int  rs_restir_set_indirect_revalidation(rs_restir* r, int enable);
 int  rs_restir_get_indirect_revalidation(const rs_restir* r, int* enabled);
 /* Test hooks.  What the pass did in the last rs_restir_indirect call: out[0] slots examined, out[1] found stale, out[2] segments walked,
@@ -1263,6 +1264,84 @@ int  rs_restir_indirect(rs_restir* r, const rs_scene* scene, const rs_camera* ca
                         int iter, int looper, int reuse, int maxDepth, unsigned long long* rays);
 /* which: 0 = the buffer the next call writes, 1 = the one the last call wrote (devIndLastTemporalReservoir) */
 int  rs_restir_download_indirect(rs_restir* r, int which, rs_indirect_reservoir* host);
+
+/* ---- ReSTIR-GI: spatial reuse of the indirect reservoirs --------------------------------------------------------------------------
+ * The reference allocates devIndSpatialReservoir (src/restir.cu:15) and never writes it: its ReSTIR-GI is the temporal half only.  This
+ * is the spatial half, opt-in and off by default; with it off every launch, buffer and image of rs_restir_indirect is bit for bit what it
+ * is without this section.  A GI sample is reused across pixels by reconnecting the neighbour's sample point xs to the receiving pixel's
+ * visible point; the weight is corrected by the Jacobian of that shift (Ouyang et al., "ReSTIR GI: Path Resampling for Real-Time Path
+ * Tracing", 2021, eq. 11).
+ *
+ * The setter.  taps in 1..RS_GI_SPATIAL_MAX_TAPS, taps <= 0 selects 5; radius in pixels, finite, in (0, 64], radius <= 0 selects 5.f (the
+ * reference's DI values); anything else is refused (also with enable == 0) and changes nothing.  The first switch-on allocates 68 B/px
+ * (the spatial reservoirs) + 12 B/px (the path kernel's own image of a call that runs the pass) + 32 KB of counters; the receiver's
+ * surface is recomputed, not stored.  A failed allocation leaves the switch off with nothing changed.  Refused while the library stream
+ * is being captured.  Independent of every other switch.
+ *
+ * When the pass runs: in an rs_restir_indirect call iff the switch is on and reuse & 2 -- on the first frame as well, as the DI spatial
+ * pass does.  reuse & 2 with the switch off stays ignored, as in the reference.  A call that does not run it launches what it launches
+ * with the switch off.
+ *
+ * The rule.  One launch after the path kernel, when every slot of this call's temporal buffer T is complete; one lane per pixel
+ * q = (x, y), index i = y * width + x.  Every expression is a tree of single IEEE float operations, no contraction; dot(a, b) is
+ * (a.x * b.x + a.y * b.y) + a.z * b.z.
+ *  1. Receiver.  The surface the path kernel computed at its primary hit in this very call: the lane seeds the same engine
+ *     seeded(sampleSeq, looper, i, 0), draws sample4D, takes cam.sample(x, y, .) and intersects.  xv_q = the hit position; nv_q = the
+ *     normal after getTexturedMaterialAndSurface, negated when dot(nv_q, wo) < 0.f with wo = primWo = -ray.direction
+ *     (src/restir.cu:286-288); primMaterial = that material.  The pixel takes part iff the hit exists and the material is neither Light nor
+ *     Dielectric.  A pixel that does not take part keeps S[i] = T[i] (all 17 words) and its image value is the one the call gives with
+ *     the switch off.
+ *  2. Start.  R = T[i] as stored (already clamped) after checkValidity (weight NaN, infinite or < 0: weight = 0, numSamples = 0).  The
+ *     engine of the pass is seeded(sampleSeq, looper, i, RS_GI_SPATIAL_DIM).
+ *  3. Every tap draws three numbers in this order, accepted or not: sample2D r for the position, then sample1D u for the merge.  The tap
+ *     is findSpatialNeighborDisk (src/restir.cu:47-85) with `radius` in place of its constant: rr = sqrt(r.x); theta = (r.y * Pi) * 2.f;
+ *     px = int((float(x) + .5f) + (cos(theta) * rr) * radius), py likewise with sin -- cos and sin correctly rounded, the conversion
+ *     truncating.  It fails the neighbour test when px, py is outside the image or is q itself, when the G-buffer ids differ, when
+ *     dot(normal[i], normal[p]) < .9f, or when |depth[i] - depth[p]| > depth[i] * .1f.
+ *  4. Candidate.  A tap that passes yields N = T[p], p = py * width + px.  N invalid (weight NaN, infinite or < 0): rejected, adding
+ *     nothing.  N.weight == 0: accepted with w = 0, no geometry evaluated.  N.weight > 0: rejected when N.ns == 0 on all three components
+ *     (a first bounce that left the scene has no reconnection vertex); otherwise
+ *         vn = N.xv - N.xs;  vq = xv_q - N.xs;  dn2 = dot(vn, vn);  dq2 = dot(vq, vq);  an = |dot(N.ns, vn)|;  aq = |dot(N.ns, vq)|;
+ *         jac = ((aq / sqrt(dq2)) * dn2) / ((an / sqrt(dn2)) * dq2)
+ *     -- the change of solid-angle measure from the neighbour's visible point to the receiver's.  Rejected, in this order of counting,
+ *     when jac is NaN or infinite or jac > RS_GI_SPATIAL_JACOBIAN_MAX ("Jacobian"), then when dot(nv_q, vq) >= 0.f ("horizon": xs is not
+ *     above the receiver's horizon).  Otherwise w = N.weight * jac.
+ *  5. Merge of an accepted tap (the reference's merge): R.weight = R.weight + w; R.numSamples += N.numSamples; if u * R.weight < w then
+ *     R.sample = N.sample with xv, nv replaced by xv_q, nv_q, and the lane's sample is "adopted".  The target is Lo (pHatIndirect), which
+ *     does not depend on the receiver: that is why weights add once the Jacobian is in.
+ *  6. Visibility, once, on the winner (the reference's own convention for RIS, src/restir.cu:172-176): a lane that adopted a sample walks
+ *     testOcclusion(xv_q, R.sample.xs) on the current geometry; blocked: R.weight = 0.f (zeroed, not cleared).  A lane whose winner is its
+ *     own sample walks nothing.
+ *  7. S[i] = R; nothing reads S in a later call and nothing clamps it.  Shade by src/restir.cu:399-412 with the non-delta factor: when R
+ *     is valid, wi = normalize(xs - xv) (v * (1.f / sqrt(dot(v, v)))), L = ((Lo / luminance(Lo)) * weight) / float(numSamples), then
+ *     L * (primMaterial.BSDF(nv, primWo, wi) * satDot(nv, wi)); NaN or infinity anywhere gives 0.  The caller's image receives
+ *     (image * float(iter) + L) / float(iter + 1) -- the spatial result only.
+ *  8. T, the history the next call merges from, everything rs_restir_download_indirect returns and the behaviour of indirect
+ *     revalidation equal a run with the switch off, bit for bit.  *rays is the path kernel's count plus one per winner walked.
+ * With the Sobol sampler the dimensions 150..197 belong to the pass; the path kernel reaches them only beyond depth 20.
+ * Stream-ordered, no host wait but the one `rays` asks for.
+ * Not done: the unbiased variant that counts Z over the neighbours' domains, feeding S back into the history, a second spatial
+ * iteration, a row-band form, re-evaluating Lo after emission or material edits. */
+#define RS_GI_SPATIAL_MAX_TAPS     16
+#define RS_GI_SPATIAL_DIM          150     /* sampler dimension of the pass's engine */
+#define RS_GI_SPATIAL_JACOBIAN_MAX 10.f
+int  rs_restir_set_indirect_spatial(rs_restir* r, int enable, int taps, float radius);
+int  rs_restir_get_indirect_spatial(const rs_restir* r, int* enabled, int* taps, float* radius);      /* taps, radius: may be null */
+/* devIndSpatialReservoir of the last call that ran the pass (zeros before one); refused before the first switch-on */
+int  rs_restir_download_indirect_spatial(rs_restir* r, rs_indirect_reservoir* host);
+/* Test hooks.  What the pass did in the last rs_restir_indirect call, in this order: pixels taking part, taps accepted, taps failing the
+ * neighbour test, taps rejected for ns == 0, for the Jacobian, for the horizon, winners walked, winners blocked; all 0 when the call did
+ * not run the pass.  Waits for the library stream. */
+int  rs_debug_restir_indirect_spatial(rs_restir* r, unsigned long long out[8]);
+/* ... and whether that call ran the pass at all: 1 or 0.  Host only. */
+int  rs_debug_restir_indirect_spatial_launched(rs_restir* r, int* launched);
+/* The receiver's surface the pass used, per pixel: xv, nv, wo as float4 (w = 0) and the material id, -1 (and zeros) for a pixel that
+ * does not take part.  The planes (52 B/px) exist only once somebody has asked: a first call -- with every output null -- allocates them,
+ * later passes record into them, and later calls copy out what the last pass recorded (outputs may be null one by one). */
+int  rs_debug_restir_indirect_primary(rs_restir* r, float* xv4, float* nv4, float* wo4, int* matId);
+/* Host only: n draws of the library's own sampler seeded(table, iter, index, dim) -- the scene's Sobol table, or the default engine
+ * when the scene is null or has none. */
+int  rs_debug_seeded_uniforms(const rs_scene* sceneOrNull, int iter, int index, int dim, int n, float* out);
 
 /* ---- display conversion (src/pathtrace.h:8) ---------------------------------------------- */
 /* copyImageToPBO(uchar4*, glm::vec3*, w, h, toneMapping, scale) (src/pathtrace.cu:108-113) */

@@ -23,6 +23,7 @@ class RestirHipError(RuntimeError):
 
 
 RS_ERR_INVALID_ARGUMENT, RS_ERR_UNSUPPORTED = 10001, 10002
+RS_GI_SPATIAL_MAX_TAPS, RS_GI_SPATIAL_DIM, RS_GI_SPATIAL_JACOBIAN_MAX = 16, 150, 10.0      # rs_restir_set_indirect_spatial
 
 # rs_transport (include/restir_hip.h): the exchange of the strip driver as callbacks
 TRANSPORT_GROUP = C.CFUNCTYPE(C.c_int, C.c_void_p)
@@ -159,6 +160,7 @@ EXPORTS = [
     "rs_restir_halo_unpack", "rs_restir_rows_bytes", "rs_restir_rows_pack", "rs_restir_rows_unpack", "rs_restir_download", "rs_restir_upload", "rs_restir_set_light_tracking", "rs_restir_download_light_ids", "rs_restir_set_light_retargeting", "rs_restir_get_light_retargeting", "rs_restir_download_light_samples", "rs_debug_restir_retarget", "rs_debug_restir_retarget_launched", "rs_debug_restir_surface_wo", "rs_scene_light_moves", "rs_restir_set_shadow_revalidation", "rs_restir_get_shadow_revalidation", "rs_scene_geometry_edits", "rs_scene_dirty_boxes", "rs_debug_restir_revalidate", "rs_debug_restir_revalidate_launched", "rs_debug_plan_dirty_box", "rs_debug_plan_revalidation", "rs_debug_segment_in_boxes", "rs_restir_set_indirect_revalidation", "rs_restir_get_indirect_revalidation", "rs_debug_restir_indirect_revalidate", "rs_debug_restir_indirect_revalidate_launched", "rs_debug_indirect_candidate_classes", "rs_restir_light_rows_bytes", "rs_restir_light_rows_pack", "rs_restir_light_rows_unpack", "rs_restir_ray_count", "rs_restir_ray_total", "rs_restir_pass_times",
     "rs_restir_enable_timing", "rs_restir_spatial_times", "rs_restir_set_probe", "rs_restir_last_launch", "rs_debug_phase_a_plan", "rs_restir_set_primary_cuts", "rs_debug_set_primary_cut_cap", "rs_debug_primary_cut_info", "rs_debug_primary_cut_missing", "rs_restir_set_primary_leaf_lists", "rs_debug_set_primary_leaf_list_cap", "rs_debug_primary_leaf_list_info", "rs_debug_primary_leaf_list_missing", "rs_debug_plan_primary_leaf_list", "rs_debug_plan_primary_cut", "rs_debug_plan_primary_cut_slot", "rs_restir_set_shadow_regroup", "rs_debug_plan_shadow_regroup", "rs_debug_shadow_pass", "rs_debug_plan_stream_choice", "rs_debug_plan_stream_switch", "rs_debug_restir_surface", "rs_pbo_register", "rs_pbo_map", "rs_pbo_unmap", "rs_pbo_unregister", "rs_save_image", "rs_save_image_jpg", "rs_write_png", "rs_write_jpg", "rs_debug_tap_estimate_error", "rs_debug_sqrt_of_uniform_mismatches", "rs_debug_sqrt_of_unit_floats_mismatches", "rs_debug_exact_ops_mismatches", "rs_debug_rng_step_mismatches", "rs_debug_rng_step_host_mismatches", "rs_debug_surface_ops", "rs_debug_div_sigma_mismatches", "rs_path_trace_init", "rs_path_trace_free", "rs_path_trace_direct",
     "rs_path_trace", "rs_path_trace_indirect", "rs_restir_indirect", "rs_restir_download_indirect",
+    "rs_restir_set_indirect_spatial", "rs_restir_get_indirect_spatial", "rs_restir_download_indirect_spatial", "rs_debug_restir_indirect_spatial", "rs_debug_restir_indirect_spatial_launched", "rs_debug_restir_indirect_primary", "rs_debug_seeded_uniforms",
     "rs_svgf_create", "rs_svgf_destroy", "rs_svgf_filter", "rs_svgf_next_frame", "rs_svgf_get_view",
     "rs_copy_image_to_pbo", "rs_copy_image2_to_pbo", "rs_copy_imagef_to_pbo", "rs_copy_imagei_to_pbo", "rs_eaw_create", "rs_eaw_destroy", "rs_eaw_set_params", "rs_eaw_get_params", "rs_eaw_set_tiled", "rs_eaw_set_fused", "rs_svgf_set_params", "rs_svgf_get_params", "rs_svgf_set_tiled", "rs_svgf_set_fused", "rs_eaw_filter", "rs_eaw_positions_rows", "rs_eaw_level_rows", "rs_modulate_albedo",
     "rs_add_image", "rs_add_image3", "rs_comm_create_rccl", "rs_comm_create_rccl_lib", "rs_comm_create", "rs_comm_destroy", "rs_comm_self_exchange", "rs_strips_create", "rs_strips_destroy", "rs_strips_rows", "rs_strips_set_comm_stream", "rs_strips_set_gbuffer_halo", "rs_strips_set_light_tracking", "rs_strips_frame", "rs_strips_eaw_filter", "rs_strips_svgf_filter", "rs_strips_exchange_svgf_history", "rs_strips_exchange_history", "rs_strips_gather", "rs_strips_gather_begin", "rs_strips_gather_end", "rs_strips_enable_timing", "rs_strips_halo_wait_ms",
@@ -274,6 +276,14 @@ def lib():
         L.rs_debug_restir_indirect_revalidate.argtypes = [vp, C.POINTER(C.c_ulonglong * 4)]
         L.rs_debug_restir_indirect_revalidate_launched.argtypes = [vp, C.POINTER(ci)]
         L.rs_debug_indirect_candidate_classes.argtypes = [ci, vp, ci, vp, ci, vp]
+    if hasattr(L, "rs_restir_set_indirect_spatial"):        # (an A/B build from before GI's spatial pass, RESTIR_HIP_LIB: tools/bench_indirect_spatial.py)
+        L.rs_restir_set_indirect_spatial.argtypes = [vp, ci, ci, C.c_float]
+        L.rs_restir_get_indirect_spatial.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_float)]
+        L.rs_restir_download_indirect_spatial.argtypes = [vp, vp]
+        L.rs_debug_restir_indirect_spatial.argtypes = [vp, C.POINTER(C.c_ulonglong * 8)]
+        L.rs_debug_restir_indirect_spatial_launched.argtypes = [vp, C.POINTER(ci)]
+        L.rs_debug_restir_indirect_primary.argtypes = [vp, vp, vp, vp, vp]
+        L.rs_debug_seeded_uniforms.argtypes = [vp, ci, ci, ci, ci, vp]
     L.rs_restir_light_rows_bytes.argtypes = [vp, ci]
     L.rs_restir_light_rows_bytes.restype = C.c_size_t
     L.rs_restir_light_rows_pack.argtypes = [vp, ci, ci, ci, vp]
@@ -705,6 +715,14 @@ def indirect_candidate_classes(reservoirs, boxes, everything=False):
     check(lib().rs_debug_indirect_candidate_classes(len(resv), _p(resv) if len(resv) else None, len(b), _p(b) if len(b) else None, 1 if everything else 0,
                                                     _p(classes)))
     return classes[:len(resv)].copy()
+
+
+def seeded_uniforms(scene, iter_, index, dim, n):
+    """rs_debug_seeded_uniforms (host only): n draws of the library's sampler seeded(table, iter, index, dim) -- `scene`'s Sobol table, or
+    the default engine when `scene` is None or has no table."""
+    out = np.zeros(max(n, 1), np.float32)
+    check(lib().rs_debug_seeded_uniforms(scene.handle if scene is not None else None, int(iter_), int(index), int(dim), int(n), _p(out)))
+    return out[:n]
 
 
 def plan_stream_choice(priority_range, asked=2, caller_priority=None, times_us=None):
@@ -1693,6 +1711,48 @@ class ReSTIR:
         on = C.c_int(0)
         check(lib().rs_debug_restir_indirect_revalidate_launched(self.handle, C.byref(on)))
         return bool(on.value)
+
+    def set_indirect_spatial(self, on=True, taps=0, radius=0.0):
+        """rs_restir_set_indirect_spatial: rs_restir_indirect calls with reuse & 2 merge up to 16 neighbours' GI reservoirs into every
+        pixel's (reconnection shift with its Jacobian), test the winner's visibility and shade that; taps / radius <= 0: 5 and 5.0."""
+        check(lib().rs_restir_set_indirect_spatial(self.handle, 1 if on else 0, int(taps), float(radius)))
+
+    def get_indirect_spatial(self):
+        """(enabled, taps, radius)"""
+        on, taps, radius = C.c_int(0), C.c_int(0), C.c_float(0)
+        check(lib().rs_restir_get_indirect_spatial(self.handle, C.byref(on), C.byref(taps), C.byref(radius)))
+        return bool(on.value), int(taps.value), float(radius.value)
+
+    def download_indirect_spatial(self):
+        """devIndSpatialReservoir of the last rs_restir_indirect call that ran the pass."""
+        out = np.zeros(self.width * self.height, INDIRECT_RESERVOIR_DTYPE)
+        check(lib().rs_restir_download_indirect_spatial(self.handle, _p(out)))
+        return out
+
+    def indirect_spatial_stats(self):
+        """rs_debug_restir_indirect_spatial: (taking part, accepted, failed the neighbour test, ns == 0, Jacobian, horizon, walked, blocked)
+        of the last rs_restir_indirect call."""
+        out = (C.c_ulonglong * 8)()
+        check(lib().rs_debug_restir_indirect_spatial(self.handle, C.byref(out)))
+        return tuple(int(x) for x in out)
+
+    def indirect_spatial_launched(self):
+        on = C.c_int(0)
+        check(lib().rs_debug_restir_indirect_spatial_launched(self.handle, C.byref(on)))
+        return bool(on.value)
+
+    def record_indirect_primary(self):
+        """rs_debug_restir_indirect_primary with null outputs: from now on the pass records the receiver's surface."""
+        check(lib().rs_debug_restir_indirect_primary(self.handle, None, None, None, None))
+
+    def indirect_primary(self):
+        """rs_debug_restir_indirect_primary: (xv (n, 3), nv (n, 3), wo (n, 3), material id (n,), -1 where the pixel does not take part) of
+        the last call that ran the pass, after record_indirect_primary()."""
+        n = self.width * self.height
+        xv, nv, wo = (np.zeros((n, 4), np.float32) for _ in range(3))
+        mat = np.zeros(n, np.int32)
+        check(lib().rs_debug_restir_indirect_primary(self.handle, _p(xv), _p(nv), _p(wo), _p(mat)))
+        return xv[:, :3].copy(), nv[:, :3].copy(), wo[:, :3].copy(), mat
 
     def light_rows_bytes(self, rows):
         return int(lib().rs_restir_light_rows_bytes(self.handle, rows))

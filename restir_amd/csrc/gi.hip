@@ -436,14 +436,19 @@ int rs_restir_indirect(rs_restir* r, const rs_scene* scene, const rs_camera* cam
     RS_TRY(rs_denoise_order(devIndirectIllum));
     // rs_restir_set_indirect_revalidation: geometry moved since the previous call -- the stale slots of the history leave before the merge
     RS_TRY(rs_indirect_revalidate_before_path(r, scene, history && !r->firstFrame && (reuse & 1), r->indResv[1], n));
-    RS_TRY(launch_path<kModeReSTIR>(scene, cam, nullptr, devIndirectIllum, r->indResv[0], r->indResv[1], gbuf_view(g), looper, iter, maxDepth,
-                                    r->firstFrame ? 1 : 0, reuse));
+    // rs_restir_set_indirect_spatial: the caller's image receives the spatial result only, so the path kernel of a call that runs the pass
+    // leaves its own radiance in a scratch image (iter 0: the value itself) and the pass accumulates with the call's iter
+    const bool spatial = rs_indirect_spatial_runs(r, reuse);
+    RS_TRY(launch_path<kModeReSTIR>(scene, cam, nullptr, spatial ? r->indSpatial.temporalImage : devIndirectIllum, r->indResv[0], r->indResv[1], gbuf_view(g),
+                                    looper, spatial ? 0 : iter, maxDepth, r->firstFrame ? 1 : 0, reuse));
+    if (spatial) RS_TRY(rs_indirect_spatial_after_path(r, scene, cam, gbuf_view(g), r->indResv[0], devIndirectIllum, iter, looper));
     { rs_indirect_reservoir* t = r->indResv[0]; r->indResv[0] = r->indResv[1]; r->indResv[1] = t; }      // std::swap (:463)
     r->firstFrame = false;                                                                                    // ReSTIRFirstFrame (:465-467)
     rs_indirect_revalidate_note(r, scene);
     RS_TRY(rs_after_launch("ReSTIR Indirect"));
     RS_TRY(rs_walk_counters_sum(rays));
-    return rs_indirect_revalidate_add_rays(r, rays);
+    RS_TRY(rs_indirect_revalidate_add_rays(r, rays));
+    return rs_indirect_spatial_add_rays(r, rays);
 }
 
 int rs_restir_download_indirect(rs_restir* r, int which, rs_indirect_reservoir* host) {

@@ -31,6 +31,7 @@
 #include "rs_cuts.h"
 #include "rs_shadow_regroup.h"
 #include "rs_revalidate.h"
+#include "rs_disk_tap.h"
 
 using namespace rs;
 
@@ -626,37 +627,7 @@ __global__ void __launch_bounds__(256) k_temporal_marked(SurfPlanes sp, GBufView
 // integer.  Result: the same pixel as the host evaluation, at a fraction of the instruction count.
 constexpr float kTapErr = 2e-5f;
 
-// sin and cos of theta in [0, 2*pi] in double precision: quadrant reduction with a two-term pi/2 and
-// the classic degree-13/14 kernels (fdlibm k_sin / k_cos coefficients), < 1 ulp(double).  Rounded to
-// float this is the correctly rounded sinf/cosf for all but ~1e-9 of the arguments.  A hand-rolled
-// routine instead of OCML's sincos(double) because the latter costs 26 VGPRs (6 instead of 8 waves per
-// SIMD for the whole spatial pass) for a path taken by ~0.03 % of the taps.
-__device__ __forceinline__ void sincos_2pi(double t, double& sn, double& cs) {
-    const double k = rint(t * 6.36619772367581382433e-01);                 // 2/pi
-    double r = fma(-k, 1.57079632673412561417e+00, t);                      // pi/2 high (33 bits)
-    r = fma(-k, 6.07710050650619224932e-11, r);                             // pi/2 low
-    const double z = r * r;
-    const double ps = -1.66666666666666324348e-01 + z * (8.33333333332248946124e-03 + z * (-1.98412698298579493134e-04 +
-                      z * (2.75573137070700676789e-06 + z * (-2.50507602534068634195e-08 + z * 1.58969099521155010221e-10))));
-    const double pc = 4.16666666666666019037e-02 + z * (-1.38888888888741095749e-03 + z * (2.48015872894767294178e-05 +
-                      z * (-2.75573143513906633035e-07 + z * (2.08757232129817482790e-09 + z * -1.13596475577881948265e-11))));
-    const double s0 = r + r * z * ps;
-    const double c0 = 1.0 - 0.5 * z + z * z * pc;
-    const int q = (int)k & 3;
-    sn = (q == 0) ? s0 : (q == 1) ? c0 : (q == 2) ? -s0 : -c0;
-    cs = (q == 0) ? c0 : (q == 1) ? -s0 : (q == 2) ? -c0 : s0;
-}
-
-// exact evaluation of the tap: correctly rounded cos/sin, then the reference's float arithmetic
-__device__ __forceinline__ void disk_tap_exact(float rx, float ry, int x, int y, int& px, int& py) {
-    const float Radius = 5.f;
-    const float rr = sqrtf(rx);
-    const float theta = ry * kPi * 2.0f;
-    double sd, cd;
-    sincos_2pi((double)theta, sd, cd);
-    px = f2i((float)x + .5f + ((float)cd * rr) * Radius);
-    py = f2i((float)y + .5f + ((float)sd * rr) * Radius);
-}
+// (sincos_2pi and disk_tap_exact, the exact evaluation of the tap: rs_disk_tap.h, shared with indirect_spatial.hip)
 
 __device__ __forceinline__ void disk_tap_estimate(float rx, float ry, int x, int y, float& fx, float& fy) {
     const float rr5 = __builtin_amdgcn_sqrtf(rx) * 5.f;
@@ -678,7 +649,7 @@ __device__ __forceinline__ void disk_tap(float rx, float ry, int x, int y, int& 
     disk_tap_estimate(rx, ry, x, y, fx, fy);
     px = f2i(fx);
     py = f2i(fy);
-    if (tap_ambiguous(fx) || tap_ambiguous(fy)) disk_tap_exact(rx, ry, x, y, px, py);
+    if (tap_ambiguous(fx) || tap_ambiguous(fy)) disk_tap_exact(rx, ry, 5.f, x, y, px, py);
 }
 
 // debug / test hook: every state k of the generator gives uniform() = (float)(k - 1) / 2^31, k - 1 in [0, 2^31 - 3]
@@ -976,6 +947,7 @@ int rs_restir_free(rs_restir* r) {
     rs_light_history_free(r->lights);
     rs_revalidate_free(r->reval);
     rs_indirect_revalidate_free(r->indReval);
+    rs_indirect_spatial_free(r->indSpatial);
     rs_primary_cuts_destroy(r->cuts);
     for (auto& e : r->ev) if (e) (void)hipEventDestroy(e);
     for (auto& pair : r->spatialEv) for (hipEvent_t& e : pair) if (e) (void)hipEventDestroy(e);

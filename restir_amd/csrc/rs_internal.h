@@ -203,6 +203,7 @@ struct rs_scene {
     bool textured = false;                        // any material map or an environment map: kernels take the textured variant
     bool hasTexcoords = false;                    // created with texcoords (rs_scene_set_materials: a first map needs them)
     uint32_t* dSampleSeq = nullptr;  // the Sobol table (rs_scene_set_sample_sequence); null: the default thrust engine
+    std::vector<uint32_t> hSampleSeq;   // its host copy, without the guard (rs_debug_seeded_uniforms); empty: none
     uint4* dOccNodes = nullptr;      // shadow-ray tree (occlusion_bvh.cpp)
     rs::BvhNode* dOccChain = nullptr;   // reference boxes + parent links by original node id
     int* dLeafOfPrim = nullptr;         // reference leaf node of every primitive (hLeafOf), with dOccChain: the leaf lists' builder reads it (rs_cuts.h)
@@ -650,6 +651,28 @@ void rs_indirect_revalidate_note(rs_restir* r, const rs_scene* scene);
 int  rs_indirect_revalidate_add_rays(rs_restir* r, unsigned long long* rays);
 void rs_indirect_revalidate_free(rs_indirect_revalidation& v);
 
+// Spatial reuse of ReSTIR-GI's reservoirs of one rs_restir (include/restir_hip.h); indirect_spatial.hip owns every field.  Everything is
+// allocated at the first switch-on and kept; the recording planes only once rs_debug_restir_indirect_primary has asked for them.
+struct rs_indirect_spatial {
+    bool on = false;
+    int taps = 5;                          // RS_GI_SPATIAL_MAX_TAPS at most
+    float radius = 5.f;                    // pixels
+    rs_indirect_reservoir* resv = nullptr; // devIndSpatialReservoir (restir.cu:15): 68 B/px, written by every call that runs the pass
+    float* temporalImage = nullptr;        // 12 B/px: where the path kernel of such a call leaves its temporal-only radiance (iter 0)
+    unsigned long long* dStats = nullptr;  // the eight counters of the last call that ran the pass, each in partial counters
+    float4* recorded = nullptr;            // 3 planes of float4 (xv, nv, wo) ...
+    int* recordedMat = nullptr;            // ... and the material id, -1 where the pixel does not take part (test hook; null until asked for)
+    bool launchedLast = false;             // the last rs_restir_indirect call ran k_spatial_indirect
+};
+// What rs_restir_indirect (gi.hip) asks, in this order: does this call run the pass (then the path kernel writes `temporalImage` with iter
+// 0 instead of the caller's image); after launch_path, the pass from `temporal` (the buffer the path kernel has just written) into the
+// caller's image; and, once the stream has been waited for, the winners walked added to *rays.
+bool rs_indirect_spatial_runs(rs_restir* r, int reuse);
+int  rs_indirect_spatial_after_path(rs_restir* r, const rs_scene* scene, const rs_camera* cam, const GBufView& g, const rs_indirect_reservoir* temporal,
+                                    float* image, int iter, int looper);
+int  rs_indirect_spatial_add_rays(rs_restir* r, unsigned long long* rays);
+void rs_indirect_spatial_free(rs_indirect_spatial& v);
+
 struct rs_restir {
     rs_context* ctx = nullptr;
     rs_primary_cuts cuts;
@@ -703,6 +726,7 @@ struct rs_restir {
     bool shadowRegroup = true;       // rs_restir_set_shadow_regroup (RS_SHADOW_REGROUP=0: off from the start); a scene without occNodes keeps the plain kernel
     rs_shadow_revalidation reval;    // rs_restir_set_shadow_revalidation (shadow_revalidate.hip)
     rs_indirect_revalidation indReval;   // rs_restir_set_indirect_revalidation (indirect_revalidate.hip)
+    rs_indirect_spatial indSpatial;      // rs_restir_set_indirect_spatial (indirect_spatial.hip)
 };
 
 static_assert(rs_context::kAux >= 1 + rs_restir::kChains, "one auxiliary stream for GBuffer::render and one per chain");

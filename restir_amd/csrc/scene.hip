@@ -329,6 +329,7 @@ extern "C" int rs_scene_set_sample_sequence(rs_scene* s, const uint32_t* data, i
     RS_TRY(rs_synchronize());                           // kernels in flight may still read the previous table
     rs_dev_free(s->dSampleSeq);
     s->dev.sampleSeq = nullptr; s->dev.sampleCount = 0;
+    s->hSampleSeq.clear();
     if (!data) return 0;
     const size_t n = (size_t)numSamples * numDims;
     // Sampler::sample reads data[ptr++] without a bound (sampler.h:20): a guard of zeros behind the table keeps the long paths of the
@@ -337,6 +338,7 @@ extern "C" int rs_scene_set_sample_sequence(rs_scene* s, const uint32_t* data, i
     RS_HIP(hipMemcpy(s->dSampleSeq, data, n * sizeof(uint32_t), hipMemcpyHostToDevice));
     RS_HIP(hipMemset(s->dSampleSeq + n, 0, kSobolGuard * sizeof(uint32_t)));
     s->dev.sampleSeq = s->dSampleSeq; s->dev.sampleCount = numSamples;
+    s->hSampleSeq.assign(data, data + n);
     return 0;
 }
 
